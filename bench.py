@@ -9,6 +9,11 @@ per-shard result rows to rank 0, overlapped with the next step on a second strea
     python bench.py --gpus 1 --steps 20 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run times the L0 loop and prints its line (value, ms_per_step, the roofline of the timed launches).  --full adds
+everything else the line has carried: the launch without the depth hint, live PMC traffic, the pure-read ceiling, the other
+configs' L0 figures, the CPU baseline with its parity check and the end-to-end blocks.  --dump-outputs DIR writes the rows of
+the last timed step as .npy files; the inputs are seeded, so two builds can be compared row for row.
 """
 from __future__ import annotations
 
@@ -754,6 +759,28 @@ def measured_read_peak():
             "what": "pure read of 2.4 GB, one wave per 24 KB segment, 16 B per lane, non-temporal (the hot kernel's shape), best of 10, measured in this run"}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, rows):
+    """--dump-outputs: what a caller of the L0 path receives from the last timed step - H1 and H2 per locus (float64, NaN = no
+    call; all ranks' loci in order at N > 1) - as phase1.npy / phase2.npy.  Above 64 MB a fixed sample of loci (seed 0, sorted)
+    is written instead, with its indices as locus_index.npy."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    p1, p2 = (np.ascontiguousarray(r, dtype=np.float64) for r in rows)
+    index_path = os.path.join(directory, "locus_index.npy")
+    if p1.nbytes + p2.nbytes > DUMP_BUDGET_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(p1.shape[0], size=DUMP_BUDGET_BYTES // (3 * 8), replace=False))
+        p1, p2 = p1[idx], p2[idx]
+        np.save(index_path, idx.astype(np.float64))
+    elif os.path.exists(index_path):
+        os.unlink(index_path)
+    np.save(os.path.join(directory, "phase1.npy"), p1)
+    np.save(os.path.join(directory, "phase2.npy"), p2)
+
+
 def _gpu_visible_count() -> int:
     import torch
 
@@ -804,7 +831,7 @@ def l2_dist(args):
 
 
 def l2_dist_core(args, rank, world, local_rank, dev, backend, loci, steps, warmup, native=True, cpu_b=True):
-    """The measurement of l2_dist() on a process group that exists already (the default `--gpus N` line carries it as its `l2_dist`
+    """The measurement of l2_dist() on a process group that exists already (the `--gpus N --full` line carries it as its `l2_dist`
     block, N > 1).  Returns the line (rank 0) or None."""
     import statistics
     import tempfile
@@ -977,8 +1004,13 @@ def l2_dist_core(args, rank, world, local_rank, dev, backend, loci, steps, warmu
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 30; --l2-dist: 3 passes over the file)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 5; --l2-dist: 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the launch without the depth hint, live PMC traffic, the pure-read ceiling, the other "
+                         "configs' L0 figures, the CPU baseline with its parity check, the end-to-end blocks (l1 / l2* / l2_dist)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the rows the last timed step computed (phase1.npy / phase2.npy, float64 per locus) into DIR")
     ap.add_argument("--workload", default="unphased100k", help="phased10k | unphased100k | shard500k | expansion50k")
     ap.add_argument("--loci-per-gpu", type=int, default=0, help="override the per-GPU shard size")
     ap.add_argument("--cpu-sample-loci", type=int, default=20_000)
@@ -1021,14 +1053,22 @@ def main():
     ap.add_argument("--l2-dist-gen-budget", type=float, default=45.0, help="seconds the file of the default N > 1 line's `l2_dist` block may take to write")
     ap.add_argument("--native-devices", default="", help="--l2-dist at one rank: the device list of the one-process run (e.g. 0,0,0,0 on a one-GPU box)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.l2_dist or args.l2):
+        raise SystemExit("--dump-outputs writes the rows of the L0 loop; --l2 / --l2-dist produce .inq text")
     if args.l2_dist:
-        if args.steps == 30 and args.warmup == 5:  # the defaults are the L0 loop's: a step here is a whole file
-            args.steps, args.warmup = 3, 1
+        # a step here is a whole file
+        args.steps = 3 if args.steps is None else args.steps
+        args.warmup = 1 if args.warmup is None else args.warmup
         l2_dist(args)
         return
     if args.l2:
         print(json.dumps(l2_end_to_end(args.workload, args.l2_loci, args.l2_threads or host_threads(), 2, args.l2_keep, args.l2_cpu_modes, args.l2_seq)), flush=True)
         return
+    args.steps = 30 if args.steps is None else args.steps
+    args.warmup = 5 if args.warmup is None else args.warmup
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line - every other block of the line is --full's
+        args.no_cpu_baseline = args.no_l2 = args.no_read_peak = args.no_live_pmc = args.no_l0_configs = True
 
     import torch
     import torch.distributed as dist
@@ -1230,11 +1270,24 @@ def main():
     rc, ties = ctx.status()
     if rc != 0:
         raise SystemExit(f"device status {rc}: {hipcall.strerror(rc)}")
+    if args.dump_outputs and rank == 0:
+        # the rows the last timed step left, before anything else launches on the context
+        lb, lg = state["last"]
+        if world == 1:
+            rows = outs[lb][lg][:, :n_mine].cpu().numpy()
+        else:
+            g = gathered[lb][:, lg].cpu().numpy()  # [world, 2, per_gpu]
+            counts = ([min(total, (r + 1) * per_gpu) - min(total, r * per_gpu) for r in range(world)] if args.scaling == "strong"
+                      else [per_gpu] * world)
+            import numpy as np
+
+            rows = np.concatenate([g[r, :, :counts[r]] for r in range(world)], axis=1)
+        dump_outputs(args.dump_outputs, rows)
     # The same launch WITHOUT the caller's depth hint: an external caller of inq_call_batch_device that does not know its deepest
     # locus gets two more launches behind the first kernel (locus_call_mid_walk and the persistent locus_call_tail, which find
     # empty work lists and leave; round 4: ~38 launches, 0.15 ms).  Same batch, same stream, HIP events around the whole sequence.
     no_hint = None
-    if world == 1:
+    if world == 1 and args.full:
         ctx.set_option("max_reads_hint", 0)
         for i in range(3):
             ctx.call_batch_device(shard.c_batch, results[0][0], main_stream.cuda_stream)

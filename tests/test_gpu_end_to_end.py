@@ -228,7 +228,7 @@ def test_session_survives_a_file_that_fails_on_the_device(tmp_path, frontend):
         os.environ.update(env_before)
 
 
-def test_call_through_a_resident_server_equals_call(tmp_path):
+def test_call_through_a_resident_server_equals_call(tmp_path, sock_dir):
     """`inquistr serve` keeps the device context; `inquistr call` with INQ_SERVER set hands it the arguments (relative paths made
     absolute) and its stdout: same bytes, same exit status and message as the call run by itself - also for a file the reference
     panics on, after which the server still answers -, and without a server at that address the call runs by itself."""
@@ -239,7 +239,7 @@ def test_call_through_a_resident_server_equals_call(tmp_path):
         prefix = str(tmp_path / f"s{k}")
         make_synth_bam.write_native("unphased100k" if k != 1 else "phased10k", 400 + 100 * k, prefix, threads=4)
         prefixes.append(prefix)
-    sock = str(tmp_path / "inq.sock")
+    sock = str(sock_dir / "inq.sock")
     env_direct = dict(os.environ, INQ_FRONTEND="device")
     env_direct.pop("INQ_SERVER", None)
     env_served = dict(env_direct, INQ_SERVER=sock)
@@ -356,7 +356,7 @@ def test_session_target_list_is_reused_only_when_it_may_be(tmp_path):
         assert in_session(S, long_, "f.inq") == want_long2
 
 
-def test_auto_server_gives_the_calls_own_rows(tmp_path):
+def test_auto_server_gives_the_calls_own_rows(tmp_path, sock_dir):
     """INQ_SERVER=auto: the first `inquistr call` starts the user's server for the device and is served by it, the next ones find
     it; rows, status and message are the call's own.  The server is asked to leave at the end (it would by itself when idle)."""
     from tools import make_synth_bam
@@ -365,8 +365,8 @@ def test_auto_server_gives_the_calls_own_rows(tmp_path):
     make_synth_bam.write_native("unphased100k", 700, prefix, threads=4)
     env_direct = dict(os.environ, INQ_FRONTEND="device")
     env_direct.pop("INQ_SERVER", None)
-    env_auto = dict(env_direct, INQ_SERVER="auto", XDG_RUNTIME_DIR=str(tmp_path), INQ_SERVER_IDLE="30")
-    sock = tmp_path / f"inquistr-{os.getuid()}-dev0.sock"
+    env_auto = dict(env_direct, INQ_SERVER="auto", XDG_RUNTIME_DIR=str(sock_dir), INQ_SERVER_IDLE="30")
+    sock = sock_dir / f"inquistr-{os.getuid()}-dev0.sock"
     cmd = [call.CLI_PATH, "call", prefix + ".bam", "-R", prefix + ".bed", "-u", "-t", "4"]
     want = subprocess.run(cmd, capture_output=True, text=True, env=env_direct)
     assert want.returncode == 0 and want.stdout.count("\n") == 701

@@ -711,6 +711,35 @@ def test_bench_two_ranks_report_every_ranks_clock_and_the_gathers_tail():
     assert line["gather"]["collectives"] == 2 and line["gather"]["bytes_per_rank_per_collective"] == 4 * 2 * 10_000 * 8
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_ones_rows(orc, tmp_path):
+    """bench.py without --full: ONE line with the contract's fields and none of --full's blocks, exactly --steps timed steps, and
+    --dump-outputs holds the rows of the last of them for every locus of the workload - the CPU oracle's rows, bit for bit."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "rows"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--workload", "phased10k",
+           "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, cwd=root, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["unit"] == "loci/s" and line["higher_is_better"] is True
+    assert line["metric"] and line["dtype"] and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(10_000 * 1e3 / line["ms_per_step"], rel=1e-9)
+    assert not {"cpu_baseline", "l0_configs", "l1", "l2", "l2_seq", "l2_phased", "l2_seq_large", "partial"} & set(line)
+    assert "no_hint" not in line["roofline"] and "peak_measured" not in line["roofline"]
+    wl = synth.WORKLOADS["phased10k"]
+    code, want = orc.call_batch(synth.generate_numpy(wl, 0, wl.n_loci))
+    assert code == 0
+    got1, got2 = np.load(out / "phase1.npy"), np.load(out / "phase2.npy")
+    assert got1.dtype == got2.dtype == np.float64
+    assert gen.same_f64(got1, want.phase1) and gen.same_f64(got2, want.phase2)
+    assert not (out / "locus_index.npy").exists()
+
+
 def test_bench_l2_dist_two_ranks_on_one_gpu():
     """bench.py --gpus 2 --l2-dist rehearsed on the one GPU (gloo, both ranks on device 0): the END-TO-END multi-rank mode - call_dist
     over one SEQ-bearing BAM, strong scaling - prints a line whose .inq equals the single-process CLI's and CPU mode B's byte for

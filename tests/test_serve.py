@@ -20,9 +20,9 @@ def _have_gpu():
 
 
 @pytest.mark.skipif(_have_gpu(), reason="the GPU twin is tests/test_gpu_end_to_end.py::test_call_through_a_resident_server_equals_call")
-def test_served_call_reports_what_the_call_itself_reports(tmp_path):
+def test_served_call_reports_what_the_call_itself_reports(tmp_path, sock_dir):
     bam, bed, loci, recs = _make_case(tmp_path, 5, n_loci=8)
-    sock = str(tmp_path / "s.sock")
+    sock = str(sock_dir / "s.sock")
     env = dict(os.environ)
     env.pop("INQ_SERVER", None)
     direct = subprocess.run([call.CLI_PATH, "call", bam, "-R", bed, "-t", "2"], capture_output=True, text=True, env=env)
@@ -56,13 +56,13 @@ def test_served_call_reports_what_the_call_itself_reports(tmp_path):
             server.wait(timeout=30)
 
 
-def test_server_leaves_on_sigterm_and_on_idle(tmp_path):
+def test_server_leaves_on_sigterm_and_on_idle(sock_dir):
     import signal
 
     env = dict(os.environ)
     env.pop("INQ_SERVER", None)
     for how in ("term", "idle"):
-        sock = str(tmp_path / f"{how}.sock")
+        sock = str(sock_dir / f"{how}.sock")
         args = [call.CLI_PATH, "serve", "--socket", sock] + (["--idle-exit", "0.5"] if how == "idle" else [])
         server = subprocess.Popen(args, env=env, stderr=subprocess.PIPE, text=True)
         try:
@@ -81,14 +81,14 @@ def test_server_leaves_on_sigterm_and_on_idle(tmp_path):
                 server.wait(timeout=30)
 
 
-def test_malformed_requests_are_refused_and_the_server_stays(tmp_path):
+def test_malformed_requests_are_refused_and_the_server_stays(tmp_path, sock_dir):
     """Garbage on the socket (no descriptor, wrong magic, a body shorter than announced) gets an error answer or a closed
     connection; the next proper request is served."""
     import socket
     import struct
 
     bam, bed, loci, recs = _make_case(tmp_path, 6, n_loci=5)
-    sock = str(tmp_path / "m.sock")
+    sock = str(sock_dir / "m.sock")
     env = dict(os.environ)
     env.pop("INQ_SERVER", None)
     server = subprocess.Popen([call.CLI_PATH, "serve", "--socket", sock, "--idle-exit", "60"], env=env, stderr=subprocess.PIPE, text=True)
@@ -129,12 +129,12 @@ def test_malformed_requests_are_refused_and_the_server_stays(tmp_path):
 
 
 @pytest.mark.skipif(_have_gpu(), reason="the GPU twin is in tests/test_gpu_end_to_end.py")
-def test_auto_server_is_started_once_and_found_again(tmp_path):
+def test_auto_server_is_started_once_and_found_again(tmp_path, sock_dir):
     """INQ_SERVER=auto: the first call starts this user's server for the device (detached, idle exit), the second finds it; the
     call's own status and message come back either way."""
     bam, bed, loci, recs = _make_case(tmp_path, 7, n_loci=6)
-    env = dict(os.environ, INQ_SERVER="auto", XDG_RUNTIME_DIR=str(tmp_path), INQ_SERVER_IDLE="20")
-    sock = tmp_path / f"inquistr-{os.getuid()}-dev0.sock"
+    env = dict(os.environ, INQ_SERVER="auto", XDG_RUNTIME_DIR=str(sock_dir), INQ_SERVER_IDLE="20")
+    sock = sock_dir / f"inquistr-{os.getuid()}-dev0.sock"
     try:
         for _ in range(2):
             r = subprocess.run([call.CLI_PATH, "call", bam, "-R", bed, "-t", "2"], capture_output=True, text=True, env=env, timeout=60)
@@ -150,7 +150,7 @@ def test_auto_server_is_started_once_and_found_again(tmp_path):
     assert not sock.exists()
 
 
-def test_auto_server_is_not_started_from_a_process_that_maps_a_gpu_runtime(tmp_path):
+def test_auto_server_is_not_started_from_a_process_that_maps_a_gpu_runtime(tmp_path, sock_dir):
     """Starting the server is fork + exec, which is only safe from a process that has not initialised the GPU.  A tool library
     preloaded into `inquistr call` (a profiler's is) may have: with a GPU runtime among the process's mappings the auto-start is
     refused - no server, no socket - and the call runs in the caller's own process, with its own status and message."""
@@ -158,8 +158,8 @@ def test_auto_server_is_not_started_from_a_process_that_maps_a_gpu_runtime(tmp_p
     if not os.path.exists(hip):
         pytest.skip("no HIP runtime library to preload")
     bam, bed, loci, recs = _make_case(tmp_path, 11, n_loci=6)
-    env = dict(os.environ, INQ_SERVER="auto", XDG_RUNTIME_DIR=str(tmp_path), INQ_SERVER_IDLE="5", LD_PRELOAD=hip)
-    sock = tmp_path / f"inquistr-{os.getuid()}-dev0.sock"
+    env = dict(os.environ, INQ_SERVER="auto", XDG_RUNTIME_DIR=str(sock_dir), INQ_SERVER_IDLE="5", LD_PRELOAD=hip)
+    sock = sock_dir / f"inquistr-{os.getuid()}-dev0.sock"
     r = subprocess.run([call.CLI_PATH, "call", bam, "-R", bed, "-t", "2"], capture_output=True, text=True, env=env, timeout=60)
     try:
         assert not sock.exists(), "a server was started from a process with the HIP runtime mapped"

@@ -22,7 +22,7 @@ CLI=inquistr_amd/lib/inquistr
 run_tests() { timeout -k 10 1000 python3 -m pytest tests -m gpu -x -q > $OUT/gpu_tests.txt 2>&1; echo "gpu tests rc $?"; tail -3 $OUT/gpu_tests.txt; }
 run_bench() {
   local s=$(date +%s)
-  timeout -k 10 1100 python3 bench.py "$@" > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc $? in $(( $(date +%s) - s )) s"
+  timeout -k 10 1100 python3 bench.py --full "$@" > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc $? in $(( $(date +%s) - s )) s"
   tail -c 400 $OUT/bench_default.err
   python3 tools/bench_digest.py $OUT/bench_default.json
 }
