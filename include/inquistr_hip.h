@@ -135,6 +135,10 @@ typedef struct inq_result {
 #define INQ_PAIR_FETCHED 0x02u /* yielded by fetch(): pos < end_ext && endpos > start_ext */
 #define INQ_PAIR_KEPT 0x04u    /* survived the read filter (src/call.rs:297-302 / 349-355) */
 
+/* Per-locus flags (the *_flags entry points below): one byte per locus, 0 or INQ_LOCUS_TIE.  INQ_LOCUS_TIE marks exactly the loci
+ * counted in n_tie_loci (unphased only; a phased batch leaves every flag 0), so the flags of a batch sum to its n_tie_loci. */
+#define INQ_LOCUS_TIE 0x01u
+
 typedef struct inq_ctx inq_ctx_t;
 
 /* Opens HIP device `device_id` (must be gfx950), creates the library's stream and
@@ -163,6 +167,12 @@ int inq_call_batch(inq_ctx_t *ctx, const inq_batch_t *batch, inq_result_t *resul
  * the stream has been synchronised. */
 int inq_call_batch_device(inq_ctx_t *ctx, const inq_batch_t *batch, inq_result_t *result,
                           void *hip_stream);
+/* The two entries above with per-locus flags (INQ_LOCUS_TIE): locus_flags[j] belongs to locus j of the batch; HOST memory of
+ * n_loci bytes for inq_call_batch_flags, DEVICE memory on the ctx's device (enqueued like the rest) for the device form.  NULL = no
+ * flags: exactly inq_call_batch / inq_call_batch_device.  The array is zeroed on the launch stream in front of the kernels. */
+int inq_call_batch_flags(inq_ctx_t *ctx, const inq_batch_t *batch, inq_result_t *result, uint8_t *locus_flags);
+int inq_call_batch_device_flags(inq_ctx_t *ctx, const inq_batch_t *batch, inq_result_t *result, uint8_t *d_locus_flags,
+                                void *hip_stream);
 
 /* Device-side status of the launches since the last inq_ctx_status() call: returns
  * INQ_OK or the first domain error (INQ_ERR_PHASE / _CIGAR_OP / _LOCUS / _RANGE /
@@ -335,6 +345,11 @@ int inq_call_flush(inq_ctx_t *ctx, inq_result_t *result, uint64_t n_loci, double
  * inquistr_amd/call_dist.py) reads them where the kernels' rows already are. */
 int inq_call_flush_device(inq_ctx_t *ctx, double *d_phase1, double *d_phase2, uint64_t cap, const uint32_t *index, uint64_t n_loci,
                           uint64_t *n_tie_loci, double *ms_call);
+/* The two flushes above with per-locus flags (INQ_LOCUS_TIE): locus_flags = HOST [n_loci], entry j for the j-th locus of the
+ * flush (append order), brought down with the rows; NULL = no flags. */
+int inq_call_flush_flags(inq_ctx_t *ctx, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags);
+int inq_call_flush_device_flags(inq_ctx_t *ctx, double *d_phase1, double *d_phase2, uint64_t cap, const uint32_t *index, uint64_t n_loci,
+                                uint64_t *n_tie_loci, double *ms_call, uint8_t *locus_flags);
 /* Row arrays in device memory for a host that does not link the HIP runtime itself: n f64, filled with quiet NaN (a locus no span
  * holds prints NaN NaN); plain synchronous copies in and out. */
 int inq_dev_alloc_rows(inq_ctx_t *ctx, uint64_t n, double **out);

@@ -38,6 +38,11 @@ typedef struct inq_call_args {
     const char *reference;   /* --reference (CRAM only; CRAM is not supported here) */
     int32_t device;          /* HIP device ordinal (not a reference argument) */
     int32_t reserved;        /* front end: 0 = auto (env INQ_FRONTEND=host|device, else device when the loci need >= 1 MiB of BAM per host thread), 1 = host sweep, 2 = device spans */
+    const char *ties_path;   /* --ties: the tie report (not a reference argument), NULL = none.  One line `chrom\tbegin\tend` per target
+                              * whose unphased split cuts through equal values of mixed Span / Clip (INQ_LOCUS_TIE: the rows the
+                              * reference itself may print differently), coordinates as given, in the .inq's row order, no header: the
+                              * file is itself a valid -R input.  Created / truncated before any device work (a path that cannot be
+                              * opened: exit status 1); empty for a phased call; its content is unspecified after a failed call. */
 } inq_call_args_t;
 
 #define INQ_EXIT_OK 0
@@ -130,6 +135,13 @@ int inq_run_rows_device(inq_run_t *run, const uint32_t *target_index, uint64_t n
 /* header + one row per target (phase1[i], phase2[i] = row of target i of the list; n_rows must equal inq_run_n_targets) to
  * out_fd: BED order for -t 1, (human_compare(chrom), start) order for -t >= 2 (src/call.rs:33-38,141).  No GPU involved. */
 int inq_run_write_inq(inq_run_t *run, const double *phase1, const double *phase2, uint64_t n_rows, int out_fd, char *errbuf, size_t errcap);
+/* The tie report (inq_call_args_t.ties_path) of a run: inq_run_tie_flags copies the per-target flags (INQ_LOCUS_TIE) of the last
+ * inq_run_rows / inq_run_rows_device, flags[k] for target target_index[k], n = that call's n_index; they are collected only when the
+ * run was opened with ties_path set (inq_run_* write no file themselves).  Returns 0, or 1 (not collected, n does not match).
+ * inq_run_write_ties writes the report for flags[i] = flag of target i of the list (n_rows = inq_run_n_targets) to fd, in the order
+ * of inq_run_write_inq's rows, by the same code.  No GPU involved. */
+int inq_run_tie_flags(const inq_run_t *run, uint8_t *flags, uint64_t n);
+int inq_run_write_ties(inq_run_t *run, const uint8_t *flags, uint64_t n_rows, int fd, char *errbuf, size_t errcap);
 void inq_run_close(inq_run_t *run);
 
 /* ---- a session: many BAMs on one device context ----

@@ -40,6 +40,8 @@ HOST_ABI_SYMBOLS = (
     "inq_run_rows",
     "inq_run_rows_device",
     "inq_run_write_inq",
+    "inq_run_tie_flags",
+    "inq_run_write_ties",
     "inq_run_close",
     "inq_session_open",
     "inq_session_call",
@@ -91,6 +93,7 @@ class CallArgsC(C.Structure):
         ("reference", C.c_char_p),
         ("device", C.c_int32),
         ("reserved", C.c_int32),
+        ("ties_path", C.c_char_p),
     ]
 
 
@@ -182,6 +185,10 @@ def load():
         L.inq_run_write_inq.restype = C.c_int
         L.inq_run_write_inq.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_char_p, C.c_size_t]
         L.inq_run_close.restype = None
+        L.inq_run_tie_flags.argtypes = [vp, C.c_void_p, C.c_uint64]
+        L.inq_run_tie_flags.restype = C.c_int
+        L.inq_run_write_ties.argtypes = [vp, C.c_void_p, C.c_uint64, C.c_int, C.c_char_p, C.c_size_t]
+        L.inq_run_write_ties.restype = C.c_int
         L.inq_run_close.argtypes = [vp]
         L.inq_session_open.restype = C.c_int
         L.inq_session_open.argtypes = [C.c_int32, C.POINTER(vp)]
@@ -256,7 +263,7 @@ FRONTENDS = {None: 0, "host": 1, "device": 2}
 
 
 def _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, reference, device=0,
-          frontend=None) -> CallArgsC:
+          frontend=None, ties=None) -> CallArgsC:
     a = CallArgsC()
     a.bam = os.fspath(bamp).encode()
     a.region = region.encode() if region is not None else None
@@ -267,17 +274,20 @@ def _args(bamp, region, region_file, minlen, support, threads, unphased, sample_
     a.reference = reference.encode() if reference is not None else None
     a.device = device
     a.reserved = FRONTENDS[frontend]
+    a.ties_path = os.fspath(ties).encode() if ties is not None else None
     return a
 
 
 def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str], minlen: int = 5, support: int = 3,
                      threads: int = 1, unphased: bool = False, sample_name: Optional[str] = None,
-                     reference: Optional[str] = None, out=None, device: int = 0, frontend: Optional[str] = None) -> None:
+                     reference: Optional[str] = None, out=None, device: int = 0, frontend: Optional[str] = None,
+                     ties: Optional[str] = None) -> None:
     """src/call.rs:76-86: same parameters, same output; raises CallError instead of exiting.
     frontend: "host" (BGZF inflate + record decode on CPU threads), "device" (inq_call_span: both on the GPU)
-    or None (env INQ_FRONTEND, else the library default)."""
+    or None (env INQ_FRONTEND, else the library default).
+    ties: path of the tie report (inquistr call --ties): the tie-ambiguous unphased loci as BED, in the rows' order."""
     L = load()
-    a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, reference, device, frontend)
+    a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, reference, device, frontend, ties)
     err = C.create_string_buffer(2048)
     out = sys.stdout if out is None else out
     out.flush()
@@ -289,11 +299,11 @@ def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str
 
 def genotype_repeats_devices(bamp: str, region: Optional[str], region_file: Optional[str], devices, minlen: int = 5, support: int = 3,
                              threads: int = 1, unphased: bool = False, sample_name: Optional[str] = None, out=None,
-                             frontend: Optional[str] = None):
+                             frontend: Optional[str] = None, ties: Optional[str] = None):
     """inq_genotype_repeats_devices: the same command on several HIP devices from this one process (one thread + one device
     context per entry of `devices`; an ordinal may repeat).  Returns the per-part statistics as a list of dicts."""
     L = load()
-    a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, None, 0, frontend)
+    a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, None, 0, frontend, ties)
     ids = (C.c_int32 * len(devices))(*[int(d) for d in devices])
     st = (PartStatsC * len(devices))()
     err = C.create_string_buffer(2048)
@@ -364,14 +374,15 @@ class Run:
     """inq_run_*: the BAM header, its index and the targets opened once (get_targets + get_bam_reader, src/call.rs:146-147,
     182-202); serves the work split, this process's rows and the ordered `.inq` output of a multi-process run.
     session: a Session whose device context, span buffers and BED cache the run's rows calls use (inq_session_run_open) - what a
-    resident rank passes file after file; the session must stay open while the run is."""
+    resident rank passes file after file; the session must stay open while the run is.
+    ties: a path (not opened by the run) that makes its rows calls collect the per-target tie flags (tie_flags())."""
 
     def __init__(self, bamp, region=None, region_file=None, minlen=5, support=3, threads=1, unphased=False, sample_name=None,
-                 device: int = 0, frontend: Optional[str] = None, session: Optional["Session"] = None):
+                 device: int = 0, frontend: Optional[str] = None, session: Optional["Session"] = None, ties: Optional[str] = None):
         self._L = load()
         self._h = C.c_void_p()
         self._session = session  # the session closes the runs still open on it before it goes (Session.close)
-        self._args = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, None, device, frontend)
+        self._args = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, None, device, frontend, ties)
         err = C.create_string_buffer(2048)
         if session is not None:
             rc = self._L.inq_session_run_open(session._h, C.byref(self._args), C.byref(self._h), err, len(err))
@@ -433,6 +444,22 @@ class Run:
         if rc != 0:
             raise CallError(rc, err.value.decode(errors="replace"))
 
+    def tie_flags(self, n: int) -> np.ndarray:
+        """inq_run_tie_flags: the per-target flags (uint8, INQ_LOCUS_TIE) of the last rows / rows_device call of n targets."""
+        flags = np.zeros(max(n, 1), dtype=np.uint8)
+        if self._L.inq_run_tie_flags(self._h, flags.ctypes.data, n) != 0:
+            raise CallError(1, "no tie flags: the run was opened without ties, or the last rows call had another length")
+        return flags[:n]
+
+    def write_ties(self, flags, out) -> None:
+        """inq_run_write_ties: the tie report for flags in target-list order, in the order write_inq writes the rows."""
+        fl = np.ascontiguousarray(flags, dtype=np.uint8)
+        out.flush()
+        err = C.create_string_buffer(2048)
+        rc = self._L.inq_run_write_ties(self._h, fl.ctypes.data, len(fl), out.fileno(), err, len(err))
+        if rc != 0:
+            raise CallError(rc, err.value.decode(errors="replace"))
+
     def close(self):
         if self._h and self._h.value:
             self._L.inq_run_close(self._h)
@@ -460,8 +487,8 @@ class Session:
             raise CallError(rc, "cannot open a session")
 
     def call(self, bamp, region=None, region_file=None, minlen=5, support=3, threads=1, unphased=False, sample_name=None, out=None,
-             frontend: Optional[str] = None) -> None:
-        a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, None, 0, frontend)
+             frontend: Optional[str] = None, ties: Optional[str] = None) -> None:
+        a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, None, 0, frontend, ties)
         err = C.create_string_buffer(2048)
         out = sys.stdout if out is None else out
         out.flush()
@@ -470,13 +497,15 @@ class Session:
             raise CallError(rc, err.value.decode(errors="replace"))
 
     def call_many(self, bams, outs, region=None, region_file=None, minlen=5, support=3, threads=1, unphased=False, sample_names=None,
-                  frontend: Optional[str] = None):
-        """Runs the files in order; returns the list of exit statuses (no exception for failing files)."""
+                  frontend: Optional[str] = None, ties=None):
+        """Runs the files in order; returns the list of exit statuses (no exception for failing files).
+        ties: None, or one tie-report path per file."""
         n = len(bams)
         arr = (CallArgsC * n)()
         keep = []
         for k, b in enumerate(bams):
-            a = _args(b, region, region_file, minlen, support, threads, unphased, sample_names[k] if sample_names else None, None, 0, frontend)
+            a = _args(b, region, region_file, minlen, support, threads, unphased, sample_names[k] if sample_names else None, None, 0, frontend,
+                      ties[k] if ties else None)
             keep.append(a)
             arr[k] = a
         for o in outs:

@@ -81,8 +81,10 @@ def genotype_repeats_distributed(bamp: str, region: Optional[str], region_file: 
                                  sample_name: Optional[str] = None, out=None, rank: int = 0, world: int = 1,
                                  device: int = 0, compute: Optional[Callable] = None, group=None,
                                  frontend: Optional[str] = None, stats: Optional[dict] = None, rows: Optional[str] = None,
-                                 session=None) -> None:
+                                 session=None, ties: Optional[str] = None) -> None:
     """Same arguments as call.genotype_repeats plus (rank, world).  Rank 0 writes header + rows.
+    ties (rank 0): path of the tie report (inquistr call --ties); every rank's per-target flags (1 byte each) are gathered to rank 0
+    on the rows' group and written there in the rows' order.  A compute hook may then return (phase1, phase2, flags).
     Raises CallError (same status on every rank) if any rank fails.  stats (rank 0): seconds of the output stage.
     rows: "device" / "host" = where this rank's rows wait for the gather; None = device memory when the backend is nccl.
     session: the call.Session this rank's device work runs on; None = one per process and device, opened at the first call and
@@ -107,11 +109,17 @@ def genotype_repeats_distributed(bamp: str, region: Optional[str], region_file: 
     t_open = time.perf_counter()
     st, msg = 0, ""
     run = None
+    ties_out = None
     order, cuts, digest = None, None, 0
     try:
+        if ties is not None and rank == 0:  # created before any device work, as by the one-process call
+            try:
+                ties_out = open(ties, "w")
+            except OSError as e:
+                raise hostcall.CallError(1, f"cannot write the tie report {ties}: {e.strerror}")
         sess = _process_session(device) if (compute is None and session is None) else session
         run = hostcall.Run(bamp, region, region_file, minlen, support, threads, unphased, sample_name, device=device, frontend=frontend,
-                           session=sess if compute is None else None)
+                           session=sess if compute is None else None, ties=ties)
         order, cuts = run.partition(world)
         digest = zlib.crc32(cuts.tobytes(), zlib.crc32(order.tobytes()))
     except hostcall.CallError as e:
@@ -120,17 +128,21 @@ def genotype_repeats_distributed(bamp: str, region: Optional[str], region_file: 
         st, msg = 1, f"{type(e).__name__}: {e}"
     if world > 1:
         got = [None] * world
-        dist.all_gather_object(got, (int(st), str(msg), int(digest)), group=group)
-        for r, (s_r, m_r, _d) in enumerate(got):
+        dist.all_gather_object(got, (int(st), str(msg), int(digest), ties is not None), group=group)
+        for r, (s_r, m_r, _d, _t) in enumerate(got):
             if s_r != 0:
                 st, msg = s_r, m_r
                 break
         else:
-            if any(d != got[0][2] for _s, _m, d in got):
+            if any(d != got[0][2] for _s, _m, d, _t in got):
                 st, msg = 1, "the ranks cut the targets differently (different files, or different versions of the host library?)"
+            elif any(t != got[0][3] for _s, _m, _d, t in got):
+                st, msg = 1, "ties: every rank must be given the tie report's path (rank 0 writes it), or none"
     if st != 0:
         if run is not None:
             run.close()
+        if ties_out is not None:
+            ties_out.close()
         raise hostcall.CallError(st, msg)
     if stats is not None:
         stats["open_s"] = time.perf_counter() - t_open  # header + index + BED + the cut (+ the exchange's wait for the slowest rank)
@@ -144,6 +156,7 @@ def genotype_repeats_distributed(bamp: str, region: Optional[str], region_file: 
     t_rows = time.perf_counter()
     p1 = np.full(len(mine), np.nan)
     p2 = np.full(len(mine), np.nan)
+    tf = np.zeros(len(mine), dtype=np.uint8)  # this rank's tie flags (ties set)
     dev_buf = None
     st, msg = 0, ""
     try:
@@ -151,10 +164,14 @@ def genotype_repeats_distributed(bamp: str, region: Optional[str], region_file: 
             # the device row buffer lives in the run until the gather is over
             d1, _d2 = run.rows_device(mine, width)
             dev_buf = torch.as_tensor(_DeviceArray(d1, (2, width)), device=torch.device("cuda", device))
+            if ties is not None:
+                tf = run.tie_flags(len(mine))
         elif len(mine) and compute is None:
             # the product path: the C++ driver on this rank's share (inq_genotype_repeats_rows), which picks the device front end
             # (inflate + record scan + join on this rank's GPU) or the host sweep by the amount of BAM; rows come back as f64
             p1, p2 = run.rows(mine)
+            if ties is not None:
+                tf = run.tie_flags(len(mine))
         elif len(mine):  # tests: per-batch compute supplied by the caller (the oracle, on CPU-only machines)
             fe_all = hostcall.FrontEnd(bamp, region=region, region_file=region_file)
             targets = fe_all.targets()
@@ -167,8 +184,10 @@ def genotype_repeats_distributed(bamp: str, region: Optional[str], region_file: 
                 fe = hostcall.FrontEnd(bamp, region_file=sub_bed, minlen=minlen, support=support, threads=threads,
                                        unphased=unphased, sample_name=sample_name)
                 for batch, idx in fe.batches():
-                    a, b = compute(batch)
-                    p1[idx], p2[idx] = a, b
+                    got = compute(batch)
+                    p1[idx], p2[idx] = got[0], got[1]
+                    if len(got) > 2:
+                        tf[idx] = got[2]
                 fe.close()
             finally:
                 os.unlink(sub_bed)
@@ -195,6 +214,8 @@ def genotype_repeats_distributed(bamp: str, region: Optional[str], region_file: 
     st, msg, bad_rank = _exchange_status(st, msg, rank, world, group)
     if st != 0:
         run.close()
+        if ties_out is not None:
+            ties_out.close()
         if own_failure == 1 and compute is None and session is None:
             # an error exit of THIS rank's device work (HIP, memory, no device - not one of the reference's panics, which a session
             # survives): the process's session is given up, the next call makes a new context
@@ -216,6 +237,20 @@ def genotype_repeats_distributed(bamp: str, region: Optional[str], region_file: 
             torch.cuda.synchronize(device)  # (the collective is enqueued; the run's buffer must outlive it)
         if stats is not None:
             stats["gather_s"] = time.perf_counter() - t_g  # exposed: nothing overlaps it in a one-file call (16 B per locus)
+        full_t = None
+        if ties is not None:  # 1 byte per target, on the rows' group (and device, on nccl)
+            tbuf = torch.zeros(width, dtype=torch.uint8)
+            tbuf[: len(mine)] = torch.from_numpy(tf)
+            if on_device:
+                tbuf = tbuf.to(torch.device("cuda", device))
+            tbufs = [torch.empty_like(tbuf) for _ in range(world)] if rank == 0 else None
+            dist.gather(tbuf, tbufs, dst=0, group=group)
+            if rank == 0:
+                got_t = torch.stack(tbufs).cpu().numpy()
+                full_t = np.zeros(n, dtype=np.uint8)
+                for r in range(world):
+                    sl = order[int(cuts[r]) : int(cuts[r + 1])]
+                    full_t[sl] = got_t[r][: len(sl)]
         if rank != 0:
             run.close()
             return
@@ -231,11 +266,19 @@ def genotype_repeats_distributed(bamp: str, region: Optional[str], region_file: 
             got = dev_buf.cpu().numpy()
             p1, p2 = got[0, : len(mine)], got[1, : len(mine)]
         full1[mine], full2[mine] = p1, p2
+        full_t = np.zeros(n, dtype=np.uint8)
+        full_t[mine] = tf
     # ---- output (rank 0), src/call.rs:137-157: BED order for -t 1, (human chrom, start) order otherwise.  One call into the
     # host library on the f64 arrays (the code inq_genotype_repeats itself ends with): 500 000 rows take tens of milliseconds
     out = sys.stdout if out is None else out
     t0 = time.perf_counter()
-    run.write_inq(full1, full2, out)
+    try:
+        run.write_inq(full1, full2, out)
+        if ties_out is not None:
+            run.write_ties(full_t, ties_out)
+    finally:
+        if ties_out is not None:
+            ties_out.close()
     if stats is not None:
         stats["output_s"] = time.perf_counter() - t0
         stats["rows"] = n
@@ -257,6 +300,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--same-device", action="store_true", help="all ranks on device 0 (rehearsal on a one-GPU box)")
     ap.add_argument("--frontend", default=None, choices=["host", "device"], help="default: by the amount of BAM each rank reads")
     ap.add_argument("--rows", default=None, choices=["device", "host"], help="where a rank's rows wait for the gather (default: device memory on nccl)")
+    ap.add_argument("--ties", default=None, help="write the loci whose unphased split is tie-ambiguous there, as BED (rank 0)")
     ap.add_argument("--stats-dir", default=None, help="every rank leaves rank<r>.json there: its loci, seconds, BAM bytes read, the gather's time")
     a = ap.parse_args(argv)
     import torch
@@ -276,7 +320,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     stats = {} if a.stats_dir else None
     try:
         genotype_repeats_distributed(a.bam, a.region, a.region_file, a.minlen, a.support, a.threads, a.unphased,
-                                     a.sample_name, out=out, rank=rank, world=world, device=device, frontend=a.frontend, stats=stats, rows=a.rows)
+                                     a.sample_name, out=out, rank=rank, world=world, device=device, frontend=a.frontend, stats=stats, rows=a.rows,
+                                     ties=a.ties)
         if stats is not None:
             import json
 

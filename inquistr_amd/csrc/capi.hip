@@ -300,7 +300,8 @@ static int check_scalars(const inq_batch_t *b, const inq_result_t *r) {
     return INQ_OK;
 }
 
-static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream) {
+// d_flags: DEVICE [n_loci] per-locus flags (INQ_LOCUS_TIE), or null - then nothing is added to the launch sequence
+static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, uint8_t *d_flags = nullptr) {
     if (!c) return INQ_ERR_ARG;
     int rc = check_scalars(b, r);
     if (rc != INQ_OK) return rc;
@@ -346,6 +347,7 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     const uint32_t hint = c->call_hint ? c->call_hint : c->max_reads_hint;
     c->call_hint = 0;
     a.max_reads_hint = hint;
+    a.locus_flags = d_flags;
 
     // CIGAR words of a read referenced by one locus only are read exactly once: stream them past the
     // caches (nt).  Reads shared by neighbouring loci keep the default policy so the second locus hits L2.
@@ -362,6 +364,7 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
         ev = &c->ev_pool[c->ev_used++];
         HIP_TRY(c, hipEventRecord(ev->e0, s));
     }
+    if (d_flags) HIP_TRY(c, hipMemsetAsync(d_flags, 0, (size_t)b->n_loci, s));  // the kernels store tie loci only
     launch_locus_call(a, b->unphased != 0, nt, grid_small, c->grid_medium, c->grid_tail, s, ev ? ev->e1 : nullptr, deep_possible ? c->deep.p : nullptr);
     HIP_TRY(c, hipGetLastError());
     if (ev) HIP_TRY(c, hipEventRecord(ev->e2, s));
@@ -369,8 +372,12 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
 }
 
 int inq_call_batch_device(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream) {
+    return inq_call_batch_device_flags(c, b, r, nullptr, hip_stream);
+}
+
+int inq_call_batch_device_flags(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *d_locus_flags, void *hip_stream) {
     try {  // nothing may unwind across the C ABI
-        return enqueue_batch(c, b, r, hip_stream);
+        return enqueue_batch(c, b, r, hip_stream, d_locus_flags);
     } catch (const std::bad_alloc &) {
         return INQ_ERR_NOMEM;
     } catch (...) {
@@ -392,7 +399,7 @@ int inq_ctx_status(inq_ctx_t *c, uint64_t *n_tie_loci) {
     return status_to_code(h.err);
 }
 
-static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r) {
+static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *h_flags) {
     if (!c) return INQ_ERR_ARG;
     int rc = check_scalars(b, r);
     if (rc != INQ_OK) return rc;
@@ -430,6 +437,7 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r) 
     if ((rc = ensure(c, c->p2, (size_t)b->n_loci * 8)) != INQ_OK) return rc;
     if (r->pair_call && (rc = ensure(c, c->pcall, (size_t)b->n_pairs * 8)) != INQ_OK) return rc;
     if (r->pair_bits && (rc = ensure(c, c->pbits, (size_t)b->n_pairs)) != INQ_OK) return rc;
+    if (h_flags && (rc = ensure(c, c->lflags, (size_t)b->n_loci)) != INQ_OK) return rc;
 
     inq_batch_t db = *b;
     db.cigar = (const uint32_t *)c->cigar.p;
@@ -445,7 +453,9 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r) 
     dr.pair_bits = r->pair_bits ? (uint8_t *)c->pbits.p : nullptr;
     dr.n_tie_loci = 0;
     c->call_hint = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(max_reads, 1), 0xffffffffull);  // skips the deep-locus launches when no locus needs them
-    if ((rc = enqueue_batch(c, &db, &dr, s)) != INQ_OK) return rc;
+    uint8_t *d_flags = h_flags ? (uint8_t *)c->lflags.p : nullptr;
+    if ((rc = enqueue_batch(c, &db, &dr, s, d_flags)) != INQ_OK) return rc;
+    if (h_flags) HIP_TRY(c, hipMemcpyAsync(h_flags, d_flags, (size_t)b->n_loci, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(r->phase1, dr.phase1, (size_t)b->n_loci * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(r->phase2, dr.phase2, (size_t)b->n_loci * 8, hipMemcpyDeviceToHost, s));
     if (r->pair_call && b->n_pairs)
@@ -463,9 +473,11 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r) 
     return status_to_code(c->h_status->err);
 }
 
-int inq_call_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r) {
+int inq_call_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r) { return inq_call_batch_flags(c, b, r, nullptr); }
+
+int inq_call_batch_flags(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *locus_flags) {
     try {
-        return call_batch_impl(c, b, r);
+        return call_batch_impl(c, b, r, locus_flags);
     } catch (const std::bad_alloc &) {
         return INQ_ERR_NOMEM;
     } catch (...) {
@@ -732,7 +744,7 @@ void inq_free_pinned(void *p) {
 
 }  // extern "C"
 
-int inq::call_batch_device_impl(inq_ctx *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream) {
-    return enqueue_batch(c, b, r, hip_stream);
+int inq::call_batch_device_impl(inq_ctx *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, uint8_t *d_locus_flags) {
+    return enqueue_batch(c, b, r, hip_stream, d_locus_flags);
 }
 

@@ -34,7 +34,7 @@ struct inq_ctx {
     inq::DevStatus *h_status = nullptr;  // pinned mirror for the host-buffer entry
     inq::DevBuf worklist, sval, smeta, deep;
     // staging for the host-buffer entry
-    inq::DevBuf cigar, reads, pair_read, off, lstart, lend, p1, p2, pcall, pbits;
+    inq::DevBuf cigar, reads, pair_read, off, lstart, lend, p1, p2, pcall, pbits, lflags;
     inq::DevBuf ovalues, olen, oflags, okeep, otrans;  // inq_outlier_rows
     uint32_t n_cus = 0;        // compute units of the device
     uint32_t grid_tail = 256;  // workgroups of the persistent locus_call_tail: they meet at grid barriers, so never more than n_cus
@@ -104,7 +104,7 @@ int device_alloc(inq_ctx *c, void **out, size_t want, size_t exact, size_t *got)
 void retire(inq_ctx *c, void *p, size_t bytes);
 void purge_retired(inq_ctx *c);  // hipFree of everything retired (waits for the device: call where it is idle)
 // enqueue-only launch sequence of the locus kernels over a device-resident batch
-int call_batch_device_impl(inq_ctx *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream);
+int call_batch_device_impl(inq_ctx *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, uint8_t *d_locus_flags = nullptr);
 int status_to_code(uint32_t st);
 void span_state_destroy(SpanState *s);
 int span_state_init(inq_ctx *c);       // device front end state, the part staging needs (streams, slots); called by inq_ctx_create

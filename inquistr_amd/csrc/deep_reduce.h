@@ -170,7 +170,10 @@ __device__ __forceinline__ void reduce_deep_select(const KArgs &a, uint64_t j, u
     if (threadIdx.x == 0) {
         a.phase1[j] = out1;
         a.phase2[j] = out2;
-        if (tie) atomicAdd((unsigned long long *)&a.status->ties, 1ull);
+        if (tie) {
+            atomicAdd((unsigned long long *)&a.status->ties, 1ull);
+            if (a.locus_flags) a.locus_flags[j] = INQ_LOCUS_TIE;
+        }
     }
     __syncthreads();
 }
@@ -318,7 +321,10 @@ __device__ __forceinline__ void sort_reduce_locus(const KArgs &a, uint64_t j, ui
     if (threadIdx.x == 0) {
         a.phase1[j] = out1;
         a.phase2[j] = out2;
-        if (UNPHASED && L.tie_span && L.tie_clip) atomicAdd((unsigned long long *)&a.status->ties, 1ull);
+        if (UNPHASED && L.tie_span && L.tie_clip) {
+            atomicAdd((unsigned long long *)&a.status->ties, 1ull);
+            if (a.locus_flags) a.locus_flags[j] = INQ_LOCUS_TIE;
+        }
     }
     __syncthreads();
 }

@@ -471,7 +471,10 @@ __device__ __forceinline__ void deep_final(const DeepArgs &a, const uint32_t nd)
             const uint32_t kh = mcount / 2u;
             const SelOut so = chain(D.split, ks.top, -1, kh < mcount ? kh : mcount - 1u, 0ull, 0u, ch);
             const uint32_t r = kh - so.below;
-            if (threadIdx.x == 0 && kh >= 1u && kh < mcount && r >= 1u && ld_u32(&D.flags) == 3u) atomicAdd((unsigned long long *)&a.k.status->ties, 1ull);
+            if (threadIdx.x == 0 && kh >= 1u && kh < mcount && r >= 1u && ld_u32(&D.flags) == 3u) {  // (the thread that wrote phase1[D.j])
+                atomicAdd((unsigned long long *)&a.k.status->ties, 1ull);
+                if (a.k.locus_flags) a.k.locus_flags[D.j] = INQ_LOCUS_TIE;
+            }
         }
         __syncthreads();
     }

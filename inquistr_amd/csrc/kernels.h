@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/inquistr_hip.h"  // INQ_LOCUS_TIE
+
 namespace inq {
 
 // Device-resident status block (one per ctx).
@@ -52,6 +54,9 @@ struct KArgs {
     uint32_t blocks_per_xcd;  // grid_small / 8
     uint32_t shard_cap;       // loci one shard can list: every locus whose block has blockIdx % kListShards == shard
     uint32_t max_reads_hint;  // caller's promise (0 = none): no locus is offered more reads than this
+    // per-locus flags [n_loci] (may be null): the thread that writes phase1[j] of a tie locus also stores INQ_LOCUS_TIE to
+    // locus_flags[j]; the entry point zeroes the array in front of the sequence, so nothing is stored for any other locus
+    uint8_t *locus_flags;
 };
 
 // deep_scratch: deep_select_scratch_bytes(n_pairs) of ctx scratch for the loci the grid-wide select takes (may be null when the

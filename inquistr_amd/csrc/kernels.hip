@@ -258,7 +258,10 @@ __device__ __forceinline__ void wave_locus(const KArgs &a, uint64_t j, uint64_t 
     if (lane == 0) {
         a.phase1[j] = out1;
         a.phase2[j] = out2;
-        if (tie) atomicAdd((unsigned long long *)&a.status->ties, 1ull);
+        if (tie) {
+            atomicAdd((unsigned long long *)&a.status->ties, 1ull);
+            if (a.locus_flags) a.locus_flags[j] = INQ_LOCUS_TIE;
+        }
     }
     if (status) atomicOr(&a.status->err, status);  // per lane: index / phase errors belong to the lane's read
 }

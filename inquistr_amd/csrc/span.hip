@@ -576,7 +576,8 @@ struct FlushToDevice {
     const uint32_t *index;  // HOST, n_loci entries
     uint64_t cap;           // entries of d1 / d2
 };
-int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_call, const FlushToDevice *dev = nullptr) {
+// h_flags: HOST [n_loci] per-locus flags (INQ_LOCUS_TIE) in append order, brought down with the rows through the same staging; may be null
+int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_call, const FlushToDevice *dev = nullptr, uint8_t *h_flags = nullptr) {
     if (!c || !r) return INQ_ERR_ARG;
     SpanState *S;
     int rc;
@@ -600,11 +601,14 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     const uint64_t nl = A.n_loci;
     if ((rc = ensure(c, S->p1, nl * 8)) != INQ_OK) return rc;
     if ((rc = ensure(c, S->p2, nl * 8)) != INQ_OK) return rc;
-    if (S->h_rows_cap < 2 * nl) {
+    if (h_flags && (rc = ensure(c, c->lflags, nl)) != INQ_OK) return rc;
+    uint8_t *const d_flags = h_flags ? (uint8_t *)c->lflags.p : nullptr;
+    const size_t staged = 2 * nl + (h_flags ? (nl + 7) / 8 : 0);  // the rows, then the flags
+    if (S->h_rows_cap < staged) {
         if (S->h_rows) (void)hipHostFree(S->h_rows);
         S->h_rows = nullptr;
         S->h_rows_cap = 0;
-        const size_t want = std::max<size_t>(2 * nl + nl / 2 + 1024, 1u << 16);
+        const size_t want = std::max<size_t>(std::max<size_t>(2 * nl + nl / 2 + 1024, staged), 1u << 16);
         HIP_TRY(c, hipHostMalloc((void **)&S->h_rows, want * sizeof(double), hipHostMallocDefault));
         S->h_rows_cap = want;
     }
@@ -637,7 +641,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     } spent{A};
     const uint64_t n_reads_all = A.n_reads, n_units_all = A.n_units, n_pairs_all = A.n_pairs;
     HIP_TRY(c, hipEventRecord(S->ev[4], s));
-    if ((rc = call_batch_device_impl(c, &db, &dr, s)) != INQ_OK) return rc;
+    if ((rc = call_batch_device_impl(c, &db, &dr, s, d_flags)) != INQ_OK) return rc;
     HIP_TRY(c, hipEventRecord(S->ev[5], s));
     // measurement builds only (make DEBUG_ENV=1; tools/profile_cli_locus.sh): the shipped library reads nothing here
     if (const char *again = debug_env("INQ_CALL_AGAIN"); again && again[0] == '1') {
@@ -661,10 +665,12 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
         HIP_TRY(c, hipMemcpyAsync(S->h_rows, dr.phase1, nl * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(S->h_rows + nl, dr.phase2, nl * 8, hipMemcpyDeviceToHost, s));
     }
+    if (h_flags) HIP_TRY(c, hipMemcpyAsync(S->h_rows + 2 * nl, d_flags, nl, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(&S->h->ks, c->d_status, sizeof(DevStatus), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemsetAsync(&c->d_status->err, 0, sizeof(unsigned int), s));
     HIP_TRY(c, hipMemsetAsync(&c->d_status->ties, 0, sizeof(unsigned long long), s));
     HIP_TRY(c, hipStreamSynchronize(s));
+    if (h_flags) std::memcpy(h_flags, S->h_rows + 2 * nl, nl);
     if (!dev) {
         std::memcpy(r->phase1, S->h_rows, nl * 8);
         std::memcpy(r->phase2, S->h_rows + nl, nl * 8);
@@ -887,8 +893,12 @@ int inq_call_span_deferred(inq_ctx_t *c, const inq_span_t *span, int slot, inq_s
 }
 
 int inq_call_flush(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call) {
+    return inq_call_flush_flags(c, result, n_loci, ms_call, nullptr);
+}
+
+int inq_call_flush_flags(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags) {
     try {
-        return call_flush_impl(c, result, n_loci, ms_call);
+        return call_flush_impl(c, result, n_loci, ms_call, nullptr, locus_flags);
     } catch (const std::bad_alloc &) {
         return INQ_ERR_NOMEM;
     } catch (...) {
@@ -898,11 +908,16 @@ int inq_call_flush(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *
 
 int inq_call_flush_device(inq_ctx_t *c, double *d_phase1, double *d_phase2, uint64_t cap, const uint32_t *index, uint64_t n_loci, uint64_t *n_tie_loci,
                           double *ms_call) {
+    return inq_call_flush_device_flags(c, d_phase1, d_phase2, cap, index, n_loci, n_tie_loci, ms_call, nullptr);
+}
+
+int inq_call_flush_device_flags(inq_ctx_t *c, double *d_phase1, double *d_phase2, uint64_t cap, const uint32_t *index, uint64_t n_loci,
+                                uint64_t *n_tie_loci, double *ms_call, uint8_t *locus_flags) {
     try {
         inq_result_t r;
         std::memset(&r, 0, sizeof r);
         const FlushToDevice dev{d_phase1, d_phase2, index, cap};
-        const int rc = call_flush_impl(c, &r, n_loci, ms_call, &dev);
+        const int rc = call_flush_impl(c, &r, n_loci, ms_call, &dev, locus_flags);
         if (n_tie_loci) *n_tie_loci = r.n_tie_loci;
         return rc;
     } catch (const std::bad_alloc &) {

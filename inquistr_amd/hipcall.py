@@ -70,6 +70,10 @@ ABI_SYMBOLS = (
     "inq_call_discard",
     "inq_span_fetch_batch",
     "inq_outlier_rows",
+    "inq_call_batch_flags",
+    "inq_call_batch_device_flags",
+    "inq_call_flush_flags",
+    "inq_call_flush_device_flags",
 )
 
 
@@ -203,6 +207,10 @@ def load(path: Optional[str] = None):
     L.inq_call_batch.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC)]
     L.inq_call_batch_device.restype = C.c_int
     L.inq_call_batch_device.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp]
+    L.inq_call_batch_flags.restype = C.c_int
+    L.inq_call_batch_flags.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp]
+    L.inq_call_batch_device_flags.restype = C.c_int
+    L.inq_call_batch_device_flags.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp, vp]
     L.inq_ctx_status.restype = C.c_int
     L.inq_ctx_status.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.inq_ctx_timing_enable.restype = C.c_int
@@ -247,6 +255,10 @@ def load(path: Optional[str] = None):
     L.inq_call_span_deferred.argtypes = [vp, C.POINTER(SpanC), C.c_int, C.POINTER(SpanStatsC)]
     L.inq_call_flush.restype = C.c_int
     L.inq_call_flush.argtypes = [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double)]
+    L.inq_call_flush_flags.restype = C.c_int
+    L.inq_call_flush_flags.argtypes = [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double), vp]
+    L.inq_call_flush_device_flags.restype = C.c_int
+    L.inq_call_flush_device_flags.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double), vp]
     L.inq_call_deferred_loci.restype = C.c_uint64
     L.inq_call_deferred_loci.argtypes = [vp]
     L.inq_call_discard.restype = None
@@ -328,6 +340,17 @@ class Context:
         if rc != INQ_OK and check:
             self._raise(rc)
         return rc, res
+
+    def call_batch_flags(self, batch: Batch, debug: bool = False, check: bool = True) -> Tuple[int, Result, np.ndarray]:
+        """inq_call_batch_flags: (code, Result, per-locus flags as uint8 [n_loci], INQ_LOCUS_TIE where a locus is tie-ambiguous)."""
+        res = Result.alloc(batch, debug=debug)
+        flags = np.full(max(batch.n_loci, 1), 0xFF, dtype=np.uint8)  # (0xFF: a byte the call did not write shows)
+        bc, rc_ = batch.as_c(), res.as_c()
+        rc = self._L.inq_call_batch_flags(self._h, C.byref(bc), C.byref(rc_), flags.ctypes.data)
+        res.n_tie_loci = int(rc_.n_tie_loci)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        return rc, res, flags[: batch.n_loci]
 
     def call_batch_device(self, bc: InqBatchC, rc_: InqResultC, stream: Optional[int] = None) -> None:
         """Device-resident entry: pointers in bc / rc_ are device pointers; enqueue only."""
@@ -439,6 +462,19 @@ class Context:
         if rc != INQ_OK and check:
             self._raise(rc)
         return rc, p1, p2, int(res.n_tie_loci), float(ms.value)
+
+    def call_flush_flags(self, check: bool = True):
+        """inq_call_flush_flags: as call_flush, plus the per-locus flags (uint8, append order) as a sixth element."""
+        n = self.deferred_loci
+        p1 = np.full(n, np.nan)
+        p2 = np.full(n, np.nan)
+        flags = np.full(max(n, 1), 0xFF, dtype=np.uint8)
+        res = InqResultC(p1.ctypes.data, p2.ctypes.data, None, None, 0)
+        ms = C.c_double(0.0)
+        rc = self._L.inq_call_flush_flags(self._h, C.byref(res), n, C.byref(ms), flags.ctypes.data)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        return rc, p1, p2, int(res.n_tie_loci), float(ms.value), flags[:n]
 
     def span_fetch_batch(self, stats: "SpanStatsC", n_loci: int):
         """The batch the last call_span built on the device, as host arrays (cigar, reads, pair_read, locus_pair_off)."""

@@ -10,6 +10,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -258,6 +259,23 @@ struct SessionHooks {
     // rows stay on the device (inq_run_rows_device): row of target k of the call -> dev_p1[k], dev_p2[k]
     double *dev_p1 = nullptr, *dev_p2 = nullptr;
     uint64_t dev_cap = 0;
+    // the tie report (inq_call_args_t::ties_path): per-target flags (INQ_LOCUS_TIE) of target k of the call -> ties_out[k] (null: not
+    // collected, the locus kernels run without flags); ties_fd >= 0: a text call writes the report there, in the .inq's row order
+    uint8_t *ties_out = nullptr;
+    int ties_fd = -1;
+};
+
+// the tie report's file: opened (created / truncated) before any device work, closed with the call
+struct TiesFile {
+    int fd = -1;
+    TiesFile() = default;
+    TiesFile(const TiesFile &) = delete;
+    TiesFile &operator=(const TiesFile &) = delete;
+    ~TiesFile() {
+        if (fd >= 0) ::close(fd);
+    }
+    // path may be null (no report): INQ_EXIT_OK; a path that cannot be opened: INQ_EXIT_ERROR and a message that names it
+    int open(const char *path, std::string &msg);
 };
 
 // rows instead of text: the targets named by idx[] (positions in the parsed target list) are called, their rows go to p1 / p2
@@ -279,18 +297,25 @@ int run_device_front(const inq_call_args_t *args, const CallView &V, AsyncCtx &a
                      char *errbuf, size_t errcap, double *t_front, double *t_dev, const SessionHooks &hooks = SessionHooks());
 int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, int out_fd, char *errbuf, size_t errcap, const RowsOut &rows,
                       std::chrono::steady_clock::time_point t_start, const SessionHooks &hooks = SessionHooks());
+// ties / ties_fd (may be null / < 0): the tie report of the same rows goes to ties_fd, in the same order
 int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, const std::string &sample, const double *p1, const double *p2,
-               int out_fd, char *errbuf, size_t errcap);
+               int out_fd, char *errbuf, size_t errcap, const uint8_t *ties = nullptr, int ties_fd = -1);
+// the order of the .inq's rows: BED order for -t 1, (human_compare(chrom), start) for -t >= 2 (src/call.rs:33-38,141)
+std::vector<uint32_t> row_order(uint64_t threads, const std::vector<RepeatInterval> &targets);
+// the tie report: `chrom\tbegin\tend\n` for every target order[k] with a flag set
+int write_ties(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const uint8_t *ties, int fd, char *errbuf,
+               size_t errcap);
 int partition_prepared(Prepared &P, uint64_t world, uint32_t *order, uint64_t *cuts);
 
 struct OwnedArgs {
     inq_call_args_t a;
-    std::string bam, region, region_file, sample_name, reference;
+    std::string bam, region, region_file, sample_name, reference, ties_path;
     explicit OwnedArgs(const inq_call_args_t &src) : a(src) {
         auto own = [](const char *&p, std::string &keep) {
             if (p) keep = p, p = keep.c_str();
         };
         own(a.bam, bam), own(a.region, region), own(a.region_file, region_file), own(a.sample_name, sample_name), own(a.reference, reference);
+        own(a.ties_path, ties_path);
     }
     OwnedArgs(const OwnedArgs &) = delete;
 };

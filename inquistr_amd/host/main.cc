@@ -29,6 +29,7 @@ static void usage(FILE *f) {
         "      --device <N>                 HIP device ordinal [default: 0]\n"
         "      --devices <N,N,...>          several HIP devices: the loci are split among them by BAM bytes, same output\n"
         "      --ctx-option <KEY=VALUE>     a device-context option (include/inquistr_hip.h, inq_ctx_set_option), repeatable\n"
+        "      --ties <FILE>                write the loci whose unphased split is tie-ambiguous there, as BED (empty when phased)\n"
         "  -h, --help                       Print help\n",
         f);
 }
@@ -109,6 +110,7 @@ int main(int argc, char **argv) {
         base.minlen = 5, base.support = 3, base.threads = 1;
         std::string out_dir, combined;
         std::vector<std::string> bams;
+        bool ties = false;  // --ties: <out-dir>/<sample>.ties.bed next to each .inq
         for (int i = 2; i < argc; ++i) {
             const std::string k = argv[i];
             auto val = [&]() -> const char * {
@@ -127,26 +129,28 @@ int main(int argc, char **argv) {
             else if (k == "--device") base.device = (int32_t)std::strtol(val(), nullptr, 10);
             else if (k == "-o" || k == "--out-dir") out_dir = val();
             else if (k == "--combined") combined = val();
+            else if (k == "--ties") ties = true;
             else if (k.size() > 1 && k[0] == '-') {
                 std::fprintf(stderr, "error: unexpected argument '%s' found\n", k.c_str());
                 return 2;
             } else bams.push_back(k);
         }
         if (bams.empty() || out_dir.empty()) {
-            std::fputs("Usage: inquistr cohort [-r REGION | -R BED] [-m N] [-s N] [-t N] [-u] [--device N] --out-dir DIR [--combined FILE] <BAM>...\n", stderr);
+            std::fputs("Usage: inquistr cohort [-r REGION | -R BED] [-m N] [-s N] [-t N] [-u] [--device N] [--ties] --out-dir DIR [--combined FILE] <BAM>...\n", stderr);
             return 2;
         }
         ::setenv("INQ_FAST_EXIT", "1", 0);
         inq_session_t *S = nullptr;
         if (inq::host_api().session_open(base.device, &S) != 0) return 1;
         std::vector<inq_call_args_t> args(bams.size(), base);
-        std::vector<std::string> outs(bams.size());
+        std::vector<std::string> outs(bams.size()), ties_paths(bams.size());
         std::vector<int> fds(bams.size(), -1), st(bams.size(), 0);
         for (size_t k = 0; k < bams.size(); ++k) {
             args[k].bam = bams[k].c_str();
             char name[4096];
             inq::host_api().host_sample_name(bams[k].c_str(), name, sizeof name);
             outs[k] = out_dir + "/" + name + ".inq";
+            if (ties) ties_paths[k] = out_dir + "/" + name + ".ties.bed", args[k].ties_path = ties_paths[k].c_str();
             fds[k] = ::open(outs[k].c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
             if (fds[k] < 0) {
                 std::fprintf(stderr, "cannot write %s\n", outs[k].c_str());
@@ -263,6 +267,7 @@ int main(int argc, char **argv) {
         else if (key == "--sample-name" || key == "--sample_name") a.sample_name = val();
         else if (key == "--reference") a.reference = val();
         else if (key == "--device") a.device = (int32_t)num(val(), "--device");
+        else if (key == "--ties") a.ties_path = val();
         else if (key == "--devices") {
             const std::string list = val();
             for (size_t b = 0; b <= list.size();) {

@@ -88,6 +88,12 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
             return INQ_EXIT_ERROR;
         }
     const auto t_start = std::chrono::steady_clock::now();
+    std::string msg;
+    TiesFile tf;
+    if (tf.open(args->ties_path, msg) != INQ_EXIT_OK) {
+        set_err(errbuf, errcap, msg);
+        return INQ_EXIT_ERROR;
+    }
     // every device's runtime context starts now, each on its own thread, while the BAM header, the index and the BED are read
     std::vector<std::unique_ptr<AsyncCtx>> actx(n_devices);
     for (size_t r = 0; r < n_devices; ++r) {
@@ -95,13 +101,14 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
         actx[r]->start(device_ids[r], (int)n_devices);
     }
     Prepared P;
-    std::string msg;
     int rc = prepare(args, P, msg);
     if (rc != INQ_EXIT_OK) {
         set_err(errbuf, errcap, msg);
         return rc;
     }
     std::vector<PartStats> pst(n_devices);
+    // the tie report: each part's flags are scattered like its rows (the parts' target sets are disjoint)
+    std::vector<uint8_t> ties(tf.fd >= 0 ? P.targets.size() : 0, 0);
     std::vector<double> p1, p2, part_s;
     std::vector<uint32_t> order;
     std::vector<uint64_t> cuts;
@@ -113,8 +120,13 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
         ro.idx = idx, ro.n = n, ro.p1 = a, ro.p2 = b, ro.active = true;
         SessionHooks hooks;
         hooks.sharers = (int)n_devices, hooks.share_index = (int)r, hooks.stats = &pst[r];
+        std::vector<uint8_t> part_ties(tf.fd >= 0 ? n : 0, 0);
+        if (tf.fd >= 0) hooks.ties_out = part_ties.data();
         // (the runtime threads of this part prefer the NUMA node of ITS device: genotype_prepared's helpers bind per thread)
-        return genotype_prepared(&oa.a, *actx[r], P, -1, err, cap, ro, t_start, hooks);
+        const int prc = genotype_prepared(&oa.a, *actx[r], P, -1, err, cap, ro, t_start, hooks);
+        if (prc == INQ_EXIT_OK && tf.fd >= 0)
+            for (uint64_t k = 0; k < n; ++k) ties[idx[k]] = part_ties[k];
+        return prc;
     };
     rc = run_parts(P, n_devices, fn, p1, p2, order, cuts, &part_rc, &part_s, errbuf, errcap);
     if (stats)
@@ -130,7 +142,7 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
             o.front = pst[r].front, o.io_threads = pst[r].io_threads;
         }
     if (rc != INQ_EXIT_OK) return rc;
-    return write_rows(args->threads, P.targets, P.sample, p1.data(), p2.data(), out_fd, errbuf, errcap);
+    return write_rows(args->threads, P.targets, P.sample, p1.data(), p2.data(), out_fd, errbuf, errcap, tf.fd >= 0 ? ties.data() : nullptr, tf.fd);
 }
 
 int inq_genotype_repeats_devices(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, inq_part_stats_t *stats,

@@ -89,6 +89,14 @@ int prepare(const inq_call_args_t *a, Prepared &P, std::string &msg, BedCache *b
     return INQ_EXIT_OK;
 }
 
+int TiesFile::open(const char *path, std::string &msg) {
+    if (!path) return INQ_EXIT_OK;
+    fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+    if (fd >= 0) return INQ_EXIT_OK;
+    msg = std::string("cannot write the tie report ") + path + ": " + std::strerror(errno);
+    return INQ_EXIT_ERROR;
+}
+
 bool write_all(int fd, const char *data, size_t len) {
     size_t off = 0;
     while (off < len) {
@@ -121,13 +129,19 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
                      (uint32_t)std::min<uint64_t>(args->support, 0xffffffffull), args->unphased != 0};
     const size_t n = V.targets.size();
     std::vector<double> p1(n, NAN), p2(n, NAN);
+    // the tie report: per-target flags, collected only when someone asked for them (the locus kernels run without flags otherwise)
+    const bool want_ties = hooks.ties_out || hooks.ties_fd >= 0;
+    std::vector<uint8_t> ties(want_ties ? n : 0, 0);
     const bool rows_on_device = rows.active && rows.d1 && rows.d2;
     if (rows_on_device && rows.dcap < n) {
         set_err(errbuf, errcap, "device row arrays smaller than the target list");
         return INQ_EXIT_ERROR;
     }
     auto emit = [&]() -> int {
-        if (!rows.active) return write_rows(args->threads, V.targets, V.sample, p1.data(), p2.data(), out_fd, errbuf, errcap);
+        if (!rows.active)
+            return write_rows(args->threads, V.targets, V.sample, p1.data(), p2.data(), out_fd, errbuf, errcap, want_ties ? ties.data() : nullptr,
+                              hooks.ties_fd);
+        if (hooks.ties_out && n) std::memcpy(hooks.ties_out, ties.data(), n);
         if (rows_on_device) return INQ_EXIT_OK;  // (device front end: they are there; host sweep: written below)
         if (n) std::memcpy(rows.p1, p1.data(), n * sizeof(double)), std::memcpy(rows.p2, p2.data(), n * sizeof(double));
         return INQ_EXIT_OK;
@@ -148,6 +162,7 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
         SessionHooks dh = hooks;
         dh.stats = ps;
         if (rows_on_device) dh.dev_p1 = rows.d1, dh.dev_p2 = rows.d2, dh.dev_cap = rows.dcap;
+        dh.ties_out = want_ties ? ties.data() : nullptr;  // (indexed like p1 / p2)
         int drc = run_device_front(args, V, actx, p1, p2, errbuf, errcap, &t_front, &t_dev, dh);
         if (drc != INQ_EXIT_OK) return drc;
         const auto t_run = clk::now();
@@ -198,6 +213,7 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
     ParallelFrontEnd pfe(args->bam, V.bam, V.targets, V.unphased, n_workers);
     auto t_ctx = clk::now();
     std::vector<double> b1, b2;
+    std::vector<uint8_t> bt;
     for (;;) {
         ParallelFrontEnd::Item item;
         std::string ferr;
@@ -239,12 +255,13 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
         }
         b1.assign(batch.n_loci, NAN);
         b2.assign(batch.n_loci, NAN);
+        if (want_ties) bt.assign(batch.n_loci, 0);
         inq_result_t res;
         std::memset(&res, 0, sizeof res);
         res.phase1 = b1.data();
         res.phase2 = b2.data();
         auto tc = clk::now();
-        int rc2 = inq_call_batch(ctx, &batch, &res);
+        int rc2 = want_ties ? inq_call_batch_flags(ctx, &batch, &res, bt.data()) : inq_call_batch(ctx, &batch, &res);
         t_dev += secs(tb, clk::now());
         if (timing && std::getenv("INQ_TIMING")[0] == '2')
             std::fprintf(stderr, "[inq batch] loci %llu pairs %llu cigar %.1f MB  wait-ctx %.2f ms  call %.2f ms\n",
@@ -261,6 +278,8 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
             p1[item.index[j]] = b1[j];
             p2[item.index[j]] = b2[j];
         }
+        if (want_ties)
+            for (uint64_t j = 0; j < batch.n_loci; ++j) ties[item.index[j]] = bt[j];
         pfe.recycle(std::move(item));
     }
     if (!need_ctx()) return INQ_EXIT_ERROR;  // no GPU is an error even for an empty target list
@@ -297,11 +316,8 @@ PartStats last_stats() {
     return g_last_stats;
 }
 
-int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, const std::string &sample, const double *p1,
-                      const double *p2, int out_fd, char *errbuf, size_t errcap) {
+std::vector<uint32_t> row_order(uint64_t threads, const std::vector<RepeatInterval> &targets) {
     const size_t n = targets.size();
-    const bool timing = std::getenv("INQ_TIMING") != nullptr;
-    const auto t_w0 = std::chrono::steady_clock::now();
     std::vector<uint32_t> order(n);
     for (size_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
     if (threads > 1) {
@@ -347,6 +363,30 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
             }
         }
     }
+    return order;
+}
+
+int write_ties(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const uint8_t *ties, int fd, char *errbuf,
+               size_t errcap) {
+    std::string text;
+    for (const uint32_t i : order)
+        if (ties[i] & INQ_LOCUS_TIE) {
+            const RepeatInterval &t = targets[i];
+            text += t.chrom + '\t' + std::to_string(t.start) + '\t' + std::to_string(t.end) + '\n';
+        }
+    if (!write_all(fd, text)) {
+        set_err(errbuf, errcap, "Failed writing the tie report.");
+        return INQ_EXIT_ERROR;
+    }
+    return INQ_EXIT_OK;
+}
+
+int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, const std::string &sample, const double *p1,
+                      const double *p2, int out_fd, char *errbuf, size_t errcap, const uint8_t *ties, int ties_fd) {
+    const size_t n = targets.size();
+    const bool timing = std::getenv("INQ_TIMING") != nullptr;
+    const auto t_w0 = std::chrono::steady_clock::now();
+    const std::vector<uint32_t> order = row_order(threads, targets);
     const auto t_w1 = std::chrono::steady_clock::now();
     // the text: rows formatted by a few threads into their own stretches of one buffer (sized from an upper bound per row,
     // written through a bare pointer: no per-character capacity checks), written in order.  Four threads at most: 500 000
@@ -396,6 +436,10 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
     if (!wrote) {
         set_err(errbuf, errcap, "Failed writing the result.");
         return INQ_EXIT_PANIC;
+    }
+    if (ties && ties_fd >= 0) {  // the tie report, in the rows' order
+        const int trc = write_ties(order, targets, ties, ties_fd, errbuf, errcap);
+        if (trc != INQ_EXIT_OK) return trc;
     }
     if (timing) {
         auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -496,16 +540,23 @@ void inq_frontend_close(inq_frontend_t *fe) { delete fe; }
 
 static int inq_genotype_repeats_impl(const inq_call_args_t *args, int out_fd, char *errbuf, size_t errcap, const RowsOut &rows = RowsOut()) {
     const auto t_start = std::chrono::steady_clock::now();
+    std::string msg;
+    TiesFile tf;  // (a call that returns rows writes no file)
+    if (args && !rows.active && tf.open(args->ties_path, msg) != INQ_EXIT_OK) {
+        set_err(errbuf, errcap, msg);
+        return INQ_EXIT_ERROR;
+    }
     AsyncCtx actx;
     if (args) actx.start(args->device);
     Prepared P;
-    std::string msg;
     int rc = prepare(args, P, msg);
     if (rc != INQ_EXIT_OK) {
         set_err(errbuf, errcap, msg);
         return rc;
     }
-    return genotype_prepared(args, actx, P, out_fd, errbuf, errcap, rows, t_start);
+    SessionHooks hooks;
+    hooks.ties_fd = tf.fd;
+    return genotype_prepared(args, actx, P, out_fd, errbuf, errcap, rows, t_start, hooks);
 }
 
 int inq_frontend_open(const inq_call_args_t *args, inq_frontend_t **out, char *errbuf, size_t errcap) {
@@ -636,6 +687,9 @@ struct inq_run {
     inq_session *sess = nullptr;
     double *d1 = nullptr, *d2 = nullptr;
     uint64_t dcap = 0;
+    // the tie flags of the last rows call (collected when the run was opened with ties_path set)
+    std::vector<uint8_t> ties;
+    bool have_ties = false;
     AsyncCtx *ctx_of_rows() { return sess ? &sess->actx : actx.get(); }
     ~inq_run() {
         AsyncCtx *c = ctx_of_rows();
@@ -694,17 +748,22 @@ static int inq_run_rows_impl(inq_run_t *r, const uint32_t *target_index, uint64_
     const auto t_start = std::chrono::steady_clock::now();
     RowsOut ro;
     ro.idx = target_index, ro.n = n_index, ro.p1 = phase1, ro.p2 = phase2, ro.active = true;
+    SessionHooks hooks;
+    r->have_ties = false;
+    if (r->args->a.ties_path) r->ties.assign(n_index, 0), hooks.ties_out = r->ties.data();
     if (r->sess) {  // the session's context and span buffers: nothing is made or torn down per call
-        SessionHooks hooks;
         hooks.pool = &r->sess->pool;
         const bool keep_leak = r->sess->actx.leak;
         const int rc = genotype_prepared(&r->args->a, r->sess->actx, r->P, -1, errbuf, errcap, ro, t_start, hooks);
         r->sess->actx.leak = keep_leak;  // the context belongs to the session
+        r->have_ties = rc == INQ_EXIT_OK && hooks.ties_out;
         return rc;
     }
     AsyncCtx actx;
     actx.start(r->args->a.device);
-    return genotype_prepared(&r->args->a, actx, r->P, -1, errbuf, errcap, ro, t_start);
+    const int rc = genotype_prepared(&r->args->a, actx, r->P, -1, errbuf, errcap, ro, t_start, hooks);
+    r->have_ties = rc == INQ_EXIT_OK && hooks.ties_out;
+    return rc;
 }
 int inq_run_rows(inq_run_t *r, const uint32_t *target_index, uint64_t n_index, double *phase1, double *phase2, char *errbuf, size_t errcap) {
     INQ_GUARD(inq_run_rows_impl(r, target_index, n_index, phase1, phase2, errbuf, errcap), errbuf, errcap)
@@ -740,10 +799,13 @@ static int inq_run_rows_device_impl(inq_run_t *r, const uint32_t *target_index, 
     ro.idx = target_index, ro.n = n_index, ro.active = true, ro.d1 = r->d1, ro.d2 = r->d2, ro.dcap = r->dcap;
     SessionHooks hooks;
     if (r->sess) hooks.pool = &r->sess->pool;
+    r->have_ties = false;
+    if (r->args->a.ties_path) r->ties.assign(n_index, 0), hooks.ties_out = r->ties.data();
     const bool keep_leak = actx.leak;
     const int rc = genotype_prepared(&r->args->a, actx, r->P, -1, errbuf, errcap, ro, t_start, hooks);
     actx.leak = keep_leak;  // the context belongs to the run (or its session)
     if (rc != INQ_EXIT_OK) return rc;
+    r->have_ties = hooks.ties_out != nullptr;
     *d_phase1 = r->d1, *d_phase2 = r->d2;
     return INQ_EXIT_OK;
 }
@@ -757,6 +819,18 @@ int inq_run_write_inq(inq_run_t *r, const double *phase1, const double *phase2, 
         return INQ_EXIT_ERROR;
     }
     INQ_GUARD(write_rows(r->args->a.threads, r->P.targets, r->P.sample, phase1, phase2, out_fd, errbuf, errcap), errbuf, errcap)
+}
+int inq_run_tie_flags(const inq_run_t *r, uint8_t *flags, uint64_t n) {
+    if (!r || !r->have_ties || n != r->ties.size() || (n && !flags)) return INQ_EXIT_ERROR;
+    if (n) std::memcpy(flags, r->ties.data(), n);
+    return INQ_EXIT_OK;
+}
+int inq_run_write_ties(inq_run_t *r, const uint8_t *flags, uint64_t n_rows, int fd, char *errbuf, size_t errcap) {
+    if (!r || n_rows != r->P.targets.size() || (n_rows && !flags)) {
+        set_err(errbuf, errcap, "flag count does not match the target list");
+        return INQ_EXIT_ERROR;
+    }
+    INQ_GUARD(write_ties(row_order(r->args->a.threads, r->P.targets), r->P.targets, flags, fd, errbuf, errcap), errbuf, errcap)
 }
 void inq_run_close(inq_run_t *r) { delete r; }
 

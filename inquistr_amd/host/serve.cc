@@ -267,8 +267,8 @@ int serve_main(const char *socket_path, int device, double idle_exit_s) {
                 Reader rd{body.data(), body.data() + body.size()};
                 inq_call_args_t a;
                 std::memset(&a, 0, sizeof a);
-                std::string s[5];
-                bool have[5] = {false, false, false, false, false};
+                std::string s[6];
+                bool have[6] = {false, false, false, false, false, false};
                 if (!bad) {
                     a.minlen = rd.get<uint32_t>();
                     a.support = rd.get<uint64_t>();
@@ -276,6 +276,7 @@ int serve_main(const char *socket_path, int device, double idle_exit_s) {
                     a.unphased = rd.get<char>() ? 1 : 0;
                     a.device = device;  // the context this server holds
                     for (int k = 0; k < 5 && rd.ok; ++k) rd.str(s[k], have[k]);
+                    if (rd.ok && rd.p < rd.e) rd.str(s[5], have[5]);  // --ties: sent only when given
                     bad = !rd.ok || !have[0];
                 }
                 if (bad) {
@@ -289,6 +290,7 @@ int serve_main(const char *socket_path, int device, double idle_exit_s) {
                 a.region_file = have[2] ? s[2].c_str() : nullptr;
                 a.sample_name = have[3] ? s[3].c_str() : nullptr;
                 a.reference = have[4] ? s[4].c_str() : nullptr;
+                a.ties_path = have[5] ? s[5].c_str() : nullptr;
                 {   // at most one file staged ahead of the one that runs: wait until the runner has taken the one before
                     std::unique_lock<std::mutex> lk(mu);
                     cv.wait(lk, [&] { return box == nullptr; });
@@ -377,6 +379,8 @@ int client_call(const char *socket_path, const inq_call_args_t *a, int out_fd, i
     // the sample name the caller's own path gives (the server sees the absolute one: same file stem, src/call.rs:91-100)
     put_str(body, a->sample_name);
     put_str(body, a->reference ? ref.c_str() : nullptr);
+    const std::string ties = absolute(a->ties_path);
+    if (a->ties_path) put_str(body, ties.c_str());  // (the server opens it: a path relative to the caller's directory would be wrong there)
     if (!send_header(sock, kMagicCall, (uint32_t)body.size(), out_fd)) {  // nothing has reached the server: the caller may do the call itself
         ::close(sock);
         return 0;

@@ -16,6 +16,7 @@ struct StagedFile {
     int rc = INQ_EXIT_OK;
     std::string msg;
     std::unique_ptr<SpanPipeline> pipe;
+    std::unique_ptr<TiesFile> ties;  // the tie report (args->ties_path), opened when the file is staged
     int slot_base = 0, front = 0;
     std::chrono::steady_clock::time_point t_start;
 };
@@ -25,6 +26,9 @@ void stage_file(inq_session *S, const inq_call_args_t *a, int slot_base, StagedF
     try {
         out.args.reset(new OwnedArgs(*a));
         out.slot_base = slot_base;
+        out.ties.reset(new TiesFile());
+        out.rc = out.ties->open(out.args->a.ties_path, out.msg);
+        if (out.rc != INQ_EXIT_OK) return;
         out.rc = prepare(&out.args->a, out.P, out.msg, &S->bed_cache);
         if (out.rc != INQ_EXIT_OK) return;
         out.front = use_device_front(&out.args->a, *out.P.bam, out.P.targets) ? 2 : 1;
@@ -45,6 +49,7 @@ int run_staged(inq_session *S, StagedFile &f, int out_fd, char *errbuf, size_t e
     hooks.pool = &S->pool;
     hooks.slot_base = f.slot_base;
     hooks.front = f.front;
+    hooks.ties_fd = f.ties ? f.ties->fd : -1;
     const bool keep_leak = S->actx.leak;
     int rc = genotype_prepared(&f.args->a, S->actx, f.P, out_fd, errbuf, errcap, RowsOut(), f.t_start, hooks);
     S->actx.leak = keep_leak;  // the context belongs to the session, whatever the single-call path decided

@@ -480,6 +480,7 @@ int run_device_front(const inq_call_args_t *args, const CallView &V, AsyncCtx &a
     inq_ctx_t *&ctx = actx.ctx;
     int &hrc = actx.hrc;
     std::vector<double> b1, b2;
+    std::vector<uint8_t> bt;  // the tie flags of a flush (hooks.ties_out set)
     {
         // the CLI sets INQ_FAST_EXIT: it is about to leave the process, so the span buffers (unmapping a GB
         // of touched pages takes ~0.1 s) and the device context are left to the operating system
@@ -519,9 +520,12 @@ int run_device_front(const inq_call_args_t *args, const CallView &V, AsyncCtx &a
             res.phase1 = b1.data();
             res.phase2 = b2.data();
             double ms_call = 0;
+            uint8_t *flags = nullptr;
+            if (hooks.ties_out) bt.assign(pending.size(), 0), flags = bt.data();
             // (rows that travel on from device memory stay there: pending[j] is the row's place in the caller's device arrays)
-            int rc2 = hooks.dev_p1 ? inq_call_flush_device(ctx, hooks.dev_p1, hooks.dev_p2, hooks.dev_cap, pending.data(), pending.size(), nullptr, &ms_call)
-                                   : inq_call_flush(ctx, &res, pending.size(), &ms_call);
+            int rc2 = hooks.dev_p1 ? inq_call_flush_device_flags(ctx, hooks.dev_p1, hooks.dev_p2, hooks.dev_cap, pending.data(), pending.size(), nullptr,
+                                                                 &ms_call, flags)
+                                   : inq_call_flush_flags(ctx, &res, pending.size(), &ms_call, flags);
             *t_dev += secs(f0, clk::now());
             if (timing == 2)
                 std::fprintf(stderr, "[inq call] @%.1f %zu loci, %.1f MB of CIGARs: locus kernels %.3f ms | wall %.2f ms\n", stamp_ms(), pending.size(),
@@ -537,6 +541,8 @@ int run_device_front(const inq_call_args_t *args, const CallView &V, AsyncCtx &a
                     p1[pending[j]] = b1[j];
                     p2[pending[j]] = b2[j];
                 }
+            if (flags)
+                for (size_t j = 0; j < pending.size(); ++j) hooks.ties_out[pending[j]] = bt[j];
             pending.clear();
             pending_words = 0;
             return INQ_EXIT_OK;
