@@ -71,8 +71,15 @@ typedef struct inq_read {
     uint8_t mapq;
     uint8_t bits;        /* INQ_READ_* */
     uint8_t phase;       /* HP value truncated to u8; meaningful iff INQ_READ_HAS_HP          */
-    uint8_t reserved;    /* must be 0                                                         */
+    uint8_t promise;     /* INQ_READ_CHECKED or 0 (see below)                                 */
 } inq_read_t;
+
+/* promise: INQ_READ_CHECKED says that the producer of the descriptor has checked the domain rules of this read:
+ * every op code is <= 8, pos >= -1 and pos + 1 + reference span < 2^31.  The device then reads the CIGAR of such a
+ * read only as far as the locus window needs (up to the op after which pos + consumed >= end + 10) and does not
+ * look for INQ_ERR_CIGAR_OP / INQ_ERR_RANGE in the rest.  A false promise leaves domain errors in the unread tail
+ * unreported; results for valid reads are the same either way.  0 = no promise: every op is read and checked. */
+#define INQ_READ_CHECKED 0x01u
 
 #define INQ_READ_UNMAPPED 0x01u /* BAM flag 0x4   */
 #define INQ_READ_REVERSE 0x02u  /* BAM flag 0x10  */

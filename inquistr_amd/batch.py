@@ -37,6 +37,8 @@ INQ_READ_REVERSE = 0x02
 INQ_READ_HAS_HP = 0x04
 INQ_READ_IS_2D = 0x08
 INQ_READ_SA_PANIC = 0x10  # has an S op and is_accidental_2d would panic: raised for kept reads only
+# inq_read_t.promise: the producer has checked op codes <= 8, pos >= -1 and pos + 1 + span < 2^31 (include/inquistr_hip.h)
+INQ_READ_CHECKED = 0x01
 
 INQ_PAIR_CLIP = 0x01
 INQ_PAIR_FETCHED = 0x02
@@ -50,7 +52,7 @@ READ_DTYPE = np.dtype(
         ("mapq", "u1"),
         ("bits", "u1"),
         ("phase", "u1"),
-        ("reserved", "u1"),
+        ("promise", "u1"),  # INQ_READ_CHECKED or 0
     ]
 )
 assert READ_DTYPE.itemsize == 16

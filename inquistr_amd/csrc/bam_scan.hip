@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void record_parse_kernel(ScanArgs a) {
     rd.mapq = (uint8_t)mapq;
     rd.bits = 0;
     rd.phase = 0;
-    rd.reserved = 0;
+    rd.promise = 0;
     RecInfo ri;
     ri.cigar_src = x + 4 + off_cigar;
     ri.sa_off = 0;
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256) void cigar_gather_kernel(ScanArgs a, uint64_t 
     uint32_t *dst = a.cigar + unit0 * 4u;
     // the extent was checked against the record for the in-record CIGAR; the CG payload by aux_size()
     int64_t rlen = 0;
-    uint32_t clip = 0;
+    uint32_t clip = 0, bad_op = 0;
     // four operations (16 bytes) per lane and step: the source lies wherever the record does, the destination is 16-byte aligned
     for (uint32_t k = lane * 4u; k < n4; k += 256u) {
         uint32_t w[4];
@@ -311,13 +311,17 @@ __global__ __launch_bounds__(256) void cigar_gather_kernel(ScanArgs a, uint64_t 
             const uint32_t op = w[j] & 0xfu;
             if ((0x18Du >> op) & 1u) rlen += (int64_t)(w[j] >> 4);  // M D N = X consume the reference
             clip |= op == 4u;
+            bad_op |= op > 8u;
         }
     }
     for (int off = 32; off; off >>= 1) {
         rlen += __shfl_xor(rlen, off);
         clip |= __shfl_xor(clip, off);
+        bad_op |= __shfl_xor(bad_op, off);
     }
     if (lane == 0) {
+        // the domain rules the locus kernel would otherwise check over the whole CIGAR (inq_read_t.promise)
+        if (!bad_op && rd.pos >= -1 && (int64_t)rd.pos + 1 + rlen < ((int64_t)1 << 31)) rd.promise = INQ_READ_CHECKED;
         if ((rd.bits & INQ_READ_UNMAPPED) || rlen == 0) rlen = 1;  // [3P] bam_endpos
         const int64_t endpos = (int64_t)rd.pos + rlen;
         a.endkey[i] = (a.key[i] & ~0xffffffffll) + (endpos + 1);

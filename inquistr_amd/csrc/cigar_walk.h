@@ -6,6 +6,8 @@
 //   read filters             src/call.rs:297-302 (unphased), 349-355 (phased)
 //   fetch() overlap rule     src/call.rs:288,338   ([3P] htslib iterator)
 // Both CIGAR walks of the reference are fused into ONE pass over the packed ops.
+// Two walks share that pass: walk_pairs_whole (every op of every read, below) and walk_pairs_rows (reads whose
+// producer set INQ_READ_CHECKED, only as far as the window needs); walk_pairs picks one per block of reads.
 //
 // Data path (per wave):
 //   * ops stream in as 256-op chunks: one buffer_load_dwordx4 per lane (16 B/lane, 1 KiB per wave
@@ -64,6 +66,7 @@ struct WaveLds {
     QueueEntry q[kQueueCap];
     unsigned long long acc[64];  // per read slot: the Call value (two's complement)
     unsigned int flags[64];      // per read slot: bit0 = a soft clip was counted
+    unsigned int endc[64];       // per read slot: reference_position after the last op walked (walk_pairs_rows)
 };
 
 // Per-lane descriptor of the pair this lane "owns" inside a block of <= 64 pairs.
@@ -182,10 +185,52 @@ __device__ __forceinline__ void drain_queue(WaveLds &L, uint32_t &qcount, const 
     __builtin_amdgcn_wave_barrier();
 }
 
-// Walks the reads of pairs [0, cnt) described by `m` (lane k owns pair k).  On return lane k holds
-// the pair's Call (src/call.rs:67-71) in `val` and PM_CLIP | PM_FETCHED | PM_KEPT | group in `meta`.
+// Per-read epilogue, one read per lane: lane k < cnt turns read k's walk (end_carry = reference_position after
+// the last op walked, the LDS accumulators) into the pair's Call and meta bits.
+template <bool UNPHASED>
+__device__ __forceinline__ void read_epilogue(const PairMeta &m, bool valid, int cnt, const Window &W, int lane,
+                                              uint32_t end_carry, uint32_t &status, WaveLds &L, int64_t &val,
+                                              uint32_t &meta) {
+    val = 0;
+    meta = 0;
+    if (lane < cnt && valid) {
+        const uint32_t pos = m.pos;
+        const uint32_t mapq = m.misc & 0xffu, bits = (m.misc >> 8) & 0xffu, phase = (m.misc >> 16) & 0xffu;
+        // [3P] bam_endpos: rlen = unmapped ? 0 : sum(ref-consuming); rlen == 0 -> 1
+        uint32_t rlen = end_carry - (pos + 1u);
+        if ((bits & RB_UNMAPPED) || rlen == 0u) rlen = 1u;
+        const uint32_t rend = pos + rlen;  // reference_end() as u32
+        // fetch(): pos < end_ext && endpos > start_ext (signed pos, pos >= -1 inside the domain)
+        const bool fetched = ((int32_t)pos < 0 || pos < W.ee) && rend > W.se;
+        bool skip;
+        if (UNPHASED)
+            skip = W.se < pos || rend < W.ee || mapq <= 10u;  // src/call.rs:297-302
+        else
+            skip = !(bits & RB_HAS_HP) || (W.se < pos && rend < W.ee) || mapq <= 10u;  // :349-355
+        const bool kept = fetched && !skip;
+        uint32_t grp = 0u;
+        bool bad_phase = false;
+        if (!UNPHASED && kept) {
+            if (phase > 2u)
+                bad_phase = true;  // calls.get_mut(&phase).unwrap() panics, src/call.rs:358
+            else
+                grp = phase;
+        }
+        if (bad_phase) status |= ST_PHASE;
+        // is_accidental_2d panics on this read's SA, but the reference only calls it from call_from_cigar,
+        // i.e. for reads that passed the filter (src/call.rs:303,357 -> :394)
+        if (kept && (bits & RB_SA_PANIC)) status |= ST_AUX;
+        val = (int64_t)L.acc[lane];
+        meta = ((L.flags[lane] & 1u) ? PM_CLIP : 0u) | (fetched ? PM_FETCHED : 0u) | (kept ? PM_KEPT : 0u) |
+               (grp << PM_GRP_SHIFT);
+    }
+}
+
+// Walks the WHOLE CIGAR of the reads of pairs [0, cnt) described by `m` (lane k owns pair k), the whole
+// wave on one read at a time.  On return lane k holds the pair's Call (src/call.rs:67-71) in `val` and
+// PM_CLIP | PM_FETCHED | PM_KEPT | group in `meta`.
 template <bool UNPHASED, int AUX>
-__device__ __forceinline__ void walk_pairs(const BatchView &b, const PairMeta &m, bool valid, int cnt,
+__device__ __forceinline__ void walk_pairs_whole(const BatchView &b, const PairMeta &m, bool valid, int cnt,
                                            const Window &W, int lane, uint32_t &status, WaveLds &L, int64_t &val,
                                            uint32_t &meta) {
     L.acc[lane] = 0ull;
@@ -291,40 +336,197 @@ __device__ __forceinline__ void walk_pairs(const BatchView &b, const PairMeta &m
     if (ballot64((lane_bad & 1u) != 0u)) status |= ST_CIGAR_OP;  // rust-htslib cigar() would panic
     if (ballot64((lane_range >> 31) != 0u)) status |= ST_RANGE;
 
-    // ---- per-read epilogue, one read per lane ----
-    val = 0;
-    meta = 0;
-    if (lane < cnt && valid) {
-        const uint32_t pos = m.pos;
-        const uint32_t mapq = m.misc & 0xffu, bits = (m.misc >> 8) & 0xffu, phase = (m.misc >> 16) & 0xffu;
-        // [3P] bam_endpos: rlen = unmapped ? 0 : sum(ref-consuming); rlen == 0 -> 1
-        uint32_t rlen = end_carry - (pos + 1u);
-        if ((bits & RB_UNMAPPED) || rlen == 0u) rlen = 1u;
-        const uint32_t rend = pos + rlen;  // reference_end() as u32
-        // fetch(): pos < end_ext && endpos > start_ext (signed pos, pos >= -1 inside the domain)
-        const bool fetched = ((int32_t)pos < 0 || pos < W.ee) && rend > W.se;
-        bool skip;
-        if (UNPHASED)
-            skip = W.se < pos || rend < W.ee || mapq <= 10u;  // src/call.rs:297-302
-        else
-            skip = !(bits & RB_HAS_HP) || (W.se < pos && rend < W.ee) || mapq <= 10u;  // :349-355
-        const bool kept = fetched && !skip;
-        uint32_t grp = 0u;
-        bool bad_phase = false;
-        if (!UNPHASED && kept) {
-            if (phase > 2u)
-                bad_phase = true;  // calls.get_mut(&phase).unwrap() panics, src/call.rs:358
-            else
-                grp = phase;
+    read_epilogue<UNPHASED>(m, valid, cnt, W, lane, end_carry, status, L, val, meta);
+}
+
+// ---- window-bounded walk ---------------------------------------------------------------------------------
+// A read whose descriptor carries INQ_READ_CHECKED (inq_read_t.promise, bits 24-31 of the uint4's .w) has had
+// the domain rules checked by its producer: op codes <= 8, pos >= -1, pos + 1 + reference span < 2^31.  Its
+// CIGAR is then only needed up to the window: no op that starts at or past end_ext counts (reference positions
+// never decrease), and a lower bound of bam_endpos that is already >= end_ext settles the fetch rule and both
+// filters (rend > start_ext, rend < end_ext) exactly as the true value does.
+//
+// Shape: the wave is 4 rows of kRowLanes = 16 lanes; a row walks one read in pieces of 64 ops (one
+// buffer_load_dwordx4 per lane: 256 contiguous bytes per row).  Four load slots per wave, as in the
+// whole walk, but every row of a slot is a read stream of its own: when a piece has been scanned the row loads
+// either its read's next piece or - the read done - piece 0 of the block's next read, so nothing is loaded past
+// the point where a read stops.  A checked read stops after the piece that takes carry = pos + 1 + consumed
+// past end_ext (carry > end_ext <=> pos + consumed >= end_ext, without the u32 wrap of pos = -1); an unchecked
+// one is walked to its end, with the device's own domain checks.
+constexpr uint32_t RP_CHECKED = 1u;  // INQ_READ_CHECKED
+
+constexpr int kRowLanes = 16;  // lanes of one row = one read stream = one DPP row
+
+// Inclusive prefix sum inside each row: the first four DPP steps of wave_inclusive_scan_u32.
+__device__ __forceinline__ uint32_t row_inclusive_scan_u32(uint32_t x) {
+    x += dpp_shr_zero<DPP_ROW_SHR1>(x);
+    x += dpp_shr_zero<DPP_ROW_SHR2>(x);
+    x += dpp_shr_zero<DPP_ROW_SHR4>(x);
+    x += dpp_shr_zero<DPP_ROW_SHR8>(x);
+    return x;
+}
+// Lane 15 of each row to every lane of the row: ds_swizzle in bit-mask mode reads lane
+// ((l & 0x10) | 0x0f) of its 32-lane half.
+__device__ __forceinline__ uint32_t row_last(uint32_t x) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, 0x10 | (0x0f << 5)); }
+
+// One read stream: the same value in every lane of a row.
+struct RowStream {
+    uint32_t cur4;   // the next 16-byte group of the read this row loads (the piece's first)
+    uint32_t carry;  // (reference_start + 1) + reference span of the ops walked so far, u32
+    uint32_t st;     // groups left << RS_LEFT | RS_LIVE | RS_STOP | is_2d << 6 | read slot; 0 = idle
+};
+constexpr uint32_t RS_STOP = 128u, RS_LIVE = 256u;
+constexpr int RS_LEFT = 9;
+// st holds at most 2^23 - 1 groups left: a read of kRowMaxGroups groups or more (n_cigar > 2^25 - 4) sends its block to
+// the whole walk
+constexpr uint32_t kRowMaxGroups = 1u << (32 - RS_LEFT);
+__host__ __device__ constexpr uint32_t cigar_groups(uint32_t nc) { return (nc + 3u) >> 2; }
+static_assert(cigar_groups((1u << 25) - 4u) == kRowMaxGroups - 1u && cigar_groups((1u << 25) - 3u) == kRowMaxGroups,
+              "the longest read the row walk takes is 2^25 - 4 ops");
+
+// Same contract as walk_pairs_whole.  Needs a window that does not wrap (end_ext >= start_ext + 1) and a batch
+// CIGAR under 4 GiB (one buffer descriptor over all of it; 32-bit byte offsets).
+template <bool UNPHASED, int AUX>
+__device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMeta &m, bool valid, int cnt,
+                                                const Window &W, int lane, uint32_t &status, WaveLds &L, int64_t &val,
+                                                uint32_t &meta) {
+    L.acc[lane] = 0ull;
+    L.flags[lane] = 0u;
+    uint32_t qcount = 0;
+    uint32_t lane_err = 0;  // bit 0: an op code 9..15 was seen, bit 1: a reference position reached 2^31
+    const int rl = lane & (kRowLanes - 1);
+    const uint64_t row_heads = 0x0001000100010001ull;  // lane 0 of each row
+    // out-of-range offsets (past num_records) load 0 = `0M`: lanes past a read's end and idle rows
+    const __amdgpu_buffer_rsrc_t rsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void *)b.cigar4, (short)0, (int)(uint32_t)(b.n_cigar4 * 16u), 0x00020000);
+
+    int next = 0;  // wave-uniform: the first read of the block no row has taken yet
+    // rows whose stream is idle take the next reads, in row order; a read with nothing to load is settled here
+    auto claim = [&](RowStream &S) {
+        for (;;) {
+            const bool idle = S.st == 0u;
+            const uint64_t need = ballot64(idle) & row_heads;
+            if (need == 0ull || next >= cnt) return;
+            // idle rows below this one: the set bits of `need` in lower lanes, less this row's own head
+            const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+            const int k = next + below - ((idle && rl != 0) ? 1 : 0);
+            next += (int)__popcll(need);
+            const int src = min(k, 63) << 2;
+            // what a row needs of read k besides off4 and pos, from lane k: groups | is_2d << 30 | checked << 31
+            const uint32_t d_w = (((m.nc & 0x0fffffffu) + 3u) >> 2) | ((m.nc >> 31) << 30) |
+                                 ((((m.misc >> 24) & RP_CHECKED) != 0u) ? 0x80000000u : 0u);
+            const uint32_t r_off4 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)m.off4);
+            const uint32_t r_w = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)d_w);
+            const uint32_t r_pos = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)m.pos);
+            if (idle && k < cnt) {
+                S.cur4 = r_off4;
+                S.carry = r_pos + 1u;  // (reference_start + 1) as u32, src/call.rs:380
+                lane_err |= (S.carry >> 31) << 1;
+                S.st = ((r_w & 0x3fffffffu) << RS_LEFT) | (uint32_t)k | (((r_w >> 30) & 1u) << 6) |
+                       ((r_w >> 31) ? RS_STOP : 0u) | RS_LIVE;
+                // an empty CIGAR, or a checked read that starts past the window: nothing to load
+                if ((S.st >> RS_LEFT) == 0u || ((S.st & RS_STOP) && S.carry > W.ee)) {
+                    if (rl == 0) L.endc[k] = S.carry;
+                    S.st = 0u;
+                }
+            }
         }
-        if (bad_phase) status |= ST_PHASE;
-        // is_accidental_2d panics on this read's SA, but the reference only calls it from call_from_cigar,
-        // i.e. for reads that passed the filter (src/call.rs:303,357 -> :394)
-        if (kept && (bits & RB_SA_PANIC)) status |= ST_AUX;
-        val = (int64_t)L.acc[lane];
-        meta = ((L.flags[lane] & 1u) ? PM_CLIP : 0u) | (fetched ? PM_FETCHED : 0u) | (kept ? PM_KEPT : 0u) |
-               (grp << PM_GRP_SHIFT);
+    };
+    auto issue = [&](const RowStream &S) -> u32x4 {
+        const uint32_t voff = (uint32_t)rl < (S.st >> RS_LEFT) ? (S.cur4 + (uint32_t)rl) * 16u : 0xfffffff0u;
+        return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, AUX);
+    };
+    auto step = [&](const u32x4 w, RowStream &S) {
+        const bool live = S.st != 0u;
+        const uint32_t e1 = ref_advance_raw(w.x);
+        const uint32_t e2 = e1 + ref_advance_raw(w.y);
+        const uint32_t e3 = e2 + ref_advance_raw(w.z);
+        const uint32_t tot = e3 + ref_advance_raw(w.w);
+        const uint32_t incl = row_inclusive_scan_u32(tot);
+        const uint32_t rtot = row_last(incl);
+        if (live) {
+            lane_err |= ((kBadOp32 >> (w.x & 31u)) | (kBadOp32 >> (w.y & 31u)) | (kBadOp32 >> (w.z & 31u)) |
+                         (kBadOp32 >> (w.w & 31u))) & 1u;
+            lane_err |= ((S.carry + incl) >> 31) << 1;
+        }
+        // the window-lane test of walk_pairs_whole, per row
+        const uint32_t x = (S.carry - W.se1) + incl;
+        const bool inw = live && x < W.width + tot;
+        const uint64_t mask = ballot64(inw);
+        if (mask) {
+            QueueEntry *const tail = &L.q[qcount];  // wave-uniform
+            if (inw) {
+                const uint32_t idx = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+                tail[idx].w = w;
+                tail[idx].info = make_uint2(x - tot, S.st & 127u);
+            }
+            qcount += (uint32_t)__popcll(mask);
+            if (qcount > 64u) drain_queue(L, qcount, W, lane);
+        }
+        S.carry += rtot;
+        S.cur4 += (uint32_t)kRowLanes;
+        if (live) {
+            if ((S.st >> RS_LEFT) <= (uint32_t)kRowLanes || ((S.st & RS_STOP) && S.carry > W.ee)) {
+                if (rl == 0) L.endc[S.st & 63u] = S.carry;
+                S.st = 0u;
+            } else {
+                S.st -= (uint32_t)kRowLanes << RS_LEFT;
+            }
+        }
+    };
+
+    RowStream sa{0u, 0u, 0u}, sb = sa, sc = sa, sd = sa;
+    claim(sa);
+    u32x4 qa = issue(sa);
+    claim(sb);
+    u32x4 qb = issue(sb);
+    claim(sc);
+    u32x4 qc = issue(sc);
+    claim(sd);
+    u32x4 qd = issue(sd);
+    // four named buffers, one load per slot and round whether its rows are live or not: each step waits only
+    // for its own load (vmcnt(3)); an idle slot's load is out of range everywhere and moves no bytes
+    while (ballot64((sa.st | sb.st | sc.st | sd.st) != 0u)) {
+        if (ballot64(sa.st != 0u)) {
+            step(qa, sa);
+            claim(sa);
+        }
+        qa = issue(sa);
+        if (ballot64(sb.st != 0u)) {
+            step(qb, sb);
+            claim(sb);
+        }
+        qb = issue(sb);
+        if (ballot64(sc.st != 0u)) {
+            step(qc, sc);
+            claim(sc);
+        }
+        qc = issue(sc);
+        if (ballot64(sd.st != 0u)) {
+            step(qd, sd);
+            claim(sd);
+        }
+        qd = issue(sd);
     }
+    if (qcount) drain_queue(L, qcount, W, lane);
+    if (ballot64((lane_err & 1u) != 0u)) status |= ST_CIGAR_OP;  // rust-htslib cigar() would panic
+    if (ballot64((lane_err & 2u) != 0u)) status |= ST_RANGE;
+    __builtin_amdgcn_wave_barrier();
+    read_epilogue<UNPHASED>(m, valid, cnt, W, lane, L.endc[lane], status, L, val, meta);
+}
+
+// The walk of pairs [0, cnt): window-bounded when some read of the block carries the producer's promise,
+// the window does not wrap and the batch's CIGAR fits one buffer descriptor; the whole walk otherwise.
+template <bool UNPHASED, int AUX>
+__device__ __forceinline__ void walk_pairs(const BatchView &b, const PairMeta &m, bool valid, int cnt,
+                                           const Window &W, int lane, uint32_t &status, WaveLds &L, int64_t &val,
+                                           uint32_t &meta) {
+    const bool checked = lane < cnt && valid && ((m.misc >> 24) & RP_CHECKED) != 0u;
+    const bool too_long = lane < cnt && valid && cigar_groups(m.nc & 0x0fffffffu) >= kRowMaxGroups;
+    if (ballot64(checked) != 0ull && ballot64(too_long) == 0ull && W.ee >= W.se1 && b.n_cigar4 < (1ull << 28))
+        walk_pairs_rows<UNPHASED, AUX>(b, m, valid, cnt, W, lane, status, L, val, meta);
+    else
+        walk_pairs_whole<UNPHASED, AUX>(b, m, valid, cnt, W, lane, status, L, val, meta);
 }
 
 }  // namespace inq

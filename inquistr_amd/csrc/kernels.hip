@@ -433,8 +433,9 @@ __device__ __forceinline__ void walk_part(const KArgs &a, MidLds &lds, const uin
 // the deeper ones walked into the scratch - and reduced there and then up to kReduceInPlace reads; the reduce of the rest is
 // locus_call_tail (deep_select.hip).  The lists are mostly empty: a launch that finds them so costs its launch and nothing else -
 // round 4 had two launches here (and ~36 more behind them).
+// (waves_per_eu 5: the window-bounded walk's streams would otherwise take the kernel from 96 to 98 VGPRs, one wave per SIMD fewer)
 template <bool UNPHASED, int AUX>
-__global__ __launch_bounds__(256) void locus_call_mid_walk(KArgs a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void locus_call_mid_walk(KArgs a) {
     __shared__ MidLds lds;
     __shared__ uint32_t cnt[kListKinds][kListShards];  // the three lists' lengths, read once (an idle launch is these 96 loads)
     const int lane = threadIdx.x & 63;

@@ -107,6 +107,15 @@ int FrontEnd::add_read(const BamRec &r, bool has_clip, std::string *err, bool *p
     rd.mapq = r.mapq;
     rd.bits = bits;
     rd.phase = phase;
+    // the domain rules the device would otherwise check over the whole CIGAR (inq_read_t.promise)
+    int64_t span = 0;
+    bool bad_op = false;
+    for (uint32_t k = 0; k < r.n_cigar; ++k) {
+        const uint32_t op = r.cigar[k] & 0xfu;
+        bad_op |= op > 8u;
+        if ((0x18Du >> op) & 1u) span += r.cigar[k] >> 4;  // M D N = X consume the reference
+    }
+    if (!bad_op && r.pos >= -1 && (int64_t)r.pos + 1 + span < ((int64_t)1 << 31)) rd.promise = INQ_READ_CHECKED;
     cig_.insert(cig_.end(), r.cigar, r.cigar + r.n_cigar);
     while (cig_.size() & 3) cig_.push_back(0u);  // 0M padding to the next 16-byte boundary
     reads_.push_back(rd);

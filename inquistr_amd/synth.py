@@ -217,7 +217,9 @@ def _gen_chunk(xp, wl: Workload, g0: int, g1: int, off4_base: int):
     padded = t < (4 * n4)[:, None]
     cigar = xp.select(word, padded)
     bits = 4  # INQ_READ_HAS_HP
-    misc = 60 + (bits << 8) + ((1 + (kk & 1)) << 16)
+    # promise byte = INQ_READ_CHECKED: every op written above is M, I, D or S, pos >= 0, and pos + 1 + span stays
+    # below 2.01e8 (start <= 200 030 063, at most 2400 ops of <= 200 reference bases each), far inside 2^31
+    misc = 60 + (bits << 8) + ((1 + (kk & 1)) << 16) + (1 << 24)
     reads4 = xp.stack4(off4[:-1] + off4_base, n_ops, pos, misc)
     return {
         "cigar": cigar,
@@ -257,6 +259,7 @@ def generate_numpy(wl: Workload, lo: int = 0, hi: int = None) -> Batch:
     reads["mapq"] = r4[:, 3] & 0xFF
     reads["bits"] = (r4[:, 3] >> 8) & 0xFF
     reads["phase"] = (r4[:, 3] >> 16) & 0xFF
+    reads["promise"] = (r4[:, 3] >> 24) & 0xFF
     return Batch(
         cigar=np.concatenate(cig) if cig else np.zeros(0, dtype=np.uint32),
         reads=reads,
