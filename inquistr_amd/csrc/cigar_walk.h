@@ -44,9 +44,23 @@ struct Window {
     uint32_t se;     // start_ext = start - 10            (src/call.rs:285,335)
     uint32_t ee;     // end_ext   = end + 10              (src/call.rs:286,336)
     uint32_t se1;    // se + 1
-    uint32_t width;  // ee - se1: an op at refpos counts iff (refpos - se1) <u width  ==  se < refpos < ee
+    uint32_t width;  // ee - se1: an op at refpos counts iff (refpos - se1) <u width  ==  se < refpos < ee; 0 when ee < se1
     uint32_t minlen;
 };
+
+// The window of a locus.  end + 10 may pass 2^32 and wrap, as it does in the reference's release build
+// (src/call.rs:286,336); then end_ext < start_ext and `start_ext < refpos && refpos < end_ext` (:387-403) holds
+// for no position at all.  ee - se1 would instead describe the positions from start_ext + 1 round to end_ext - 1,
+// 0 .. end + 9 - 2^32 among them, so a wrapped window gets width 0: no op counts.
+__device__ __forceinline__ Window make_window(uint32_t start, uint32_t end, uint32_t minlen) {
+    Window W;
+    W.se = start - 10u;
+    W.ee = end + 10u;
+    W.se1 = W.se + 1u;
+    W.width = W.ee >= W.se1 ? W.ee - W.se1 : 0u;
+    W.minlen = minlen;
+    return W;
+}
 
 struct BatchView {
     const uint4 *cigar4;  // packed ops viewed as 16-byte groups

@@ -221,12 +221,7 @@ __device__ __forceinline__ void reduce_locus_in_lanes(const int64_t (&val)[E], c
 template <bool UNPHASED, int AUX, int E>
 __device__ __forceinline__ void wave_locus(const KArgs &a, uint64_t j, uint64_t p0, int n, uint32_t start, uint32_t end,
                                            int lane, WaveLds &L) {
-    Window W;
-    W.se = start - 10u;
-    W.ee = end + 10u;
-    W.se1 = W.se + 1u;
-    W.width = W.ee - W.se1;
-    W.minlen = a.minlen;
+    const Window W = make_window(start, end, a.minlen);
     BatchView b{a.cigar4, a.reads, a.pair_read, a.n_reads, a.n_cigar4};
     uint32_t status = 0;
     int64_t val[E];
@@ -340,12 +335,7 @@ __device__ __forceinline__ void walk_locus(const KArgs &a, const BatchView &b, u
                                            uint32_t wave, WaveLds &L) {
     const uint32_t bstep = 4u * n_wg;  // blocks between two of this wave's
     const uint32_t start = a.locus_start[j], end = a.locus_end[j];
-    Window W;
-    W.se = start - 10u;
-    W.ee = end + 10u;
-    W.se1 = W.se + 1u;
-    W.width = W.ee - W.se1;
-    W.minlen = a.minlen;
+    const Window W = make_window(start, end, a.minlen);
     uint32_t status = 0;
     const uint32_t nblk = (n + kBigBlock - 1) / kBigBlock;
     auto blk_cnt = [&](uint32_t blk) { return blk < nblk ? (int)min((uint32_t)kBigBlock, n - blk * kBigBlock) : 0; };

@@ -202,3 +202,270 @@ def mixed_depth_case(seed: int, case_index: int = 0):
         sh = rng.choice([-10, 0, 0, 10])  # (windows shifted against each other: not every locus sees the same Calls)
         bb.add_locus(start + sh, end + sh, [ids[k] for k in order[off : off + d]])
     return bb.build(), depths
+
+
+# ---- promise variants -------------------------------------------------------------------------------------------
+# Which reads of a batch carry the producer promise (inq_read_t.promise = INQ_READ_CHECKED) decides which walk a
+# block of 64 pairs takes (csrc/cigar_walk.h walk_pairs) and, inside the row walk, which reads stop at the window.
+# The oracle never reads the byte, so one oracle result serves every variant of a batch.
+
+PROMISE_VARIANTS = ("none", "all", "half", "lone_promise", "lone_unpromised")
+DEEP_PROMISE_VARIANTS = ("none", "all", "half")  # for batches whose every call is expensive
+
+
+def checked_share(batch: Batch) -> float:
+    """Share of the batch's reads that `mark_checked` promises (1.0 when the batch is empty)."""
+    from inquistr_amd.window_bytes import checked_mask
+
+    return float(checked_mask(batch).mean()) if batch.n_reads else 1.0
+
+
+def _blocks(batch: Batch):
+    """Per pair: the index of its block (up to 64 consecutive pairs of one locus); per block: its first pair, its size."""
+    off = batch.locus_pair_off.astype(np.int64)
+    assert off[0] == 0 and off[-1] == batch.n_pairs and (np.diff(off) >= 0).all(), "set the variant before damaging the layout"
+    n = np.diff(off)
+    nblk = (n + 63) // 64
+    blk0 = np.concatenate([[0], np.cumsum(nblk)])
+    locus = np.repeat(np.arange(batch.n_loci, dtype=np.int64), n)
+    k = np.arange(batch.n_pairs, dtype=np.int64) - off[locus]
+    block = blk0[locus] + k // 64
+    first = np.repeat(off[:-1], nblk) + 64 * (np.arange(int(blk0[-1]), dtype=np.int64) - np.repeat(blk0[:-1], nblk))
+    size = np.minimum(64, np.repeat(off[1:], nblk) - first)
+    return block, first, size
+
+
+def set_promise(batch: Batch, variant: str, seed: int = 0) -> str:
+    """Rewrites batch.reads["promise"] in place to one of PROMISE_VARIANTS and returns a name for messages and ids.
+
+    Every variant is `mark_checked(batch)` AND a mask, so no variant makes a false promise:
+      none             nothing promised (what BatchBuilder leaves)
+      all              every read whose domain rules hold
+      half             a seeded Bernoulli(0.5) draw per read
+      lone_promise     one read of every 64-pair block, the rest of the block unpromised (where loci share reads a read
+                       is promised if any block chose it: at least one per block, not exactly one)
+      lone_unpromised  the converse
+    For half and lone_* the draw is repeated (seed, seed + 1, ...) until some block holds both kinds, whenever a block
+    with two distinct promisable reads exists; the function asserts that, and the per-block rule of lone_*."""
+    from inquistr_amd.batch import INQ_READ_CHECKED
+    from inquistr_amd.window_bytes import checked_mask
+
+    assert variant in PROMISE_VARIANTS, variant
+    name = f"promise={variant}"
+    if batch.n_reads == 0:
+        return name
+    ok = checked_mask(batch)
+
+    def store(mask):
+        batch.reads["promise"] = np.where(ok & mask, INQ_READ_CHECKED, 0).astype(np.uint8)
+        assert not (batch.reads["promise"].astype(bool) & ~ok).any(), "a variant never sets a false promise"
+        return name
+
+    if variant == "none":
+        return store(np.zeros(batch.n_reads, dtype=bool))
+    if variant == "all":
+        return store(np.ones(batch.n_reads, dtype=bool))
+    if batch.n_pairs == 0:
+        return store(np.zeros(batch.n_reads, dtype=bool))
+    block, first, size = _blocks(batch)
+    n_blocks = int(first.shape[0])
+    r = batch.pair_read.astype(np.int64)
+    assert (r < batch.n_reads).all(), "set the variant before damaging the layout"
+    good = ok[r]  # per pair: its read may be promised
+    # per block: the smallest and the largest promisable read index (two distinct ones <=> they differ)
+    lo = np.full(n_blocks, batch.n_reads, dtype=np.int64)
+    hi = np.full(n_blocks, -1, dtype=np.int64)
+    np.minimum.at(lo, block[good], r[good])
+    np.maximum.at(hi, block[good], r[good])
+    has_good = hi >= 0
+    can_mix = bool((hi > lo).any())
+
+    def per_block_counts(mask):
+        promised = np.bincount(block, weights=(good & mask[r]).astype(np.float64), minlength=n_blocks)
+        unpromised = np.bincount(block, weights=(good & ~mask[r]).astype(np.float64), minlength=n_blocks)
+        return promised, unpromised
+
+    for attempt in range(64):
+        rng = np.random.default_rng([seed + attempt, PROMISE_VARIANTS.index(variant)])
+        if variant == "half":
+            mask = rng.random(batch.n_reads) < 0.5
+        else:
+            # one promisable pair of every block that has one: the u-th of its promisable pairs
+            gcount = np.bincount(block, weights=good.astype(np.float64), minlength=n_blocks).astype(np.int64)
+            pick_rank = (rng.random(n_blocks) * np.maximum(gcount, 1)).astype(np.int64)
+            rank = np.cumsum(good) - 1  # rank of a promisable pair among all promisable pairs
+            base = np.concatenate([[0], np.cumsum(gcount)])[:-1]
+            chosen_pair = np.nonzero(good & (rank - base[block] == pick_rank[block]))[0]
+            assert chosen_pair.shape[0] == int(has_good.sum())
+            chosen = np.zeros(batch.n_reads, dtype=bool)
+            chosen[r[chosen_pair]] = True
+            mask = chosen if variant == "lone_promise" else ~chosen
+        promised, unpromised = per_block_counts(mask)
+        if not can_mix or bool(((promised > 0) & (unpromised > 0)).any()):
+            break
+    else:
+        raise AssertionError(f"{name}: no block holds both kinds after 64 draws")
+    if variant == "lone_promise":
+        assert (promised[has_good] >= 1).all(), "every block with a promisable read holds a promised one"
+    if variant == "lone_unpromised":
+        assert (unpromised[has_good] >= 1).all(), "every block with a promisable read holds an unpromised one"
+    return store(mask)
+
+
+def promise_variants(batch: Batch, variants=PROMISE_VARIANTS, seed: int = 0):
+    """Sets each variant in turn on the same batch and yields its name."""
+    for v in variants:
+        yield set_promise(batch, v, seed)
+
+
+# ---- cases shaped after the row walk (csrc/cigar_walk.h walk_pairs_rows) -------------------------------------------
+# The dimensions are the kernel's: pairs per locus around the tiers of the locus kernels, ops per read around the
+# 64-op piece and the "at most 16 groups left" test, the piece in which a promised read passes end_ext, window widths
+# that make the lane queue drain many times, runs of reads claim() settles without a load.
+
+ROW_DEPTHS_SMALL = (1, 2, 3, 4, 5, 16, 17, 63, 64)  # one wave, one block
+ROW_DEPTHS_MID = (65, 128, 129, 256, 257, 300)  # wave_locus<4>; walk_locus with the in-place reduce
+ROW_DEPTHS_DEEP = (2048, 2049)  # walk_locus: the last in-place reduce, the first into the tail kernel
+ROW_OPS = (0, 1, 3, 4, 5, 60, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1000, 5000)
+ROW_WIDTHS = (0, 1, 100, 5_000, 40_000)
+ROW_STOP_PIECES = (0, 1, 2, 5, 9)
+_CONSUMES = np.zeros(16, dtype=bool)
+_CONSUMES[[0, 2, 3, 7, 8]] = True
+
+
+def _short_ops(rng, n, max_m):
+    """n ops: M runs of 1 .. max_m bases alternating with short I / D / S ops (lengths on both sides of every minlen in use)."""
+    op = np.where(np.arange(n) % 2 == 0, 0, rng.choice([1, 1, 2, 2, 4], size=n))
+    ln = np.where(op == 0, rng.integers(1, max_m + 1, size=n), rng.choice([1, 2, 3, 4, 9, 13, 14], size=n))
+    return op.astype(np.int64), ln.astype(np.int64)
+
+
+def _span(op, ln):
+    return int(ln[_CONSUMES[op]].sum())
+
+
+def row_walk_case(seed: int, unphased: bool = None, max_depth: int = None):
+    """One batch around a main window (end_ext = ee) plus shifted and narrow windows over the same reads.
+    Returns (Batch, info); info["per_locus"] holds pyoracle Records per locus when the case is small enough for the
+    Python oracle, else None; info["depths"], info["width"], info["stop_pieces"], info["settled_runs"] describe the draw."""
+    rng = np.random.default_rng([seed, 20260])
+    if unphased is None:
+        unphased = bool(seed & 1)
+    minlen = (0, 2, 12)[seed % 3]
+    support = (1, 3)[(seed // 3) % 2]
+    width = ROW_WIDTHS[seed % 5]
+    start = 200_000 + int(rng.integers(0, 1000))
+    end = start + width
+    se, ee = start - 10, end + 10
+    bb = BatchBuilder(minlen=minlen, support=support, unphased=unphased)
+    attrs = []  # per read: (pos, flag, hp, sa, mapq) for the Python oracle
+    stop_pieces = set()
+
+    def add(pos, op, ln, settled=False):
+        words = ((ln << 4) | op).astype(np.uint32)
+        reverse, unmapped = bool(rng.random() < 0.3), bool(rng.random() < 0.03)
+        mapq = int(rng.choice([5, 60, 60, 60]))
+        phase = [None, 0, 1, 1, 2, 2][int(rng.integers(0, 6))]
+        twod = bool(rng.random() < 0.2)
+        sa = None
+        if twod:  # one supplementary alignment on the other strand over the read's own start: is_accidental_2d
+            sa = ("Z", f"chr7,{pos},{'+' if reverse else '-'},{max(1, _span(op, ln))}M,60,0;")
+        attrs.append((pos, (0x10 if reverse else 0) | (0x4 if unmapped else 0), None if phase is None else ("C", phase), sa, mapq))
+        return bb.add_read(pos, words, mapq=mapq, phase=phase, reverse=reverse, unmapped=unmapped, is_2d=twod)
+
+    def edge_read():
+        """The first 64 * (P + 1) ops take pos + consumed to ee + d exactly: a promised read stops after piece P (d >= 0)
+        or one piece later (d < 0); with fewer ops than that, the stop and the read's end fall into the same piece."""
+        n = int(rng.choice(ROW_OPS))
+        op, ln = _short_ops(rng, n, 3)
+        p = min(int(rng.choice(ROW_STOP_PIECES)), max(0, (n - 1) // 64))
+        cut = min(n, 64 * (p + 1))
+        d = int(rng.choice([-2, -1, 0, 1]))
+        if n:
+            stop_pieces.add(p)
+        return add(ee + d - _span(op[:cut], ln[:cut]), op, ln)
+
+    def wide_read(n=None):
+        """1 - 30 bp M runs between short I / D / S ops, starting up to a third of its span left of the window."""
+        n = int(rng.choice(ROW_OPS)) if n is None else n
+        op, ln = _short_ops(rng, n, 30)
+        return add(se - int(rng.integers(0, max(1, _span(op, ln) // 3) + 1)), op, ln)
+
+    def any_op_read():
+        n = int(rng.choice(ROW_OPS))
+        op = rng.choice([0, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8], size=n).astype(np.int64)
+        ln = rng.integers(1, 61, size=n).astype(np.int64)
+        pos = se - int(rng.integers(0, 400)) if rng.random() < 0.7 else int(rng.integers(se, ee + 1))
+        return add(pos, op, ln)
+
+    def neg_read():
+        op, ln = _short_ops(rng, int(rng.choice([5, 64, 129, 1000])), 30)
+        op = np.concatenate([[0], op])
+        ln = np.concatenate([[se - int(rng.integers(0, 300))], ln])
+        return add(-1, op, ln)
+
+    first = wide_read(int(rng.choice([1, 5, 64, 257])))  # the read at cigar_off4 == 0
+    pool = [first]
+    for _ in range(40):
+        r = rng.random()
+        pool.append(edge_read() if r < 0.40 else wide_read() if r < 0.75 else any_op_read() if r < 0.93 else neg_read())
+    # reads claim() settles without a load: no CIGAR at all, or (promised) a start at or past end_ext of every window here;
+    # pos = ee - 1 (pos + 1 == end_ext of the main window) is the last start that is NOT settled
+    far = ee + 200
+    settled = [add(int(rng.integers(se - 50, far)), np.zeros(0, np.int64), np.zeros(0, np.int64)) for _ in range(2)]
+    for pos in (far, far + 1, far + 40_000):
+        op, ln = _short_ops(rng, int(rng.choice([1, 64, 200])), 30)
+        settled.append(add(pos, op, ln))
+    for pos in (ee - 1, ee, ee + 1):
+        op, ln = _short_ops(rng, int(rng.choice([3, 65, 129])), 30)
+        pool.append(add(pos, op, ln))
+    last = wide_read(int(rng.choice([1, 4, 63, 129])))  # its last group is the batch's last
+    pool.append(last)
+
+    depths = [int(x) for x in rng.choice(ROW_DEPTHS_SMALL, size=3)] + [ROW_DEPTHS_MID[seed % 6]]
+    depths.append(ROW_DEPTHS_DEEP[(seed // 4) % 2] if seed % 4 == 0 else int(rng.choice(ROW_DEPTHS_SMALL + ROW_DEPTHS_MID)))
+    if max_depth is not None:
+        depths = [d for d in depths if d <= max_depth]
+    windows = [(start, end), (start, end), (start - 25, end - 25), (start + 15, end + 15), (ee - 15, ee - 14)]
+    loci = []
+    settled_runs = []
+    for k, depth in enumerate(depths):
+        idx = [int(x) for x in rng.choice(pool, size=depth)]  # with replacement: a read may be offered twice to one locus
+        nblk = (depth + 63) // 64
+        b = int(rng.integers(0, nblk))
+        size = min(64, depth - 64 * b)
+        run = min(size, int(rng.choice([1, 2, 3, 4, 5, 8, 16, 33, 64])))
+        at = 64 * b + (0, (size - run) // 2, size - run)[int(rng.integers(0, 3))]
+        idx[at : at + run] = [int(x) for x in rng.choice(settled, size=run)]
+        settled_runs.append(run)
+        if depth >= 128 and rng.random() < 0.6:  # one block made only of them
+            b2 = (b + 1) % nblk
+            size2 = min(64, depth - 64 * b2)
+            idx[64 * b2 : 64 * b2 + size2] = [int(x) for x in rng.choice(settled, size=size2)]
+            settled_runs.append(size2)
+        loci.append((windows[k % len(windows)] if k else windows[0], idx))
+    loci.append((windows[0], [first, last, first]))
+    order = rng.permutation(len(loci))
+    per_locus_idx = []
+    for k in order:
+        (s, e), idx = loci[int(k)]
+        bb.add_locus(s, e, idx)
+        per_locus_idx.append(idx)
+    batch = bb.build()
+    assert batch.reads["cigar_off4"][first] == 0 and batch.reads["n_cigar"][first] > 0
+    assert int(batch.reads["cigar_off4"][last]) + (int(batch.reads["n_cigar"][last]) + 3) // 4 == batch.cigar.shape[0] // 4
+    info = {"depths": [len(x) for x in per_locus_idx], "width": width, "stop_pieces": stop_pieces, "settled_runs": settled_runs,
+            "per_locus": None}
+    # the Python oracle walks op by op, and looks at the SA entry (a second walk of the CIGAR) at every S op
+    n_ops = batch.reads["n_cigar"].astype(np.int64)
+    n_s = np.array([int(((batch.cigar[4 * int(o) : 4 * int(o) + int(n)] & 15) == 4).sum()) if attrs[i][3] else 0
+                    for i, (o, n) in enumerate(zip(batch.reads["cigar_off4"], n_ops))], dtype=np.int64)
+    r = batch.pair_read.astype(np.int64)
+    if int((n_ops[r] * (1 + n_s[r])).sum()) <= 400_000:
+        recs = {}
+        for i in set(int(x) for x in r):
+            w = batch.cigar[4 * int(batch.reads["cigar_off4"][i]) : 4 * int(batch.reads["cigar_off4"][i]) + int(n_ops[i])]
+            pos, flag, hp, sa, mapq = attrs[i]
+            recs[i] = py.Record(pos=pos, cigar=[(py.OPS[int(x) & 15], int(x) >> 4) for x in w], mapq=mapq, flag=flag, hp=hp, sa=sa)
+        info["per_locus"] = [[recs[i] for i in idx] for idx in per_locus_idx]
+    return batch, info

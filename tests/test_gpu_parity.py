@@ -36,6 +36,19 @@ def _assert_same(got, want, what=""):
     assert got.n_tie_loci == want.n_tie_loci, what
 
 
+def _other_variants(ctx, batch, want, what, variants=gen.PROMISE_VARIANTS, share=1.0):
+    """The batch has just been called as BatchBuilder leaves it (no read promised: the whole walk).  Calls it again under
+    every other promise variant of tests/gen.py - the window-bounded row walk - against the same oracle result; `share` is
+    the share of its reads the domain rules let a producer promise (1.0: `all` sends every block down the row walk)."""
+    assert not batch.reads["promise"].any()
+    assert gen.checked_share(batch) == share, what
+    for name in gen.promise_variants(batch, variants[1:]):
+        rc, got = ctx.call_batch(batch, debug=True)
+        assert rc == 0, f"{what} {name}"
+        _assert_same(got, want, f"{what} {name}")
+    gen.set_promise(batch, "none")
+
+
 def test_kat_loci(ctx, orc, kat):
     """The hand-derived locus vectors of tests/golden/kat_call.json, one batch per mode."""
     from oracle import pyoracle as py
@@ -65,7 +78,9 @@ def test_kat_loci(ctx, orc, kat):
                 want = [_num(x) for x in v["expect"]]
                 assert gen.same_f64(np.array([got.phase1[j], got.phase2[j]]), np.array(want)), v["name"]
             assert got.n_tie_loci == sum(1 for v in vs if v.get("tie"))
-            _assert_same(got, orc.call_batch(batch, debug=True)[1], mode)
+            want = orc.call_batch(batch, debug=True)[1]
+            _assert_same(got, want, mode)
+            _other_variants(ctx, batch, want, f"{mode} minlen={minlen} support={support}")
 
 
 def test_kat_call_from_cigar(ctx, kat):
@@ -85,12 +100,14 @@ def test_kat_call_from_cigar(ctx, kat):
                              is_2d=py.is_accidental_2d(rec))
             bb.add_locus(v["start"] + 10, v["end"] - 10, [ri])
         batch = bb.build()
-        rc, got = ctx.call_batch(batch, debug=True)
-        assert rc == 0
-        for j, v in enumerate(vs):
-            kind, val = v["expect"]
-            assert got.pair_call[j] == val, v["name"]
-            assert bool(got.pair_bits[j] & B.INQ_PAIR_CLIP) == (kind == "Clip"), v["name"]
+        assert gen.checked_share(batch) == 1.0
+        for what in gen.promise_variants(batch):
+            rc, got = ctx.call_batch(batch, debug=True)
+            assert rc == 0
+            for j, v in enumerate(vs):
+                kind, val = v["expect"]
+                assert got.pair_call[j] == val, (v["name"], what)
+                assert bool(got.pair_bits[j] & B.INQ_PAIR_CLIP) == (kind == "Clip"), (v["name"], what)
 
 
 @pytest.mark.parametrize("seed", range(48))
@@ -104,6 +121,7 @@ def test_random_vs_oracle(ctx, orc, seed, unphased):
     oc, want = orc.call_batch(batch, debug=True)
     assert rc == oc == 0
     _assert_same(got, want, f"seed={seed} unphased={unphased}")
+    _other_variants(ctx, batch, want, f"seed={seed} unphased={unphased}")
 
 
 @pytest.mark.parametrize("unphased", [False, True])
@@ -118,6 +136,7 @@ def test_deep_loci(ctx, orc, unphased, max_reads):
     oc, want = orc.call_batch(batch, debug=True)
     assert rc == oc == 0
     _assert_same(got, want, f"max_reads={max_reads}")
+    _other_variants(ctx, batch, want, f"max_reads={max_reads} unphased={unphased}")
 
 
 def test_clip_heavy_ties(ctx, orc):
@@ -148,6 +167,7 @@ def test_clip_heavy_ties(ctx, orc):
         if unphased:
             assert want.n_tie_loci > 0
         _assert_same(got, want, f"unphased={unphased}")
+        _other_variants(ctx, batch, want, f"clip heavy unphased={unphased}")
 
 
 @pytest.mark.parametrize("unphased", [False, True])
@@ -179,6 +199,7 @@ def test_huge_values(ctx, orc, unphased):
     assert rc == oc == 0
     assert np.abs(want.pair_call).max() > (1 << 32)
     _assert_same(got, want, f"huge unphased={unphased}")
+    _other_variants(ctx, batch, want, f"huge unphased={unphased}")
 
 
 @pytest.mark.parametrize("unphased", [False, True])
@@ -209,6 +230,7 @@ def test_wide_windows_fill_the_lane_queue(ctx, orc, unphased):
     assert rc == oc == 0
     assert (np.abs(want.pair_call) > 100).sum() > 10
     _assert_same(got, want, f"wide unphased={unphased}")
+    _other_variants(ctx, batch, want, f"wide unphased={unphased}")
 
 
 def test_empty_and_ragged(ctx, orc):
@@ -226,6 +248,11 @@ def test_empty_and_ragged(ctx, orc):
     assert rc == oc == 0
     _assert_same(got, want)
     assert np.isnan(got.phase1[0]) and np.isnan(got.phase2[0])
+    _other_variants(ctx, batch, want, "ragged")
+    empty = B.BatchBuilder().build()
+    for what in gen.promise_variants(empty):
+        rc, res = ctx.call_batch(empty)
+        assert rc == 0 and res.phase1.shape == (0,), what
 
 
 def test_long_cigars(ctx, orc):
@@ -245,6 +272,7 @@ def test_long_cigars(ctx, orc):
     oc, want = orc.call_batch(batch, debug=True)
     assert rc == oc == 0
     _assert_same(got, want)
+    _other_variants(ctx, batch, want, "long cigars")
 
 
 @pytest.mark.parametrize("unphased,support", [(False, 3), (True, 3), (False, 15_000), (True, 10_000)])
@@ -278,6 +306,15 @@ def test_one_locus_of_100000_reads(ctx, orc, unphased, support):
     _assert_same(got, want, f"100k reads unphased={unphased} support={support}")
     assert not np.isnan(got.phase2[1]), "the deep locus must yield a number for the test to mean anything"
     assert dt < 2.0, f"{dt:.2f} s for the host-buffer call (upload + kernels + download)"
+    # the same built batch under the promised variants (the row walk): exact; the time is printed, not bounded
+    assert gen.checked_share(batch) == 1.0
+    for what in gen.promise_variants(batch, gen.DEEP_PROMISE_VARIANTS[1:]):
+        t0 = time.perf_counter()
+        rc, got = ctx.call_batch(batch, debug=True)
+        dt = time.perf_counter() - t0
+        assert rc == 0
+        _assert_same(got, want, f"100k reads unphased={unphased} support={support} {what}")
+        print(f"100 000-read locus, unphased={unphased} support={support} {what}: {dt * 1e3:.1f} ms for the host-buffer call")
 
 
 _MILLION = {}
@@ -321,6 +358,18 @@ def test_one_locus_of_a_million_reads(ctx, orc, unphased, support):
     assert np.isnan(got.phase2[2]) == (support > 3)  # the 70 000-read locus: a number, or (fewer Calls per group than `support`) NaN
     print(f"1 000 000-read locus, unphased={unphased} support={support}: launch sequence {seq_ms:.2f} ms")
     assert launches == 1 and seq_ms < 5.0, f"{seq_ms:.2f} ms for walk + reduce of the batch"
+    # the same built batch under the promised variants (the row walk): exact, one launch sequence; its time is printed, not bounded
+    assert gen.checked_share(batch) == 1.0
+    for what in gen.promise_variants(batch, gen.DEEP_PROMISE_VARIANTS[1:]):
+        ctx.timing_enable(True)
+        ctx.timing_reset()
+        rc, got = ctx.call_batch(batch, debug=True)
+        seq_ms, launches = ctx.timing_read(0)
+        ctx.timing_enable(False)
+        assert rc == 0
+        _assert_same(got, want, f"a million reads unphased={unphased} support={support} {what}")
+        print(f"1 000 000-read locus, unphased={unphased} support={support} {what}: launch sequence {seq_ms:.2f} ms")
+        assert launches == 1, what
 
 
 @pytest.mark.parametrize("seed,unphased", [(1, False), (2, True), (3, False), (4, True)])
@@ -370,6 +419,7 @@ def test_very_deep_loci_at_the_edges_of_the_clip_rule(ctx, orc, seed, unphased):
         oc, want = orc.call_batch(b, debug=True, threads=8)
         assert rc == oc == 0
         _assert_same(got, want, f"very deep loci seed={seed} unphased={unphased} support={support} (ng {ng}, ns {ns})")
+        _other_variants(ctx, b, want, f"very deep loci seed={seed} unphased={unphased} support={support}", gen.DEEP_PROMISE_VARIANTS)
     assert ng > 10_000
 
 
@@ -420,6 +470,7 @@ def test_very_deep_locus_with_calls_of_every_spread(ctx, orc, unphased, spread):
         oc, want = orc.call_batch(batch, debug=True, threads=8)
         assert rc == oc == 0
         _assert_same(got, want, f"spread={spread} unphased={unphased} support={support}")
+        _other_variants(ctx, batch, want, f"spread={spread} unphased={unphased} support={support}", gen.DEEP_PROMISE_VARIANTS)
         if spread == "five_bytes":
             assert np.abs(want.pair_call).max() > (1 << 31)
         if support == 3:
@@ -441,6 +492,11 @@ def test_batches_that_mix_every_depth_class(ctx, orc, case):
     oc, want = orc.call_batch(batch, debug=True, threads=8)
     assert rc == oc == 0
     _assert_same(got, want, f"mixed depths case {case}: {sorted(depths)[-4:]}")
+    ctx.set_option("max_reads_hint", 0 if case % 3 else int(max(depths)))
+    try:
+        _other_variants(ctx, batch, want, f"mixed depths case {case}", gen.DEEP_PROMISE_VARIANTS)
+    finally:
+        ctx.set_option("max_reads_hint", 0)
     assert max(depths) > (65_536 if case % 4 == 0 else 16_384) and batch.n_loci == len(depths)
 
 
@@ -475,27 +531,44 @@ def test_domain_errors(ctx, orc):
         bb.add_locus(kw.get("start", 1010), kw.get("end", 1090), [r])
         return bb.build()
 
-    def both(b):
-        rc, _ = ctx.call_batch(b, check=False)
-        assert rc == orc.call_batch(b)[0]
-        return rc
+    def both(b, share=1.0, damage=None):
+        """The status code, which must be the oracle's under every promise variant.  `damage` breaks the layout of a fresh
+        one() after the variant has been set on it (a producer sets the byte on a descriptor that was valid then)."""
+        assert gen.checked_share(b) == share
+        codes = set()
+        for v in gen.PROMISE_VARIANTS:
+            if damage is not None:
+                b = one()
+            what = gen.set_promise(b, v)
+            if damage is not None:
+                damage(b)
+            rc, _ = ctx.call_batch(b, check=False)
+            assert rc == orc.call_batch(b)[0], what
+            codes.add(rc)
+        assert len(codes) == 1
+        return codes.pop()
 
     assert both(one(support=0)) == B.INQ_ERR_SUPPORT_ZERO
     assert both(one(start=9, end=90)) == B.INQ_ERR_LOCUS
     assert both(one(start=100, end=99)) == B.INQ_ERR_LOCUS
     assert both(one(phase=3)) == B.INQ_ERR_PHASE
     assert both(one(phase=3, unphased=True)) == B.INQ_OK
-    assert both(one(cigar=np.array([(300 << 4) | 9], dtype=np.uint32))) == B.INQ_ERR_CIGAR_OP
-    assert both(one(pos=2**31 - 200)) == B.INQ_ERR_RANGE
-    b = one()
-    b.pair_read[0] = 5
-    assert both(b) == B.INQ_ERR_INDEX
-    b = one()
-    b.reads["n_cigar"][0] = 9
-    assert both(b) == B.INQ_ERR_INDEX
-    b = one()
-    b.locus_pair_off[1] = 2
-    assert both(b) == B.INQ_ERR_ARG
+    # a read that breaks a domain rule is never promised (mark_checked leaves it clear): share 0 of these one-read batches
+    assert both(one(cigar=np.array([(300 << 4) | 9], dtype=np.uint32)), share=0.0) == B.INQ_ERR_CIGAR_OP
+    assert both(one(pos=2**31 - 200), share=0.0) == B.INQ_ERR_RANGE
+
+    def bad_index(b):
+        b.pair_read[0] = 5
+
+    def bad_n_cigar(b):
+        b.reads["n_cigar"][0] = 9
+
+    def bad_offsets(b):
+        b.locus_pair_off[1] = 2
+
+    assert both(one(), damage=bad_index) == B.INQ_ERR_INDEX
+    assert both(one(), damage=bad_n_cigar) == B.INQ_ERR_INDEX
+    assert both(one(), damage=bad_offsets) == B.INQ_ERR_ARG
     # INQ_READ_SA_PANIC: raised for a KEPT read only (src/call.rs:303,357 -> :394); the read below has a soft clip
     def sa(mapq, phase, unphased, pos=900, depth=1):
         bb = B.BatchBuilder(unphased=unphased)
@@ -546,6 +619,7 @@ def test_golden_random_fixture(ctx):
         want = B.Result(phase1=z[f"c{i}_p1"], phase2=z[f"c{i}_p2"], pair_call=z[f"c{i}_pair_call"],
                         pair_bits=z[f"c{i}_pair_bits"], n_tie_loci=int(z[f"c{i}_params"][3]))
         _assert_same(got, want, f"fixture case {i}")
+        _other_variants(ctx, batch, want, f"fixture case {i}")
 
 
 def test_full_size_roofline_workload(ctx, orc):

@@ -94,6 +94,14 @@ def test_batch_flags_match_oracle(ctx, orc, name):
     assert rc2 == 0
     assert gen.same_f64(got.phase1, plain.phase1) and gen.same_f64(got.phase2, plain.phase2)
     assert got.n_tie_loci == plain.n_tie_loci
+    # the same built batch and the same oracle flags under the promised variants (the window-bounded row walk)
+    assert not batch.reads["promise"].any() and gen.checked_share(batch) == 1.0
+    for what in gen.promise_variants(batch, gen.DEEP_PROMISE_VARIANTS[1:]):
+        rc3, got3, flags3 = ctx.call_batch_flags(batch)
+        assert rc3 == 0, what
+        assert np.array_equal(flags3, want), f"{name} {what}: flags differ at {np.nonzero(flags3 != want)[0][:8]}"
+        assert int(flags3.sum()) == got3.n_tie_loci == got.n_tie_loci, what
+        assert gen.same_f64(got3.phase1, got.phase1) and gen.same_f64(got3.phase2, got.phase2), what
 
 
 def test_device_entry_flags(ctx, orc):

@@ -52,6 +52,32 @@ def _both(ctx, orc, batch, what=""):
     return codes[0]
 
 
+def _all_variants(ctx, orc, batch, what=""):
+    """One oracle result (the oracle never reads the byte), the batch called under every promise variant of tests/gen.py;
+    returns the status code."""
+    oc, want = orc.call_batch(batch, debug=True)
+    for name in gen.promise_variants(batch):
+        rc, got = ctx.call_batch(batch, debug=True, check=False)
+        assert rc == oc, (what, name, rc, oc)
+        if rc == B.INQ_OK:
+            _assert_same(got, want, f"{what} {name}")
+    return oc
+
+
+@pytest.mark.parametrize("seed", range(256))
+@pytest.mark.parametrize("unphased", [False, True])
+def test_row_walk_cases(ctx, orc, seed, unphased):
+    """gen.row_walk_case: batches whose dimensions are walk_pairs_rows' own - pairs per locus on both sides of every tier of
+    the locus kernels (1 ... 64, 65 ... 300, 2 048 / 2 049), ops per read around the 64-op piece and the 16-groups-left test,
+    the piece (0, 1, 2, 5, 9) in which a promised read passes end_ext with pos + consumed on end_ext - 2 ... + 1 at the piece
+    boundary, windows of 0 ... 40 000 bp under reads of short ops (the lane queue drains many times, fed by 16 row streams),
+    runs of 1 ... 64 reads that claim() settles without a load and whole blocks of them, reads shared between loci with
+    different windows - each under the five promise variants, bit for bit against the oracle."""
+    batch, info = gen.row_walk_case(seed, unphased)
+    assert gen.checked_share(batch) == 1.0
+    assert _all_variants(ctx, orc, batch, f"row walk case {seed} unphased={unphased} {info['depths']}") == B.INQ_OK
+
+
 @pytest.mark.parametrize("seed,unphased,long_every", [(1, False, 0), (2, True, 0), (3, False, 5), (4, True, 7)])
 def test_random_cases(ctx, orc, seed, unphased, long_every):
     batch, _ = gen.random_case(7000 + seed, n_loci=60, unphased=unphased, long_every=long_every)
@@ -123,14 +149,36 @@ def test_stop_rule_edges(ctx, orc, unphased):
 
 @pytest.mark.parametrize("unphased", [False, True])
 def test_wrapped_window(ctx, orc, unphased):
-    """locus_end + 10 past 2^32: the window wraps and every read is walked whole, promise or not."""
+    """locus_end + 10 past 2^32: the window wraps and every read is walked whole, promise or not.  With end_ext < start_ext
+    the reference's `start_ext < pos && pos < end_ext` holds for no position (u32, src/call.rs:387-403), so the I / D / S ops
+    that reads starting at -1, 0 and 2 have at reference positions 0 ... end + 9 - 2^32 count for nothing."""
     bb = B.BatchBuilder(minlen=2, support=1, unphased=unphased)
     idx = [bb.add_read(100 + 7 * k, B.encode_cigar([("M", 30), ("I", 9), ("M", 5), ("D", 4)] * 50), phase=1 + k % 2)
            for k in range(20)]
-    bb.add_locus(2**32 - 40, 2**32 - 5, idx)
-    bb.add_locus(2**32 - 40, 2**32 - 11, idx)
-    bb.add_locus(1010, 1090, idx)
-    assert _both(ctx, orc, bb.build(), "wrapped") == B.INQ_OK
+    low = []
+    for k, pos in enumerate((-1, 0, 2) * 4):
+        head = [[("I", 9), ("M", 1), ("D", 4), ("S", 7), ("M", 1), ("I", 3)], [("S", 12), ("M", 2), ("I", 5), ("M", 1), ("D", 3)],
+                [("M", 1), ("D", 3), ("I", 8), ("M", 2), ("S", 6)], [("D", 5), ("I", 6), ("M", 3), ("I", 4)]][k // 3]
+        low.append(bb.add_read(pos, B.encode_cigar(head + [("M", 30), ("I", 9), ("M", 5), ("D", 4)] * (3 + 20 * (k % 2))),
+                               phase=1 + k % 2, is_2d=(k == 7)))
+    bb.add_locus(2**32 - 40, 2**32 - 5, idx + low)
+    bb.add_locus(2**32 - 40, 2**32 - 11, idx + low)
+    bb.add_locus(1010, 1090, idx + low)
+    bb.add_locus(2**32 - 40, 2**32 - 1, low)  # end_ext = 9: reference positions 0 ... 8 lie "inside" the wrapped difference
+    bb.add_locus(2**32 - 300, 2**32 - 10, low + idx)  # end_ext = 0
+    bb.add_locus(2**32 - 40, 2**32 - 3, (idx + low) * 3)  # 96 pairs: wave_locus<4>
+    bb.add_locus(2**32 - 25, 2**32 - 1, (low + idx) * 10)  # 320 pairs: walk_locus
+    batch = bb.build()
+    assert _both(ctx, orc, batch, "wrapped") == B.INQ_OK
+    assert gen.checked_share(batch) == 1.0
+    assert _all_variants(ctx, orc, batch, "wrapped") == B.INQ_OK
+    # what the oracle says of the wrapped loci: no Call, no clip bit, though the same reads have Calls in the ordinary window
+    code, want = orc.call_batch(batch, debug=True)
+    off = batch.locus_pair_off.astype(np.int64)
+    wrapped = np.ones(batch.n_pairs, dtype=bool)
+    wrapped[off[1] : off[3]] = False  # (the second locus ends at 2^32 - 1: far from every read, but not wrapped)
+    assert code == B.INQ_OK and not want.pair_call[wrapped].any() and not (want.pair_bits[wrapped] & B.INQ_PAIR_CLIP).any()
+    assert (want.pair_call[off[2] : off[3]] != 0).sum() >= 20
 
 
 @pytest.mark.parametrize("unphased", [False, True])

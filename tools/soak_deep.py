@@ -4,7 +4,8 @@ CPU oracle (GPU box; not part of the test-suite: run by hand).  Every case is on
 - <= 64 offered reads, 65 - 256, 257 - 2 048 (reduced by the workgroup that walked them), 2 049 - 16 384, 16 385 - 65 536 (several
 of them: walked by a group of workgroups each) and, every few cases, one locus beyond 65 536 (the whole grid) -, reads drawn from a
 pool of shapes so that equal Calls are everywhere, HP / mapq / strand / 2D bits random per read, `support` from 1 to beyond a group's
-size, both modes, with and without the caller's depth hint.  Rows, per-pair Calls and bits, tie counts must equal the oracle's.
+size, both modes, with and without the caller's depth hint, the producer promise on no read, on every read or on half of them
+(tests/gen.py set_promise, drawn from the seed).  Rows, per-pair Calls and bits, tie counts must equal the oracle's.
 usage: python tools/soak_deep.py [--cases 60] [--seed0 500000]"""
 import argparse
 import os
@@ -31,6 +32,8 @@ with hipcall.Context(0) as ctx:
         batch, depths = gen.mixed_depth_case(seed, i)
         unphased, support, minlen = bool(batch.unphased), int(batch.support), int(batch.minlen)
         hint = 0 if i % 3 else int(max(depths))
+        variant = gen.DEEP_PROMISE_VARIANTS[seed % 3]  # which reads carry the producer promise: whole walk, row walk, mixed blocks
+        gen.set_promise(batch, variant, seed)
         ctx.set_option("max_reads_hint", hint)
         rc, got = ctx.call_batch(batch, debug=True, check=False)
         oc, want = orc.call_batch(batch, debug=True, threads=8)
@@ -41,7 +44,7 @@ with hipcall.Context(0) as ctx:
             bad += 1
             where = np.nonzero(~((np.isnan(got.phase1) & np.isnan(want.phase1)) | (got.phase1 == want.phase1)) |
                                ~((np.isnan(got.phase2) & np.isnan(want.phase2)) | (got.phase2 == want.phase2)))[0]
-            print(f"MISMATCH seed={seed} unphased={unphased} support={support} minlen={minlen} hint={hint} rc={rc}/{oc} loci {where[:8].tolist()} "
+            print(f"MISMATCH seed={seed} promise={variant} unphased={unphased} support={support} minlen={minlen} hint={hint} rc={rc}/{oc} loci {where[:8].tolist()} "
                   f"depths {[depths[k] for k in where[:8]]}", flush=True)
         if (i + 1) % 10 == 0:
             print(f"{i + 1} cases, {bad} mismatches, {time.time() - t0:.0f}s ({batch.n_pairs} pairs, {int(np.sum(~np.isnan(got.phase1)))} of {batch.n_loci} rows numeric)", flush=True)
