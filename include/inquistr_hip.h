@@ -77,8 +77,9 @@ typedef struct inq_read {
 /* promise: INQ_READ_CHECKED says that the producer of the descriptor has checked the domain rules of this read:
  * every op code is <= 8, pos >= -1 and pos + 1 + reference span < 2^31.  The device then reads the CIGAR of such a
  * read only as far as the locus window needs (up to the op after which pos + consumed >= end + 10) and does not
- * look for INQ_ERR_CIGAR_OP / INQ_ERR_RANGE in the rest.  A false promise leaves domain errors in the unread tail
- * unreported; results for valid reads are the same either way.  0 = no promise: every op is read and checked. */
+ * look for INQ_ERR_CIGAR_OP / INQ_ERR_RANGE in the rest, nor in the part it reads when every read offered beside it
+ * is promised too.  A false promise may therefore leave the read's domain errors unreported; results for valid
+ * reads are the same either way.  0 = no promise: every op is read and checked. */
 #define INQ_READ_CHECKED 0x01u
 
 #define INQ_READ_UNMAPPED 0x01u /* BAM flag 0x4   */

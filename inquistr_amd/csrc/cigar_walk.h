@@ -21,6 +21,8 @@
 //     The whole wave therefore pays the per-op window/minlen/sign logic once per ~64 window
 //     lanes instead of once per chunk.
 #pragma once
+#include <type_traits>
+
 #include "wave_primitives.h"
 
 namespace inq {
@@ -362,11 +364,12 @@ __device__ __forceinline__ void walk_pairs_whole(const BatchView &b, const PairM
 //
 // Shape: the wave is 4 rows of kRowLanes = 16 lanes; a row walks one read in pieces of 64 ops (one
 // buffer_load_dwordx4 per lane: 256 contiguous bytes per row).  Four load slots per wave, as in the
-// whole walk, but every row of a slot is a read stream of its own: when a piece has been scanned the row loads
-// either its read's next piece or - the read done - piece 0 of the block's next read, so nothing is loaded past
-// the point where a read stops.  A checked read stops after the piece that takes carry = pos + 1 + consumed
-// past end_ext (carry > end_ext <=> pos + consumed >= end_ext, without the u32 wrap of pos = -1); an unchecked
-// one is walked to its end, with the device's own domain checks.
+// whole walk, but every row of a slot is a read stream of its own: piece 0 of the block's reads is dealt to the
+// rows in order, and from piece 1 on a row that has scanned a piece loads either its read's next piece or - the
+// read done - the next piece 1 waiting, so nothing is loaded past the point where a read stops.  A checked read
+// stops after the piece that takes carry = pos + 1 + consumed past end_ext (carry > end_ext <=> pos + consumed >=
+// end_ext, without the u32 wrap of pos = -1); an unchecked one is walked to its end, with the device's own domain
+// checks.
 constexpr uint32_t RP_CHECKED = 1u;  // INQ_READ_CHECKED
 
 constexpr int kRowLanes = 16;  // lanes of one row = one read stream = one DPP row
@@ -399,58 +402,43 @@ static_assert(cigar_groups((1u << 25) - 4u) == kRowMaxGroups - 1u && cigar_group
               "the longest read the row walk takes is 2^25 - 4 ops");
 
 // Same contract as walk_pairs_whole.  Needs a window that does not wrap (end_ext >= start_ext + 1) and a batch
-// CIGAR under 4 GiB (one buffer descriptor over all of it; 32-bit byte offsets).
+// CIGAR under 4 GiB (one buffer descriptor over all of it; 32-bit byte offsets).  `checks` (wave-uniform): some
+// read of the block is not promised, so every piece gets the device's own domain checks; a block whose reads are
+// all promised walks without them.
+//
+// Two phases.  Piece 0 is needed of every read that is not settled by its descriptor alone, so it is walked
+// statically: read 4s + row in turn s, four loads in flight, no queue of idle rows.  The reads that have not
+// stopped after piece 0 are then compacted into a list in LDS (the spare words of the lane queue's entries) and
+// walked from piece 1 on by rows that take the next of them whenever they fall idle.
 template <bool UNPHASED, int AUX>
 __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMeta &m, bool valid, int cnt,
-                                                const Window &W, int lane, uint32_t &status, WaveLds &L, int64_t &val,
-                                                uint32_t &meta) {
+                                                const Window &W, int lane, bool checks, uint32_t &status, WaveLds &L,
+                                                int64_t &val, uint32_t &meta) {
     L.acc[lane] = 0ull;
     L.flags[lane] = 0u;
+    L.endc[lane] = m.pos + 1u;  // (reference_start + 1) as u32, src/call.rs:380: where a read with nothing to load ends
     uint32_t qcount = 0;
-    uint32_t lane_err = 0;  // bit 0: an op code 9..15 was seen, bit 1: a reference position reached 2^31
+    // bit 0: an op code 9..15 was seen, bit 1: a reference position reached 2^31
+    uint32_t lane_err = ((m.pos + 1u) >> 31) << 1;
     const int rl = lane & (kRowLanes - 1);
+    const int row = lane >> 4;
     const uint64_t row_heads = 0x0001000100010001ull;  // lane 0 of each row
     // out-of-range offsets (past num_records) load 0 = `0M`: lanes past a read's end and idle rows
     const __amdgpu_buffer_rsrc_t rsrc =
         __builtin_amdgcn_make_buffer_rsrc((void *)b.cigar4, (short)0, (int)(uint32_t)(b.n_cigar4 * 16u), 0x00020000);
 
-    int next = 0;  // wave-uniform: the first read of the block no row has taken yet
-    // rows whose stream is idle take the next reads, in row order; a read with nothing to load is settled here
-    auto claim = [&](RowStream &S) {
-        for (;;) {
-            const bool idle = S.st == 0u;
-            const uint64_t need = ballot64(idle) & row_heads;
-            if (need == 0ull || next >= cnt) return;
-            // idle rows below this one: the set bits of `need` in lower lanes, less this row's own head
-            const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
-            const int k = next + below - ((idle && rl != 0) ? 1 : 0);
-            next += (int)__popcll(need);
-            const int src = min(k, 63) << 2;
-            // what a row needs of read k besides off4 and pos, from lane k: groups | is_2d << 30 | checked << 31
-            const uint32_t d_w = (((m.nc & 0x0fffffffu) + 3u) >> 2) | ((m.nc >> 31) << 30) |
-                                 ((((m.misc >> 24) & RP_CHECKED) != 0u) ? 0x80000000u : 0u);
-            const uint32_t r_off4 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)m.off4);
-            const uint32_t r_w = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)d_w);
-            const uint32_t r_pos = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)m.pos);
-            if (idle && k < cnt) {
-                S.cur4 = r_off4;
-                S.carry = r_pos + 1u;  // (reference_start + 1) as u32, src/call.rs:380
-                lane_err |= (S.carry >> 31) << 1;
-                S.st = ((r_w & 0x3fffffffu) << RS_LEFT) | (uint32_t)k | (((r_w >> 30) & 1u) << 6) |
-                       ((r_w >> 31) ? RS_STOP : 0u) | RS_LIVE;
-                // an empty CIGAR, or a checked read that starts past the window: nothing to load
-                if ((S.st >> RS_LEFT) == 0u || ((S.st & RS_STOP) && S.carry > W.ee)) {
-                    if (rl == 0) L.endc[k] = S.carry;
-                    S.st = 0u;
-                }
-            }
-        }
-    };
+    // what a row needs of read k besides off4 and pos, in lane k: groups (< kRowMaxGroups) | is_2d << 30 | promised << 31;
+    // lanes that own no read hold an empty one
+    const uint32_t groups = cigar_groups(m.nc & 0x0fffffffu);
+    const bool promised = ((m.misc >> 24) & RP_CHECKED) != 0u;
+    const uint32_t d_w = groups | ((m.nc >> 31) << 30) | (promised ? 0x80000000u : 0u);
+
     auto issue = [&](const RowStream &S) -> u32x4 {
         const uint32_t voff = (uint32_t)rl < (S.st >> RS_LEFT) ? (S.cur4 + (uint32_t)rl) * 16u : 0xfffffff0u;
         return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, AUX);
     };
-    auto step = [&](const u32x4 w, RowStream &S) {
+    // PIECE0: the row's state is not carried on; the position reached goes to the read's owner through L.endc
+    auto step = [&](const u32x4 w, RowStream &S, auto piece0) {
         const bool live = S.st != 0u;
         const uint32_t e1 = ref_advance_raw(w.x);
         const uint32_t e2 = e1 + ref_advance_raw(w.y);
@@ -458,10 +446,12 @@ __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMe
         const uint32_t tot = e3 + ref_advance_raw(w.w);
         const uint32_t incl = row_inclusive_scan_u32(tot);
         const uint32_t rtot = row_last(incl);
-        if (live) {
-            lane_err |= ((kBadOp32 >> (w.x & 31u)) | (kBadOp32 >> (w.y & 31u)) | (kBadOp32 >> (w.z & 31u)) |
-                         (kBadOp32 >> (w.w & 31u))) & 1u;
-            lane_err |= ((S.carry + incl) >> 31) << 1;
+        if (checks) {
+            if (live) {
+                lane_err |= ((kBadOp32 >> (w.x & 31u)) | (kBadOp32 >> (w.y & 31u)) | (kBadOp32 >> (w.z & 31u)) |
+                             (kBadOp32 >> (w.w & 31u))) & 1u;
+                lane_err |= ((S.carry + incl) >> 31) << 1;
+            }
         }
         // the window-lane test of walk_pairs_whole, per row
         const uint32_t x = (S.carry - W.se1) + incl;
@@ -478,49 +468,134 @@ __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMe
             if (qcount > 64u) drain_queue(L, qcount, W, lane);
         }
         S.carry += rtot;
-        S.cur4 += (uint32_t)kRowLanes;
-        if (live) {
-            if ((S.st >> RS_LEFT) <= (uint32_t)kRowLanes || ((S.st & RS_STOP) && S.carry > W.ee)) {
-                if (rl == 0) L.endc[S.st & 63u] = S.carry;
-                S.st = 0u;
-            } else {
-                S.st -= (uint32_t)kRowLanes << RS_LEFT;
+        if (decltype(piece0)::value) {
+            if (live && rl == 0) L.endc[S.st & 63u] = S.carry;
+        } else {
+            S.cur4 += (uint32_t)kRowLanes;
+            if (live) {
+                if ((S.st >> RS_LEFT) <= (uint32_t)kRowLanes || ((S.st & RS_STOP) && S.carry > W.ee)) {
+                    if (rl == 0) L.endc[S.st & 63u] = S.carry;
+                    S.st = 0u;
+                } else {
+                    S.st -= (uint32_t)kRowLanes << RS_LEFT;
+                }
             }
         }
     };
+    using Piece0 = std::true_type;
+    using Later = std::false_type;
 
+    // ---- piece 0: rows of turn k0 / 4 take reads k0 .. k0 + 3 ----
+    auto assign = [&](RowStream &S, int k0) {
+        S.st = 0u;
+        if (k0 < cnt) {  // wave-uniform; k0 + row <= 63
+            const int src = (k0 + row) << 2;
+            const uint32_t r_off4 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)m.off4);
+            const uint32_t r_w = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)d_w);
+            const uint32_t r_pos = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)m.pos);
+            S.cur4 = r_off4;
+            S.carry = r_pos + 1u;
+            // an empty CIGAR, or a promised read that starts past the window: nothing to load
+            if ((r_w & 0x3fffffffu) != 0u && !((r_w >> 31) && S.carry > W.ee))
+                S.st = ((r_w & 0x3fffffffu) << RS_LEFT) | (uint32_t)(k0 + row) | (((r_w >> 30) & 1u) << 6) |
+                       ((r_w >> 31) ? RS_STOP : 0u) | RS_LIVE;
+        }
+    };
     RowStream sa{0u, 0u, 0u}, sb = sa, sc = sa, sd = sa;
-    claim(sa);
+    assign(sa, 0);
     u32x4 qa = issue(sa);
-    claim(sb);
+    assign(sb, 4);
     u32x4 qb = issue(sb);
-    claim(sc);
+    assign(sc, 8);
     u32x4 qc = issue(sc);
-    claim(sd);
+    assign(sd, 12);
     u32x4 qd = issue(sd);
     // four named buffers, one load per slot and round whether its rows are live or not: each step waits only
     // for its own load (vmcnt(3)); an idle slot's load is out of range everywhere and moves no bytes
-    while (ballot64((sa.st | sb.st | sc.st | sd.st) != 0u)) {
-        if (ballot64(sa.st != 0u)) {
-            step(qa, sa);
-            claim(sa);
-        }
+    for (int k0 = 0; k0 < cnt; k0 += 16) {
+        step(qa, sa, Piece0{});
+        assign(sa, k0 + 16);
         qa = issue(sa);
-        if (ballot64(sb.st != 0u)) {
-            step(qb, sb);
-            claim(sb);
-        }
+        if (k0 + 4 < cnt) step(qb, sb, Piece0{});
+        assign(sb, k0 + 20);
         qb = issue(sb);
-        if (ballot64(sc.st != 0u)) {
-            step(qc, sc);
-            claim(sc);
-        }
+        if (k0 + 8 < cnt) step(qc, sc, Piece0{});
+        assign(sc, k0 + 24);
         qc = issue(sc);
-        if (ballot64(sd.st != 0u)) {
-            step(qd, sd);
-            claim(sd);
-        }
+        if (k0 + 12 < cnt) step(qd, sd, Piece0{});
+        assign(sd, k0 + 28);
         qd = issue(sd);
+    }
+
+    // ---- later pieces: the reads piece 0 has not settled, as a list of ncont entries in LDS ----
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t endc0 = L.endc[lane];
+    const bool cont = groups > (uint32_t)kRowLanes && !(promised && endc0 > W.ee);
+    const uint64_t cmask = ballot64(cont);
+    if (cmask) {
+        const int ncont = (int)__popcll(cmask);
+        // the queue entries' spare words carry the list: entry i holds the i-th read to go on as off4 and
+        // groups left | slot << 23 | is_2d << 30 | promised << 31, entry 64 + i the position it has reached.
+        // The list outlives the pushes and drains of the queue only because those touch .w and .info and
+        // never store a whole QueueEntry: keep it so, or move the list.
+        if (cont) {
+            const uint32_t i = __builtin_amdgcn_mbcnt_hi((uint32_t)(cmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cmask, 0u));
+            L.q[i].pad = make_uint2(m.off4 + (uint32_t)kRowLanes, (d_w - (uint32_t)kRowLanes) | ((uint32_t)lane << 23));
+            L.q[64u + i].pad.x = endc0;
+        }
+        __builtin_amdgcn_wave_barrier();
+
+        int next = 0;  // wave-uniform: the first read of the list no row has taken yet
+        // rows whose stream is idle take the next reads of the list, in row order; every one of them has a piece to load
+        auto claim = [&](RowStream &S) {
+            if (next >= ncont) return;
+            const bool idle = S.st == 0u;
+            const uint64_t need = ballot64(idle) & row_heads;
+            if (need == 0ull) return;
+            // idle rows below this one: the set bits of `need` in lower lanes, less this row's own head
+            const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+            const int k = next + below - ((idle && rl != 0) ? 1 : 0);
+            next += (int)__popcll(need);
+            if (idle && k < ncont) {
+                const uint2 r = L.q[k].pad;
+                const uint32_t r_w = r.y;
+                S.cur4 = r.x;
+                S.carry = L.q[64 + k].pad.x;
+                S.st = ((r_w & (kRowMaxGroups - 1u)) << RS_LEFT) | ((r_w >> 23) & 63u) | (((r_w >> 30) & 1u) << 6) |
+                       ((r_w >> 31) ? RS_STOP : 0u) | RS_LIVE;
+            }
+        };
+        sa.st = sb.st = sc.st = sd.st = 0u;
+        claim(sa);
+        qa = issue(sa);
+        claim(sb);
+        qb = issue(sb);
+        claim(sc);
+        qc = issue(sc);
+        claim(sd);
+        qd = issue(sd);
+        while (ballot64((sa.st | sb.st | sc.st | sd.st) != 0u)) {
+            if (ballot64(sa.st != 0u)) {
+                step(qa, sa, Later{});
+                claim(sa);
+            }
+            qa = issue(sa);
+            if (ballot64(sb.st != 0u)) {
+                step(qb, sb, Later{});
+                claim(sb);
+            }
+            qb = issue(sb);
+            if (ballot64(sc.st != 0u)) {
+                step(qc, sc, Later{});
+                claim(sc);
+            }
+            qc = issue(sc);
+            if (ballot64(sd.st != 0u)) {
+                step(qd, sd, Later{});
+                claim(sd);
+            }
+            qd = issue(sd);
+        }
     }
     if (qcount) drain_queue(L, qcount, W, lane);
     if (ballot64((lane_err & 1u) != 0u)) status |= ST_CIGAR_OP;  // rust-htslib cigar() would panic
@@ -537,10 +612,12 @@ __device__ __forceinline__ void walk_pairs(const BatchView &b, const PairMeta &m
                                            uint32_t &meta) {
     const bool checked = lane < cnt && valid && ((m.misc >> 24) & RP_CHECKED) != 0u;
     const bool too_long = lane < cnt && valid && cigar_groups(m.nc & 0x0fffffffu) >= kRowMaxGroups;
-    if (ballot64(checked) != 0ull && ballot64(too_long) == 0ull && W.ee >= W.se1 && b.n_cigar4 < (1ull << 28))
-        walk_pairs_rows<UNPHASED, AUX>(b, m, valid, cnt, W, lane, status, L, val, meta);
-    else
+    if (ballot64(checked) != 0ull && ballot64(too_long) == 0ull && W.ee >= W.se1 && b.n_cigar4 < (1ull << 28)) {
+        const bool checks = ballot64(lane < cnt && valid && !checked) != 0ull;
+        walk_pairs_rows<UNPHASED, AUX>(b, m, valid, cnt, W, lane, checks, status, L, val, meta);
+    } else {
         walk_pairs_whole<UNPHASED, AUX>(b, m, valid, cnt, W, lane, status, L, val, meta);
+    }
 }
 
 }  // namespace inq
