@@ -362,8 +362,8 @@ __device__ __forceinline__ void walk_pairs_whole(const BatchView &b, const PairM
 // never decrease), and a lower bound of bam_endpos that is already >= end_ext settles the fetch rule and both
 // filters (rend > start_ext, rend < end_ext) exactly as the true value does.
 //
-// Shape: the wave is 4 rows of kRowLanes = 16 lanes; a row walks one read in pieces of 64 ops (one
-// buffer_load_dwordx4 per lane: 256 contiguous bytes per row).  Four load slots per wave, as in the
+// Shape: the wave is 4 rows of kRowLanes = 16 lanes; a row walks one read in pieces of up to 64 ops (one
+// buffer_load_dwordx4 per lane: up to 256 contiguous bytes per row, see kLineMask below for where they lie).  Four load slots per wave, as in the
 // whole walk, but every row of a slot is a read stream of its own: piece 0 of the block's reads is dealt to the
 // rows in order, and from piece 1 on a row that has scanned a piece loads either its read's next piece or - the
 // read done - the next piece 1 waiting, so nothing is loaded past the point where a read stops.  A checked read
@@ -394,6 +394,12 @@ struct RowStream {
 };
 constexpr uint32_t RS_STOP = 128u, RS_LIVE = 256u;
 constexpr int RS_LEFT = 9;
+// Where the pieces lie.  A read starts on a 16-byte boundary, off4 & 7 groups into a 128-byte line of the batch's CIGAR.
+// Piece 0 keeps the read's own start (16 groups from off4: laid from the line's start it would hold fewer of the read's
+// ops and send 0.78 of the reads on to a later piece instead of 0.46).  Every later piece ends on the second line boundary
+// behind its start: lane rl of the row loads group (cur4 & ~7) + rl, and the lanes before cur4 and past the read's end
+// get the out-of-range offset.  So piece 1 holds 16 - (off4 & 7) groups and every piece behind it two whole lines.
+constexpr uint32_t kLineMask = 7u;  // groups of a 128-byte line - 1
 // st holds at most 2^23 - 1 groups left: a read of kRowMaxGroups groups or more (n_cigar > 2^25 - 4) sends its block to
 // the whole walk
 constexpr uint32_t kRowMaxGroups = 1u << (32 - RS_LEFT);
@@ -433,9 +439,16 @@ __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMe
     const bool promised = ((m.misc >> 24) & RP_CHECKED) != 0u;
     const uint32_t d_w = groups | ((m.nc >> 31) << 30) | (promised ? 0x80000000u : 0u);
 
-    auto issue = [&](const RowStream &S) -> u32x4 {
+    // piece 0 from the read's own start
+    auto issue0 = [&](const RowStream &S) -> u32x4 {
         const uint32_t voff = (uint32_t)rl < (S.st >> RS_LEFT) ? (S.cur4 + (uint32_t)rl) * 16u : 0xfffffff0u;
         return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, AUX);
+    };
+    // a piece on the line grid: the lanes from cur4 to the piece's end that the read still has groups for
+    auto issue = [&](const RowStream &S) -> u32x4 {
+        const uint32_t g = (S.cur4 & ~kLineMask) + (uint32_t)rl;
+        const bool on = g - S.cur4 < (S.st >> RS_LEFT);
+        return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(on ? g * 16u : 0xfffffff0u), 0, AUX);
     };
     // PIECE0: the row's state is not carried on; the position reached goes to the read's owner through L.endc
     auto step = [&](const u32x4 w, RowStream &S, auto piece0) {
@@ -471,13 +484,16 @@ __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMe
         if (decltype(piece0)::value) {
             if (live && rl == 0) L.endc[S.st & 63u] = S.carry;
         } else {
-            S.cur4 += (uint32_t)kRowLanes;
+            // the piece ran from cur4 to a line boundary: lim groups
+            const uint32_t end4 = (S.cur4 & ~kLineMask) + (uint32_t)kRowLanes;
+            const uint32_t lim = end4 - S.cur4;
+            S.cur4 = end4;
             if (live) {
-                if ((S.st >> RS_LEFT) <= (uint32_t)kRowLanes || ((S.st & RS_STOP) && S.carry > W.ee)) {
+                if ((S.st >> RS_LEFT) <= lim || ((S.st & RS_STOP) && S.carry > W.ee)) {
                     if (rl == 0) L.endc[S.st & 63u] = S.carry;
                     S.st = 0u;
                 } else {
-                    S.st -= (uint32_t)kRowLanes << RS_LEFT;
+                    S.st -= lim << RS_LEFT;
                 }
             }
         }
@@ -503,28 +519,28 @@ __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMe
     };
     RowStream sa{0u, 0u, 0u}, sb = sa, sc = sa, sd = sa;
     assign(sa, 0);
-    u32x4 qa = issue(sa);
+    u32x4 qa = issue0(sa);
     assign(sb, 4);
-    u32x4 qb = issue(sb);
+    u32x4 qb = issue0(sb);
     assign(sc, 8);
-    u32x4 qc = issue(sc);
+    u32x4 qc = issue0(sc);
     assign(sd, 12);
-    u32x4 qd = issue(sd);
+    u32x4 qd = issue0(sd);
     // four named buffers, one load per slot and round whether its rows are live or not: each step waits only
     // for its own load (vmcnt(3)); an idle slot's load is out of range everywhere and moves no bytes
     for (int k0 = 0; k0 < cnt; k0 += 16) {
         step(qa, sa, Piece0{});
         assign(sa, k0 + 16);
-        qa = issue(sa);
+        qa = issue0(sa);
         if (k0 + 4 < cnt) step(qb, sb, Piece0{});
         assign(sb, k0 + 20);
-        qb = issue(sb);
+        qb = issue0(sb);
         if (k0 + 8 < cnt) step(qc, sc, Piece0{});
         assign(sc, k0 + 24);
-        qc = issue(sc);
+        qc = issue0(sc);
         if (k0 + 12 < cnt) step(qd, sd, Piece0{});
         assign(sd, k0 + 28);
-        qd = issue(sd);
+        qd = issue0(sd);
     }
 
     // ---- later pieces: the reads piece 0 has not settled, as a list of ncont entries in LDS ----

@@ -48,8 +48,32 @@ def mark_checked(batch: Batch) -> Batch:
     return batch
 
 
-def _walked_groups(batch: Batch, piece_ops: int):
-    """Per pair: (first 16-byte group of its read, groups the walk loads)."""
+LAYOUTS = ("read", "line", "line_half", "tail", "tail_half")
+PIECE_GROUPS = 16  # cigar_walk.h kRowLanes: a full piece, two 128-byte lines
+HALF_GROUPS = 8  # a half piece: lanes 0-7 of a row, one line
+HALF_NUM, HALF_DEN = 7, 8  # the rule's factor, tuned on configs #3 and #5 (profiles/r08_line_pieces/summary.md)
+HALF_SAT = (1 << 24) - 1  # the distance to end_ext and the bases covered saturate here: 24-bit multiplies in the kernel
+
+
+def half_piece_next(d, lim, rtot, c=HALF_GROUPS, num: int = HALF_NUM, den: int = HALF_DEN):
+    """THE half-piece rule, stated here once; cigar_walk.h (`half_piece_next` there) computes the same bits.
+
+    After a piece of `lim` lanes (16-byte groups) that covered `rtot` reference bases and left the read `d` = end_ext -
+    carry bases short of the window's end, the next piece of a promised read is a half piece - it ends on the next
+    128-byte boundary and holds `c` groups, 8 unless the piece before ended inside a line - when such a piece, at the
+    last piece's bases per group, is expected to pass end_ext with room to spare:
+
+        d <= (num / den) * rtot * c / lim    <=>    d * lim * den <= num * rtot * c
+
+    in integers, d and rtot each saturated at 2^24 - 1.  For c = 8 this is 2 * d <= (num / den) * rtot * 16 / lim.  With
+    num / den = 7 / 8 the kernel evaluates min(d, 2^24 - 1) * (lim * 8) <= min(rtot, 2^24 - 1) * (7 * c).  The choice
+    touches speed only: a half piece that falls short is followed by another piece, a full piece where half would have
+    done reads one line too many."""
+    return np.minimum(d, HALF_SAT) * lim * den <= num * np.minimum(rtot, HALF_SAT) * c
+
+
+def _bounded(batch: Batch, piece_ops: int):
+    """What every layout shares, per pair."""
     csum, before, _, _ = _spans(batch)
     r = batch.pair_read.astype(np.int64)
     off = batch.locus_pair_off.astype(np.int64)
@@ -62,12 +86,6 @@ def _walked_groups(batch: Batch, piece_ops: int):
     pos = batch.reads["pos"].astype(np.int64)[r]
     carry0 = (pos + 1) & 0xFFFFFFFF
     promised = (batch.reads["promise"][r] & INQ_READ_CHECKED) != 0
-    # first op i of the read after which carry = pos + 1 + consumed > end_ext
-    thr = ee - carry0 + before[r]
-    i = np.searchsorted(csum, thr, side="right") - o
-    stop_piece = np.where((i >= 0) & (i < n), i // piece_ops, -1)
-    groups = np.where(stop_piece >= 0, np.minimum(n4, (stop_piece + 1) * (piece_ops // 4)), n4)
-    groups = np.where(carry0 > ee, 0, groups)  # starts past the window: nothing loaded
     # whole reads: no promise, a wrapped window, a block (up to 64 pairs of a locus) that holds a read of 2^23 groups
     # (more than 2^25 - 4 ops), a batch CIGAR of 4 GiB or more
     k = np.arange(batch.n_pairs, dtype=np.int64) - off[locus]
@@ -75,25 +93,91 @@ def _walked_groups(batch: Batch, piece_ops: int):
     block_long = np.zeros(inv.max() + 1, dtype=bool)
     np.logical_or.at(block_long, inv, n4 >= ROW_MAX_GROUPS)
     bounded = promised & (ee >= se1) & ~block_long[inv] & (batch.cigar.shape[0] // 4 < (1 << 28))
+    return csum, before[r], ee, n, n4, o, carry0, bounded, inv
+
+
+def _walked_pieces(batch: Batch, piece_ops: int = 64, layout: str = "read", factor=(HALF_NUM, HALF_DEN)):
+    """Per pair: (first 16-byte group of its read, groups the walk loads, pieces it loads them in, its 64-pair block).
+
+    Layouts of the pieces of a read that starts at group g0 (skip = g0 & 7 groups into its 128-byte line):
+      "read"       pieces of 16 groups from g0 (what the walk did before the aligned grid)
+      "line"       pieces of 16 groups from g0 - skip: piece 0 holds 16 - skip groups of the read, every later one two whole lines
+      "line_half"  "line", and from piece 1 on a promised read takes half pieces where `half_piece_next` says so
+      "tail"       piece 0 as in "read"; every later piece ends on the second line boundary behind its start, so piece 1
+                   holds 16 - skip groups and the rest two whole lines
+      "tail_half"  "tail" with half pieces, which end on the first line boundary: piece 1 then holds 8 - skip groups
+    A promised read stops after the piece that takes carry = pos + 1 + consumed past end_ext, and loads nothing when it
+    starts past it."""
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout {layout!r}: one of {LAYOUTS}")
+    if layout != "read" and piece_ops != 4 * PIECE_GROUPS:
+        raise ValueError("the line layouts are pieces of 64 ops")
+    csum, before, ee, n, n4, o, carry0, bounded, block = _bounded(batch, piece_ops)
+    g0 = o // 4
+    full = piece_ops // 4
+    skip = g0 & 7 if layout != "read" else np.zeros_like(g0)
+    halves = layout.endswith("_half")
+    groups = np.zeros_like(n4)
+    pieces = np.zeros_like(n4)
+    carry = carry0.copy()
+    lim = full - skip if layout.startswith("line") else np.full_like(n4, full)
+    live = (n4 > 0) & ~(bounded & (carry0 > ee))  # an empty CIGAR, or starts past the window: nothing loaded
+    while live.any():
+        g_new = np.where(live, np.minimum(groups + lim, n4), groups)
+        at = o + np.minimum(4 * g_new, n) - 1
+        c_new = np.where(g_new > 0, carry0 + csum[np.maximum(at, 0)] - before, carry0)
+        rtot = c_new - carry
+        ends = (n4 - groups <= lim) | (bounded & (c_new > ee))
+        pieces += live
+        groups, carry = g_new, np.where(live, c_new, carry)
+        live = live & ~ends
+        into = (skip + groups) & 7  # groups of its line that lie before the next piece
+        half = bounded & half_piece_next(ee - carry, lim, rtot, HALF_GROUPS - into, *factor) if halves else False
+        lim = np.where(half, HALF_GROUPS, full) - into
+    return g0, groups, pieces, block
+
+
+def _walked_groups(batch: Batch, piece_ops: int, layout: str = "read"):
+    """Per pair: (first 16-byte group of its read, groups the walk loads)."""
+    if layout != "read":
+        return _walked_pieces(batch, piece_ops, layout)[:2]
+    csum, before, ee, n, n4, o, carry0, bounded, _ = _bounded(batch, piece_ops)
+    # first op i of the read after which carry = pos + 1 + consumed > end_ext
+    thr = ee - carry0 + before
+    i = np.searchsorted(csum, thr, side="right") - o
+    stop_piece = np.where((i >= 0) & (i < n), i // piece_ops, -1)
+    groups = np.where(stop_piece >= 0, np.minimum(n4, (stop_piece + 1) * (piece_ops // 4)), n4)
+    groups = np.where(carry0 > ee, 0, groups)  # starts past the window: nothing loaded
     return o // 4, np.where(bounded, groups, n4)
 
 
-def window_bounded_cigar_bytes(batch: Batch, piece_ops: int = 64) -> int:
+def window_bounded_cigar_bytes(batch: Batch, piece_ops: int = 64, layout: str = "read") -> int:
     """CIGAR bytes the row walk loads for every pair of the batch (pieces of `piece_ops` ops)."""
     if batch.n_pairs == 0:
         return 0
-    return int(16 * _walked_groups(batch, piece_ops)[1].sum())
+    return int(16 * _walked_groups(batch, piece_ops, layout)[1].sum())
 
 
-def window_bounded_line_bytes(batch: Batch, piece_ops: int = 64, line: int = 128) -> int:
+def window_bounded_line_bytes(batch: Batch, piece_ops: int = 64, line: int = 128, layout: str = "read") -> int:
     """The same stretches counted in whole `line`-byte cache lines: every line a walked stretch touches, once per pair
     (reads start on 16-byte boundaries, so a stretch's first and last lines are usually shared with the neighbours)."""
     if batch.n_pairs == 0:
         return 0
-    g0, groups = _walked_groups(batch, piece_ops)
+    g0, groups = _walked_groups(batch, piece_ops, layout)
     b0, b1 = g0 * 16, (g0 + groups) * 16
     lines = np.where(groups > 0, (b1 + line - 1) // line - b0 // line, 0)
     return int(line * lines.sum())
+
+
+def row_steps(batch: Batch, layout: str = "read", factor=(HALF_NUM, HALF_DEN)) -> float:
+    """Row-steps of the walk over the batch, the instruction side's estimate: a block of cnt <= 64 pairs takes ceil(cnt / 4)
+    piece-0 turns, and its pieces behind piece 0 are shared among the four rows."""
+    if batch.n_pairs == 0:
+        return 0.0
+    _, groups, pieces, block = _walked_pieces(batch, 64, layout, factor)
+    cnt = np.bincount(block)
+    later = pieces - (pieces > 0)
+    return float(((cnt + 3) // 4).sum() + later.sum() / 4.0)
 
 
 def window_bounded_bytes(batch: Batch, piece_ops: int = 64) -> int:
