@@ -5,21 +5,21 @@
 //   Record::reference_end    src/call.rs:298,351   ([3P] htslib bam_endpos: second CIGAR walk)
 //   read filters             src/call.rs:297-302 (unphased), 349-355 (phased)
 //   fetch() overlap rule     src/call.rs:288,338   ([3P] htslib iterator)
-// Both CIGAR walks of the reference are fused into ONE pass over the packed ops.
-// Two walks share that pass: walk_pairs_whole (every op of every read, below) and walk_pairs_rows (reads whose
-// producer set INQ_READ_CHECKED, only as far as the window needs); walk_pairs picks one per block of reads.
+// Both CIGAR walks of the reference are fused into ONE pass over the packed ops.  Two walks make that pass: walk_pairs_whole
+// (every op of every read) and walk_pairs_rows (reads whose producer set INQ_READ_CHECKED, only as far as the window needs);
+// walk_pairs picks one per block of <= 64 reads.  What they share stands above them, once: advance4, bad_ops,
+// push_window_lanes, drain_queue, read_epilogue.
 //
 // Data path (per wave):
-//   * ops stream in as 256-op chunks: one buffer_load_dwordx4 per lane (16 B/lane, 1 KiB per wave
-//     instruction, coalesced).  The buffer descriptor's range check returns 0 (= `0M`, a no-op)
-//     past the read's end, so the load is never predicated.  Four chunk loads are always in
-//     flight per wave (flattened over reads and over the chunks of long reads).
-//   * reference positions: 4-wide in-lane prefix + DPP wave scan + scalar carry between chunks.
-//   * only the few lanes whose ops can start inside [start_ext, end_ext) matter for the call:
-//     they are compacted into an LDS queue and evaluated 64 at a time (one queue entry per
-//     lane), their signed lengths land in the owning read's LDS accumulator (ds_add_u64).
-//     The whole wave therefore pays the per-op window/minlen/sign logic once per ~64 window
-//     lanes instead of once per chunk.
+//   * both: one buffer_load_dwordx4 per lane (4 ops, 16 B), four loads in flight per wave, never predicated: the buffer
+//     descriptor's range check returns 0 (= `0M`, a no-op) for an offset past num_records.
+//   * whole: the wave is on one read at a time, in 256-op chunks (1 KiB per wave instruction, coalesced), flattened over reads
+//     and the chunks of long reads.  Reference positions: advance4 in the lane + DPP wave scan + scalar carry between chunks.
+//   * rows: the wave is four rows of 16 lanes, each a read stream of its own, in pieces of up to 64 ops: piece 0 of every read
+//     statically, the reads it has not settled from a list in LDS.  Positions: advance4 + DPP row scan + a carry per row.
+//   * both: only the few lanes whose ops can start inside [start_ext, end_ext) matter for the call: they are compacted into an
+//     LDS queue (push_window_lanes) and evaluated 64 at a time (drain_queue, one entry per lane); their signed lengths land in
+//     the owning read's LDS accumulator (ds_add_u64).  The per-op window/minlen/sign logic runs once per ~64 window lanes.
 #pragma once
 #include <type_traits>
 
@@ -76,7 +76,7 @@ struct BatchView {
 struct QueueEntry {
     u32x4 w;     // the lane's 4 packed ops
     uint2 info;  // .x = reference position of the first op minus (start_ext+1); .y = read slot | is2d<<6
-    uint2 pad;   // 32-byte stride: one address register serves both stores
+    uint2 pad;   // 32-byte stride: one address register serves both stores; holds the continuation list (cont_put)
 };
 struct WaveLds {
     QueueEntry q[kQueueCap];
@@ -84,6 +84,23 @@ struct WaveLds {
     unsigned int flags[64];      // per read slot: bit0 = a soft clip was counted
     unsigned int endc[64];       // per read slot: reference_position after the last op walked (walk_pairs_rows)
 };
+
+// four waves x 5 120 B = 20 480 B per workgroup: eight workgroups fill a CU's 160 KB at 8 waves per SIMD
+static_assert(sizeof(WaveLds) == 5120, "a larger WaveLds costs resident workgroups per CU");
+// The continuation list of walk_pairs_rows, up to 64 reads to go on behind piece 0: entry i is the read's next group and its
+// row word (rw_pack) in q[i].pad, the position reached in q[64 + i].pad.x.  It outlives the queue's pushes and drains because
+// push_window_lanes, the one store to the queue, writes .w and .info and never a whole QueueEntry.  (i is unsigned in put and
+// signed in get, as the two callers hold it: a cast at either changes the addresses the compiler forms.)
+static_assert(kQueueCap >= 128, "the list takes the spare words of 128 queue entries");
+__device__ __forceinline__ void cont_put(WaveLds &L, uint32_t i, uint32_t cur4, uint32_t rw, uint32_t carry) {
+    L.q[i].pad = make_uint2(cur4, rw);
+    L.q[64u + i].pad.x = carry;
+}
+__device__ __forceinline__ void cont_get(const WaveLds &L, int i, uint32_t &cur4, uint32_t &rw, uint32_t &carry) {
+    const uint2 r = L.q[i].pad;
+    cur4 = r.x, rw = r.y;
+    carry = L.q[64 + i].pad.x;
+}
 
 // Per-lane descriptor of the pair this lane "owns" inside a block of <= 64 pairs.
 struct PairMeta {
@@ -148,7 +165,7 @@ __device__ __forceinline__ PairMeta meta_stage_c(const BatchView &b, const uint4
 // ops that consume the reference: M D N = X -> bits 0,2,3,7,8 (src/call.rs:384-392,404)
 constexpr uint32_t kConsume = 0x18Du;
 
-// len if the op consumes the reference, else 0 (v_bfe_i32 + v_and)
+// len if the op consumes the reference, else 0 (v_bfe_i32 + v_and): drain_queue's form
 __device__ __forceinline__ uint32_t ref_advance(uint32_t op, uint32_t len) {
     return len & (uint32_t)__builtin_amdgcn_sbfe((int)kConsume, op, 1u);
 }
@@ -160,8 +177,17 @@ __device__ __forceinline__ uint32_t ref_advance_raw(uint32_t w) {
 }
 // bit 0 of (kBadOp32 >> (w & 31)) is set iff the op code is 9..15 (rust-htslib cigar() panics)
 constexpr uint32_t kBadOp32 = 0xFE00FE00u;
+__device__ __forceinline__ uint32_t bad_ops(const u32x4 w) {
+    return (kBadOp32 >> (w.x & 31u)) | (kBadOp32 >> (w.y & 31u)) | (kBadOp32 >> (w.z & 31u)) | (kBadOp32 >> (w.w & 31u));
+}
+// Reference span of a lane's four ops: up to the second, third and fourth op, and of all four.
+__device__ __forceinline__ void advance4(const u32x4 w, uint32_t &e1, uint32_t &e2, uint32_t &e3, uint32_t &tot) {
+    e1 = ref_advance_raw(w.x), e2 = e1 + ref_advance_raw(w.y);
+    e3 = e2 + ref_advance_raw(w.z), tot = e3 + ref_advance_raw(w.w);
+}
 
-// Evaluates the queued window lanes: entry e -> lane e.  src/call.rs:387-403 for 4 ops per lane.
+// Evaluates the queued window lanes: entry e -> lane e.  src/call.rs:387-403 for 4 ops per lane.  (The ops are extracted here
+// anyway, so the advance is taken from (op, len): through advance4 the compiler lays the whole kernel out differently.)
 __device__ __forceinline__ void drain_queue(WaveLds &L, uint32_t &qcount, const Window &W, int lane) {
     // single-wave LDS traffic: DS instructions of one wave execute in issue order, so the queue
     // writes above are visible to the reads below without a fence; wave_barrier only pins the
@@ -199,6 +225,24 @@ __device__ __forceinline__ void drain_queue(WaveLds &L, uint32_t &qcount, const 
     }
     qcount = 0;
     __builtin_amdgcn_wave_barrier();
+}
+
+// Compacts the lanes with `inw` set behind the queue's qcount entries.  x = position after the lane's ops relative to
+// start_ext + 1, tot = their span, info & info_mask = read slot | is_2d << 6: x - tot and the mask are taken under `inw`, where
+// only window lanes pay for them.  True when the queue has grown past 64 entries: the caller drains it.
+__device__ __forceinline__ bool push_window_lanes(WaveLds &L, uint32_t &qcount, bool inw, const u32x4 w, uint32_t x,
+                                                  uint32_t tot, uint32_t info, uint32_t info_mask) {
+    const uint64_t mask = ballot64(inw);
+    if (mask) {
+        QueueEntry *const tail = &L.q[qcount];  // wave-uniform
+        if (inw) {
+            const uint32_t idx = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+            tail[idx].w = w;  // .w and .info, never a whole QueueEntry: .pad is the continuation list's
+            tail[idx].info = make_uint2(x - tot, info & info_mask);
+        }
+        qcount += (uint32_t)__popcll(mask);
+    }
+    return mask != 0ull && qcount > 64u;
 }
 
 // Per-read epilogue, one read per lane: lane k < cnt turns read k's walk (end_carry = reference_position after
@@ -302,31 +346,17 @@ __device__ __forceinline__ void walk_pairs_whole(const BatchView &b, const PairM
     tail_load();
 
     auto step = [&](const u32x4 w) {
-        const uint32_t e1 = ref_advance_raw(w.x);
-        const uint32_t e2 = e1 + ref_advance_raw(w.y);
-        const uint32_t e3 = e2 + ref_advance_raw(w.z);
-        const uint32_t tot = e3 + ref_advance_raw(w.w);
+        uint32_t e1, e2, e3, tot;
+        advance4(w, e1, e2, e3, tot);
         const uint32_t incl = wave_inclusive_scan_u32(tot);
-        lane_bad |= (kBadOp32 >> (w.x & 31u)) | (kBadOp32 >> (w.y & 31u)) | (kBadOp32 >> (w.z & 31u)) |
-                    (kBadOp32 >> (w.w & 31u));
+        lane_bad |= bad_ops(w);
         lane_range |= carry + incl;
         // x = position after this lane's ops, relative to start_ext + 1.  One of the lane's ops can start
         // inside the window only if 0 <= x and x - tot < width  <=>  x <u width + tot  (all < 2^31 inside
         // the parity domain).  Zero-filled lanes behind a read that ends inside the window pass the test too;
         // they queue four `0M` that contribute nothing, which is cheaper than a second compare on every chunk.
         const uint32_t x = (carry - W.se1) + incl;
-        const bool inw = x < W.width + tot;
-        const uint64_t mask = ballot64(inw);
-        if (mask) {
-            QueueEntry *const tail = &L.q[qcount];  // wave-uniform
-            if (inw) {
-                const uint32_t idx = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-                tail[idx].w = w;
-                tail[idx].info = make_uint2(x - tot, t_info);
-            }
-            qcount += (uint32_t)__popcll(mask);
-            if (qcount > 64u) drain_queue(L, qcount, W, lane);
-        }
+        if (push_window_lanes(L, qcount, x < W.width + tot, w, x, tot, t_info, ~0u)) drain_queue(L, qcount, W, lane);
         carry += readlane_u32(incl, 63);
         ++tc;
         if (tc >= t_nchunks) {
@@ -406,6 +436,23 @@ constexpr uint32_t kRowMaxGroups = 1u << (32 - RS_LEFT);
 __host__ __device__ constexpr uint32_t cigar_groups(uint32_t nc) { return (nc + 3u) >> 2; }
 static_assert(cigar_groups((1u << 25) - 4u) == kRowMaxGroups - 1u && cigar_groups((1u << 25) - 3u) == kRowMaxGroups,
               "the longest read the row walk takes is 2^25 - 4 ops");
+// The row word, what a row needs of a read besides where it is and how far it has got: groups left (< kRowMaxGroups) |
+// slot << 23 | is_2d << 30 | promised << 31.  The owning lane's register holds it with slot 0, the continuation list with the slot.
+constexpr int RW_SLOT = 23, RW_2D = 30, RW_PROMISED = 31;
+static_assert((kRowMaxGroups - 1u) >> RW_SLOT == 0u && (63u << RW_SLOT) >> RW_2D == 0u, "the fields of the row word lie apart");
+__device__ __forceinline__ uint32_t rw_pack(uint32_t groups, uint32_t is_2d, bool promised) {
+    return groups | (is_2d << RW_2D) | (promised ? 1u << RW_PROMISED : 0u);
+}
+__device__ __forceinline__ uint32_t rw_groups(uint32_t rw) { return rw & (kRowMaxGroups - 1u); }
+// of a word with slot 0, for `assign`: with rw_groups' 23-bit mask there the compiler allocates locus_call_small's registers
+// differently (60 VGPRs, 76 instructions fewer, a kernel nobody has timed), so `assign` keeps the 30-bit mask it always had
+__device__ __forceinline__ uint32_t rw_groups_slot0(uint32_t rw) { return rw & ((1u << RW_2D) - 1u); }
+__device__ __forceinline__ uint32_t rw_slot(uint32_t rw) { return (rw >> RW_SLOT) & 63u; }
+__device__ __forceinline__ uint32_t rw_2d(uint32_t rw) { return (rw >> RW_2D) & 1u; }
+__device__ __forceinline__ bool rw_promised(uint32_t rw) { return (rw >> RW_PROMISED) != 0u; }
+__device__ __forceinline__ uint32_t row_state(uint32_t groups, uint32_t slot, uint32_t is_2d, bool promised) {  // RowStream::st
+    return (groups << RS_LEFT) | slot | (is_2d << 6) | (promised ? RS_STOP : 0u) | RS_LIVE;
+}
 
 // Same contract as walk_pairs_whole.  Needs a window that does not wrap (end_ext >= start_ext + 1) and a batch
 // CIGAR under 4 GiB (one buffer descriptor over all of it; 32-bit byte offsets).  `checks` (wave-uniform): some
@@ -414,7 +461,7 @@ static_assert(cigar_groups((1u << 25) - 4u) == kRowMaxGroups - 1u && cigar_group
 //
 // Two phases.  Piece 0 is needed of every read that is not settled by its descriptor alone, so it is walked
 // statically: read 4s + row in turn s, four loads in flight, no queue of idle rows.  The reads that have not
-// stopped after piece 0 are then compacted into a list in LDS (the spare words of the lane queue's entries) and
+// stopped after piece 0 are then compacted into a list in LDS (cont_put: the spare words of the lane queue's entries) and
 // walked from piece 1 on by rows that take the next of them whenever they fall idle.
 template <bool UNPHASED, int AUX>
 __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMeta &m, bool valid, int cnt,
@@ -433,11 +480,9 @@ __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMe
     const __amdgpu_buffer_rsrc_t rsrc =
         __builtin_amdgcn_make_buffer_rsrc((void *)b.cigar4, (short)0, (int)(uint32_t)(b.n_cigar4 * 16u), 0x00020000);
 
-    // what a row needs of read k besides off4 and pos, in lane k: groups (< kRowMaxGroups) | is_2d << 30 | promised << 31;
-    // lanes that own no read hold an empty one
     const uint32_t groups = cigar_groups(m.nc & 0x0fffffffu);
     const bool promised = ((m.misc >> 24) & RP_CHECKED) != 0u;
-    const uint32_t d_w = groups | ((m.nc >> 31) << 30) | (promised ? 0x80000000u : 0u);
+    const uint32_t d_w = rw_pack(groups, m.nc >> 31, promised);  // read k's row word in lane k; an empty read where none is owned
 
     // piece 0 from the read's own start
     auto issue0 = [&](const RowStream &S) -> u32x4 {
@@ -453,33 +498,19 @@ __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMe
     // PIECE0: the row's state is not carried on; the position reached goes to the read's owner through L.endc
     auto step = [&](const u32x4 w, RowStream &S, auto piece0) {
         const bool live = S.st != 0u;
-        const uint32_t e1 = ref_advance_raw(w.x);
-        const uint32_t e2 = e1 + ref_advance_raw(w.y);
-        const uint32_t e3 = e2 + ref_advance_raw(w.z);
-        const uint32_t tot = e3 + ref_advance_raw(w.w);
+        uint32_t e1, e2, e3, tot;
+        advance4(w, e1, e2, e3, tot);
         const uint32_t incl = row_inclusive_scan_u32(tot);
         const uint32_t rtot = row_last(incl);
         if (checks) {
             if (live) {
-                lane_err |= ((kBadOp32 >> (w.x & 31u)) | (kBadOp32 >> (w.y & 31u)) | (kBadOp32 >> (w.z & 31u)) |
-                             (kBadOp32 >> (w.w & 31u))) & 1u;
+                lane_err |= bad_ops(w) & 1u;
                 lane_err |= ((S.carry + incl) >> 31) << 1;
             }
         }
         // the window-lane test of walk_pairs_whole, per row
         const uint32_t x = (S.carry - W.se1) + incl;
-        const bool inw = live && x < W.width + tot;
-        const uint64_t mask = ballot64(inw);
-        if (mask) {
-            QueueEntry *const tail = &L.q[qcount];  // wave-uniform
-            if (inw) {
-                const uint32_t idx = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-                tail[idx].w = w;
-                tail[idx].info = make_uint2(x - tot, S.st & 127u);
-            }
-            qcount += (uint32_t)__popcll(mask);
-            if (qcount > 64u) drain_queue(L, qcount, W, lane);
-        }
+        if (push_window_lanes(L, qcount, live && x < W.width + tot, w, x, tot, S.st, 127u)) drain_queue(L, qcount, W, lane);
         S.carry += rtot;
         if (decltype(piece0)::value) {
             if (live && rl == 0) L.endc[S.st & 63u] = S.carry;
@@ -512,9 +543,8 @@ __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMe
             S.cur4 = r_off4;
             S.carry = r_pos + 1u;
             // an empty CIGAR, or a promised read that starts past the window: nothing to load
-            if ((r_w & 0x3fffffffu) != 0u && !((r_w >> 31) && S.carry > W.ee))
-                S.st = ((r_w & 0x3fffffffu) << RS_LEFT) | (uint32_t)(k0 + row) | (((r_w >> 30) & 1u) << 6) |
-                       ((r_w >> 31) ? RS_STOP : 0u) | RS_LIVE;
+            if (rw_groups_slot0(r_w) != 0u && !(rw_promised(r_w) && S.carry > W.ee))
+                S.st = row_state(rw_groups_slot0(r_w), (uint32_t)(k0 + row), rw_2d(r_w), rw_promised(r_w));
         }
     };
     RowStream sa{0u, 0u, 0u}, sb = sa, sc = sa, sd = sa;
@@ -550,14 +580,10 @@ __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMe
     const uint64_t cmask = ballot64(cont);
     if (cmask) {
         const int ncont = (int)__popcll(cmask);
-        // the queue entries' spare words carry the list: entry i holds the i-th read to go on as off4 and
-        // groups left | slot << 23 | is_2d << 30 | promised << 31, entry 64 + i the position it has reached.
-        // The list outlives the pushes and drains of the queue only because those touch .w and .info and
-        // never store a whole QueueEntry: keep it so, or move the list.
+        // the i-th read to go on: behind piece 0, which took kRowLanes of its groups, for the row that claims it
         if (cont) {
             const uint32_t i = __builtin_amdgcn_mbcnt_hi((uint32_t)(cmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cmask, 0u));
-            L.q[i].pad = make_uint2(m.off4 + (uint32_t)kRowLanes, (d_w - (uint32_t)kRowLanes) | ((uint32_t)lane << 23));
-            L.q[64u + i].pad.x = endc0;
+            cont_put(L, i, m.off4 + (uint32_t)kRowLanes, (d_w - (uint32_t)kRowLanes) | ((uint32_t)lane << RW_SLOT), endc0);
         }
         __builtin_amdgcn_wave_barrier();
 
@@ -573,12 +599,9 @@ __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMe
             const int k = next + below - ((idle && rl != 0) ? 1 : 0);
             next += (int)__popcll(need);
             if (idle && k < ncont) {
-                const uint2 r = L.q[k].pad;
-                const uint32_t r_w = r.y;
-                S.cur4 = r.x;
-                S.carry = L.q[64 + k].pad.x;
-                S.st = ((r_w & (kRowMaxGroups - 1u)) << RS_LEFT) | ((r_w >> 23) & 63u) | (((r_w >> 30) & 1u) << 6) |
-                       ((r_w >> 31) ? RS_STOP : 0u) | RS_LIVE;
+                uint32_t r_w;
+                cont_get(L, k, S.cur4, r_w, S.carry);
+                S.st = row_state(rw_groups(r_w), rw_slot(r_w), rw_2d(r_w), rw_promised(r_w));
             }
         };
         sa.st = sb.st = sc.st = sd.st = 0u;

@@ -1,12 +1,12 @@
-// kernels.hip — the two gfx950 kernels of the `inquiSTR call` hot path.
+// kernels.hip — the gfx950 kernels of the `inquiSTR call` hot path that walk CIGARs.
 //
-//   locus_call_small : one wavefront per locus (<= 64 offered reads).  Walks every read's
-//                      CIGAR (cigar_walk.h), keeps the per-read Call in the lane that owns
-//                      the read and reduces the locus to its two medians in registers.
-//                      Loci with more reads are appended to a work list.
-//   locus_call_big   : one 256-thread workgroup per work-list locus; the four waves share the
-//                      reads, per-read Calls go through a global scratch, the medians are
-//                      found by rank counting over the scratch.
+//   locus_call_small    : one wavefront per locus (<= 64 offered reads).  Walks the reads' CIGARs (cigar_walk.h), keeps the
+//                         per-read Call in the lane that owns the read and reduces the locus to its two medians in
+//                         registers.  Loci with more reads are appended to one of three work lists, by depth.
+//   locus_call_mid_walk : persistent workgroups over the lists.  65 .. 256 reads: one wave per locus, four reads per lane,
+//                         called outright.  Deeper: the waves of a workgroup (of a group of them past kWalkSplit reads)
+//                         share the locus' 64-read blocks and leave the Calls in a global scratch, which the workgroup
+//                         reduces on the spot up to kReduceInPlace reads and locus_call_tail (deep_select.hip) beyond.
 //
 // Reference semantics restated here (wdecoster/inquiSTR v0.13.0):
 //   genotype_repeat_unphased  src/call.rs:279-327   sort by value, split at n/2
@@ -261,7 +261,7 @@ __device__ __forceinline__ void wave_locus(const KArgs &a, uint64_t j, uint64_t 
     if (status) atomicOr(&a.status->err, status);  // per lane: index / phase errors belong to the lane's read
 }
 
-constexpr int kMediumSlots = 4;  // locus_call_medium: up to 256 reads per wave
+constexpr int kMediumSlots = 4;  // one wave per locus up to 256 reads (the shallowest of locus_call_mid_walk's lists)
 
 // AUX: cache policy of the CIGAR stream loads (0 = default, 2 = nt: read-once data)
 template <bool UNPHASED, int AUX>

@@ -13,6 +13,7 @@ import pytest
 from inquistr_amd import batch as B
 from inquistr_amd.window_bytes import _walked_pieces, mark_checked
 from tests import gen
+from tests.walkutil import _all_variants, open_ctx
 
 pytestmark = pytest.mark.gpu
 
@@ -23,32 +24,7 @@ SKIPS = range(8)
 
 @pytest.fixture(scope="module")
 def ctx():
-    from inquistr_amd import hipcall
-
-    c = hipcall.Context(0)
-    assert c.backend.startswith("hip:gfx950")
-    yield c
-    c.close()
-
-
-def _same(got, want, what):
-    assert gen.same_f64(got.phase1, want.phase1), f"phase1 differs {what}"
-    assert gen.same_f64(got.phase2, want.phase2), f"phase2 differs {what}"
-    bad = np.nonzero(got.pair_call != want.pair_call)[0]
-    assert bad.size == 0, f"pair_call differs at {bad[:8]} {what}"
-    bad = np.nonzero(got.pair_bits != want.pair_bits)[0]
-    assert bad.size == 0, f"pair_bits differs at {bad[:8]} {what}"
-    assert got.n_tie_loci == want.n_tie_loci, what
-
-
-def _all_variants(ctx, orc, batch, what, code=B.INQ_OK):
-    oc, want = orc.call_batch(batch, debug=True)
-    assert oc == code, (what, oc)
-    for name in gen.promise_variants(batch):
-        rc, got = ctx.call_batch(batch, debug=True, check=False)
-        assert rc == oc, (what, name, rc, oc)
-        if rc == B.INQ_OK:
-            _same(got, want, f"{what} {name}")
+    yield from open_ctx()
 
 
 def _add_at(bb, skip, pos, cigar, k=0):

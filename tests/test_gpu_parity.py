@@ -590,6 +590,40 @@ def test_domain_errors(ctx, orc):
     assert both(one()) == B.INQ_OK
 
 
+def _bad_index(b, k):
+    b.pair_read[k] = b.n_reads
+
+
+def _bad_n_cigar(b, k):
+    b.reads["n_cigar"][b.pair_read[k]] = b.cigar.shape[0] + 1  # past the CIGAR buffer from wherever the read starts
+
+
+@pytest.mark.parametrize("unphased", [False, True])
+@pytest.mark.parametrize("damage", [_bad_index, _bad_n_cigar])
+@pytest.mark.parametrize("depth,k", [(65, 0), (65, 64), (257, 0), (257, 256)])
+def test_descriptor_errors_in_deeper_loci(ctx, orc, depth, k, damage, unphased):
+    """bad_index / bad_n_cigar of test_domain_errors where the descriptors are loaded otherwise: depth 65 is one wave's
+    load_pair_meta per 64-read slot (pair 64: the second slot), depth 257 walk_locus' staged loads (pair 256: the block
+    a wave reaches second, its index and descriptor fetched while the wave walked its first).  The host layer checks
+    neither, so every case reaches the device.  As there, the variant is set on the valid batch and the damage done
+    after; the oracle ignores the promise byte and runs once."""
+    bb = B.BatchBuilder(unphased=unphased)
+    idx = [bb.add_read(900, B.encode_cigar([("M", 300)]), phase=1 + i % 2) for i in range(depth)]
+    bb.add_locus(1010, 1090, idx)
+    good = bb.build()
+    assert gen.checked_share(good) == 1.0
+    want = None
+    for v in gen.PROMISE_VARIANTS:
+        b = bb.build()
+        what = gen.set_promise(b, v)
+        damage(b, k)
+        if want is None:
+            want = orc.call_batch(b)[0]
+        rc, _ = ctx.call_batch(b, check=False)
+        assert rc == want == B.INQ_ERR_INDEX, (what, rc, want)
+    assert ctx.call_batch(good, check=False)[0] == B.INQ_OK  # the ctx stays usable
+
+
 @pytest.mark.parametrize("name", ["phased10k", "unphased100k", "expansion50k"])
 def test_synthetic_workload_sample(ctx, orc, name):
     wl = synth.WORKLOADS[name]

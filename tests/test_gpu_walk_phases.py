@@ -9,7 +9,7 @@ import pytest
 
 from inquistr_amd import batch as B
 from inquistr_amd.window_bytes import mark_checked
-from tests import gen
+from tests.walkutil import _all_variants, _assert_same, open_ctx
 
 pytestmark = pytest.mark.gpu
 
@@ -19,22 +19,7 @@ COUNTS = (1, 3, 4, 5, 63, 64)
 
 @pytest.fixture(scope="module")
 def ctx():
-    from inquistr_amd import hipcall
-
-    c = hipcall.Context(0)
-    assert c.backend.startswith("hip:gfx950")
-    yield c
-    c.close()
-
-
-def _assert_same(got, want, what):
-    assert gen.same_f64(got.phase1, want.phase1), f"phase1 differs {what}"
-    assert gen.same_f64(got.phase2, want.phase2), f"phase2 differs {what}"
-    bad = np.nonzero(got.pair_call != want.pair_call)[0]
-    assert bad.size == 0, f"pair_call differs at {bad[:8]} {what}"
-    bad = np.nonzero(got.pair_bits != want.pair_bits)[0]
-    assert bad.size == 0, f"pair_bits differs at {bad[:8]} {what}"
-    assert got.n_tie_loci == want.n_tie_loci, what
+    yield from open_ctx()
 
 
 def _call(ctx, orc, batch, what):
@@ -44,11 +29,6 @@ def _call(ctx, orc, batch, what):
     if rc == B.INQ_OK:
         _assert_same(got, want, what)
     return rc
-
-
-def _all_variants(ctx, orc, batch, what):
-    for name in gen.promise_variants(batch):
-        assert _call(ctx, orc, batch, f"{what} {name}") == B.INQ_OK
 
 
 def _stops(k):

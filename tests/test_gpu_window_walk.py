@@ -10,28 +10,14 @@ import pytest
 from inquistr_amd import batch as B
 from inquistr_amd.window_bytes import mark_checked
 from tests import gen
+from tests.walkutil import _all_variants, _assert_same, open_ctx
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def ctx():
-    from inquistr_amd import hipcall
-
-    c = hipcall.Context(0)
-    assert c.backend.startswith("hip:gfx950")
-    yield c
-    c.close()
-
-
-def _assert_same(got, want, what):
-    assert gen.same_f64(got.phase1, want.phase1), f"phase1 differs {what}"
-    assert gen.same_f64(got.phase2, want.phase2), f"phase2 differs {what}"
-    bad = np.nonzero(got.pair_call != want.pair_call)[0]
-    assert bad.size == 0, f"pair_call differs at {bad[:8]} {what}"
-    bad = np.nonzero(got.pair_bits != want.pair_bits)[0]
-    assert bad.size == 0, f"pair_bits differs at {bad[:8]} {what}"
-    assert got.n_tie_loci == want.n_tie_loci, what
+    yield from open_ctx()
 
 
 def _both(ctx, orc, batch, what=""):
@@ -50,18 +36,6 @@ def _both(ctx, orc, batch, what=""):
         codes.append(rc)
     assert codes[0] == codes[1]
     return codes[0]
-
-
-def _all_variants(ctx, orc, batch, what=""):
-    """One oracle result (the oracle never reads the byte), the batch called under every promise variant of tests/gen.py;
-    returns the status code."""
-    oc, want = orc.call_batch(batch, debug=True)
-    for name in gen.promise_variants(batch):
-        rc, got = ctx.call_batch(batch, debug=True, check=False)
-        assert rc == oc, (what, name, rc, oc)
-        if rc == B.INQ_OK:
-            _assert_same(got, want, f"{what} {name}")
-    return oc
 
 
 @pytest.mark.parametrize("seed", range(256))
