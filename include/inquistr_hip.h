@@ -201,8 +201,8 @@ int inq_ctx_timing_reset(inq_ctx_t *ctx);
  * the following batches is offered more than N reads (N <= 64 skips the two launches behind the first kernel - which cost a few
  * microseconds when nothing deep is there; a violated promise is reported as INQ_ERR_ARG), 0 (default) = unknown;
  * "verify_crc" = 0 skips the CRC32 check of the device front end (default 1);
- * "inflate_algo" = 0 inflates with one workgroup per BGZF block (no latency floor, 0.54-0.82 ms per 1000 blocks), 1 with one
- * lane per block (36-56 ms for up to ~65 000 blocks), 2 (default) = the quicker one, which is 0 at every size measured;
+ * "inflate_algo" = 0 or 2: accepted, no effect - the inflate runs one workgroup per BGZF block, the one kernel there is (0 named
+ * it and 2 meant "the quicker one" while a lane-per-block kernel was selectable as 1); 1 and any other value: INQ_ERR_ARG;
  * "inflate_lit_pairs" = 1 / 0: the workgroup inflate's symbol loop decodes a second literal from the same 32 bits as the first
  * (+18 - 24 % on sequence / quality bytes) or not (CIGAR-only records lose 4.6 % to the wasted look); -1 (default) = decided per
  * call from the code lengths in a few sampled block headers;
@@ -270,8 +270,8 @@ typedef struct inq_bgzf_block {
 #define INQ_INFLATE_BAD_STORED 0x20u    /* stored block LEN / NLEN mismatch                                    */
 #define INQ_INFLATE_BAD_CRC 0x40u       /* inflated bytes do not match the CRC32 of the block's trailer        */
 
-/* Inflates n_blocks BGZF payloads; every pointer is HOST memory (the call uploads, runs one workgroup or one
- * lane per block - ctx option "inflate_algo" -, downloads, synchronises).  block_status may be NULL.  Returns INQ_ERR_INFLATE if any block
+/* Inflates n_blocks BGZF payloads; every pointer is HOST memory (the call uploads, runs one workgroup
+ * per block - ctx option "inflate_algo" no longer selects anything: 0 and 2 are accepted, 1 is INQ_ERR_ARG -, downloads, synchronises).  block_status may be NULL.  Returns INQ_ERR_INFLATE if any block
  * failed.  `comp` holds whole BGZF blocks: the 8 bytes behind every payload are its CRC32 / ISIZE trailer,
  * and the inflated bytes are checked against that CRC32 as htslib does (ctx option "verify_crc", default 1). */
 int inq_bgzf_inflate(inq_ctx_t *ctx, const uint8_t *comp, uint64_t comp_bytes, const inq_bgzf_block_t *blocks,

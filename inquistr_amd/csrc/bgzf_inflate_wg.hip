@@ -1,9 +1,10 @@
 // bgzf_inflate_wg.hip — DEFLATE (RFC 1951) of BGZF blocks, ONE WORKGROUP PER BLOCK, every lane decoding.
 //
 // Replaces, for the device front end, the zlib inflate htslib runs under bam.fetch()/rc_records()
-// (reference call sites src/call.rs:288,294,338,345; [3P] htslib bgzf.c).  The lane-per-block kernel
-// (bgzf_inflate.hip) is bound by the latency of one lane's serial decode (~36 ms per 64 KB block, whatever
-// the number of blocks), so a file of 20 000 blocks keeps a quarter of the chip busy for 36 ms.  Here a
+// (reference call sites src/call.rs:288,294,338,345; [3P] htslib bgzf.c).  Round 1's kernel gave every
+// block a lane of its own; it was bound by the latency of one lane's serial decode (a floor of 36-56 ms, whatever
+// the number of blocks, against 0.54-0.82 ms per 1000 blocks here), so a file of 20 000 blocks kept a quarter of the
+// chip busy for 36 ms.  It lost at every size measured since round 2 and was removed.  Here a
 // workgroup of T lanes decodes ONE block together:
 //
 //   * Huffman decode is parallel INSIDE the deflate stream.  A round hands every lane a 32-byte segment of
@@ -58,9 +59,6 @@ namespace {
 #define INQ_WG_DISTBITS 8
 #endif
 constexpr int kLitBits = INQ_WG_LITBITS, kDistBits = INQ_WG_DISTBITS;
-#ifndef INQ_WG_LITFIRST
-#define INQ_WG_LITFIRST 1
-#endif
 #ifndef INQ_WG_STRETCH_SEGS
 #define INQ_WG_STRETCH_SEGS (INQ_WG_T / 2)
 #endif
@@ -72,38 +70,11 @@ constexpr int kMaxLit = 288, kMaxDist = 32;
 
 constexpr uint32_t E_LIT = 0u, E_LEN = 1u, E_EOB = 2u, E_LONG = 3u;
 // table entry: bits 0-3 code length (0 = not a code), 4-5 type, 6 = everything the decode loop leaves its fast path for
-// (end of block, not a code, a code longer than the table's index), and
-//   32-bit form (INQ_WG_LUT16 = 0): 8-11 extra bits, 16-31 literal / base value
-//   16-bit form (INQ_WG_LUT16 = 1): 7-15 a literal's byte, or a length / distance symbol's INDEX - extra bits and base are
-//     arithmetic in the index (RFC 1951 3.2.5), a handful of operations on the match path in exchange for 2.5 KB of LDS
-//     (17.9 instead of 20.4 KB per workgroup: nine BGZF blocks in flight per CU instead of eight)
-#ifndef INQ_WG_LUT16
-#define INQ_WG_LUT16 0
-#endif
+// (end of block, not a code, a code longer than the table's index), 8-11 extra bits, 16-31 literal / base value.  (A 16-bit
+// entry that holds a symbol's index instead was built, measured and removed: DESIGN.md 3.3.)
 constexpr uint32_t kSpecial = 0x40u;
 constexpr uint32_t kLongEntry = (E_LONG << 4) | kSpecial;  // code longer than the table's index: canonical path
 constexpr uint32_t kNoCode = kSpecial;
-#if INQ_WG_LUT16
-typedef uint16_t lut_t;
-constexpr uint32_t kValShift = 7u;
-__device__ __forceinline__ uint32_t mk_entry(uint32_t n, uint32_t type, uint32_t, uint32_t val) { return n | (type << 4) | (val << kValShift); }
-__device__ __forceinline__ uint32_t len_xbits(uint32_t e) {
-    const uint32_t s = e >> kValShift;
-    return (s < 8u || s == 28u) ? 0u : (s - 4u) >> 2;
-}
-__device__ __forceinline__ uint32_t len_base(uint32_t e, uint32_t xb) {
-    const uint32_t s = e >> kValShift;
-    return s < 8u ? 3u + s : s == 28u ? 258u : 3u + ((4u + (s & 3u)) << xb);
-}
-__device__ __forceinline__ uint32_t dist_xbits(uint32_t d) {
-    const uint32_t s = d >> kValShift;
-    return s < 4u ? 0u : (s - 2u) >> 1;
-}
-__device__ __forceinline__ uint32_t dist_base(uint32_t d, uint32_t xb) {
-    const uint32_t s = d >> kValShift;
-    return s < 4u ? 1u + s : 1u + ((2u + (s & 1u)) << xb);
-}
-#else
 typedef uint32_t lut_t;
 constexpr uint32_t kValShift = 16u;
 __device__ __forceinline__ uint32_t mk_entry(uint32_t n, uint32_t type, uint32_t xb, uint32_t val) {
@@ -113,31 +84,22 @@ __device__ __forceinline__ uint32_t len_xbits(uint32_t e) { return (e >> 8) & 15
 __device__ __forceinline__ uint32_t len_base(uint32_t e, uint32_t) { return e >> kValShift; }
 __device__ __forceinline__ uint32_t dist_xbits(uint32_t d) { return (d >> 8) & 15u; }
 __device__ __forceinline__ uint32_t dist_base(uint32_t d, uint32_t) { return d >> kValShift; }
-#endif
 // RFC 1951 3.2.5: literal/length symbol -> entry
 __device__ __forceinline__ uint32_t ll_entry(uint32_t sym, uint32_t n) {
     if (sym < 256u) return mk_entry(n, E_LIT, 0u, sym);
     if (sym == 256u) return mk_entry(n, E_EOB, 0u, 0u) | kSpecial;
     const uint32_t s = sym - 257u;
     if (s >= 29u) return kNoCode;  // 286, 287 take part in the fixed code but never appear in valid data
-#if INQ_WG_LUT16
-    return mk_entry(n, E_LEN, 0u, s);
-#else
     if (s < 8u) return mk_entry(n, E_LEN, 0u, 3u + s);
     if (s == 28u) return mk_entry(n, E_LEN, 0u, 258u);
     const uint32_t xb = (s - 4u) >> 2;
     return mk_entry(n, E_LEN, xb, 3u + ((4u + (s & 3u)) << xb));
-#endif
 }
 __device__ __forceinline__ uint32_t dist_entry(uint32_t sym, uint32_t n) {
     if (sym >= 30u) return kNoCode;
-#if INQ_WG_LUT16
-    return mk_entry(n, E_LEN, 0u, sym);
-#else
     if (sym < 4u) return mk_entry(n, E_LEN, 0u, 1u + sym);
     const uint32_t xb = (sym - 2u) >> 1;
     return mk_entry(n, E_LEN, xb, 1u + ((2u + (sym & 1u)) << xb));
-#endif
 }
 
 template <int T>
@@ -180,9 +142,6 @@ struct WgLds {
     // block-uniform state
     uint32_t P, out, status, last, type, eob, hlit, hdist, flag;
     uint32_t red[T / 64], red2[T / 64];
-#ifdef INQ_WG_PAD  // experiments only (tools/inflate_occupancy.sh): bytes of LDS nobody uses, so that fewer workgroups share a CU
-    uint32_t pad[INQ_WG_PAD / 4];
-#endif
 };
 
 // root values: < 32768 a byte of an earlier stretch (deflate distances are <= 32768), 32768 .. 32768 + kRoundCap a byte of
@@ -367,15 +326,10 @@ __device__ __forceinline__ uint32_t decode_segment(WgLds<T> &L, uint32_t start, 
     while (b.pos < lim) {
         const uint32_t bits = b.peek();
         uint32_t e = L.lut_ll[bits & ((1u << kLitBits) - 1u)];
-#if INQ_WG_LITFIRST
         // a plain literal - the table's most frequent answer in sequence / quality bytes - is recognised by ONE test; everything
         // else (a length, or one of the three rare cases behind kSpecial) takes the second
         bool lit = !(e & (kSpecial | (E_LEN << 4)));
         if (!lit && (e & kSpecial)) {
-#else
-        bool lit;
-        if (e & kSpecial) {  // one test keeps the three rare cases out of the loop's fast path
-#endif
             if (e == kLongEntry) e = canon_entry<T>(L, 0, __brev(bits) >> 17, kLitBits + 1);
             if (e & kSpecial) {
                 if (e & 15u) {  // end of block (a code has a length; "not a code" has none)
@@ -384,18 +338,9 @@ __device__ __forceinline__ uint32_t decode_segment(WgLds<T> &L, uint32_t start, 
                 } else stop = kStopped;
                 break;
             }
-#if INQ_WG_LITFIRST
             lit = !(e & (E_LEN << 4));
-#endif
         }
-#if !INQ_WG_LITFIRST
-        lit = !(e & (E_LEN << 4));
-#endif
-#if INQ_WG_LUT16
-        const uint32_t n = e & 15u;  // (extra bits: computed on the match path only, below)
-#else
         const uint32_t n = e & 15u, xb = len_xbits(e);  // a literal has no extra bits
-#endif
         constexpr bool PAIR = FORM == 1;
         if constexpr (PAIR) {
             if (lit) {
@@ -430,11 +375,7 @@ __device__ __forceinline__ uint32_t decode_segment(WgLds<T> &L, uint32_t start, 
                 continue;
             }
         } else {
-#if INQ_WG_LUT16
-            if (lit) b.consume(n);
-#else
             b.consume(n + xb);
-#endif
             if (lit) {
                 if (MODE == 2) out[o + nb] = (uint8_t)(e >> kValShift);
                 if (MODE == 1) L.root[o + nb - r0] = (uint16_t)(kRootLit | (e >> kValShift));  // the byte itself: stored by the gather, coalesced
@@ -446,12 +387,7 @@ __device__ __forceinline__ uint32_t decode_segment(WgLds<T> &L, uint32_t start, 
                 continue;
             }
         }
-#if INQ_WG_LUT16
-        const uint32_t xb = len_xbits(e);
-        b.consume(n + xb);
-#else
         if constexpr (PAIR) b.consume(n + xb);
-#endif
         const uint32_t len = len_base(e, xb) + __builtin_amdgcn_ubfe(bits, n, xb);
         const uint32_t dbits = b.peek();
         uint32_t d = L.lut_d[dbits & ((1u << kDistBits) - 1u)];
@@ -1166,16 +1102,10 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(INQ_WG_WAVES,
 #endif
 }
 
-#ifndef INQ_WG_T
-#define INQ_WG_T 128
-#endif
 uint64_t inflate_token_words(uint64_t n_blocks) { return n_blocks * (uint64_t)kTokCap * INQ_WG_T; }
 
 void launch_bgzf_inflate_wg(const InflateArgs &a, hipStream_t s) {
     if (!a.n_blocks) return;
-#ifndef INQ_WG_T
-#define INQ_WG_T 128
-#endif
     constexpr int T = INQ_WG_T;
     // two forms of the symbol loop: a second literal decoded from the same peek (literal-heavy data: sequence / quality
     // bytes, +18 - 24 %), or not (match-heavy data, CIGAR-only records: the second look costs 4.6 % there).  The caller says

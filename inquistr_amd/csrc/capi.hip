@@ -662,9 +662,8 @@ int inq_ctx_set_option(inq_ctx_t *c, const char *key, int64_t value) {
         return INQ_OK;
     }
     if (std::strcmp(key, "inflate_algo") == 0) {
-        if (value < 0 || value > 2) return INQ_ERR_ARG;
-        c->inflate_algo = (uint32_t)value;
-        return INQ_OK;
+        // one kernel is left (a workgroup per BGZF block): 0 names it, 2 used to mean "the quicker one", 1 was the removed one
+        return value == 0 || value == 2 ? INQ_OK : INQ_ERR_ARG;
     }
     if (std::strcmp(key, "inflate_lit_pairs") == 0) {
         c->inflate_lit_pairs = value < 0 ? -1 : (value != 0);

@@ -62,7 +62,6 @@ struct inq_ctx {
     // kernels behind it run at 5.4 - 6.2 instead of 4.9 - 5.3 TB/s of algorithmic bytes (profiles/r04_results/locus_kernels_in_the_cli.txt)
     bool gather_nt = true;
     uint64_t batch_loci_hint = 0;  // inq_call_span_deferred: loci the caller lets a batch collect before it flushes (0 = no word)
-    uint32_t inflate_algo = 2;  // 0 = workgroup per BGZF block, 1 = lane per block, 2 = the quicker one (0 since round 2)
     // Buffers that were outgrown.  Growing one used to mean hipDeviceSynchronize + hipFree + hipMalloc on the spot; both calls wait for
     // EVERY stream of the device - in the span loop that is the 5 ms upload of the next span on the copy stream, ten times per file
     // (profiles/r04_results/span_loop_growth_stalls.txt).  hipMalloc alone costs 10 - 200 us whatever the size (tools/alloc_probe.hip),

@@ -1,4 +1,4 @@
-// front_kernels.h — argument blocks and launchers of the device front end (bgzf_inflate.hip, bam_scan.hip),
+// front_kernels.h — argument blocks and launchers of the device front end (bgzf_inflate.hip, bgzf_inflate_wg.hip, bam_scan.hip, outlier.hip),
 // shared with span.hip which sequences them behind inq_call_span().
 #pragma once
 #include <hip/hip_runtime.h>
@@ -17,13 +17,13 @@ struct InflateArgs {
     uint64_t out_bytes;
     uint32_t *block_status;  // [n_blocks] or null
     unsigned int *err;       // OR of the INQ_INFLATE_* bits of all blocks
-    uint32_t debug_flags;    // timing experiments only: 1 = drop literal stores, 2 = drop match copies, 4 = block_status receives shader kilo-cycles
+    uint32_t debug_flags;    // bit 8: block_status receives the inflate kernel's per-block probe (counts, kilo-cycles); only in a build with -DINQ_INFLATE_DEBUG_ENV
     uint32_t verify_crc;     // also check every block against the CRC32 of its trailer (comp holds whole blocks)
-    uint32_t algo;           // 0 = one workgroup per block (bgzf_inflate_wg.hip), 1 = one lane per block (bgzf_inflate.hip), 2 = by block count
-    // workgroup kernel: scratch for the symbols of a round as decoded by the counting passes (inflate_token_words(n_blocks)
+    uint32_t : 32;           // (the slot of a retired field: what lies behind it keeps its offset in the kernels' argument block)
+    // scratch for the symbols of a round as decoded by the counting passes (inflate_token_words(n_blocks)
     // u32), so that the commit does not decode them again; null = the commit decodes (round 2's form)
     uint32_t *tokens;
-    uint32_t lit_pairs;  // workgroup kernel: 1 = the symbol loop looks for a second literal behind a literal (literal-heavy data)
+    uint32_t lit_pairs;  // 1 = the symbol loop looks for a second literal behind a literal (literal-heavy data)
 };
 uint64_t inflate_token_words(uint64_t n_blocks);
 void launch_bgzf_inflate(const InflateArgs &a, hipStream_t s);

@@ -230,14 +230,13 @@ int upload_and_inflate(inq_ctx *c, SpanState *S, const uint8_t *comp, uint64_t c
     ia.err = &S->d_st->inflate;
     ia.verify_crc = c->verify_crc ? 1u : 0u;
     ia.debug_flags = 0u;
-    // timing experiments only (drops stores: wrong bytes); reads nothing unless built with -DINQ_DEBUG_ENV
+    // the inflate kernel's probe (InflateArgs::debug_flags); reads nothing unless built with -DINQ_DEBUG_ENV
     if (const char *dbg = debug_env("INQ_INFLATE_DEBUG")) ia.debug_flags = (uint32_t)std::atoi(dbg);
-    ia.algo = c->inflate_algo;
     // literal-heavy or match-heavy?  (the host still has the compressed bytes: a few block headers are read; option
     // "inflate_lit_pairs" = 0 / 1 forces a form, -1 = look)
     ia.lit_pairs = c->inflate_lit_pairs < 0 ? inflate_wants_literal_pairs(comp, comp_bytes, blocks, n_blocks) : (uint32_t)c->inflate_lit_pairs;
     ia.tokens = nullptr;
-    if (ia.algo != 1u && (c->inflate_tokens < 0 ? ia.lit_pairs == 0u : c->inflate_tokens != 0)) {
+    if (c->inflate_tokens < 0 ? ia.lit_pairs == 0u : c->inflate_tokens != 0) {
         if ((rc = ensure(c, S->tok, inflate_token_words(n_blocks) * 4)) != INQ_OK) return rc;
         ia.tokens = (uint32_t *)S->tok.p;
     }
@@ -774,10 +773,9 @@ int span_stage_begin_impl(inq_ctx *c, const inq_span_t *sp, int slot) {
         ia.err = g.d_err;
         ia.verify_crc = c->verify_crc ? 1u : 0u;
         ia.debug_flags = 0u;
-        ia.algo = c->inflate_algo;
         ia.lit_pairs = c->inflate_lit_pairs < 0 ? inflate_wants_literal_pairs(sp->comp, sp->comp_bytes, sp->blocks, nb) : (uint32_t)c->inflate_lit_pairs;
         ia.tokens = nullptr;
-        if (ia.algo != 1u && (c->inflate_tokens < 0 ? ia.lit_pairs == 0u : c->inflate_tokens != 0)) {
+        if (c->inflate_tokens < 0 ? ia.lit_pairs == 0u : c->inflate_tokens != 0) {
             if ((rc = ensure(c, g.tok, inflate_token_words(nb) * 4)) != INQ_OK) return rc;
             ia.tokens = (uint32_t *)g.tok.p;
         }

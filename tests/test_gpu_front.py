@@ -12,12 +12,12 @@ from inquistr_amd import hipcall
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module", params=[(0, 0, 1), (0, 1, 0), (0, -1, -1), (1, 0, -1)],
-                ids=["inflate_wg_literal_pairs", "inflate_wg_no_pairs_commit_from_tokens", "inflate_wg_form_by_the_data", "inflate_lane"])
+@pytest.fixture(scope="module", params=[(0, 0, 1), (0, 1, 0), (0, -1, -1)],
+                ids=["inflate_wg_literal_pairs", "inflate_wg_no_pairs_commit_from_tokens", "inflate_wg_form_by_the_data"])
 def ctx(request):
-    """Both inflate kernels go through every test of this file: workgroup per block - its symbol loop with and without the second
-    literal per peek, its commit decoding again and fed from tokens, and the form chosen from the block headers as the product
-    does - and lane per block."""
+    """The inflate kernel (a workgroup per block) goes through every test of this file in three forms: its symbol loop with and
+    without the second literal per peek, its commit decoding again and fed from tokens, and the form chosen from the block
+    headers as the product does."""
     c = hipcall.Context(0)
     c.set_option("inflate_algo", request.param[0])
     c.set_option("inflate_tokens", request.param[1])
@@ -918,3 +918,17 @@ def test_many_spans_with_staged_uploads_equal_the_host_front_end(tmp_path, monke
     assert texts["host"] == texts["device64"] == texts["device64_inflated_when_staged"] == texts["device"] == texts["auto"]
     rows = texts["host"].splitlines()
     assert len(rows) == 20_001 and not any(r.endswith("NaN\tNaN") for r in rows[1:])
+
+
+def test_inflate_algo_option_names_the_one_kernel_left():
+    """Option "inflate_algo" through the C ABI on a live context: 0 (a workgroup per block) and 2 (once "the quicker one", which
+    was 0) are accepted and change nothing; 1 (the lane-per-block kernel, removed) and values that never meant anything are
+    INQ_ERR_ARG."""
+    c = hipcall.Context(0)
+    try:
+        for v in (0, 2):
+            assert c._L.inq_ctx_set_option(c._h, b"inflate_algo", v) == hipcall.INQ_OK
+        for v in (1, 3, -1):
+            assert c._L.inq_ctx_set_option(c._h, b"inflate_algo", v) == hipcall.INQ_ERR_ARG
+    finally:
+        c.close()

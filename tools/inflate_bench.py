@@ -109,10 +109,6 @@ def main():
             names = ["deflate blocks", "rounds", "count passes", "kcyc header parse", "kcyc tables", "kcyc counting", "kcyc commit", "kcyc matches"]
             for k, nm in enumerate(names):
                 print(f"  {nm}: mean {v[:, k].mean():.1f} median {np.median(v[:, k]):.1f} max {v[:, k].max():.0f}")
-        if int(os.environ["INQ_INFLATE_DEBUG"]) & 4:
-            kc = st.astype(np.float64)
-            print(f"shader kilo-cycles per lane: median {np.median(kc):.0f}, max {kc.max():.0f}; with the kernel time above that is "
-                  f"{kc.max() * 1024 / (ms * 1e-3) / 1e9:.2f} GHz if the slowest lane spans the kernel")
         return
     # spot check against zlib
     b = blocks[len(blocks) // 2]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU box: the inflate fuzz of tests/test_gpu_front.py with other seeds (accept / reject and bytes vs zlib).
-usage: python tools/soak_inflate.py [rounds of 4000 damaged streams] [rounds of 1500 valid blocks per kernel]"""
+usage: python tools/soak_inflate.py [rounds of 4000 damaged streams] [rounds of 1500 valid blocks per form of the kernel]"""
 import os
 import random
 import sys
@@ -10,7 +10,7 @@ import tests.test_gpu_front as t  # noqa: E402
 from inquistr_amd import hipcall  # noqa: E402
 
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-valid_rounds = int(sys.argv[2]) if len(sys.argv) > 2 else max(1, rounds // 2)  # 1500 blocks each, per kernel (slow to generate)
+valid_rounds = int(sys.argv[2]) if len(sys.argv) > 2 else max(1, rounds // 2)  # 1500 blocks each, per form (slow to generate)
 ctx = hipcall.Context(0)
 orig = random.Random
 for r in range(rounds):
@@ -37,7 +37,7 @@ for r in range(rounds):
         print(f"round {r}: 3000 damaged libdeflate-written streams agree with zlib", flush=True)
 print(f"inflate soak done: {rounds} rounds, 0 disagreements")
 
-# ---- valid streams of many shapes, thousands of blocks per launch, both kernels, bytes against the input
+# ---- valid streams of many shapes, thousands of blocks per launch, both forms of the kernel, bytes against the input
 import struct
 import zlib
 
@@ -88,11 +88,10 @@ def _blocks(rng, n):
     return out
 
 
-for algo, tokens in ((0, 0), (0, 1), (1, 0)):  # workgroup kernel (commit decodes / commit from tokens), lane kernel
-    ctx.set_option("inflate_algo", algo)
+for tokens in (0, 1):  # commit decodes / commit from tokens
     ctx.set_option("inflate_tokens", tokens)
     ctx.set_option("inflate_lit_pairs", 1 - tokens)  # both forms of the symbol loop
-    rng = orig(int(os.environ.get("INQ_SOAK_SEED", "4242")) + algo + 10 * tokens)
+    rng = orig(int(os.environ.get("INQ_SOAK_SEED", "4242")) + 10 * tokens)
     n_blocks = 0
     for r in range(valid_rounds):
         items = _blocks(rng, 1500)
@@ -100,8 +99,8 @@ for algo, tokens in ((0, 0), (0, 1), (1, 0)):  # workgroup kernel (commit decode
         blocks = hipcall.scan_bgzf(comp)
         assert len(blocks) == len(items)
         rc, out, status = ctx.bgzf_inflate(comp, blocks, check=False)
-        assert rc == 0 and not status.any(), (algo, r, [hex(int(s)) for s in status if s][:5])
-        assert out.tobytes() == b"".join(d for _, d in items), (algo, r)
+        assert rc == 0 and not status.any(), (tokens, r, [hex(int(s)) for s in status if s][:5])
+        assert out.tobytes() == b"".join(d for _, d in items), (tokens, r)
         n_blocks += len(items)
-        print(f"  inflate_algo {algo} tokens {tokens} round {r}: {len(items)} blocks ok", flush=True)
-    print(f"inflate_algo {algo} tokens {tokens}: {n_blocks} valid blocks of nine shapes inflate to their input", flush=True)
+        print(f"  inflate_tokens {tokens} round {r}: {len(items)} blocks ok", flush=True)
+    print(f"inflate_tokens {tokens}: {n_blocks} valid blocks of nine shapes inflate to their input", flush=True)
