@@ -2,10 +2,6 @@
 // HIP only: there is no CPU fallback; without a gfx950 device every entry fails loudly.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-
-#include <chrono>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -114,6 +110,39 @@ int status_to_code(uint32_t st) {
     return INQ_OK;
 }
 
+int status_readback(inq_ctx *c, DevStatus *dst, hipStream_t s) {
+    HIP_TRY(c, hipMemcpyAsync(dst, c->d_status, sizeof(DevStatus), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemsetAsync(&c->d_status->err, 0, sizeof(unsigned int), s));
+    HIP_TRY(c, hipMemsetAsync(&c->d_status->ties, 0, sizeof(unsigned long long), s));
+    return INQ_OK;
+}
+
+DevBatch device_batch(const void *cigar, const void *reads, const void *pair_read, const void *off, const void *lstart, const void *lend,
+                      uint64_t n_reads, uint64_t n_cigar_words, uint64_t n_pairs, uint64_t n_loci, uint32_t minlen, uint32_t support,
+                      uint32_t unphased, void *p1, void *p2, void *pair_call, void *pair_bits) {
+    DevBatch d;
+    d.b = {n_reads, n_cigar_words, n_pairs, n_loci, (const uint32_t *)cigar, (const inq_read_t *)reads, (const uint32_t *)pair_read,
+           (const uint64_t *)off, (const uint32_t *)lstart, (const uint32_t *)lend, minlen, support, unphased, 0u};
+    d.r = {(double *)p1, (double *)p2, (int64_t *)pair_call, (uint8_t *)pair_bits, 0};
+    return d;
+}
+
+// with timing on: an event triple from the pool (grown as needed), its e0 recorded on s; *ev stays null with timing off
+static int timing_begin(inq_ctx *c, hipStream_t s, EvTriple **ev) {
+    *ev = nullptr;
+    if (!c->timing) return INQ_OK;
+    if (c->ev_used == c->ev_pool.size()) {
+        EvTriple t;
+        HIP_TRY(c, hipEventCreate(&t.e0));
+        HIP_TRY(c, hipEventCreate(&t.e1));
+        HIP_TRY(c, hipEventCreate(&t.e2));
+        c->ev_pool.push_back(t);
+    }
+    *ev = &c->ev_pool[c->ev_used++];
+    HIP_TRY(c, hipEventRecord((*ev)->e0, s));
+    return INQ_OK;
+}
+
 }  // namespace inq
 
 extern "C" {
@@ -154,17 +183,9 @@ int inq_ctx_create_early(int device_id, inq_ctx_t **out, volatile int *stage_rea
     if (stage_ready) *stage_ready = 0;
     int n = 0;
     // INQ_TIMING=2: where the start-up goes (the runtime's own initialisation is most of a short run)
-    const char *tenv = std::getenv("INQ_TIMING");
-    const bool verbose = tenv && tenv[0] == '2';
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!verbose) return;
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[inq ctx] %-34s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
+    HostClock clock("[inq ctx]");
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return INQ_ERR_NO_DEVICE;
-    lap("hipGetDeviceCount (runtime init)");
+    clock.lap("hipGetDeviceCount (runtime init)");
     if (device_id < 0 || device_id >= n) return INQ_ERR_ARG;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device_id) != hipSuccess) return INQ_ERR_HIP;
@@ -180,7 +201,7 @@ int inq_ctx_create_early(int device_id, inq_ctx_t **out, volatile int *stage_rea
         if (!published) inq_ctx_destroy(c);  // (a published context is the caller's to destroy: another thread may be using it)
         return code;
     };
-    lap("device properties");
+    clock.lap("device properties");
     {   // "blocking_sync" has to be known before the first stream and event are made
         int64_t v = 0;
         if (default_option("blocking_sync", &v) && v) {
@@ -194,7 +215,7 @@ int inq_ctx_create_early(int device_id, inq_ctx_t **out, volatile int *stage_rea
     // inflates behind them start while the rest of the context is still being made
     if (span_state_init(c) != INQ_OK) return fail(INQ_ERR_HIP);
     apply_default_options(c);
-    lap("hipSetDevice + copy / inflate streams, slots");
+    clock.lap("hipSetDevice + copy / inflate streams, slots");
     *out = c;
     if (stage_ready) {
         published = true;
@@ -202,17 +223,17 @@ int inq_ctx_create_early(int device_id, inq_ctx_t **out, volatile int *stage_rea
     }
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return fail(INQ_ERR_HIP);
     if (span_state_init_rest(c) != INQ_OK) return fail(INQ_ERR_HIP);
-    lap("main stream, span state");
+    clock.lap("main stream, span state");
     if (hipMalloc((void **)&c->d_status, sizeof(DevStatus)) != hipSuccess) return fail(INQ_ERR_NOMEM);
     if (hipMemset(c->d_status, 0, sizeof(DevStatus)) != hipSuccess) return fail(INQ_ERR_HIP);
     if (hipHostMalloc((void **)&c->h_status, sizeof(DevStatus), hipHostMallocDefault) != hipSuccess) return fail(INQ_ERR_NOMEM);
-    lap("status buffers");
+    clock.lap("status buffers");
     // load the code objects while the caller is still busy opening its input
     preload_locus(c->stream);
     preload_inflate(c->stream);
     preload_scan(c->stream);
     if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(INQ_ERR_HIP);
-    lap("code objects (3 empty launches)");
+    clock.lap("code objects (3 empty launches)");
     return INQ_OK;
 }
 
@@ -254,8 +275,7 @@ void inq_ctx_destroy(inq_ctx_t *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->span) span_state_destroy(c->span);
     purge_retired(c);
-    for (DevBuf *b : {&c->worklist, &c->sval, &c->smeta, &c->deep, &c->cigar, &c->reads, &c->pair_read, &c->off, &c->lstart,
-                      &c->lend, &c->p1, &c->p2, &c->pcall, &c->pbits, &c->ovalues, &c->olen, &c->oflags, &c->okeep, &c->otrans})
+    for (DevBuf *b : c->bufs())
         if (b->p) (void)hipFree(b->p);
     for (auto &e : c->ev_pool) {
         (void)hipEventDestroy(e.e0);
@@ -317,8 +337,8 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     if ((rc = ensure(c, c->smeta, (size_t)b->n_pairs)) != INQ_OK) return rc;
     // loci of more than kGridSelectMin reads are reduced over the whole grid (deep_select.hip): a state of 74 KB each, and there
     // cannot be more of them than n_pairs / kGridSelectMin; nothing is allocated or launched when the depth hint rules them out
-    const uint32_t hint0 = c->call_hint ? c->call_hint : c->max_reads_hint;
-    const bool deep_possible = b->n_pairs > kGridSelectMin && !(hint0 && hint0 <= kGridSelectMin);
+    const uint32_t hint = c->call_hint ? c->call_hint : c->max_reads_hint;
+    const bool deep_possible = b->n_pairs > kGridSelectMin && !(hint && hint <= kGridSelectMin);
     if (deep_possible && (rc = ensure(c, c->deep, deep_select_scratch_bytes(b->n_pairs))) != INQ_OK) return rc;
 
     KArgs a;
@@ -344,7 +364,6 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     a.smeta = (uint8_t *)c->smeta.p;
     a.blocks_per_xcd = per_xcd;
     a.shard_cap = shard_cap;
-    const uint32_t hint = c->call_hint ? c->call_hint : c->max_reads_hint;
     c->call_hint = 0;
     a.max_reads_hint = hint;
     a.locus_flags = d_flags;
@@ -352,18 +371,8 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     // CIGAR words of a read referenced by one locus only are read exactly once: stream them past the
     // caches (nt).  Reads shared by neighbouring loci keep the default policy so the second locus hits L2.
     const bool nt = c->nt_loads < 0 ? (b->n_pairs <= b->n_reads) : (c->nt_loads != 0);
-    EvTriple *ev = nullptr;
-    if (c->timing) {
-        if (c->ev_used == c->ev_pool.size()) {
-            EvTriple t;
-            HIP_TRY(c, hipEventCreate(&t.e0));
-            HIP_TRY(c, hipEventCreate(&t.e1));
-            HIP_TRY(c, hipEventCreate(&t.e2));
-            c->ev_pool.push_back(t);
-        }
-        ev = &c->ev_pool[c->ev_used++];
-        HIP_TRY(c, hipEventRecord(ev->e0, s));
-    }
+    EvTriple *ev;
+    if ((rc = timing_begin(c, s, &ev)) != INQ_OK) return rc;
     if (d_flags) HIP_TRY(c, hipMemsetAsync(d_flags, 0, (size_t)b->n_loci, s));  // the kernels store tie loci only
     launch_locus_call(a, b->unphased != 0, nt, grid_small, c->grid_medium, c->grid_tail, s, ev ? ev->e1 : nullptr, deep_possible ? c->deep.p : nullptr);
     HIP_TRY(c, hipGetLastError());
@@ -376,27 +385,18 @@ int inq_call_batch_device(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, v
 }
 
 int inq_call_batch_device_flags(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *d_locus_flags, void *hip_stream) {
-    try {  // nothing may unwind across the C ABI
-        return enqueue_batch(c, b, r, hip_stream, d_locus_flags);
-    } catch (const std::bad_alloc &) {
-        return INQ_ERR_NOMEM;
-    } catch (...) {
-        return INQ_ERR_HIP;
-    }
+    return guarded([&] { return enqueue_batch(c, b, r, hip_stream, d_locus_flags); });
 }
 
 int inq_ctx_status(inq_ctx_t *c, uint64_t *n_tie_loci) {
     if (!c) return INQ_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipDeviceSynchronize());
-    DevStatus h;
-    HIP_TRY(c, hipMemcpy(&h, c->d_status, sizeof h, hipMemcpyDeviceToHost));
-    if (n_tie_loci) *n_tie_loci = h.ties;
-    // clear err and ties, keep the work-list counters
-    HIP_TRY(c, hipMemsetAsync(&c->d_status->err, 0, sizeof(unsigned int), c->stream));
-    HIP_TRY(c, hipMemsetAsync(&c->d_status->ties, 0, sizeof(unsigned long long), c->stream));
+    const int rc = status_readback(c, c->h_status, c->stream);
+    if (rc != INQ_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return status_to_code(h.err);
+    if (n_tie_loci) *n_tie_loci = c->h_status->ties;
+    return status_to_code(c->h_status->err);
 }
 
 static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *h_flags) {
@@ -409,7 +409,7 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
         if (b->locus_pair_off[0] != 0 || b->locus_pair_off[b->n_loci] != b->n_pairs) return INQ_ERR_ARG;
         for (uint64_t j = 0; j < b->n_loci; ++j) {
             if (b->locus_pair_off[j] > b->locus_pair_off[j + 1]) return INQ_ERR_ARG;
-            if (b->locus_start[j] < 10 || b->locus_end[j] < b->locus_start[j]) return INQ_ERR_LOCUS;
+            if (!locus_ok(b->locus_start[j], b->locus_end[j])) return INQ_ERR_LOCUS;
             max_reads = std::max<uint64_t>(max_reads, b->locus_pair_off[j + 1] - b->locus_pair_off[j]);
         }
     }
@@ -439,22 +439,13 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
     if (r->pair_bits && (rc = ensure(c, c->pbits, (size_t)b->n_pairs)) != INQ_OK) return rc;
     if (h_flags && (rc = ensure(c, c->lflags, (size_t)b->n_loci)) != INQ_OK) return rc;
 
-    inq_batch_t db = *b;
-    db.cigar = (const uint32_t *)c->cigar.p;
-    db.reads = (const inq_read_t *)c->reads.p;
-    db.pair_read = (const uint32_t *)c->pair_read.p;
-    db.locus_pair_off = (const uint64_t *)c->off.p;
-    db.locus_start = (const uint32_t *)c->lstart.p;
-    db.locus_end = (const uint32_t *)c->lend.p;
-    inq_result_t dr;
-    dr.phase1 = (double *)c->p1.p;
-    dr.phase2 = (double *)c->p2.p;
-    dr.pair_call = r->pair_call ? (int64_t *)c->pcall.p : nullptr;
-    dr.pair_bits = r->pair_bits ? (uint8_t *)c->pbits.p : nullptr;
-    dr.n_tie_loci = 0;
+    DevBatch d = device_batch(c->cigar.p, c->reads.p, c->pair_read.p, c->off.p, c->lstart.p, c->lend.p, b->n_reads, b->n_cigar_words,
+                              b->n_pairs, b->n_loci, b->minlen, b->support, b->unphased, c->p1.p, c->p2.p,
+                              r->pair_call ? c->pcall.p : nullptr, r->pair_bits ? c->pbits.p : nullptr);
+    const inq_result_t &dr = d.r;
     c->call_hint = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(max_reads, 1), 0xffffffffull);  // skips the deep-locus launches when no locus needs them
     uint8_t *d_flags = h_flags ? (uint8_t *)c->lflags.p : nullptr;
-    if ((rc = enqueue_batch(c, &db, &dr, s, d_flags)) != INQ_OK) return rc;
+    if ((rc = enqueue_batch(c, &d.b, &d.r, s, d_flags)) != INQ_OK) return rc;
     if (h_flags) HIP_TRY(c, hipMemcpyAsync(h_flags, d_flags, (size_t)b->n_loci, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(r->phase1, dr.phase1, (size_t)b->n_loci * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(r->phase2, dr.phase2, (size_t)b->n_loci * 8, hipMemcpyDeviceToHost, s));
@@ -462,12 +453,8 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
         HIP_TRY(c, hipMemcpyAsync(r->pair_call, dr.pair_call, (size_t)b->n_pairs * 8, hipMemcpyDeviceToHost, s));
     if (r->pair_bits && b->n_pairs)
         HIP_TRY(c, hipMemcpyAsync(r->pair_bits, dr.pair_bits, (size_t)b->n_pairs, hipMemcpyDeviceToHost, s));
-    // status travels with the results: one synchronisation per call; the device copy is cleared on the
-    // same stream, i.e. before the next host-entry call's kernels
-    HIP_TRY(c, hipMemcpyAsync(c->h_status, c->d_status, sizeof(DevStatus), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemsetAsync(&c->d_status->err, 0, sizeof(unsigned int), s));
-    HIP_TRY(c, hipMemsetAsync(&c->d_status->ties, 0, sizeof(unsigned long long), s));
-    HIP_TRY(c, hipStreamSynchronize(s));
+    if ((rc = status_readback(c, c->h_status, s)) != INQ_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(s));  // the one synchronisation of the call
     purge_retired(c);  // the stream is idle: buffers this call outgrew go back now
     r->n_tie_loci = c->h_status->ties;
     return status_to_code(c->h_status->err);
@@ -476,13 +463,7 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
 int inq_call_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r) { return inq_call_batch_flags(c, b, r, nullptr); }
 
 int inq_call_batch_flags(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *locus_flags) {
-    try {
-        return call_batch_impl(c, b, r, locus_flags);
-    } catch (const std::bad_alloc &) {
-        return INQ_ERR_NOMEM;
-    } catch (...) {
-        return INQ_ERR_HIP;
-    }
+    return guarded([&] { return call_batch_impl(c, b, r, locus_flags); });
 }
 
 static int outlier_rows_impl(inq_ctx_t *c, const float *values, const uint32_t *row_len, uint64_t n_rows, uint32_t stride,
@@ -516,18 +497,8 @@ static int outlier_rows_impl(inq_ctx_t *c, const float *values, const uint32_t *
     a.mincluster = mincluster;
     a.flags = (uint8_t *)c->oflags.p;
     a.keep = (uint8_t *)c->okeep.p;
-    EvTriple *ev = nullptr;
-    if (c->timing) {
-        if (c->ev_used == c->ev_pool.size()) {
-            EvTriple t;
-            HIP_TRY(c, hipEventCreate(&t.e0));
-            HIP_TRY(c, hipEventCreate(&t.e1));
-            HIP_TRY(c, hipEventCreate(&t.e2));
-            c->ev_pool.push_back(t);
-        }
-        ev = &c->ev_pool[c->ev_used++];
-        HIP_TRY(c, hipEventRecord(ev->e0, s));
-    }
+    EvTriple *ev;
+    if ((rc = timing_begin(c, s, &ev)) != INQ_OK) return rc;
     launch_outlier(a, method, (float *)c->otrans.p, s, tile);
     HIP_TRY(c, hipGetLastError());
     if (ev) {
@@ -542,13 +513,7 @@ static int outlier_rows_impl(inq_ctx_t *c, const float *values, const uint32_t *
 
 int inq_outlier_rows(inq_ctx_t *c, const float *values, const uint32_t *row_len, uint64_t n_rows, uint32_t stride, int method,
                      uint32_t minsize, float zscore_cutoff, uint32_t mincluster, uint8_t *flags, uint8_t *keep) {
-    try {
-        return outlier_rows_impl(c, values, row_len, n_rows, stride, method, minsize, zscore_cutoff, mincluster, flags, keep);
-    } catch (const std::bad_alloc &) {
-        return INQ_ERR_NOMEM;
-    } catch (...) {
-        return INQ_ERR_HIP;
-    }
+    return guarded([&] { return outlier_rows_impl(c, values, row_len, n_rows, stride, method, minsize, zscore_cutoff, mincluster, flags, keep); });
 }
 
 int inq_ctx_timing_enable(inq_ctx_t *c, int on) {

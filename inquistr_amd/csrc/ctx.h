@@ -2,8 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <array>
+#include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <mutex>
+#include <new>
 #include <string>
 #include <utility>
 #include <vector>
@@ -36,6 +40,11 @@ struct inq_ctx {
     // staging for the host-buffer entry
     inq::DevBuf cigar, reads, pair_read, off, lstart, lend, p1, p2, pcall, pbits, lflags;
     inq::DevBuf ovalues, olen, oflags, okeep, otrans;  // inq_outlier_rows
+    // every DevBuf above, for inq_ctx_destroy (DevBuf frees nothing itself): a member missing here leaks
+    auto bufs() {
+        return std::array{&worklist, &sval, &smeta, &deep, &cigar, &reads, &pair_read, &off, &lstart, &lend, &p1, &p2, &pcall, &pbits, &lflags,
+                          &ovalues, &olen, &oflags, &okeep, &otrans};
+    }
     uint32_t n_cus = 0;        // compute units of the device
     uint32_t grid_tail = 256;  // workgroups of the persistent locus_call_tail: they meet at grid barriers, so never more than n_cus
     uint32_t grid_medium = 4096;  // (8 192: + 3 us for the launch that finds the lists empty, 0 - 4 % quicker where they are full)
@@ -97,6 +106,38 @@ inline const char *debug_env(const char *name) { return std::getenv(name); }
 #else
 inline const char *debug_env(const char *) { return nullptr; }
 #endif
+// every ABI entry that can throw runs its body through this: nothing may unwind across the C ABI
+template <class F> int guarded(F &&body) {
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        return INQ_ERR_NOMEM;
+    } catch (...) {
+        return INQ_ERR_HIP;
+    }
+}
+// INQ_TIMING=2: host clocks on stderr, each line behind `prefix` ("[inq ctx]", "[inq span host]", "[inq stage host] slot N")
+struct HostClock {
+    using clk = std::chrono::steady_clock;
+    const char *prefix;
+    bool on;
+    clk::time_point t0 = clk::now(), last = t0;
+    explicit HostClock(const char *prefix_) : prefix(prefix_) {
+        const char *e = std::getenv("INQ_TIMING");
+        on = e && e[0] == '2';
+    }
+    static double ms(clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+    void lap(const char *what) {  // since the last lap
+        if (!on) return;
+        const auto now = clk::now();
+        std::fprintf(stderr, "%s %-34s %7.2f ms\n", prefix, what, ms(last, now));
+        last = now;
+    }
+    void at(const char *what) const {  // since the start
+        if (on) std::fprintf(stderr, "%s %-28s at %.2f ms\n", prefix, what, ms(t0, clk::now()));
+    }
+};
+inline bool locus_ok(uint32_t start, uint32_t end) { return start >= 10 && end >= start; }  // else INQ_ERR_LOCUS
 // grows b to at least `bytes` (with headroom); the old buffer is retired, not freed: no synchronisation, contents NOT kept
 int ensure(inq_ctx *c, DevBuf &b, size_t bytes);
 int device_alloc(inq_ctx *c, void **out, size_t want, size_t exact, size_t *got);
@@ -105,6 +146,17 @@ void purge_retired(inq_ctx *c);  // hipFree of everything retired (waits for the
 // enqueue-only launch sequence of the locus kernels over a device-resident batch
 int call_batch_device_impl(inq_ctx *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, uint8_t *d_locus_flags = nullptr);
 int status_to_code(uint32_t st);
+// The kernels' status travels with the results: enqueues DevStatus -> dst (page-locked), then clears err and ties on the same stream,
+// i.e. before the next call's kernels (the work-list counters stay).  No synchronisation: dst is valid once the caller has waited for s.
+int status_readback(inq_ctx *c, DevStatus *dst, hipStream_t s);
+// a batch whose arrays are on the device, with the rows (and the optional per-pair outputs) it is called into
+struct DevBatch {
+    inq_batch_t b;
+    inq_result_t r;
+};
+DevBatch device_batch(const void *cigar, const void *reads, const void *pair_read, const void *off, const void *lstart, const void *lend,
+                      uint64_t n_reads, uint64_t n_cigar_words, uint64_t n_pairs, uint64_t n_loci, uint32_t minlen, uint32_t support,
+                      uint32_t unphased, void *p1, void *p2, void *pair_call = nullptr, void *pair_bits = nullptr);
 void span_state_destroy(SpanState *s);
 int span_state_init(inq_ctx *c);       // device front end state, the part staging needs (streams, slots); called by inq_ctx_create
 int span_state_init_rest(inq_ctx *c);  // ... and the part the calls need

@@ -4,7 +4,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -22,11 +21,15 @@ struct SpanState {
     DevBuf tok;  // the workgroup inflate's token scratch
     DevBuf comp, blocks, u, block_status, anchors, anchor_cnt, anchor_base, rec_off, reads, info, key, endkey, pmax, cig_off, cigar,
         anchor_stop, ltid, lstart, lend, locus_cnt, locus_off, pair_read, p1, p2, tmp;
+    auto bufs() {  // every DevBuf above, for span_state_destroy
+        return std::array{&tok, &comp, &blocks, &u, &block_status, &anchors, &anchor_cnt, &anchor_base, &rec_off, &reads, &info, &key, &endkey,
+                          &pmax, &cig_off, &cigar, &anchor_stop, &ltid, &lstart, &lend, &locus_cnt, &locus_off, &pair_read, &p1, &p2, &tmp};
+    }
     FrontStatus *d_st = nullptr;
     struct Host {  // pinned readback area
         FrontStatus st;
         DevStatus ks;
-        uint64_t val[4];
+        uint64_t count;  // what a stage of call_span_impl reads back to size the next one
         unsigned long long init_n_valid;
     } *h = nullptr;
     // pinned staging of the rows: the caller's result arrays are ordinary memory, and the FIRST copy to or from pageable
@@ -39,7 +42,7 @@ struct SpanState {
     // inq_span_stage: compressed bytes + block table + anchors of up to three spans, uploaded on their own
     // stream (possibly by another host thread) while an earlier span is being inflated
     struct Stage {
-        DevBuf comp, blocks, anchors, anchor_stop;
+        DevBuf comp;
         const void *host_comp = nullptr;
         uint64_t comp_bytes = 0, n_blocks = 0, n_anchors = 0;
         bool valid = false;
@@ -54,7 +57,10 @@ struct SpanState {
         // spans' 268 MB), and the caller's tables are free again at once
         uint8_t *h_tab = nullptr;
         size_t h_tab_cap = 0;
-        DevBuf tab;  // device side of it: blocks | anchors | anchor_stop, each 16-byte aligned
+        DevBuf tab;  // device side of it: blocks | anchors | anchor_stop, each 16-byte aligned ...
+        const inq_bgzf_block_t *blocks = nullptr;  // ... and where each of them starts in tab: pointers INTO it, nothing to grow or free
+        const uint64_t *anchors = nullptr, *anchor_stop = nullptr;
+        auto bufs() { return std::array{&comp, &u, &tok, &tab}; }  // every DevBuf of a slot
         bool pending = false;  // inq_span_stage_begin went through, inq_span_stage_wait has not
     } stage[INQ_SPAN_SLOTS];  // two sets of four: the spans of the NEXT file of a cohort are staged while this file's are still being called
     hipStream_t copy_stream = nullptr;
@@ -69,6 +75,8 @@ struct SpanState {
         DevBuf cigar, reads, pair_read, off, lstart, lend;
         uint64_t n_units = 0, n_reads = 0, n_pairs = 0, n_loci = 0, n_spans = 0;
         uint32_t minlen = 0, support = 0, unphased = 0, max_reads = 0;
+        auto bufs() { return std::array{&cigar, &reads, &pair_read, &off, &lstart, &lend}; }
+        void reset() { *this = Acc{cigar, reads, pair_read, off, lstart, lend}; }  // the batch is gone, its buffers stay
     } acc;
 };
 
@@ -80,12 +88,10 @@ double span_last_inflate_ms(SpanState *S) {
 
 void span_state_destroy(SpanState *S) {
     if (!S) return;
-    for (DevBuf *b : {&S->comp, &S->blocks, &S->u, &S->block_status, &S->anchors, &S->anchor_cnt, &S->anchor_base, &S->rec_off,
-                      &S->reads, &S->info, &S->key, &S->endkey, &S->pmax, &S->cig_off, &S->cigar, &S->anchor_stop, &S->ltid, &S->lstart, &S->lend, &S->locus_cnt,
-                      &S->locus_off, &S->pair_read, &S->p1, &S->p2, &S->tmp, &S->tok})
+    for (DevBuf *b : S->bufs())
         if (b->p) (void)hipFree(b->p);
     for (auto &g : S->stage) {
-        for (DevBuf *b : {&g.comp, &g.u, &g.tok, &g.tab})  // (blocks / anchors / anchor_stop are views into tab)
+        for (DevBuf *b : g.bufs())
             if (b->p) (void)hipFree(b->p);
         if (g.d_err) (void)hipFree(g.d_err);
         if (g.h_tab) (void)hipHostFree(g.h_tab);
@@ -93,7 +99,7 @@ void span_state_destroy(SpanState *S) {
             if (e) (void)hipEventDestroy(e);
     }
     if (S->ahead_stream) (void)hipStreamDestroy(S->ahead_stream);
-    for (DevBuf *b : {&S->acc.cigar, &S->acc.reads, &S->acc.pair_read, &S->acc.off, &S->acc.lstart, &S->acc.lend})
+    for (DevBuf *b : S->acc.bufs())
         if (b->p) (void)hipFree(b->p);
     if (S->copy_stream) (void)hipStreamDestroy(S->copy_stream);
     if (S->h_warm) (void)hipHostFree(S->h_warm);
@@ -172,6 +178,18 @@ int ensure_keep(inq_ctx *c, DevBuf &b, size_t bytes, size_t used, hipStream_t s,
     return INQ_OK;
 }
 
+// the page-locked row staging (SpanState::h_rows) holds at least `needed` doubles for a call of nl loci; contents NOT kept
+int ensure_row_staging(inq_ctx *c, SpanState *S, uint64_t nl, size_t needed) {
+    if (S->h_rows_cap >= needed) return INQ_OK;
+    if (S->h_rows) (void)hipHostFree(S->h_rows);
+    S->h_rows = nullptr;
+    S->h_rows_cap = 0;
+    const size_t want = std::max<size_t>(std::max<size_t>(2 * nl + nl / 2 + 1024, needed), 1u << 16);
+    HIP_TRY(c, hipHostMalloc((void **)&S->h_rows, want * sizeof(double), hipHostMallocDefault));
+    S->h_rows_cap = want;
+    return INQ_OK;
+}
+
 // host-side shape checks of the block table: everything the inflate grid assumes
 int check_blocks(const uint8_t *comp, uint64_t comp_bytes, const inq_bgzf_block_t *blocks, uint64_t n_blocks, uint64_t out_bytes,
                  bool dense) {
@@ -188,6 +206,36 @@ int check_blocks(const uint8_t *comp, uint64_t comp_bytes, const inq_bgzf_block_
     return INQ_OK;
 }
 
+// One inflate launch.  comp / blocks: on the device; h_comp / h_blocks: the host's copies of them, of which a few block headers are
+// read to tell literal-heavy from match-heavy (option "inflate_lit_pairs" = 0 / 1 forces a form, -1 = look); tok: the token scratch,
+// grown where option "inflate_tokens" asks for it
+int inflate_launch(inq_ctx *c, const void *comp, const void *blocks, const uint8_t *h_comp, uint64_t comp_bytes, const inq_bgzf_block_t *h_blocks,
+                   uint64_t n_blocks, void *out, uint64_t out_bytes, uint32_t *block_status, unsigned int *err, DevBuf &tok, hipStream_t s) {
+    InflateArgs ia;
+    ia.comp = (const uint8_t *)comp;
+    ia.comp_bytes = comp_bytes;
+    ia.blocks = (const inq_bgzf_block_t *)blocks;
+    ia.n_blocks = n_blocks;
+    ia.out = (uint8_t *)out;
+    ia.out_bytes = out_bytes;
+    ia.block_status = block_status;
+    ia.err = err;
+    ia.verify_crc = c->verify_crc ? 1u : 0u;
+    ia.debug_flags = 0u;
+    // the inflate kernel's probe (InflateArgs::debug_flags); reads nothing unless built with -DINQ_DEBUG_ENV
+    if (const char *dbg = debug_env("INQ_INFLATE_DEBUG")) ia.debug_flags = (uint32_t)std::atoi(dbg);
+    ia.lit_pairs = c->inflate_lit_pairs < 0 ? inflate_wants_literal_pairs(h_comp, comp_bytes, h_blocks, n_blocks) : (uint32_t)c->inflate_lit_pairs;
+    ia.tokens = nullptr;
+    if (c->inflate_tokens < 0 ? ia.lit_pairs == 0u : c->inflate_tokens != 0) {
+        const int rc = ensure(c, tok, inflate_token_words(n_blocks) * 4);
+        if (rc != INQ_OK) return rc;
+        ia.tokens = (uint32_t *)tok.p;
+    }
+    launch_bgzf_inflate(ia, s);
+    HIP_TRY(c, hipGetLastError());
+    return INQ_OK;
+}
+
 // uploads the compressed bytes and the block table, clears the front status, inflates into S->u
 int upload_and_inflate(inq_ctx *c, SpanState *S, const uint8_t *comp, uint64_t comp_bytes, const inq_bgzf_block_t *blocks,
                        uint64_t n_blocks, uint64_t out_bytes, bool want_block_status, hipStream_t s,
@@ -197,7 +245,7 @@ int upload_and_inflate(inq_ctx *c, SpanState *S, const uint8_t *comp, uint64_t c
     const void *d_comp, *d_blocks;
     if (staged) {  // already on the device (inq_span_stage)
         d_comp = staged->comp.p;
-        d_blocks = staged->blocks.p;
+        d_blocks = staged->blocks;
     } else {
         if ((rc = ensure(c, S->comp, comp_bytes + kPad)) != INQ_OK) return rc;
         if ((rc = ensure(c, S->blocks, n_blocks * sizeof(inq_bgzf_block_t))) != INQ_OK) return rc;
@@ -219,30 +267,8 @@ int upload_and_inflate(inq_ctx *c, SpanState *S, const uint8_t *comp, uint64_t c
     if (want_block_status && (rc = ensure(c, S->block_status, n_blocks * 4)) != INQ_OK) return rc;
     HIP_TRY(c, hipMemsetAsync((uint8_t *)S->u.p + out_bytes, 0, kPad, s));
     HIP_TRY(c, hipEventRecord(S->ev[1], s));
-    InflateArgs ia;
-    ia.comp = (const uint8_t *)d_comp;
-    ia.comp_bytes = comp_bytes;
-    ia.blocks = (const inq_bgzf_block_t *)d_blocks;
-    ia.n_blocks = n_blocks;
-    ia.out = (uint8_t *)S->u.p;
-    ia.out_bytes = out_bytes;
-    ia.block_status = want_block_status ? (uint32_t *)S->block_status.p : nullptr;
-    ia.err = &S->d_st->inflate;
-    ia.verify_crc = c->verify_crc ? 1u : 0u;
-    ia.debug_flags = 0u;
-    // the inflate kernel's probe (InflateArgs::debug_flags); reads nothing unless built with -DINQ_DEBUG_ENV
-    if (const char *dbg = debug_env("INQ_INFLATE_DEBUG")) ia.debug_flags = (uint32_t)std::atoi(dbg);
-    // literal-heavy or match-heavy?  (the host still has the compressed bytes: a few block headers are read; option
-    // "inflate_lit_pairs" = 0 / 1 forces a form, -1 = look)
-    ia.lit_pairs = c->inflate_lit_pairs < 0 ? inflate_wants_literal_pairs(comp, comp_bytes, blocks, n_blocks) : (uint32_t)c->inflate_lit_pairs;
-    ia.tokens = nullptr;
-    if (c->inflate_tokens < 0 ? ia.lit_pairs == 0u : c->inflate_tokens != 0) {
-        if ((rc = ensure(c, S->tok, inflate_token_words(n_blocks) * 4)) != INQ_OK) return rc;
-        ia.tokens = (uint32_t *)S->tok.p;
-    }
-    launch_bgzf_inflate(ia, s);
-    HIP_TRY(c, hipGetLastError());
-    return INQ_OK;
+    return inflate_launch(c, d_comp, d_blocks, comp, comp_bytes, blocks, n_blocks, S->u.p, out_bytes,
+                          want_block_status ? (uint32_t *)S->block_status.p : nullptr, &S->d_st->inflate, S->tok, s);
 }
 
 int bgzf_inflate_impl(inq_ctx *c, const uint8_t *comp, uint64_t comp_bytes, const inq_bgzf_block_t *blocks, uint64_t n_blocks,
@@ -283,7 +309,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     }
     for (uint64_t j = 0; j < sp->n_loci; ++j) {
         if (sp->locus_tid[j] < 0) return INQ_ERR_ARG;
-        if (sp->locus_start[j] < 10 || sp->locus_end[j] < sp->locus_start[j]) return INQ_ERR_LOCUS;
+        if (!locus_ok(sp->locus_start[j], sp->locus_end[j])) return INQ_ERR_LOCUS;
     }
     if (r) r->n_tie_loci = 0;
     if (sp->n_loci == 0) return INQ_OK;
@@ -302,12 +328,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     }
 
     // ---- stage 1: upload, inflate, count the records
-    const bool verbose = std::getenv("INQ_TIMING") && std::getenv("INQ_TIMING")[0] == '2';
-    using clk = std::chrono::steady_clock;
-    const auto w0 = clk::now();
-    auto wall = [&](const char *what) {
-        if (verbose) std::fprintf(stderr, "[inq span host] %-28s at %.2f ms\n", what, std::chrono::duration<double, std::milli>(clk::now() - w0).count());
-    };
+    const HostClock clock("[inq span host]");
     HIP_TRY(c, hipEventRecord(S->ev[0], s));
     if (!staged) {
         if ((rc = ensure(c, S->anchors, na * 8)) != INQ_OK) return rc;
@@ -330,18 +351,18 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     HIP_TRY(c, hipMemcpyAsync(S->lend.p, sp->locus_end, nl * 4, hipMemcpyHostToDevice, s));
     if ((rc = upload_and_inflate(c, S, sp->comp, sp->comp_bytes, sp->blocks, nb, u_bytes, false, s, staged)) != INQ_OK) return rc;
     HIP_TRY(c, hipEventRecord(S->ev[2], s));
-    wall("buffers + uploads enqueued");
+    clock.at("buffers + uploads enqueued");
 
     ScanArgs a;
     std::memset(&a, 0, sizeof a);
     const bool ahead = staged && staged->inflated;
     a.u = (const uint8_t *)(ahead ? staged->u.p : S->u.p);
     a.u_bytes = u_bytes;
-    a.anchors = (const uint64_t *)(staged ? staged->anchors.p : S->anchors.p);
+    a.anchors = staged ? staged->anchors : (const uint64_t *)S->anchors.p;
     a.n_anchors = na;
     a.anchor_cnt = (uint32_t *)S->anchor_cnt.p;
     a.anchor_base = (uint64_t *)S->anchor_base.p;
-    a.anchor_stop = (const uint64_t *)(staged ? staged->anchor_stop.p : S->anchor_stop.p);
+    a.anchor_stop = staged ? staged->anchor_stop : (const uint64_t *)S->anchor_stop.p;
     a.locus_tid = (const int32_t *)S->ltid.p;
     a.unphased = sp->unphased;
     a.locus_start = (const uint32_t *)S->lstart.p;
@@ -353,14 +374,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     launch_chain_count(a, s);
     launch_scan_u32_to_u64(a.anchor_cnt, a.anchor_base, na, (uint64_t *)S->tmp.p, s);
     HIP_TRY(c, hipGetLastError());
-    if (S->h_rows_cap < 2 * nl) {
-        if (S->h_rows) (void)hipHostFree(S->h_rows);
-        S->h_rows = nullptr;
-        S->h_rows_cap = 0;
-        const size_t want = std::max<size_t>(2 * nl + nl / 2 + 1024, 1u << 16);
-        HIP_TRY(c, hipHostMalloc((void **)&S->h_rows, want * sizeof(double), hipHostMallocDefault));
-        S->h_rows_cap = want;
-    }
+    if ((rc = ensure_row_staging(c, S, nl, 2 * nl)) != INQ_OK) return rc;
     if (!S->copy_path_warm && u_bytes >= (512u << 10)) {
         // the first device-to-host copy of this size costs the host ~8 ms inside the runtime; spent here, on the copy stream (the
         // other direction of the uploads), it hides behind the inflate that was just enqueued instead of sitting behind the last
@@ -370,9 +384,6 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
         HIP_TRY(c, hipMemcpyAsync(S->h_warm, ahead ? staged->u.p : S->u.p, 512u << 10, hipMemcpyDeviceToHost, S->copy_stream));
         S->copy_path_warm = true;
     }
-    HIP_TRY(c, hipMemcpyAsync(&S->h->val[0], a.anchor_base + na, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&S->h->st, S->d_st, sizeof(FrontStatus), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
     auto front_fail = [&](const FrontStatus &st) -> int {
         if (stats) {
             stats->front_status = st.err | (st.inflate << 16);
@@ -383,9 +394,17 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
         if (st.err & (FS_HP_TYPE | FS_SA_TYPE | FS_SA_FORMAT)) return INQ_ERR_AUX;
         return INQ_OK;
     };
-    if ((rc = front_fail(S->h->st)) != INQ_OK) return rc;
-    const uint64_t n_rec = S->h->val[0];
-    wall("inflate + chain count done");
+    // the readback that ends each of the stages 1 - 3: one count and the front status come down, the stream drains
+    auto read_count = [&](const uint64_t *d_count, uint64_t *count) -> int {
+        HIP_TRY(c, hipMemcpyAsync(&S->h->count, d_count, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(&S->h->st, S->d_st, sizeof(FrontStatus), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        *count = S->h->count;
+        return front_fail(S->h->st);
+    };
+    uint64_t n_rec, n_units, n_pairs;
+    if ((rc = read_count(a.anchor_base + na, &n_rec)) != INQ_OK) return rc;
+    clock.at("inflate + chain count done");
 
     // ---- stage 2: record offsets, fields, CIGAR sizes
     if ((rc = ensure(c, S->rec_off, n_rec * 8)) != INQ_OK) return rc;
@@ -410,18 +429,16 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     launch_record_parse(a, s);
     launch_scan_cigar_units(a.reads, &S->d_st->n_valid, a.cig_off, n_rec, (uint64_t *)S->tmp.p, s);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(&S->h->val[1], a.cig_off + n_rec, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&S->h->st, S->d_st, sizeof(FrontStatus), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if ((rc = front_fail(S->h->st)) != INQ_OK) return rc;
-    const uint64_t n_valid = S->h->st.n_valid, n_units = S->h->val[1];
-    wall("parse done");
+    if ((rc = read_count(a.cig_off + n_rec, &n_units)) != INQ_OK) return rc;
+    const uint64_t n_valid = S->h->st.n_valid;
+    clock.at("parse done");
     if (n_valid > n_rec || n_valid >= 0xfffffff0ull || n_units >= 0xffffffffull) {
         if (stats) stats->front_status = FS_TOO_BIG;
         return INQ_ERR_BAM;
     }
 
     // ---- stage 3: CIGAR gather, reference spans, overlap join (count)
+    double batch_spans = 0.0;  // spans the batch will hold, known for the first span of a batch with the caller's word on its loci
     if (defer) {  // behind the CIGARs and reads of the spans already deferred
         if (A.n_units + n_units >= 0xffffffffull || A.n_reads + n_valid >= 0xfffffff0ull) {
             if (stats) stats->front_status = FS_TOO_BIG;
@@ -431,16 +448,14 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
         // hold ("batch_loci_hint": the driver flushes at that many) the buffers are made for the whole batch at once, instead of
         // being outgrown span after span - every growth copies what is there (0.7 GB for a CIGAR-only span) with ordinary stores
         // right in front of the locus kernels that stream the batch (profiles/r04_results/locus_kernels_in_the_cli.txt)
-        size_t res_units = 0, res_reads = 0;
-        if (A.n_spans == 0 && c->batch_loci_hint > nl && nl) {
-            const double spans = std::min(64.0, std::ceil((double)c->batch_loci_hint / (double)nl)) * 1.04;  // the flush comes with the span that reaches the hint
-            res_units = (size_t)std::min((double)(12ull << 30), (double)n_units * 16.0 * spans);
-            res_reads = (size_t)std::min((double)(4ull << 30), (double)n_valid * (double)sizeof(inq_read_t) * spans);
-        }
+        if (A.n_spans == 0 && c->batch_loci_hint > nl)
+            batch_spans = std::min(64.0, std::ceil((double)c->batch_loci_hint / (double)nl)) * 1.04;  // the flush comes with the span that reaches the hint
+        const size_t res_units = (size_t)std::min((double)(12ull << 30), (double)n_units * 16.0 * batch_spans);
+        const size_t res_reads = (size_t)std::min((double)(4ull << 30), (double)n_valid * (double)sizeof(inq_read_t) * batch_spans);
         if ((rc = ensure_keep(c, A.cigar, (A.n_units + n_units) * 16, A.n_units * 16, s, res_units)) != INQ_OK) return rc;
-        wall("  batch CIGAR buffer ready");
+        clock.at("  batch CIGAR buffer ready");
         if ((rc = ensure_keep(c, A.reads, (A.n_reads + n_valid) * sizeof(inq_read_t), A.n_reads * sizeof(inq_read_t), s, res_reads)) != INQ_OK) return rc;
-        wall("  batch read buffer ready");
+        clock.at("  batch read buffer ready");
         a.cigar = (uint32_t *)A.cigar.p + A.n_units * 4;
         a.unit_base = (uint32_t)A.n_units;
         a.read_base = (uint32_t)A.n_reads;
@@ -458,13 +473,9 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     launch_join_count(a, n_valid, s);
     launch_scan_u32_to_u64(a.locus_cnt, a.locus_pair_off, nl, (uint64_t *)S->tmp.p, s);
     HIP_TRY(c, hipGetLastError());
-    wall("  gather + join count enqueued");
-    HIP_TRY(c, hipMemcpyAsync(&S->h->val[2], a.locus_pair_off + nl, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&S->h->st, S->d_st, sizeof(FrontStatus), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if ((rc = front_fail(S->h->st)) != INQ_OK) return rc;
-    const uint64_t n_pairs = S->h->val[2];
-    wall("gather + join count done");
+    clock.at("  gather + join count enqueued");
+    if ((rc = read_count(a.locus_pair_off + nl, &n_pairs)) != INQ_OK) return rc;
+    clock.at("gather + join count done");
     if (n_pairs >= (1ull << 40)) return INQ_ERR_ARG;
 
     // ---- stage 4: pairs, then the locus kernels on the device-resident batch
@@ -494,9 +505,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     };
     if (defer) {
         if (A.n_pairs + n_pairs >= (1ull << 40) || A.n_loci + nl >= 0xfffffff0ull) return INQ_ERR_ARG;
-        size_t res_pairs = 0;
-        if (A.n_spans == 0 && c->batch_loci_hint > nl && nl)
-            res_pairs = (size_t)std::min((double)(4ull << 30), (double)n_pairs * 4.0 * std::min(64.0, std::ceil((double)c->batch_loci_hint / (double)nl)) * 1.04);
+        const size_t res_pairs = (size_t)std::min((double)(4ull << 30), (double)n_pairs * 4.0 * batch_spans);
         if ((rc = ensure_keep(c, A.pair_read, (A.n_pairs + n_pairs) * 4, A.n_pairs * 4, s, res_pairs)) != INQ_OK) return rc;
         if ((rc = ensure_keep(c, A.off, (A.n_loci + nl + 1) * 8, (A.n_loci + 1) * 8, s)) != INQ_OK) return rc;
         if ((rc = ensure_keep(c, A.lstart, (A.n_loci + nl) * 4, A.n_loci * 4, s)) != INQ_OK) return rc;
@@ -515,7 +524,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
         if (A.n_spans == 0) A.minlen = sp->minlen, A.support = sp->support, A.unphased = sp->unphased, A.max_reads = 0;
         A.max_reads = std::max<uint32_t>(A.max_reads, S->h->st.max_reads);
         A.n_units += n_units, A.n_reads += n_valid, A.n_pairs += n_pairs, A.n_loci += nl, ++A.n_spans;
-        wall("appended to the deferred batch");
+        clock.at("appended to the deferred batch");
         return INQ_OK;
     }
     if ((rc = ensure(c, S->pair_read, n_pairs * 4)) != INQ_OK) return rc;
@@ -523,40 +532,19 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     launch_join_fill(a, n_valid, s);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(S->ev[4], s));
-    inq_batch_t db;
-    std::memset(&db, 0, sizeof db);
-    db.n_reads = n_valid;
-    db.n_cigar_words = n_units * 4;
-    db.n_pairs = n_pairs;
-    db.n_loci = nl;
-    db.cigar = a.cigar;
-    db.reads = a.reads;
-    db.pair_read = a.pair_read;
-    db.locus_pair_off = a.locus_pair_off;
-    db.locus_start = a.locus_start;
-    db.locus_end = a.locus_end;
-    db.minlen = sp->minlen;
-    db.support = sp->support;
-    db.unphased = sp->unphased;
-    inq_result_t dr;
-    dr.phase1 = (double *)S->p1.p;
-    dr.phase2 = (double *)S->p2.p;
-    dr.pair_call = nullptr;
-    dr.pair_bits = nullptr;
-    dr.n_tie_loci = 0;
+    DevBatch d = device_batch(a.cigar, a.reads, a.pair_read, a.locus_pair_off, a.locus_start, a.locus_end, n_valid, n_units * 4, n_pairs, nl,
+                              sp->minlen, sp->support, sp->unphased, S->p1.p, S->p2.p);
     c->call_hint = std::max<uint32_t>(S->h->st.max_reads, 1u);
-    if ((rc = call_batch_device_impl(c, &db, &dr, s)) != INQ_OK) return rc;
+    if ((rc = call_batch_device_impl(c, &d.b, &d.r, s)) != INQ_OK) return rc;
     HIP_TRY(c, hipEventRecord(S->ev[5], s));
-    HIP_TRY(c, hipMemcpyAsync(S->h_rows, dr.phase1, nl * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(S->h_rows + nl, dr.phase2, nl * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&S->h->ks, c->d_status, sizeof(DevStatus), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(S->h_rows, d.r.phase1, nl * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(S->h_rows + nl, d.r.phase2, nl * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(&S->h->st, S->d_st, sizeof(FrontStatus), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemsetAsync(&c->d_status->err, 0, sizeof(unsigned int), s));
-    HIP_TRY(c, hipMemsetAsync(&c->d_status->ties, 0, sizeof(unsigned long long), s));
+    if ((rc = status_readback(c, &S->h->ks, s)) != INQ_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
     std::memcpy(r->phase1, S->h_rows, nl * 8);
     std::memcpy(r->phase2, S->h_rows + nl, nl * 8);
-    wall("call done");
+    clock.at("call done");
     S->n_reads = n_valid;
     S->n_cigar_words = n_units * 4;
     S->n_pairs = n_pairs;
@@ -586,7 +574,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     if (ms_call) *ms_call = 0.0;
     if (n_loci != A.n_loci) return INQ_ERR_ARG;
     if (A.n_loci == 0) {
-        A = SpanState::Acc{A.cigar, A.reads, A.pair_read, A.off, A.lstart, A.lend};
+        A.reset();
         return INQ_OK;
     }
     if (!dev && (!r->phase1 || !r->phase2)) return INQ_ERR_ARG;
@@ -602,41 +590,16 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     if ((rc = ensure(c, S->p2, nl * 8)) != INQ_OK) return rc;
     if (h_flags && (rc = ensure(c, c->lflags, nl)) != INQ_OK) return rc;
     uint8_t *const d_flags = h_flags ? (uint8_t *)c->lflags.p : nullptr;
-    const size_t staged = 2 * nl + (h_flags ? (nl + 7) / 8 : 0);  // the rows, then the flags
-    if (S->h_rows_cap < staged) {
-        if (S->h_rows) (void)hipHostFree(S->h_rows);
-        S->h_rows = nullptr;
-        S->h_rows_cap = 0;
-        const size_t want = std::max<size_t>(std::max<size_t>(2 * nl + nl / 2 + 1024, staged), 1u << 16);
-        HIP_TRY(c, hipHostMalloc((void **)&S->h_rows, want * sizeof(double), hipHostMallocDefault));
-        S->h_rows_cap = want;
-    }
-    inq_batch_t db;
-    std::memset(&db, 0, sizeof db);
-    db.n_reads = A.n_reads;
-    db.n_cigar_words = A.n_units * 4;
-    db.n_pairs = A.n_pairs;
-    db.n_loci = nl;
-    db.cigar = (const uint32_t *)A.cigar.p;
-    db.reads = (const inq_read_t *)A.reads.p;
-    db.pair_read = (const uint32_t *)A.pair_read.p;
-    db.locus_pair_off = (const uint64_t *)A.off.p;
-    db.locus_start = (const uint32_t *)A.lstart.p;
-    db.locus_end = (const uint32_t *)A.lend.p;
-    db.minlen = A.minlen;
-    db.support = A.support;
-    db.unphased = A.unphased;
-    inq_result_t dr;
-    dr.phase1 = (double *)S->p1.p;
-    dr.phase2 = (double *)S->p2.p;
-    dr.pair_call = nullptr;
-    dr.pair_bits = nullptr;
-    dr.n_tie_loci = 0;
+    if ((rc = ensure_row_staging(c, S, nl, 2 * nl + (h_flags ? (nl + 7) / 8 : 0))) != INQ_OK) return rc;  // the rows, then the flags
+    DevBatch d = device_batch(A.cigar.p, A.reads.p, A.pair_read.p, A.off.p, A.lstart.p, A.lend.p, A.n_reads, A.n_units * 4, A.n_pairs, nl,
+                              A.minlen, A.support, A.unphased, S->p1.p, S->p2.p);
+    inq_batch_t &db = d.b;
+    inq_result_t &dr = d.r;
     c->call_hint = std::max<uint32_t>(A.max_reads, 1u);
     // whatever happens from here on, the batch is spent: a failed flush must not leave its spans for the next file of a session
     struct Spent {
         SpanState::Acc &a;
-        ~Spent() { a = SpanState::Acc{a.cigar, a.reads, a.pair_read, a.off, a.lstart, a.lend}; }
+        ~Spent() { a.reset(); }
     } spent{A};
     const uint64_t n_reads_all = A.n_reads, n_units_all = A.n_units, n_pairs_all = A.n_pairs;
     HIP_TRY(c, hipEventRecord(S->ev[4], s));
@@ -665,9 +628,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
         HIP_TRY(c, hipMemcpyAsync(S->h_rows + nl, dr.phase2, nl * 8, hipMemcpyDeviceToHost, s));
     }
     if (h_flags) HIP_TRY(c, hipMemcpyAsync(S->h_rows + 2 * nl, d_flags, nl, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&S->h->ks, c->d_status, sizeof(DevStatus), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemsetAsync(&c->d_status->err, 0, sizeof(unsigned int), s));
-    HIP_TRY(c, hipMemsetAsync(&c->d_status->ties, 0, sizeof(unsigned long long), s));
+    if ((rc = status_readback(c, &S->h->ks, s)) != INQ_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
     if (h_flags) std::memcpy(h_flags, S->h_rows + 2 * nl, nl);
     if (!dev) {
@@ -717,11 +678,9 @@ int span_stage_begin_impl(inq_ctx *c, const inq_span_t *sp, int slot) {
     g.valid = false;
     constexpr size_t kPad = 64;
     hipStream_t s = S->copy_stream;
-    const bool verbose = std::getenv("INQ_TIMING") && std::getenv("INQ_TIMING")[0] == '2';
-    const auto w0 = std::chrono::steady_clock::now();
-    auto wall = [&](const char *what) {
-        if (verbose) std::fprintf(stderr, "[inq stage host] slot %d %-28s at %.2f ms\n", slot, what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count());
-    };
+    char prefix[40];
+    std::snprintf(prefix, sizeof prefix, "[inq stage host] slot %d", slot);
+    const HostClock clock(prefix);
     auto al16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
     const size_t off_blocks = 0, off_anch = al16(nb * sizeof(inq_bgzf_block_t)), off_stop = off_anch + al16(na * 8), tab_bytes = off_stop + al16(na * 8);
     if ((rc = ensure(c, g.comp, sp->comp_bytes + kPad)) != INQ_OK) return rc;
@@ -735,10 +694,10 @@ int span_stage_begin_impl(inq_ctx *c, const inq_span_t *sp, int slot) {
     }
     if (nb) std::memcpy(g.h_tab + off_blocks, sp->blocks, nb * sizeof(inq_bgzf_block_t));
     if (na) std::memcpy(g.h_tab + off_anch, sp->anchors, na * 8), std::memcpy(g.h_tab + off_stop, sp->anchor_stop, na * 8);
-    // the views the rest of the code reads (no buffers of their own any more)
-    g.blocks.p = (uint8_t *)g.tab.p + off_blocks, g.blocks.cap = 0;
-    g.anchors.p = (uint8_t *)g.tab.p + off_anch, g.anchors.cap = 0;
-    g.anchor_stop.p = (uint8_t *)g.tab.p + off_stop, g.anchor_stop.cap = 0;
+    // where the rest of the code reads them
+    g.blocks = (const inq_bgzf_block_t *)((uint8_t *)g.tab.p + off_blocks);
+    g.anchors = (const uint64_t *)((uint8_t *)g.tab.p + off_anch);
+    g.anchor_stop = (const uint64_t *)((uint8_t *)g.tab.p + off_stop);
     // From here on the copy engine may be reading the caller's span buffer and this slot's table: an error exit must not hand them back
     // while it does (the slot stays invalid, `pending` is not raised, so nobody will wait for this upload later).
     struct DrainOnError {
@@ -752,7 +711,7 @@ int span_stage_begin_impl(inq_ctx *c, const inq_span_t *sp, int slot) {
     HIP_TRY(c, hipMemsetAsync((uint8_t *)g.comp.p + sp->comp_bytes, 0, kPad, s));
     if (tab_bytes) HIP_TRY(c, hipMemcpyAsync(g.tab.p, g.h_tab, tab_bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipEventRecord(g.ev_up, s));
-    wall("copies enqueued");
+    clock.at("copies enqueued");
     g.inflated = false;
     if (c->inflate_ahead && nb) {
         // the inflate behind the upload, on the ahead stream (the copy stream goes on with the next span's bytes)
@@ -762,28 +721,10 @@ int span_stage_begin_impl(inq_ctx *c, const inq_span_t *sp, int slot) {
         HIP_TRY(c, hipMemsetAsync((uint8_t *)g.u.p + u_bytes, 0, kPad, sa));
         HIP_TRY(c, hipMemsetAsync(g.d_err, 0, sizeof(unsigned int), sa));
         HIP_TRY(c, hipEventRecord(g.ev_inf0, sa));
-        InflateArgs ia;
-        ia.comp = (const uint8_t *)g.comp.p;
-        ia.comp_bytes = sp->comp_bytes;
-        ia.blocks = (const inq_bgzf_block_t *)g.blocks.p;
-        ia.n_blocks = nb;
-        ia.out = (uint8_t *)g.u.p;
-        ia.out_bytes = u_bytes;
-        ia.block_status = nullptr;
-        ia.err = g.d_err;
-        ia.verify_crc = c->verify_crc ? 1u : 0u;
-        ia.debug_flags = 0u;
-        ia.lit_pairs = c->inflate_lit_pairs < 0 ? inflate_wants_literal_pairs(sp->comp, sp->comp_bytes, sp->blocks, nb) : (uint32_t)c->inflate_lit_pairs;
-        ia.tokens = nullptr;
-        if (c->inflate_tokens < 0 ? ia.lit_pairs == 0u : c->inflate_tokens != 0) {
-            if ((rc = ensure(c, g.tok, inflate_token_words(nb) * 4)) != INQ_OK) return rc;
-            ia.tokens = (uint32_t *)g.tok.p;
-        }
-        launch_bgzf_inflate(ia, sa);
-        HIP_TRY(c, hipGetLastError());
+        if ((rc = inflate_launch(c, g.comp.p, g.blocks, sp->comp, sp->comp_bytes, sp->blocks, nb, g.u.p, u_bytes, nullptr, g.d_err, g.tok, sa)) != INQ_OK) return rc;
         HIP_TRY(c, hipEventRecord(g.ev_inf1, sa));
         g.inflated = true;
-        wall("inflate enqueued");
+        clock.at("inflate enqueued");
     }
     g.host_comp = sp->comp;
     g.comp_bytes = sp->comp_bytes;
@@ -828,31 +769,15 @@ extern "C" {
 
 int inq_bgzf_inflate(inq_ctx_t *c, const uint8_t *comp, uint64_t comp_bytes, const inq_bgzf_block_t *blocks, uint64_t n_blocks,
                      uint8_t *out, uint64_t out_bytes, uint32_t *block_status) {
-    try {  // nothing may unwind across the C ABI
-        return bgzf_inflate_impl(c, comp, comp_bytes, blocks, n_blocks, out, out_bytes, block_status);
-    } catch (const std::bad_alloc &) {
-        return INQ_ERR_NOMEM;
-    } catch (...) {
-        return INQ_ERR_HIP;
-    }
+    return guarded([&] { return bgzf_inflate_impl(c, comp, comp_bytes, blocks, n_blocks, out, out_bytes, block_status); });
 }
 
 int inq_span_stage_begin(inq_ctx_t *c, const inq_span_t *span, int slot) {
-    try {
-        return span_stage_begin_impl(c, span, slot);
-    } catch (const std::bad_alloc &) {
-        return INQ_ERR_NOMEM;
-    } catch (...) {
-        return INQ_ERR_HIP;
-    }
+    return guarded([&] { return span_stage_begin_impl(c, span, slot); });
 }
 
 int inq_span_stage_wait(inq_ctx_t *c, int slot) {
-    try {
-        return span_stage_wait_impl(c, slot);
-    } catch (...) {
-        return INQ_ERR_HIP;
-    }
+    return guarded([&] { return span_stage_wait_impl(c, slot); });
 }
 
 int inq_span_stage(inq_ctx_t *c, const inq_span_t *span, int slot) {
@@ -861,33 +786,15 @@ int inq_span_stage(inq_ctx_t *c, const inq_span_t *span, int slot) {
 }
 
 int inq_call_span_staged(inq_ctx_t *c, const inq_span_t *span, int slot, inq_result_t *result, inq_span_stats_t *stats) {
-    try {
-        return slot < 0 ? INQ_ERR_ARG : call_span_impl(c, span, result, stats, slot);
-    } catch (const std::bad_alloc &) {
-        return INQ_ERR_NOMEM;
-    } catch (...) {
-        return INQ_ERR_HIP;
-    }
+    return guarded([&] { return slot < 0 ? INQ_ERR_ARG : call_span_impl(c, span, result, stats, slot); });
 }
 
 int inq_call_span(inq_ctx_t *c, const inq_span_t *span, inq_result_t *result, inq_span_stats_t *stats) {
-    try {
-        return call_span_impl(c, span, result, stats, -1);
-    } catch (const std::bad_alloc &) {
-        return INQ_ERR_NOMEM;
-    } catch (...) {
-        return INQ_ERR_HIP;
-    }
+    return guarded([&] { return call_span_impl(c, span, result, stats, -1); });
 }
 
 int inq_call_span_deferred(inq_ctx_t *c, const inq_span_t *span, int slot, inq_span_stats_t *stats) {
-    try {
-        return call_span_impl(c, span, nullptr, stats, slot < 0 ? -1 : slot, true);
-    } catch (const std::bad_alloc &) {
-        return INQ_ERR_NOMEM;
-    } catch (...) {
-        return INQ_ERR_HIP;
-    }
+    return guarded([&] { return call_span_impl(c, span, nullptr, stats, slot < 0 ? -1 : slot, true); });
 }
 
 int inq_call_flush(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call) {
@@ -895,13 +802,7 @@ int inq_call_flush(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *
 }
 
 int inq_call_flush_flags(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags) {
-    try {
-        return call_flush_impl(c, result, n_loci, ms_call, nullptr, locus_flags);
-    } catch (const std::bad_alloc &) {
-        return INQ_ERR_NOMEM;
-    } catch (...) {
-        return INQ_ERR_HIP;
-    }
+    return guarded([&] { return call_flush_impl(c, result, n_loci, ms_call, nullptr, locus_flags); });
 }
 
 int inq_call_flush_device(inq_ctx_t *c, double *d_phase1, double *d_phase2, uint64_t cap, const uint32_t *index, uint64_t n_loci, uint64_t *n_tie_loci,
@@ -911,18 +812,14 @@ int inq_call_flush_device(inq_ctx_t *c, double *d_phase1, double *d_phase2, uint
 
 int inq_call_flush_device_flags(inq_ctx_t *c, double *d_phase1, double *d_phase2, uint64_t cap, const uint32_t *index, uint64_t n_loci,
                                 uint64_t *n_tie_loci, double *ms_call, uint8_t *locus_flags) {
-    try {
+    return guarded([&] {
         inq_result_t r;
         std::memset(&r, 0, sizeof r);
         const FlushToDevice dev{d_phase1, d_phase2, index, cap};
         const int rc = call_flush_impl(c, &r, n_loci, ms_call, &dev, locus_flags);
         if (n_tie_loci) *n_tie_loci = r.n_tie_loci;
         return rc;
-    } catch (const std::bad_alloc &) {
-        return INQ_ERR_NOMEM;
-    } catch (...) {
-        return INQ_ERR_HIP;
-    }
+    });
 }
 
 // device memory for a caller that does not link the runtime itself (the host library's device-resident row arrays)
@@ -962,16 +859,11 @@ uint64_t inq_call_deferred_loci(const inq_ctx_t *c) { return c && c->span ? c->s
 
 void inq_call_discard(inq_ctx_t *c) {
     if (!c || !c->span) return;
-    SpanState::Acc &A = c->span->acc;
-    A = SpanState::Acc{A.cigar, A.reads, A.pair_read, A.off, A.lstart, A.lend};
+    c->span->acc.reset();
 }
 
 int inq_span_fetch_batch(inq_ctx_t *c, uint32_t *cigar, inq_read_t *reads, uint32_t *pair_read, uint64_t *locus_pair_off) {
-    try {
-        return fetch_batch_impl(c, cigar, reads, pair_read, locus_pair_off);
-    } catch (...) {
-        return INQ_ERR_HIP;
-    }
+    return guarded([&] { return fetch_batch_impl(c, cigar, reads, pair_read, locus_pair_off); });
 }
 
 }  // extern "C"

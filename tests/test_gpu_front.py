@@ -620,6 +620,58 @@ def test_call_span_rejects_malformed_spans(ctx, tmp_path):
     assert ctx._L.inq_call_span_staged(ctx._h, other, 2, None, None) == hipcall.INQ_ERR_ARG
 
 
+def test_status_is_read_and_cleared_once_by_every_entry(ctx, orc, tmp_path):
+    """The kernels' status words (error bits, tie count) come down and are cleared in one shared step behind the host-buffer call,
+    the span call, the flush and inq_ctx_status: on ONE context, a batch that fails, a span without ties, a deferred span with
+    exactly one tie locus and a status query each see their own outcome and nothing of the call before."""
+    from inquistr_amd import batch as B
+    from inquistr_amd import call
+    from tests import gen
+    from tests.test_host_frontend import _expected, _make_case
+    from tests.test_tie_report import TIE_LOCUS, make_tie_case
+
+    span_args = lambda s, unphased: (s["comp"], s["blocks"], s["anchors"], s["anchor_stop"], s["locus_tid"], s["locus_start"], s["locus_end"], 5, 3, unphased)
+    # 1. the host-buffer entry: one locus, two reads, the second with op code 9
+    bb = B.BatchBuilder(minlen=5, support=3)
+    good = bb.add_read(950, B.encode_cigar([("M", 200)]), phase=1)
+    bad = bb.add_read(950, np.array([(200 << 4) | 9], dtype=np.uint32), phase=1)
+    bb.add_locus(1010, 1090, [good, bad])
+    batch = bb.build()
+    assert orc.call_batch(batch)[0] == B.INQ_ERR_CIGAR_OP
+    rc, _res = ctx.call_batch(batch, check=False)
+    assert rc == B.INQ_ERR_CIGAR_OP
+    # 2. a good span, phased (no ties by construction): the error of step 1 is gone
+    (tmp_path / "good").mkdir()
+    bam, bed, loci, recs = _make_case(tmp_path / "good", 33, n_loci=3)
+    sp = call.Spans(bam, region_file=bed, minlen=5, support=3, threads=1, unphased=False)
+    got1, got2 = np.full(len(loci), np.nan), np.full(len(loci), np.nan)
+    for s in sp.spans():
+        rc, p1, p2, ties, _stats = ctx.call_span(*span_args(s, False), check=False)
+        assert rc == 0 and ties == 0
+        got1[s["locus_index"]], got2[s["locus_index"]] = p1, p2
+    sp.close()
+    want1, want2 = _expected(loci, recs, False, 5, 3)
+    assert gen.same_f64(got1, want1) and gen.same_f64(got2, want2)
+    # 3. deferred + flush with flags: the hand-made tie locus among loci that are none
+    (tmp_path / "tie").mkdir()
+    bam, bed, loci, recs, want_ties = make_tie_case(tmp_path / "tie", n_random=2)
+    assert sum(want_ties) == 1 and want_ties[[l[:3] for l in loci].index(TIE_LOCUS)]
+    sp = call.Spans(bam, region_file=bed, minlen=5, support=3, threads=1, unphased=True)
+    order = []
+    for s in sp.spans():
+        rc, _stats = ctx.call_span_deferred(*span_args(s, True), check=False)
+        assert rc == 0
+        order.extend(int(i) for i in s["locus_index"])
+    sp.close()
+    rc, p1, p2, ties, _ms, flags = ctx.call_flush_flags(check=False)
+    assert rc == 0 and [l[:3] for l in loci].index(TIE_LOCUS) in order  # (a locus no record comes near is in no span)
+    assert ties == 1 and [int(f) for f in flags] == [int(want_ties[i]) for i in order]
+    want1, want2 = _expected(loci, recs, True, 5, 3)
+    assert gen.same_f64(p1, want1[order]) and gen.same_f64(p2, want2[order])
+    # 4. nothing is left for the status query
+    assert ctx.status() == (hipcall.INQ_OK, 0)
+
+
 def test_inflate_fuzz_agrees_with_zlib_on_mutated_streams(ctx):
     """Thousands of damaged DEFLATE payloads: the kernel must accept exactly what zlib accepts (stream ends, ISIZE
     bytes produced), with the same bytes, and flag everything else - without faulting or hanging on any of them."""
