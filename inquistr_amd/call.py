@@ -262,6 +262,49 @@ def load():
 FRONTENDS = {None: 0, "host": 1, "device": 2}
 
 
+def _checked(fn, *args, ok=(0,)) -> int:
+    """fn(*args, errbuf, errcap) of the host library; a status outside `ok` raises CallError with the message the library left
+    (the inq_*_next entries return their failures negated)."""
+    err = C.create_string_buffer(2048)
+    rc = fn(*args, err, len(err))
+    if rc not in ok:
+        raise CallError(abs(rc), err.value.decode(errors="replace"))
+    return rc
+
+
+def _copy_array(ptr, n, dt) -> np.ndarray:
+    """a numpy copy of n items of dtype dt at a pointer of the library"""
+    if not n:
+        return np.zeros(0, dtype=dt)
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(n * np.dtype(dt).itemsize,)).view(dt).copy()
+
+
+class _Handle:
+    """A handle of the host library and the entry that closes it (_CLOSE)."""
+    _CLOSE = ""
+
+    def _open(self, fn, *args) -> None:
+        """fn(*args, &handle, errbuf, errcap)"""
+        self._L = load()
+        self._h = C.c_void_p()
+        try:
+            _checked(getattr(self._L, fn), *args, C.byref(self._h))
+        except CallError:
+            self._h = C.c_void_p()
+            raise
+
+    def close(self):
+        if self._h and self._h.value:
+            getattr(self._L, self._CLOSE)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, reference, device=0,
           frontend=None, ties=None) -> CallArgsC:
     a = CallArgsC()
@@ -288,13 +331,9 @@ def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str
     ties: path of the tie report (inquistr call --ties): the tie-ambiguous unphased loci as BED, in the rows' order."""
     L = load()
     a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, reference, device, frontend, ties)
-    err = C.create_string_buffer(2048)
     out = sys.stdout if out is None else out
     out.flush()
-    fd = out.fileno()
-    rc = L.inq_genotype_repeats(C.byref(a), fd, err, len(err))
-    if rc != 0:
-        raise CallError(rc, err.value.decode(errors="replace"))
+    _checked(L.inq_genotype_repeats, C.byref(a), out.fileno())
 
 
 def genotype_repeats_devices(bamp: str, region: Optional[str], region_file: Optional[str], devices, minlen: int = 5, support: int = 3,
@@ -306,12 +345,9 @@ def genotype_repeats_devices(bamp: str, region: Optional[str], region_file: Opti
     a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, None, 0, frontend, ties)
     ids = (C.c_int32 * len(devices))(*[int(d) for d in devices])
     st = (PartStatsC * len(devices))()
-    err = C.create_string_buffer(2048)
     out = sys.stdout if out is None else out
     out.flush()
-    rc = L.inq_genotype_repeats_devices(C.byref(a), ids, len(devices), out.fileno(), st, err, len(err))
-    if rc != 0:
-        raise CallError(rc, err.value.decode(errors="replace"))
+    _checked(L.inq_genotype_repeats_devices, C.byref(a), ids, len(devices), out.fileno(), st)
     return [{f: getattr(x, f) for f, _ in PartStatsC._fields_} for x in st]
 
 
@@ -328,11 +364,8 @@ def devices_selftest(bamp: str, region: Optional[str], region_file: Optional[str
     L = load()
     a = _args(bamp, region, region_file, 5, 3, threads, False, "S", None)
     cuts = np.zeros(n_parts + 1, dtype=np.uint64)
-    err = C.create_string_buffer(2048)
     out.flush()
-    rc = L.inq_host_devices_selftest(C.byref(a), n_parts, fail_part, out.fileno(), cuts.ctypes.data, err, len(err))
-    if rc != 0:
-        raise CallError(rc, err.value.decode(errors="replace"))
+    _checked(L.inq_host_devices_selftest, C.byref(a), n_parts, fail_part, out.fileno(), cuts.ctypes.data)
     return cuts.astype(np.int64)
 
 
@@ -344,10 +377,7 @@ def genotype_repeats_rows(bamp: str, region: Optional[str], region_file: Optiona
     a = _args(bamp, region, region_file, minlen, support, threads, unphased, None, None, device, frontend)
     p1 = np.full(len(idx), np.nan)
     p2 = np.full(len(idx), np.nan)
-    err = C.create_string_buffer(2048)
-    rc = L.inq_genotype_repeats_rows(C.byref(a), idx.ctypes.data, len(idx), p1.ctypes.data, p2.ctypes.data, err, len(err))
-    if rc != 0:
-        raise CallError(rc, err.value.decode(errors="replace"))
+    _checked(L.inq_genotype_repeats_rows, C.byref(a), idx.ctypes.data, len(idx), p1.ctypes.data, p2.ctypes.data)
     return p1, p2
 
 
@@ -370,29 +400,24 @@ def partition(bamp: str, region: Optional[str], region_file: Optional[str], worl
         return order[: n.value].copy(), cuts.astype(np.int64)
 
 
-class Run:
+class Run(_Handle):
     """inq_run_*: the BAM header, its index and the targets opened once (get_targets + get_bam_reader, src/call.rs:146-147,
     182-202); serves the work split, this process's rows and the ordered `.inq` output of a multi-process run.
     session: a Session whose device context, span buffers and BED cache the run's rows calls use (inq_session_run_open) - what a
     resident rank passes file after file; the session must stay open while the run is.
     ties: a path (not opened by the run) that makes its rows calls collect the per-target tie flags (tie_flags())."""
 
+    _CLOSE = "inq_run_close"
+
     def __init__(self, bamp, region=None, region_file=None, minlen=5, support=3, threads=1, unphased=False, sample_name=None,
                  device: int = 0, frontend: Optional[str] = None, session: Optional["Session"] = None, ties: Optional[str] = None):
-        self._L = load()
-        self._h = C.c_void_p()
         self._session = session  # the session closes the runs still open on it before it goes (Session.close)
         self._args = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, None, device, frontend, ties)
-        err = C.create_string_buffer(2048)
         if session is not None:
-            rc = self._L.inq_session_run_open(session._h, C.byref(self._args), C.byref(self._h), err, len(err))
-        else:
-            rc = self._L.inq_run_open(C.byref(self._args), C.byref(self._h), err, len(err))
-        if rc != 0:
-            self._h = C.c_void_p()
-            raise CallError(rc, err.value.decode(errors="replace"))
-        if session is not None:
+            self._open("inq_session_run_open", session._h, C.byref(self._args))
             session._runs.add(self)
+        else:
+            self._open("inq_run_open", C.byref(self._args))
 
     @property
     def n_targets(self) -> int:
@@ -406,20 +431,14 @@ class Run:
         n = self.n_targets
         order = np.zeros(max(n, 1), dtype=np.uint32)
         cuts = np.zeros(world + 1, dtype=np.uint64)
-        err = C.create_string_buffer(2048)
-        rc = self._L.inq_run_partition(self._h, world, order.ctypes.data, cuts.ctypes.data, err, len(err))
-        if rc != 0:
-            raise CallError(rc, err.value.decode(errors="replace"))
+        _checked(self._L.inq_run_partition, self._h, world, order.ctypes.data, cuts.ctypes.data)
         return order[:n].copy(), cuts.astype(np.int64)
 
     def rows(self, target_index):
         idx = np.ascontiguousarray(target_index, dtype=np.uint32)
         p1 = np.full(len(idx), np.nan)
         p2 = np.full(len(idx), np.nan)
-        err = C.create_string_buffer(2048)
-        rc = self._L.inq_run_rows(self._h, idx.ctypes.data, len(idx), p1.ctypes.data, p2.ctypes.data, err, len(err))
-        if rc != 0:
-            raise CallError(rc, err.value.decode(errors="replace"))
+        _checked(self._L.inq_run_rows, self._h, idx.ctypes.data, len(idx), p1.ctypes.data, p2.ctypes.data)
         return p1, p2
 
     def rows_device(self, target_index, width: int):
@@ -427,10 +446,7 @@ class Run:
         target_index[k], NaN behind the last), owned by the run and valid until its next call or close()."""
         idx = np.ascontiguousarray(target_index, dtype=np.uint32)
         d1, d2 = C.c_void_p(), C.c_void_p()
-        err = C.create_string_buffer(2048)
-        rc = self._L.inq_run_rows_device(self._h, idx.ctypes.data, len(idx), int(width), C.byref(d1), C.byref(d2), err, len(err))
-        if rc != 0:
-            raise CallError(rc, err.value.decode(errors="replace"))
+        _checked(self._L.inq_run_rows_device, self._h, idx.ctypes.data, len(idx), int(width), C.byref(d1), C.byref(d2))
         return int(d1.value), int(d2.value)
 
     def write_inq(self, phase1, phase2, out=None) -> None:
@@ -439,10 +455,7 @@ class Run:
         p2 = np.ascontiguousarray(phase2, dtype=np.float64)
         out = sys.stdout if out is None else out
         out.flush()
-        err = C.create_string_buffer(2048)
-        rc = self._L.inq_run_write_inq(self._h, p1.ctypes.data, p2.ctypes.data, len(p1), out.fileno(), err, len(err))
-        if rc != 0:
-            raise CallError(rc, err.value.decode(errors="replace"))
+        _checked(self._L.inq_run_write_inq, self._h, p1.ctypes.data, p2.ctypes.data, len(p1), out.fileno())
 
     def tie_flags(self, n: int) -> np.ndarray:
         """inq_run_tie_flags: the per-target flags (uint8, INQ_LOCUS_TIE) of the last rows / rows_device call of n targets."""
@@ -455,25 +468,12 @@ class Run:
         """inq_run_write_ties: the tie report for flags in target-list order, in the order write_inq writes the rows."""
         fl = np.ascontiguousarray(flags, dtype=np.uint8)
         out.flush()
-        err = C.create_string_buffer(2048)
-        rc = self._L.inq_run_write_ties(self._h, fl.ctypes.data, len(fl), out.fileno(), err, len(err))
-        if rc != 0:
-            raise CallError(rc, err.value.decode(errors="replace"))
-
-    def close(self):
-        if self._h and self._h.value:
-            self._L.inq_run_close(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        _checked(self._L.inq_run_write_ties, self._h, fl.ctypes.data, len(fl), out.fileno())
 
 
-class Session:
+class Session(_Handle):
     """inq_session_*: many BAMs on one device context (the HIP runtime starts once; file k + 1 is staged while file k is called)."""
+    _CLOSE = "inq_session_close"
 
     def __init__(self, device: int = 0):
         import weakref
@@ -489,12 +489,9 @@ class Session:
     def call(self, bamp, region=None, region_file=None, minlen=5, support=3, threads=1, unphased=False, sample_name=None, out=None,
              frontend: Optional[str] = None, ties: Optional[str] = None) -> None:
         a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, None, 0, frontend, ties)
-        err = C.create_string_buffer(2048)
         out = sys.stdout if out is None else out
         out.flush()
-        rc = self._L.inq_session_call(self._h, C.byref(a), out.fileno(), err, len(err))
-        if rc != 0:
-            raise CallError(rc, err.value.decode(errors="replace"))
+        _checked(self._L.inq_session_call, self._h, C.byref(a), out.fileno())
 
     def call_many(self, bams, outs, region=None, region_file=None, minlen=5, support=3, threads=1, unphased=False, sample_names=None,
                   frontend: Optional[str] = None, ties=None):
@@ -521,8 +518,7 @@ class Session:
         if self._h and self._h.value:
             for r in list(self._runs):  # a run uses the session's context to its end (its device rows are freed on it)
                 r.close()
-            self._L.inq_session_close(self._h)
-            self._h = C.c_void_p()
+        super().close()
 
     def __enter__(self):
         return self
@@ -530,27 +526,18 @@ class Session:
     def __exit__(self, *a):
         self.close()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def plan_spans(bamp, region=None, region_file=None, max_comp_bytes: int = 0, n_targets_cap: int = 1 << 20):
     """inq_host_plan_spans: (segments as an array of (vo_begin, vo_limit, span), per-target span number) - the plan alone."""
     L = load()
     a = _args(bamp, region, region_file, 5, 3, 1, False, None, None)
-    err = C.create_string_buffer(2048)
     n = C.c_uint64(0)
     cap = 1024
     tspan = np.zeros(n_targets_cap, dtype=np.uint32)
     while True:
         vb, vl, sp = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint32)
-        rc = L.inq_host_plan_spans(C.byref(a), max_comp_bytes, vb.ctypes.data, vl.ctypes.data, sp.ctypes.data, cap, C.byref(n), tspan.ctypes.data,
-                                   len(tspan), err, len(err))
-        if rc != 0:
-            raise CallError(rc, err.value.decode(errors="replace"))
+        _checked(L.inq_host_plan_spans, C.byref(a), max_comp_bytes, vb.ctypes.data, vl.ctypes.data, sp.ctypes.data, cap, C.byref(n), tspan.ctypes.data,
+                 len(tspan))
         if n.value > cap:
             cap = int(n.value)
             continue
@@ -564,10 +551,7 @@ def combine(calls, out=None) -> None:
     out = sys.stdout if out is None else out
     out.flush()
     arr = (C.c_char_p * len(calls))(*[os.fspath(c).encode() for c in calls])
-    err = C.create_string_buffer(2048)
-    rc = L.inq_combine(arr, len(calls), out.fileno(), err, len(err))
-    if rc != 0:
-        raise CallError(rc, err.value.decode(errors="replace"))
+    _checked(L.inq_combine, arr, len(calls), out.fileno())
 
 
 def outlier(combined, minsize: int = 10, zscore: float = 3.0, method: str = "zscore", sample: Optional[str] = None,
@@ -582,27 +566,19 @@ def outlier(combined, minsize: int = 10, zscore: float = 3.0, method: str = "zsc
     a.sample = sample.encode() if sample is not None else None
     a.subset_file = os.fspath(subset).encode() if subset is not None else None
     a.device = device
-    err = C.create_string_buffer(2048)
     out = sys.stdout if out is None else out
     out.flush()
-    rc = L.inq_outlier(C.byref(a), out.fileno(), err, len(err))
-    if rc != 0:
-        raise CallError(rc, err.value.decode(errors="replace"))
+    _checked(L.inq_outlier, C.byref(a), out.fileno())
 
 
-class FrontEnd:
+class FrontEnd(_Handle):
     """BAM + targets -> batches (the fetch()/rc_records() stage), no GPU involved."""
+    _CLOSE = "inq_frontend_close"
 
     def __init__(self, bamp, region=None, region_file=None, minlen=5, support=3, threads=1, unphased=False,
                  sample_name=None, max_batch_words: int = 0):
-        self._L = load()
-        self._h = C.c_void_p()
         self._args = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, None)
-        err = C.create_string_buffer(2048)
-        rc = self._L.inq_frontend_open(C.byref(self._args), C.byref(self._h), err, len(err))
-        if rc != 0:
-            self._h = C.c_void_p()
-            raise CallError(rc, err.value.decode(errors="replace"))
+        self._open("inq_frontend_open", C.byref(self._args))
         if max_batch_words:
             self._L.inq_frontend_set_batch_words(self._h, max_batch_words)
 
@@ -620,21 +596,12 @@ class FrontEnd:
 
     def batches(self) -> Iterator[Tuple[Batch, np.ndarray]]:
         """Yields (Batch copy, locus_index) until the BAM is exhausted."""
+        arr = _copy_array
         while True:
             bc = InqBatchC()
             idx = C.POINTER(C.c_uint32)()
-            err = C.create_string_buffer(2048)
-            rc = self._L.inq_frontend_next(self._h, C.byref(bc), C.byref(idx), err, len(err))
-            if rc < 0:
-                raise CallError(-rc, err.value.decode(errors="replace"))
-            if rc == 0:
+            if _checked(self._L.inq_frontend_next, self._h, C.byref(bc), C.byref(idx), ok=(0, 1)) == 0:
                 return
-
-            def arr(ptr, n, dt):
-                if not n:
-                    return np.zeros(0, dtype=dt)
-                return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(n * np.dtype(dt).itemsize,)).view(dt).copy()
-
             b = Batch(
                 cigar=arr(bc.cigar, bc.n_cigar_words, np.uint32),
                 reads=arr(bc.reads, bc.n_reads, READ_DTYPE),
@@ -646,32 +613,16 @@ class FrontEnd:
             )
             yield b, np.ctypeslib.as_array(idx, shape=(max(int(bc.n_loci), 1),))[: int(bc.n_loci)].copy()
 
-    def close(self):
-        if self._h and self._h.value:
-            self._L.inq_frontend_close(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Spans:
+class Spans(_Handle):
     """Host half of the device front end (inq_spans_*): yields, per span, everything inq_call_span takes.
     No GPU involved."""
+    _CLOSE = "inq_spans_close"
 
     def __init__(self, bamp, region=None, region_file=None, minlen=5, support=3, threads=1, unphased=False,
                  max_comp_bytes: int = 0):
-        self._L = load()
-        self._h = C.c_void_p()
         self._args = _args(bamp, region, region_file, minlen, support, threads, unphased, None, None)
-        err = C.create_string_buffer(2048)
-        rc = self._L.inq_spans_open(C.byref(self._args), max_comp_bytes, C.byref(self._h), err, len(err))
-        if rc != 0:
-            self._h = C.c_void_p()
-            raise CallError(rc, err.value.decode(errors="replace"))
+        self._open("inq_spans_open", C.byref(self._args), max_comp_bytes)
 
     @property
     def n_targets(self) -> int:
@@ -682,22 +633,13 @@ class Spans:
         locus_index, file_begin."""
         from .hipcall import BGZF_BLOCK_DTYPE, SpanC
 
+        arr = _copy_array
         while True:
             sp = SpanC()
             idx = C.POINTER(C.c_uint32)()
             fb = C.c_uint64(0)
-            err = C.create_string_buffer(2048)
-            rc = self._L.inq_spans_next(self._h, C.byref(sp), C.byref(idx), C.byref(fb), err, len(err))
-            if rc < 0:
-                raise CallError(-rc, err.value.decode(errors="replace"))
-            if rc == 0:
+            if _checked(self._L.inq_spans_next, self._h, C.byref(sp), C.byref(idx), C.byref(fb), ok=(0, 1)) == 0:
                 return
-
-            def arr(ptr, n, dt):
-                if not n:
-                    return np.zeros(0, dtype=dt)
-                return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(n * np.dtype(dt).itemsize,)).view(dt).copy()
-
             n = int(sp.n_loci)
             yield dict(
                 comp=arr(sp.comp, sp.comp_bytes, np.uint8), blocks=arr(sp.blocks, sp.n_blocks, BGZF_BLOCK_DTYPE),
@@ -706,14 +648,3 @@ class Spans:
                 locus_index=np.ctypeslib.as_array(idx, shape=(max(n, 1),))[:n].copy(), file_begin=int(fb.value),
                 minlen=int(sp.minlen), support=int(sp.support), unphased=bool(sp.unphased),
             )
-
-    def close(self):
-        if self._h and self._h.value:
-            self._L.inq_spans_close(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -49,6 +49,21 @@ inline const char *debug_env(const char *name) { return std::getenv(name); }
 inline const char *debug_env(const char *) { return nullptr; }
 #endif
 
+// The two switches every piece of the driver asks about, each read from the environment here and nowhere else in the library.
+// INQ_FAST_EXIT=1 (the CLI sets it): the process is about to end, what it holds may be left to the operating system.
+inline bool fast_exit() {
+    const char *e = std::getenv("INQ_FAST_EXIT");
+    return e && e[0] == '1';
+}
+// INQ_TIMING: 0 = silent, 1 = the [inq timing] lines of a call, 2 = every stage as well
+inline int timing_level() {
+    const char *e = std::getenv("INQ_TIMING");
+    return !e ? 0 : e[0] == '2' ? 2 : 1;
+}
+using Clock = std::chrono::steady_clock;
+inline double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+inline double ms(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+
 inline void set_err(char *buf, size_t cap, const std::string &m) {
     if (buf && cap) std::snprintf(buf, cap, "%s", m.c_str());
 }
@@ -74,17 +89,30 @@ struct Prepared {
 // A cohort is called with ONE BED: inside a session (inquistr cohort / serve) the parsed and validated target list of the last BED is
 // kept and taken again when the file is the same (device, inode, size, modification time) and the BAM's contigs are (names and lengths
 // decide every check of from_bed, src/repeats.rs:96-115).  100 000 targets: 12 - 25 ms of a 70 ms call.
-struct BedCache {
-    std::mutex mu;
+struct BedKey {
     std::string path;
     uint64_t dev = 0, ino = 0, size = 0;
     int64_t mtime_ns = 0;
     std::map<std::string, uint64_t> lengths;
+    bool operator==(const BedKey &o) const {
+        return path == o.path && dev == o.dev && ino == o.ino && size == o.size && mtime_ns == o.mtime_ns && lengths == o.lengths;
+    }
+};
+struct BedCache {
+    std::mutex mu;
+    BedKey key;
     TargetsResult tr;
     bool valid = false;
 };
 
 int prepare(const inq_call_args_t *a, Prepared &P, std::string &msg, BedCache *bed_cache = nullptr);
+// ... for an entry of the C ABI: the message goes to the caller's buffer
+inline int prepare(const inq_call_args_t *a, Prepared &P, char *errbuf, size_t errcap, BedCache *bed_cache = nullptr) {
+    std::string msg;
+    const int rc = prepare(a, P, msg, bed_cache);
+    if (rc != INQ_EXIT_OK) set_err(errbuf, errcap, msg);
+    return rc;
+}
 
 
 // The device context is created on its own thread from the first instruction of the command: HIP start-up
@@ -127,7 +155,7 @@ struct AsyncCtx {
     std::atomic<bool> &ready = st->ready;
     std::thread th;
     bool started = false;
-    bool leak = false;  // set after a clean run when the process is about to exit (INQ_FAST_EXIT)
+    bool leak = false;  // set by the OWNER after a clean run when the process is about to end: the context is left to the operating system
     std::chrono::steady_clock::time_point t_start;
     AsyncCtx() = default;
     AsyncCtx(const AsyncCtx &) = delete;
@@ -151,8 +179,7 @@ struct AsyncCtx {
                 s->ready.store(true);
             }
             s->cv.notify_all();
-            const char *e = std::getenv("INQ_TIMING");
-            if (e && e[0] == '2') std::fprintf(stderr, "[inq ctx] @%.1f device context ready (inq_ctx_create %.1f ms), GPU on NUMA node %d\n", stamp_ms(), stamp_ms() - a, node);
+            if (timing_level() == 2) std::fprintf(stderr, "[inq ctx] @%.1f device context ready (inq_ctx_create %.1f ms), GPU on NUMA node %d\n", stamp_ms(), stamp_ms() - a, node);
         });
     }
     // marks the context as failed because its thread did not finish in time; the thread is left to itself
@@ -238,13 +265,22 @@ struct PartStats {
 void publish_last_stats(const PartStats &s);
 PartStats last_stats();  // of the last call that ended in this process (any thread)
 
+// the options of a call as the device takes them (an inq_batch_t through HostBatch::view, an inq_span_t through apply)
+struct CallOptions {
+    uint32_t minlen = 5, support = 3;
+    bool unphased = false;
+    CallOptions() = default;
+    explicit CallOptions(const inq_call_args_t &a)
+        : minlen(a.minlen), support((uint32_t)std::min<uint64_t>(a.support, 0xffffffffull)), unphased(a.unphased != 0) {}
+    void apply(inq_span_t &sp) const { sp.minlen = minlen, sp.support = support, sp.unphased = unphased ? 1u : 0u; }
+};
+
 // what one call works on: the opened BAM (header + index), the targets it was asked for, the options
 struct CallView {
     BamFile &bam;
     const std::vector<RepeatInterval> &targets;
     const std::string &sample;
-    uint32_t minlen, support;
-    bool unphased;
+    CallOptions opt;
 };
 
 // what a session adds to one call: a pipeline that was started ahead of it (its loader has been reading and uploading while the
@@ -263,6 +299,9 @@ struct SessionHooks {
     // collected, the locus kernels run without flags); ties_fd >= 0: a text call writes the report there, in the .inq's row order
     uint8_t *ties_out = nullptr;
     int ties_fd = -1;
+    // the caller owns the context AND the process ends with this call (fast_exit()): a pipeline the call made itself is left to the
+    // operating system after a clean run (unmapping a GB of touched pages takes ~0.1 s), as the caller then leaves its context
+    bool process_is_leaving = false;
 };
 
 // the tie report's file: opened (created / truncated) before any device work, closed with the call
@@ -287,6 +326,35 @@ struct RowsOut {
     double *d1 = nullptr, *d2 = nullptr;  // DEVICE arrays of dcap entries on the call's device: the rows are left there
     uint64_t dcap = 0;
 };
+
+// src[j] -> dst[index[j]]: rows and tie flags of a batch, a flush or a device part into their targets' places
+template <class T>
+inline void scatter(const T *src, const uint32_t *index, size_t n, T *dst) {
+    for (size_t j = 0; j < n; ++j) dst[index[j]] = src[j];
+}
+// the result buffers of one device call over n loci (rows start as NaN, flags as 0), and their way into the call's arrays
+struct BatchRows {
+    std::vector<double> b1, b2;
+    std::vector<uint8_t> bt;
+    inq_result_t res;
+    uint8_t *flags = nullptr;  // null: the call collects none
+    void begin(size_t n, bool want_flags) {
+        b1.assign(n, NAN), b2.assign(n, NAN);
+        std::memset(&res, 0, sizeof res);
+        res.phase1 = b1.data(), res.phase2 = b2.data();
+        flags = nullptr;
+        if (want_flags) bt.assign(n, 0), flags = bt.data();
+    }
+    // p1 null: the rows went elsewhere (device memory); ties is asked for only where flags were
+    void scatter_to(const uint32_t *index, double *p1, double *p2, uint8_t *ties) const {
+        if (p1) scatter(b1.data(), index, b1.size(), p1), scatter(b2.data(), index, b2.size(), p2);
+        if (flags) scatter(flags, index, bt.size(), ties);
+    }
+};
+
+// a device call that returned rc != INQ_OK: "device call failed: <inq_strerror>" (+ the runtime's own text for INQ_ERR_HIP, + suffix)
+// goes to errbuf; returns the exit status - domain errors are the reference's panics (HP > 2, bad CIGAR op, ...)
+int device_call_failed(int rc, inq_ctx_t *ctx, char *errbuf, size_t errcap, const std::string &suffix = std::string());
 
 bool use_device_front(const inq_call_args_t *args, const BamFile &bam, const std::vector<RepeatInterval> &targets);
 std::string ctx_failure_message(AsyncCtx &actx);
@@ -322,14 +390,15 @@ struct OwnedArgs {
 
 }  // namespace inqhost
 
-// public entries: no C++ exception may unwind across the C ABI
-#define INQ_GUARD(expr, errbuf, errcap)                                   \
+// public entries: no C++ exception may unwind across the C ABI; `fail` is what the entry returns for one
+#define INQ_GUARD_AS(fail, expr, errbuf, errcap)                           \
     try {                                                                  \
         return expr;                                                       \
     } catch (const std::exception &e) {                                    \
         set_err(errbuf, errcap, std::string("internal error: ") + e.what()); \
-        return INQ_EXIT_ERROR;                                             \
+        return fail;                                                       \
     } catch (...) {                                                        \
         set_err(errbuf, errcap, "internal error");                         \
-        return INQ_EXIT_ERROR;                                             \
+        return fail;                                                       \
     }
+#define INQ_GUARD(expr, errbuf, errcap) INQ_GUARD_AS(INQ_EXIT_ERROR, expr, errbuf, errcap)

@@ -79,12 +79,8 @@ static int inq_host_plan_spans_impl(const inq_call_args_t *args, uint64_t max_co
                                     char *errbuf, size_t errcap) {
     if (!n_segs) return INQ_EXIT_ERROR;
     Prepared P;
-    std::string msg;
-    int rc = prepare(args, P, msg);
-    if (rc != INQ_EXIT_OK) {
-        set_err(errbuf, errcap, msg);
-        return rc;
-    }
+    const int rc = prepare(args, P, errbuf, errcap);
+    if (rc != INQ_EXIT_OK) return rc;
     if (target_span) {
         if (target_cap < P.targets.size()) {
             set_err(errbuf, errcap, "target_span[] too small for the target list");

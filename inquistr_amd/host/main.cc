@@ -34,6 +34,32 @@ static void usage(FILE *f) {
         f);
 }
 
+// the value of the option at argv[i]: the part behind `=` when the option carried one, else the next argument (i moves on to it)
+static const char *need(int argc, char **argv, int &i, const char *inl = nullptr) {
+    if (inl) return inl;
+    if (i + 1 >= argc) {
+        std::fprintf(stderr, "error: a value is required for '%s' but none was supplied\n", argv[i]);
+        std::exit(2);
+    }
+    return argv[++i];
+}
+
+// a command's message on stderr: the reference's panic form for 101
+static void complain(int rc, const char *err) {
+    if (rc != 0) std::fprintf(stderr, rc == INQ_EXIT_PANIC ? "thread 'main' panicked:\n%s\n" : "%s\n", err);
+}
+
+// How a command that used the device ends: its message, then - the rows went out through write(2), nothing is buffered - past the
+// atexit handlers of the HIP runtime (0.15 - 0.2 s of tear-down for a process that is over).  Every such command sets INQ_FAST_EXIT=1
+// unless the user set it: INQ_FAST_EXIT=0 leaves normally (profilers write their output at exit).
+static int leave(int rc, const char *err) {
+    if (err) complain(rc, err);
+    std::fflush(nullptr);
+    const char *fast = std::getenv("INQ_FAST_EXIT");
+    if (fast && fast[0] == '1') std::_Exit(rc);
+    return rc;
+}
+
 int main(int argc, char **argv) {
     if (argc >= 2 && std::strcmp(argv[1], "combine") == 0) {  // src/main.rs:65-71: one or more .inq files
         if (argc < 3) {
@@ -42,7 +68,7 @@ int main(int argc, char **argv) {
         }
         char err[1024] = {0};
         int rc = inq::host_api().combine(argv + 2, (size_t)(argc - 2), 1, err, sizeof err);
-        if (rc != 0) std::fprintf(stderr, rc == INQ_EXIT_PANIC ? "thread 'main' panicked:\n%s\n" : "%s\n", err);
+        complain(rc, err);
         return rc;
     }
     if (argc >= 2 && std::strcmp(argv[1], "outlier") == 0) {  // src/main.rs:75-99
@@ -57,14 +83,7 @@ int main(int argc, char **argv) {
             auto eq = s.find('=');
             std::string key = (s.size() > 2 && s[0] == '-' && s[1] == '-' && eq != std::string::npos) ? s.substr(0, eq) : s;
             const char *inl = (key.size() != s.size()) ? argv[i] + eq + 1 : nullptr;
-            auto val = [&]() -> const char * {
-                if (inl) return inl;
-                if (i + 1 >= argc) {
-                    std::fprintf(stderr, "error: a value is required for '%s' but none was supplied\n", argv[i]);
-                    std::exit(2);
-                }
-                return argv[++i];
-            };
+            auto val = [&] { return need(argc, argv, i, inl); };
             if (key == "--minsize") o.minsize = (uint32_t)std::strtoul(val(), nullptr, 10);
             else if (key == "-z" || key == "--zscore") o.zscore = std::strtof(val(), nullptr);
             else if (key == "--method") {
@@ -94,12 +113,7 @@ int main(int argc, char **argv) {
         o.combined = combined;
         char err[1024] = {0};
         ::setenv("INQ_FAST_EXIT", "1", 0);  // this process ends with the command: the device context is left to the operating system
-        int rc = inq::host_api().outlier(&o, 1, err, sizeof err);
-        if (rc != 0) std::fprintf(stderr, rc == INQ_EXIT_PANIC ? "thread 'main' panicked:\n%s\n" : "%s\n", err);
-        std::fflush(nullptr);
-        const char *fast = std::getenv("INQ_FAST_EXIT");  // the lines went out through write(2): skip the runtime's tear-down (0.15 - 0.2 s)
-        if (fast && fast[0] == '1') std::_Exit(rc);
-        return rc;
+        return leave(inq::host_api().outlier(&o, 1, err, sizeof err), err);
     }
     if (argc >= 2 && std::strcmp(argv[1], "cohort") == 0) {
         // Not a subcommand of the reference: the loop a user writes around `inquiSTR call` for a cohort (one call per BAM with the
@@ -113,13 +127,7 @@ int main(int argc, char **argv) {
         bool ties = false;  // --ties: <out-dir>/<sample>.ties.bed next to each .inq
         for (int i = 2; i < argc; ++i) {
             const std::string k = argv[i];
-            auto val = [&]() -> const char * {
-                if (i + 1 >= argc) {
-                    std::fprintf(stderr, "error: a value is required for '%s' but none was supplied\n", argv[i]);
-                    std::exit(2);
-                }
-                return argv[++i];
-            };
+            auto val = [&] { return need(argc, argv, i); };
             if (k == "-r" || k == "--region") base.region = val();
             else if (k == "-R" || k == "--region-file" || k == "--region_file") base.region_file = val();
             else if (k == "-m" || k == "--minlen") base.minlen = (uint32_t)std::strtoul(val(), nullptr, 10);
@@ -162,7 +170,7 @@ int main(int argc, char **argv) {
         for (int fd : fds) ::close(fd);
         for (size_t k = 0; k < bams.size(); ++k)
             if (st[k] != 0) std::fprintf(stderr, "%s: exit status %d\n", bams[k].c_str(), st[k]);
-        if (rc != 0) std::fprintf(stderr, rc == INQ_EXIT_PANIC ? "thread 'main' panicked:\n%s\n" : "%s\n", err);
+        complain(rc, err);
         if (rc == 0 && !combined.empty()) {
             int cfd = ::open(combined.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
             std::vector<const char *> files;
@@ -171,9 +179,7 @@ int main(int argc, char **argv) {
             if (cfd >= 0) ::close(cfd);
             if (rc != 0) std::fprintf(stderr, "%s\n", err);
         }
-        std::fflush(nullptr);
-        const char *fast = std::getenv("INQ_FAST_EXIT");
-        if (fast && fast[0] == '1') std::_Exit(rc);
+        rc = leave(rc, nullptr);  // (what there was to say has been said)
         inq::host_api().session_close(S);
         return rc;
     }
@@ -186,13 +192,7 @@ int main(int argc, char **argv) {
         double idle = 0.0;
         for (int i = 2; i < argc; ++i) {
             const std::string k = argv[i];
-            auto val = [&]() -> const char * {
-                if (i + 1 >= argc) {
-                    std::fprintf(stderr, "error: a value is required for '%s' but none was supplied\n", argv[i]);
-                    std::exit(2);
-                }
-                return argv[++i];
-            };
+            auto val = [&] { return need(argc, argv, i); };
             if (k == "--socket") sock = val();
             else if (k == "--device") device = (int)std::strtol(val(), nullptr, 10);
             else if (k == "--idle-exit") idle = std::strtod(val(), nullptr);
@@ -232,13 +232,6 @@ int main(int argc, char **argv) {
     std::string bam;
     std::vector<int32_t> devices;  // --devices: one part of the targets per entry (an ordinal may repeat: N parts on one GPU)
     std::vector<std::pair<std::string, long long>> ctx_options;  // --ctx-option key=value
-    auto need = [&](int &i) -> const char * {
-        if (i + 1 >= argc) {
-            std::fprintf(stderr, "error: a value is required for '%s' but none was supplied\n", argv[i]);
-            std::exit(2);
-        }
-        return argv[++i];
-    };
     auto num = [&](const char *s, const char *flag) -> unsigned long long {
         char *e = nullptr;
         if (!*s || *s == '-') {
@@ -257,7 +250,7 @@ int main(int argc, char **argv) {
         auto eq = s.find('=');
         std::string key = (s.size() > 2 && s[0] == '-' && s[1] == '-' && eq != std::string::npos) ? s.substr(0, eq) : s;
         const char *inl = (key.size() != s.size()) ? argv[i] + eq + 1 : nullptr;
-        auto val = [&]() { return inl ? inl : need(i); };
+        auto val = [&] { return need(argc, argv, i, inl); };
         if (key == "-r" || key == "--region") a.region = val();
         else if (key == "-R" || key == "--region-file" || key == "--region_file") a.region_file = val();
         else if (key == "-m" || key == "--minlen") a.minlen = (uint32_t)num(val(), "--minlen");
@@ -277,7 +270,7 @@ int main(int argc, char **argv) {
             }
         }
         else if (s == "--ctx-option" || s.rfind("--ctx-option=", 0) == 0) {
-            const std::string kv = s == "--ctx-option" ? std::string(need(i)) : s.substr(13);
+            const std::string kv = s == "--ctx-option" ? std::string(need(argc, argv, i)) : s.substr(13);
             const size_t e2 = kv.find('=');
             char *endp = nullptr;
             const long long v = e2 == std::string::npos ? 0 : std::strtoll(kv.c_str() + e2 + 1, &endp, 10);
@@ -314,7 +307,7 @@ int main(int argc, char **argv) {
         ::setenv("INQ_FAST_EXIT", "1", 0);
         std::vector<inq_part_stats_t> st(devices.size());
         int rc = inq::host_api().genotype_repeats_devices(&a, devices.data(), devices.size(), 1 /* stdout */, st.data(), err, sizeof err);
-        if (rc != 0) std::fprintf(stderr, rc == INQ_EXIT_PANIC ? "thread 'main' panicked:\n%s\n" : "%s\n", err);
+        complain(rc, err);
         if (std::getenv("INQ_TIMING"))
             for (size_t r = 0; r < st.size(); ++r)
                 std::fprintf(stderr,
@@ -324,10 +317,7 @@ int main(int argc, char **argv) {
                              st[r].bam_bytes_read / 1e6, st[r].io_threads, st[r].rows_s, st[r].span_loop_s,
                              st[r].span_loop_s > 0 ? st[r].bam_bytes_read / 1e9 / st[r].span_loop_s : 0.0, st[r].wait_loader_s, st[r].device_calls_s,
                              st[r].front == 2 ? "device" : st[r].front == 1 ? "host" : "-");
-        std::fflush(nullptr);
-        const char *fast = std::getenv("INQ_FAST_EXIT");
-        if (fast && fast[0] == '1') std::_Exit(rc);
-        return rc;
+        return leave(rc, nullptr);
     }
     if (const char *server_env = std::getenv("INQ_SERVER"); server_env && *server_env) {
         // INQ_SERVER=auto: this user's server for the device, started (detached; it leaves after INQ_SERVER_IDLE seconds without a
@@ -348,7 +338,7 @@ int main(int argc, char **argv) {
         std::string msg;
         const int got = inq::client_call(server, &a, 1 /* stdout */, &st, &msg);
         if (got > 0) {
-            if (st != 0) std::fprintf(stderr, st == INQ_EXIT_PANIC ? "thread 'main' panicked:\n%s\n" : "%s\n", msg.c_str());
+            complain(st, msg.c_str());
             return st;
         }
         if (got < 0) {
@@ -358,18 +348,6 @@ int main(int argc, char **argv) {
         // no server there: the call runs here, as without INQ_SERVER
     }
     char err[1024] = {0};
-    ::setenv("INQ_FAST_EXIT", "1", 0);  // this process ends with the call: see run_device_front
-    int rc = inq::host_api().genotype_repeats(&a, 1 /* stdout */, err, sizeof err);
-    if (rc != 0) {
-        if (rc == INQ_EXIT_PANIC)
-            std::fprintf(stderr, "thread 'main' panicked:\n%s\n", err);
-        else
-            std::fprintf(stderr, "%s\n", err);
-    }
-    // the rows went out through write(2); nothing is buffered.  Skip the atexit handlers of the HIP runtime
-    // (tens of milliseconds of tear-down for a process that is over).
-    std::fflush(nullptr);
-    const char *fast = std::getenv("INQ_FAST_EXIT");  // INQ_FAST_EXIT=0: leave normally (profilers write their output at exit)
-    if (fast && fast[0] == '1') std::_Exit(rc);
-    return rc;
+    ::setenv("INQ_FAST_EXIT", "1", 0);  // this process ends with the call: see leave()
+    return leave(inq::host_api().genotype_repeats(&a, 1 /* stdout */, err, sizeof err), err);
 }

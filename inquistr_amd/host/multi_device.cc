@@ -40,7 +40,7 @@ int run_parts(Prepared &P, size_t world, const PartFn &fn, std::vector<double> &
         parts[r].a.assign(hi - lo, NAN);
         parts[r].b.assign(hi - lo, NAN);
         th.emplace_back([&, r, lo, hi] {
-            const auto t0 = std::chrono::steady_clock::now();
+            const auto t0 = Clock::now();
             try {
                 parts[r].rc = fn(r, order.data() + lo, hi - lo, parts[r].a.data(), parts[r].b.data(), parts[r].err, sizeof parts[r].err);
             } catch (const std::exception &e) {
@@ -50,7 +50,7 @@ int run_parts(Prepared &P, size_t world, const PartFn &fn, std::vector<double> &
                 parts[r].rc = INQ_EXIT_ERROR;
                 std::snprintf(parts[r].err, sizeof parts[r].err, "internal error");
             }
-            parts[r].seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            parts[r].seconds = secs(t0, Clock::now());
         });
     }
     for (auto &t : th) t.join();
@@ -67,8 +67,10 @@ int run_parts(Prepared &P, size_t world, const PartFn &fn, std::vector<double> &
     }
     if (first_bad != INQ_EXIT_OK) return first_bad;
     // the gather of the one-process-per-GPU form, here: rows to their targets' places
-    for (size_t r = 0; r < world; ++r)
-        for (uint64_t k = cuts[r]; k < cuts[r + 1]; ++k) p1[order[k]] = parts[r].a[k - cuts[r]], p2[order[k]] = parts[r].b[k - cuts[r]];
+    for (size_t r = 0; r < world; ++r) {
+        const uint32_t *idx = order.data() + cuts[r];
+        scatter(parts[r].a.data(), idx, parts[r].a.size(), p1.data()), scatter(parts[r].b.data(), idx, parts[r].b.size(), p2.data());
+    }
     return INQ_EXIT_OK;
 }
 
@@ -87,7 +89,7 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
             set_err(errbuf, errcap, "device list: negative device ordinal");
             return INQ_EXIT_ERROR;
         }
-    const auto t_start = std::chrono::steady_clock::now();
+    const auto t_start = Clock::now();
     std::string msg;
     TiesFile tf;
     if (tf.open(args->ties_path, msg) != INQ_EXIT_OK) {
@@ -101,11 +103,8 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
         actx[r]->start(device_ids[r], (int)n_devices);
     }
     Prepared P;
-    int rc = prepare(args, P, msg);
-    if (rc != INQ_EXIT_OK) {
-        set_err(errbuf, errcap, msg);
-        return rc;
-    }
+    int rc = prepare(args, P, errbuf, errcap);
+    if (rc != INQ_EXIT_OK) return rc;
     std::vector<PartStats> pst(n_devices);
     // the tie report: each part's flags are scattered like its rows (the parts' target sets are disjoint)
     std::vector<uint8_t> ties(tf.fd >= 0 ? P.targets.size() : 0, 0);
@@ -120,12 +119,13 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
         ro.idx = idx, ro.n = n, ro.p1 = a, ro.p2 = b, ro.active = true;
         SessionHooks hooks;
         hooks.sharers = (int)n_devices, hooks.share_index = (int)r, hooks.stats = &pst[r];
+        hooks.process_is_leaving = fast_exit();  // the contexts are this call's own, and so is the process's end (`call --devices`)
         std::vector<uint8_t> part_ties(tf.fd >= 0 ? n : 0, 0);
         if (tf.fd >= 0) hooks.ties_out = part_ties.data();
         // (the runtime threads of this part prefer the NUMA node of ITS device: genotype_prepared's helpers bind per thread)
         const int prc = genotype_prepared(&oa.a, *actx[r], P, -1, err, cap, ro, t_start, hooks);
-        if (prc == INQ_EXIT_OK && tf.fd >= 0)
-            for (uint64_t k = 0; k < n; ++k) ties[idx[k]] = part_ties[k];
+        actx[r]->leak = prc == INQ_EXIT_OK && hooks.process_is_leaving;  // only after a clean run: error paths tear down normally
+        if (prc == INQ_EXIT_OK && tf.fd >= 0) scatter(part_ties.data(), idx, n, ties.data());
         return prc;
     };
     rc = run_parts(P, n_devices, fn, p1, p2, order, cuts, &part_rc, &part_s, errbuf, errcap);
@@ -157,12 +157,8 @@ int inq_genotype_repeats_devices(const inq_call_args_t *args, const int32_t *dev
 static int devices_selftest_impl(const inq_call_args_t *args, size_t n_parts, int fail_part, int out_fd, uint64_t *cuts_out, char *errbuf, size_t errcap) {
     if (!args || n_parts == 0 || n_parts > 64) return INQ_EXIT_ERROR;
     Prepared P;
-    std::string msg;
-    int rc = prepare(args, P, msg);
-    if (rc != INQ_EXIT_OK) {
-        set_err(errbuf, errcap, msg);
-        return rc;
-    }
+    int rc = prepare(args, P, errbuf, errcap);
+    if (rc != INQ_EXIT_OK) return rc;
     std::vector<double> p1, p2;
     std::vector<uint32_t> order;
     std::vector<uint64_t> cuts;

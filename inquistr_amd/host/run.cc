@@ -28,7 +28,7 @@ int prepare(const inq_call_args_t *a, Prepared &P, std::string &msg, BedCache *b
     }
     P.sample = a->sample_name ? std::string(a->sample_name) : sample_name_from_path(bamp);  // :91-100
     // get_chrom_lengths_from_bam_header opens the BAM before the target arguments are looked at (:187)
-    const auto t_open = std::chrono::steady_clock::now();
+    const auto t_open = Clock::now();
     P.bam.reset(new BamFile(1));  // header + index; with -t > 1 every sweep worker opens its own reader
     std::string e;
     if (!P.bam->open(bamp, &e)) {
@@ -40,28 +40,28 @@ int prepare(const inq_call_args_t *a, Prepared &P, std::string &msg, BedCache *b
         msg = e;
         return INQ_EXIT_PANIC;
     }
-    const auto t_targets = std::chrono::steady_clock::now();
+    const auto t_targets = Clock::now();
     TargetsResult tr;
     if (a->region && !a->region_file)
         tr = targets_from_string(a->region, lengths);  // :190
     else if (!a->region && a->region_file) {
         struct stat sb;
         const bool have_stat = bed_cache && ::stat(a->region_file, &sb) == 0;
+        BedKey key;
+        if (have_stat)
+            key = BedKey{a->region_file, (uint64_t)sb.st_dev, (uint64_t)sb.st_ino, (uint64_t)sb.st_size,
+                         (int64_t)sb.st_mtim.tv_sec * 1000000000ll + sb.st_mtim.tv_nsec, lengths};
         bool hit = false;
         if (have_stat) {
             std::lock_guard<std::mutex> lk(bed_cache->mu);
-            hit = bed_cache->valid && bed_cache->path == a->region_file && bed_cache->dev == (uint64_t)sb.st_dev && bed_cache->ino == (uint64_t)sb.st_ino &&
-                  bed_cache->size == (uint64_t)sb.st_size &&
-                  bed_cache->mtime_ns == (int64_t)sb.st_mtim.tv_sec * 1000000000ll + sb.st_mtim.tv_nsec && bed_cache->lengths == lengths;
+            hit = bed_cache->valid && bed_cache->key == key;
             if (hit) tr = bed_cache->tr;
         }
         if (!hit) {
             tr = targets_from_bed(a->region_file, lengths);  // :192-195
             if (have_stat) {
                 std::lock_guard<std::mutex> lk(bed_cache->mu);
-                bed_cache->path = a->region_file, bed_cache->dev = (uint64_t)sb.st_dev, bed_cache->ino = (uint64_t)sb.st_ino;
-                bed_cache->size = (uint64_t)sb.st_size, bed_cache->mtime_ns = (int64_t)sb.st_mtim.tv_sec * 1000000000ll + sb.st_mtim.tv_nsec;
-                bed_cache->lengths = lengths, bed_cache->tr = tr, bed_cache->valid = true;
+                bed_cache->key = std::move(key), bed_cache->tr = tr, bed_cache->valid = true;
             }
         }
     } else {
@@ -80,12 +80,9 @@ int prepare(const inq_call_args_t *a, Prepared &P, std::string &msg, BedCache *b
         }
     }
     P.targets.swap(tr.data);
-    if (const char *tm = std::getenv("INQ_TIMING"); tm && tm[0] == '2') {
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[inq prepare] header + index %.2f ms, targets (%zu) %.2f ms\n",
-                     std::chrono::duration<double, std::milli>(t_targets - t_open).count(), P.targets.size(),
-                     std::chrono::duration<double, std::milli>(now - t_targets).count());
-    }
+    if (timing_level() == 2)
+        std::fprintf(stderr, "[inq prepare] header + index %.2f ms, targets (%zu) %.2f ms\n", ms(t_open, t_targets), P.targets.size(),
+                     ms(t_targets, Clock::now()));
     return INQ_EXIT_OK;
 }
 
@@ -107,13 +104,18 @@ bool write_all(int fd, const char *data, size_t len) {
     return true;
 }
 
+int device_call_failed(int rc, inq_ctx_t *ctx, char *errbuf, size_t errcap, const std::string &suffix) {
+    std::string m = std::string("device call failed: ") + inq_strerror(rc);
+    if (rc == INQ_ERR_HIP) m += std::string(" [") + inq_last_error(ctx) + "]";
+    set_err(errbuf, errcap, m + suffix);
+    return (rc == INQ_ERR_HIP || rc == INQ_ERR_NOMEM || rc == INQ_ERR_NO_DEVICE) ? INQ_EXIT_ERROR : INQ_EXIT_PANIC;
+}
+
 // the call on an opened BAM + parsed targets, on a device context that may outlive it (a session calls many BAMs on one)
 int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, int out_fd, char *errbuf, size_t errcap,
-                             const RowsOut &rows, std::chrono::steady_clock::time_point t_start, const SessionHooks &hooks) {
-    using clk = std::chrono::steady_clock;
-    const bool timing = std::getenv("INQ_TIMING") != nullptr;
+                             const RowsOut &rows, Clock::time_point t_start, const SessionHooks &hooks) {
+    const int timing = timing_level();
     double t_front = 0, t_dev = 0;
-    auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
     std::vector<RepeatInterval> sub;
     if (rows.active) {  // this caller's share of the targets (one process per GPU: inquistr_amd/call_dist.py)
         sub.reserve(rows.n);
@@ -125,8 +127,7 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
             sub.push_back(P.targets[rows.idx[k]]);
         }
     }
-    const CallView V{*P.bam, rows.active ? sub : P.targets, P.sample, args->minlen,
-                     (uint32_t)std::min<uint64_t>(args->support, 0xffffffffull), args->unphased != 0};
+    const CallView V{*P.bam, rows.active ? sub : P.targets, P.sample, CallOptions(*args)};
     const size_t n = V.targets.size();
     std::vector<double> p1(n, NAN), p2(n, NAN);
     // the tie report: per-target flags, collected only when someone asked for them (the locus kernels run without flags otherwise)
@@ -147,7 +148,7 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
         return INQ_EXIT_OK;
     };
 
-    const auto t_open = clk::now();
+    const auto t_open = Clock::now();
     const bool device_front = hooks.front ? hooks.front == 2 : use_device_front(args, V.bam, V.targets);
     // what the call did, for whoever asks afterwards (a device part's inq_part_stats_t, inq_host_last_call_stats)
     PartStats local_stats;
@@ -158,25 +159,25 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
     } publish{ps};
     ps->front = device_front ? 2 : 1;
     if (device_front) {
-        const auto t_choice = clk::now();
+        const auto t_choice = Clock::now();
         SessionHooks dh = hooks;
         dh.stats = ps;
         if (rows_on_device) dh.dev_p1 = rows.d1, dh.dev_p2 = rows.d2, dh.dev_cap = rows.dcap;
         dh.ties_out = want_ties ? ties.data() : nullptr;  // (indexed like p1 / p2)
         int drc = run_device_front(args, V, actx, p1, p2, errbuf, errcap, &t_front, &t_dev, dh);
         if (drc != INQ_EXIT_OK) return drc;
-        const auto t_run = clk::now();
+        const auto t_run = Clock::now();
         drc = emit();
         if (timing)
             std::fprintf(stderr,
                          "[inq timing] device front end: open+targets %.3fs  front-end choice %.3fs  spans %.3fs (waiting for the loader "
                          "%.3fs, device calls %.3fs)  output %.3fs  total %.3fs\n",
-                         secs(t_start, t_open), secs(t_open, t_choice), secs(t_choice, t_run), t_front, t_dev, secs(t_run, clk::now()),
-                         secs(t_start, clk::now()));
+                         secs(t_start, t_open), secs(t_open, t_choice), secs(t_choice, t_run), t_front, t_dev, secs(t_run, Clock::now()),
+                         secs(t_start, Clock::now()));
         return drc;
     }
 
-    auto t_prep = clk::now();
+    auto t_prep = Clock::now();
     inq_ctx_t *&ctx = actx.ctx;
     int &hrc = actx.hrc;
     bool ctx_ready = false;
@@ -210,17 +211,16 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
         }
     } pin;
     const int n_workers = (int)std::max<uint64_t>(1, std::min<uint64_t>(args->threads > 1 ? args->threads - 1 : 1, 64));
-    ParallelFrontEnd pfe(args->bam, V.bam, V.targets, V.unphased, n_workers);
-    auto t_ctx = clk::now();
-    std::vector<double> b1, b2;
-    std::vector<uint8_t> bt;
+    ParallelFrontEnd pfe(args->bam, V.bam, V.targets, V.opt.unphased, n_workers);
+    auto t_ctx = Clock::now();
+    BatchRows br;
     for (;;) {
         ParallelFrontEnd::Item item;
         std::string ferr;
         bool fpanic = false;
-        auto ta = clk::now();
+        auto ta = Clock::now();
         int nb = pfe.next(item, &ferr, &fpanic);
-        auto tb = clk::now();
+        auto tb = Clock::now();
         t_front += secs(ta, tb);
         if (nb < 0) {
             set_err(errbuf, errcap, ferr);
@@ -229,7 +229,7 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
         if (nb == 0) break;
         if (!need_ctx()) return INQ_EXIT_ERROR;
         inq_batch_t batch;
-        item.batch.view(&batch, V.minlen, V.support, V.unphased);
+        item.batch.view(&batch, V.opt.minlen, V.opt.support, V.opt.unphased);
         {
             auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
             const size_t s0 = al(batch.n_cigar_words * 4), s1 = al(batch.n_reads * sizeof(inq_read_t)),
@@ -253,33 +253,16 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
             batch.locus_start = (const uint32_t *)put(batch.locus_start, batch.n_loci * 4, off, s4);
             batch.locus_end = (const uint32_t *)put(batch.locus_end, batch.n_loci * 4, off, s4);
         }
-        b1.assign(batch.n_loci, NAN);
-        b2.assign(batch.n_loci, NAN);
-        if (want_ties) bt.assign(batch.n_loci, 0);
-        inq_result_t res;
-        std::memset(&res, 0, sizeof res);
-        res.phase1 = b1.data();
-        res.phase2 = b2.data();
-        auto tc = clk::now();
-        int rc2 = want_ties ? inq_call_batch_flags(ctx, &batch, &res, bt.data()) : inq_call_batch(ctx, &batch, &res);
-        t_dev += secs(tb, clk::now());
-        if (timing && std::getenv("INQ_TIMING")[0] == '2')
+        br.begin(batch.n_loci, want_ties);
+        auto tc = Clock::now();
+        int rc2 = want_ties ? inq_call_batch_flags(ctx, &batch, &br.res, br.flags) : inq_call_batch(ctx, &batch, &br.res);
+        t_dev += secs(tb, Clock::now());
+        if (timing == 2)
             std::fprintf(stderr, "[inq batch] loci %llu pairs %llu cigar %.1f MB  wait-ctx %.2f ms  call %.2f ms\n",
                          (unsigned long long)batch.n_loci, (unsigned long long)batch.n_pairs, batch.n_cigar_words * 4 / 1e6,
-                         secs(tb, tc) * 1e3, secs(tc, clk::now()) * 1e3);
-        if (rc2 != INQ_OK) {
-            std::string m = std::string("device call failed: ") + inq_strerror(rc2);
-            if (rc2 == INQ_ERR_HIP) m += std::string(" [") + inq_last_error(ctx) + "]";
-            set_err(errbuf, errcap, m);
-            // domain errors are the reference's panics (HP > 2, bad CIGAR op, ...)
-            return (rc2 == INQ_ERR_HIP || rc2 == INQ_ERR_NOMEM || rc2 == INQ_ERR_NO_DEVICE) ? INQ_EXIT_ERROR : INQ_EXIT_PANIC;
-        }
-        for (uint64_t j = 0; j < batch.n_loci; ++j) {
-            p1[item.index[j]] = b1[j];
-            p2[item.index[j]] = b2[j];
-        }
-        if (want_ties)
-            for (uint64_t j = 0; j < batch.n_loci; ++j) ties[item.index[j]] = bt[j];
+                         secs(tb, tc) * 1e3, secs(tc, Clock::now()) * 1e3);
+        if (rc2 != INQ_OK) return device_call_failed(rc2, ctx, errbuf, errcap);
+        br.scatter_to(item.index.data(), p1.data(), p2.data(), ties.data());
         pfe.recycle(std::move(item));
     }
     if (!need_ctx()) return INQ_EXIT_ERROR;  // no GPU is an error even for an empty target list
@@ -294,13 +277,9 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
         int wrc = emit();
         if (wrc != INQ_EXIT_OK) return wrc;
     }
-    {  // the CLI is about to leave the process: the device context is left to the operating system (see run_device_front)
-        const char *fast_env = std::getenv("INQ_FAST_EXIT");
-        actx.leak = fast_env && fast_env[0] == '1';
-    }
     if (timing)
         std::fprintf(stderr, "[inq timing] open+targets %.3fs  hip ctx %.3fs  front end %.3fs  device calls %.3fs  total %.3fs\n",
-                     secs(t_start, t_prep), secs(t_prep, t_ctx), t_front, t_dev, secs(t_start, clk::now()));
+                     secs(t_start, t_prep), secs(t_prep, t_ctx), t_front, t_dev, secs(t_start, Clock::now()));
     return INQ_EXIT_OK;
 }
 
@@ -384,10 +363,9 @@ int write_ties(const std::vector<uint32_t> &order, const std::vector<RepeatInter
 int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, const std::string &sample, const double *p1,
                       const double *p2, int out_fd, char *errbuf, size_t errcap, const uint8_t *ties, int ties_fd) {
     const size_t n = targets.size();
-    const bool timing = std::getenv("INQ_TIMING") != nullptr;
-    const auto t_w0 = std::chrono::steady_clock::now();
+    const auto t_w0 = Clock::now();
     const std::vector<uint32_t> order = row_order(threads, targets);
-    const auto t_w1 = std::chrono::steady_clock::now();
+    const auto t_w1 = Clock::now();
     // the text: rows formatted by a few threads into their own stretches of one buffer (sized from an upper bound per row,
     // written through a bare pointer: no per-character capacity checks), written in order.  Four threads at most: 500 000
     // rows are 17 MB of text, ~20 ms on one core, and starting a thread costs up to 2 ms on virtualised hosts.
@@ -404,7 +382,7 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
         }
         part_off[k + 1] = part_off[k] + ((cap + 63) & ~(size_t)63);
     }
-    const auto t_w1b = std::chrono::steady_clock::now();
+    const auto t_w1b = Clock::now();
     const size_t huge = 2u << 20, map_len = (part_off[n_parts] + huge - 1) / huge * huge;
     char *const base = (char *)::mmap(nullptr, map_len, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
     if (base == (char *)MAP_FAILED) {
@@ -429,7 +407,7 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
         format_part(0);
         for (auto &x : th) x.join();
     }
-    const auto t_w2 = std::chrono::steady_clock::now();
+    const auto t_w2 = Clock::now();
     bool wrote = true;
     for (size_t k = 0; k < n_parts && wrote; ++k) wrote = write_all(out_fd, base + part_off[k], part_len[k]);
     ::munmap(base, map_len);
@@ -441,11 +419,9 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
         const int trc = write_ties(order, targets, ties, ties_fd, errbuf, errcap);
         if (trc != INQ_EXIT_OK) return trc;
     }
-    if (timing) {
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    if (timing_level())
         std::fprintf(stderr, "[inq output] %zu rows: order %.2f ms, bounds %.2f ms, text %.2f ms (%zu threads), write %.2f ms\n", n, ms(t_w0, t_w1), ms(t_w1, t_w1b), ms(t_w1b, t_w2),
-                     n_parts, ms(t_w2, std::chrono::steady_clock::now()));
-    }
+                     n_parts, ms(t_w2, Clock::now()));
     return INQ_EXIT_OK;
 }
 
@@ -458,10 +434,18 @@ struct inq_frontend {
     ParallelFrontEnd::Item item;
     HostBatch batch;
     std::string bam_path;
-    uint32_t minlen = 5, support = 3;
+    CallOptions opt;
     uint64_t threads = 1, max_words = 0;
-    bool unphased = false;
 };
+
+// target i of a prepared call, for the two handles that show their list (0, or -1 past its end)
+static int target_at(const Prepared &P, uint64_t i, const char **chrom, uint32_t *start, uint32_t *end) {
+    if (i >= P.targets.size()) return -1;
+    if (chrom) *chrom = P.targets[i].chrom.c_str();
+    if (start) *start = P.targets[i].start;
+    if (end) *end = P.targets[i].end;
+    return 0;
+}
 
 extern "C" {
 
@@ -469,18 +453,12 @@ static int inq_frontend_open_impl(const inq_call_args_t *args, inq_frontend_t **
     if (!out) return INQ_EXIT_ERROR;
     *out = nullptr;
     std::unique_ptr<inq_frontend> F(new inq_frontend());
-    std::string msg;
-    int rc = prepare(args, F->P, msg);
-    if (rc != INQ_EXIT_OK) {
-        set_err(errbuf, errcap, msg);
-        return rc;
-    }
-    F->minlen = args->minlen;
-    F->support = (uint32_t)std::min<uint64_t>(args->support, 0xffffffffull);
-    F->unphased = args->unphased != 0;
+    const int rc = prepare(args, F->P, errbuf, errcap);
+    if (rc != INQ_EXIT_OK) return rc;
+    F->opt = CallOptions(*args);
     F->threads = args->threads;
     F->bam_path = args->bam;
-    if (F->threads <= 1) F->fe.reset(new FrontEnd(*F->P.bam, F->P.targets, F->unphased));
+    if (F->threads <= 1) F->fe.reset(new FrontEnd(*F->P.bam, F->P.targets, F->opt.unphased));
     *out = F.release();
     return INQ_EXIT_OK;
 }
@@ -488,11 +466,7 @@ static int inq_frontend_open_impl(const inq_call_args_t *args, inq_frontend_t **
 uint64_t inq_frontend_n_targets(const inq_frontend_t *fe) { return fe ? fe->P.targets.size() : 0; }
 
 int inq_frontend_target(const inq_frontend_t *fe, uint64_t i, const char **chrom, uint32_t *start, uint32_t *end) {
-    if (!fe || i >= fe->P.targets.size()) return -1;
-    if (chrom) *chrom = fe->P.targets[i].chrom.c_str();
-    if (start) *start = fe->P.targets[i].start;
-    if (end) *end = fe->P.targets[i].end;
-    return 0;
+    return fe ? target_at(fe->P, i, chrom, start, end) : -1;
 }
 
 const char *inq_frontend_sample(const inq_frontend_t *fe) { return fe ? fe->P.sample.c_str() : ""; }
@@ -510,7 +484,7 @@ static int inq_frontend_next_impl(inq_frontend_t *fe, inq_batch_t *batch, const 
     bool panic = false;
     if (fe->threads > 1) {  // batches arrive in completion order; locus_index says where each row belongs
         if (!fe->pfe)
-            fe->pfe.reset(new ParallelFrontEnd(fe->bam_path, *fe->P.bam, fe->P.targets, fe->unphased,
+            fe->pfe.reset(new ParallelFrontEnd(fe->bam_path, *fe->P.bam, fe->P.targets, fe->opt.unphased,
                                                (int)std::min<uint64_t>(fe->threads, 64), fe->max_words));
         fe->pfe->recycle(std::move(fe->item));
         fe->item = ParallelFrontEnd::Item();
@@ -520,7 +494,7 @@ static int inq_frontend_next_impl(inq_frontend_t *fe, inq_batch_t *batch, const 
             return -INQ_EXIT_PANIC;
         }
         if (rc == 0) return 0;
-        fe->item.batch.view(batch, fe->minlen, fe->support, fe->unphased);
+        fe->item.batch.view(batch, fe->opt.minlen, fe->opt.support, fe->opt.unphased);
         if (locus_index) *locus_index = fe->item.index.data();
         return 1;
     }
@@ -530,7 +504,7 @@ static int inq_frontend_next_impl(inq_frontend_t *fe, inq_batch_t *batch, const 
         return -INQ_EXIT_PANIC;  // read errors are expect()/unwrap() panics too (:294,346)
     }
     if (rc == 0) return 0;
-    fe->batch.view(batch, fe->minlen, fe->support, fe->unphased);
+    fe->batch.view(batch, fe->opt.minlen, fe->opt.support, fe->opt.unphased);
     if (locus_index) *locus_index = fe->batch.locus_index.data();
     return 1;
 }
@@ -539,7 +513,7 @@ void inq_frontend_close(inq_frontend_t *fe) { delete fe; }
 
 
 static int inq_genotype_repeats_impl(const inq_call_args_t *args, int out_fd, char *errbuf, size_t errcap, const RowsOut &rows = RowsOut()) {
-    const auto t_start = std::chrono::steady_clock::now();
+    const auto t_start = Clock::now();
     std::string msg;
     TiesFile tf;  // (a call that returns rows writes no file)
     if (args && !rows.active && tf.open(args->ties_path, msg) != INQ_EXIT_OK) {
@@ -549,26 +523,21 @@ static int inq_genotype_repeats_impl(const inq_call_args_t *args, int out_fd, ch
     AsyncCtx actx;
     if (args) actx.start(args->device);
     Prepared P;
-    int rc = prepare(args, P, msg);
-    if (rc != INQ_EXIT_OK) {
-        set_err(errbuf, errcap, msg);
-        return rc;
-    }
+    int rc = prepare(args, P, errbuf, errcap);
+    if (rc != INQ_EXIT_OK) return rc;
     SessionHooks hooks;
     hooks.ties_fd = tf.fd;
-    return genotype_prepared(args, actx, P, out_fd, errbuf, errcap, rows, t_start, hooks);
+    hooks.process_is_leaving = fast_exit();  // the context is this call's own, and so is the process's end (the CLI's `call`)
+    rc = genotype_prepared(args, actx, P, out_fd, errbuf, errcap, rows, t_start, hooks);
+    actx.leak = rc == INQ_EXIT_OK && hooks.process_is_leaving;  // only after a clean run: error paths tear down normally
+    return rc;
 }
 
 int inq_frontend_open(const inq_call_args_t *args, inq_frontend_t **out, char *errbuf, size_t errcap) {
     INQ_GUARD(inq_frontend_open_impl(args, out, errbuf, errcap), errbuf, errcap)
 }
 int inq_frontend_next(inq_frontend_t *fe, inq_batch_t *batch, const uint32_t **locus_index, char *errbuf, size_t errcap) {
-    try {
-        return inq_frontend_next_impl(fe, batch, locus_index, errbuf, errcap);
-    } catch (...) {
-        set_err(errbuf, errcap, "internal error");
-        return -INQ_EXIT_ERROR;
-    }
+    INQ_GUARD_AS(-INQ_EXIT_ERROR, inq_frontend_next_impl(fe, batch, locus_index, errbuf, errcap), errbuf, errcap)
 }
 int inq_genotype_repeats(const inq_call_args_t *args, int out_fd, char *errbuf, size_t errcap) {
     INQ_GUARD(inq_genotype_repeats_impl(args, out_fd, errbuf, errcap), errbuf, errcap)
@@ -658,12 +627,8 @@ static int inq_host_partition_impl(const inq_call_args_t *args, uint64_t world, 
         return INQ_EXIT_ERROR;
     }
     Prepared P;
-    std::string msg;
-    int rc = prepare(args, P, msg);
-    if (rc != INQ_EXIT_OK) {
-        set_err(errbuf, errcap, msg);
-        return rc;
-    }
+    const int rc = prepare(args, P, errbuf, errcap);
+    if (rc != INQ_EXIT_OK) return rc;
     const size_t n = P.targets.size();
     *n_targets = n;
     if (n > order_cap || (n && !order)) {
@@ -704,12 +669,8 @@ static int inq_run_open_impl(const inq_call_args_t *args, inq_run_t **out, char 
     R->args.reset(new OwnedArgs(*args));
     R->sess = sess;
     if (sess) R->args->a.device = sess->device;
-    std::string msg;
-    int rc = prepare(&R->args->a, R->P, msg, sess ? &sess->bed_cache : nullptr);
-    if (rc != INQ_EXIT_OK) {
-        set_err(errbuf, errcap, msg);
-        return rc;
-    }
+    const int rc = prepare(&R->args->a, R->P, errbuf, errcap, sess ? &sess->bed_cache : nullptr);
+    if (rc != INQ_EXIT_OK) return rc;
     *out = R.release();
     return INQ_EXIT_OK;
 }
@@ -726,11 +687,7 @@ int inq_session_run_open(inq_session_t *s, const inq_call_args_t *args, inq_run_
 uint64_t inq_run_n_targets(const inq_run_t *r) { return r ? r->P.targets.size() : 0; }
 const char *inq_run_sample(const inq_run_t *r) { return r ? r->P.sample.c_str() : ""; }
 int inq_run_target(const inq_run_t *r, uint64_t i, const char **chrom, uint32_t *start, uint32_t *end) {
-    if (!r || i >= r->P.targets.size()) return -1;
-    if (chrom) *chrom = r->P.targets[i].chrom.c_str();
-    if (start) *start = r->P.targets[i].start;
-    if (end) *end = r->P.targets[i].end;
-    return 0;
+    return r ? target_at(r->P, i, chrom, start, end) : -1;
 }
 int inq_run_partition(inq_run_t *r, uint64_t world, uint32_t *order, uint64_t *cuts, char *errbuf, size_t errcap) {
     if (!r || !world || !cuts || (!order && !r->P.targets.empty())) {
@@ -739,31 +696,33 @@ int inq_run_partition(inq_run_t *r, uint64_t world, uint32_t *order, uint64_t *c
     }
     INQ_GUARD(partition_prepared(r->P, world, order, cuts), errbuf, errcap)
 }
+// The rows of the targets target_index[0 .. n_index) on actx, which outlives the call (the session's, or the run's own: nothing is made
+// or torn down per call) or is the caller's to end; ro says where they go.  The tie flags are collected when the run was opened
+// with ties_path set.
+static int run_rows_on(inq_run_t *r, AsyncCtx &actx, RowsOut ro, const uint32_t *target_index, uint64_t n_index, Clock::time_point t_start,
+                       char *errbuf, size_t errcap) {
+    ro.idx = target_index, ro.n = n_index, ro.active = true;
+    SessionHooks hooks;
+    if (r->sess) hooks.pool = &r->sess->pool;  // the session's span buffers
+    r->have_ties = false;
+    if (r->args->a.ties_path) r->ties.assign(n_index, 0), hooks.ties_out = r->ties.data();
+    const int rc = genotype_prepared(&r->args->a, actx, r->P, -1, errbuf, errcap, ro, t_start, hooks);
+    r->have_ties = rc == INQ_EXIT_OK && hooks.ties_out;
+    return rc;
+}
 static int inq_run_rows_impl(inq_run_t *r, const uint32_t *target_index, uint64_t n_index, double *phase1, double *phase2, char *errbuf,
                              size_t errcap) {
     if (!r || (n_index && (!target_index || !phase1 || !phase2))) {
         set_err(errbuf, errcap, "null argument");
         return INQ_EXIT_ERROR;
     }
-    const auto t_start = std::chrono::steady_clock::now();
+    const auto t_start = Clock::now();
     RowsOut ro;
-    ro.idx = target_index, ro.n = n_index, ro.p1 = phase1, ro.p2 = phase2, ro.active = true;
-    SessionHooks hooks;
-    r->have_ties = false;
-    if (r->args->a.ties_path) r->ties.assign(n_index, 0), hooks.ties_out = r->ties.data();
-    if (r->sess) {  // the session's context and span buffers: nothing is made or torn down per call
-        hooks.pool = &r->sess->pool;
-        const bool keep_leak = r->sess->actx.leak;
-        const int rc = genotype_prepared(&r->args->a, r->sess->actx, r->P, -1, errbuf, errcap, ro, t_start, hooks);
-        r->sess->actx.leak = keep_leak;  // the context belongs to the session
-        r->have_ties = rc == INQ_EXIT_OK && hooks.ties_out;
-        return rc;
-    }
-    AsyncCtx actx;
+    ro.p1 = phase1, ro.p2 = phase2;
+    if (r->sess) return run_rows_on(r, r->sess->actx, ro, target_index, n_index, t_start, errbuf, errcap);
+    AsyncCtx actx;  // this call's own, destroyed with it
     actx.start(r->args->a.device);
-    const int rc = genotype_prepared(&r->args->a, actx, r->P, -1, errbuf, errcap, ro, t_start, hooks);
-    r->have_ties = rc == INQ_EXIT_OK && hooks.ties_out;
-    return rc;
+    return run_rows_on(r, actx, ro, target_index, n_index, t_start, errbuf, errcap);
 }
 int inq_run_rows(inq_run_t *r, const uint32_t *target_index, uint64_t n_index, double *phase1, double *phase2, char *errbuf, size_t errcap) {
     INQ_GUARD(inq_run_rows_impl(r, target_index, n_index, phase1, phase2, errbuf, errcap), errbuf, errcap)
@@ -775,7 +734,7 @@ static int inq_run_rows_device_impl(inq_run_t *r, const uint32_t *target_index, 
         return INQ_EXIT_ERROR;
     }
     *d_phase1 = *d_phase2 = nullptr;
-    const auto t_start = std::chrono::steady_clock::now();
+    const auto t_start = Clock::now();
     if (!r->sess && !r->actx) {
         r->actx.reset(new AsyncCtx());
         r->actx->start(r->args->a.device);
@@ -796,16 +755,9 @@ static int inq_run_rows_device_impl(inq_run_t *r, const uint32_t *target_index, 
     }
     r->d2 = r->d1 + w, r->dcap = w;
     RowsOut ro;
-    ro.idx = target_index, ro.n = n_index, ro.active = true, ro.d1 = r->d1, ro.d2 = r->d2, ro.dcap = r->dcap;
-    SessionHooks hooks;
-    if (r->sess) hooks.pool = &r->sess->pool;
-    r->have_ties = false;
-    if (r->args->a.ties_path) r->ties.assign(n_index, 0), hooks.ties_out = r->ties.data();
-    const bool keep_leak = actx.leak;
-    const int rc = genotype_prepared(&r->args->a, actx, r->P, -1, errbuf, errcap, ro, t_start, hooks);
-    actx.leak = keep_leak;  // the context belongs to the run (or its session)
+    ro.d1 = r->d1, ro.d2 = r->d2, ro.dcap = r->dcap;
+    const int rc = run_rows_on(r, actx, ro, target_index, n_index, t_start, errbuf, errcap);
     if (rc != INQ_EXIT_OK) return rc;
-    r->have_ties = hooks.ties_out != nullptr;
     *d_phase1 = r->d1, *d_phase2 = r->d2;
     return INQ_EXIT_OK;
 }

@@ -18,11 +18,11 @@ struct StagedFile {
     std::unique_ptr<SpanPipeline> pipe;
     std::unique_ptr<TiesFile> ties;  // the tie report (args->ties_path), opened when the file is staged
     int slot_base = 0, front = 0;
-    std::chrono::steady_clock::time_point t_start;
+    Clock::time_point t_start;
 };
 
 void stage_file(inq_session *S, const inq_call_args_t *a, int slot_base, StagedFile &out) {
-    out.t_start = std::chrono::steady_clock::now();
+    out.t_start = Clock::now();
     try {
         out.args.reset(new OwnedArgs(*a));
         out.slot_base = slot_base;
@@ -50,10 +50,8 @@ int run_staged(inq_session *S, StagedFile &f, int out_fd, char *errbuf, size_t e
     hooks.slot_base = f.slot_base;
     hooks.front = f.front;
     hooks.ties_fd = f.ties ? f.ties->fd : -1;
-    const bool keep_leak = S->actx.leak;
     int rc = genotype_prepared(&f.args->a, S->actx, f.P, out_fd, errbuf, errcap, RowsOut(), f.t_start, hooks);
-    S->actx.leak = keep_leak;  // the context belongs to the session, whatever the single-call path decided
-    f.pipe.reset();            // joins the loader, hands the span buffers back to the pool
+    f.pipe.reset();  // joins the loader, hands the span buffers back to the pool
     return rc;
 }
 }  // namespace
@@ -85,7 +83,7 @@ int inq_session_call(inq_session_t *S, const inq_call_args_t *args, int out_fd, 
 static int inq_session_call_many_impl(inq_session_t *S, const inq_call_args_t *args, size_t n, const int *out_fds, int *statuses, char *errbuf,
                                       size_t errcap) {
     if (!S || (n && (!args || !out_fds))) return INQ_EXIT_ERROR;
-    const bool timing = std::getenv("INQ_TIMING") != nullptr;
+    const int timing = timing_level();
     std::vector<StagedFile> st(n);
     int worst = INQ_EXIT_OK;
     bool have_msg = false;
@@ -95,7 +93,7 @@ static int inq_session_call_many_impl(inq_session_t *S, const inq_call_args_t *a
         std::future<void> next;
         if (k + 1 < n) next = std::async(std::launch::async, [&, k] { stage_file(S, &args[k + 1], SpanPipeline::kSlotsPerSet * (int)((k + 1) & 1), st[k + 1]); });
         char msg[1024] = {0};
-        const auto t0 = std::chrono::steady_clock::now();
+        const auto t0 = Clock::now();
         int rc;
         try {
             rc = run_staged(S, st[k], out_fds[k], msg, sizeof msg);
@@ -105,7 +103,7 @@ static int inq_session_call_many_impl(inq_session_t *S, const inq_call_args_t *a
         }
         if (timing)
             std::fprintf(stderr, "[inq session] @%.1f file %zu (%s): status %d, %.1f ms since the previous file finished\n", stamp_ms(), k,
-                         args[k].bam ? args[k].bam : "?", rc, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+                         args[k].bam ? args[k].bam : "?", rc, ms(t0, Clock::now()));
         if (statuses) statuses[k] = rc;
         if (rc != INQ_EXIT_OK) {
             if (!have_msg) set_err(errbuf, errcap, std::string(args[k].bam ? args[k].bam : "?") + ": " + msg), have_msg = true;
@@ -148,8 +146,7 @@ void inq_session_discard(inq_staged_t *st) { delete st; }
 
 void inq_session_close(inq_session_t *S) {
     if (!S) return;
-    const char *fast_env = std::getenv("INQ_FAST_EXIT");
-    S->actx.leak = fast_env && fast_env[0] == '1';  // the CLI is about to leave the process (see run_device_front)
+    S->actx.leak = fast_exit();  // the CLI is about to leave the process: the session's context goes with it
     if (S->actx.leak) {
         S->actx.wait();
         S->pool.free_list.clear();  // left to the operating system as well

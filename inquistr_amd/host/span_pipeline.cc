@@ -53,12 +53,21 @@ int guess_gpu_numa_node(int device) {
     return node;
 }
 
+namespace {
+struct NodeMask {  // the one-node mask set_mempolicy / mbind take; ok = false for no node (or one beyond the mask)
+    unsigned long bits[16] = {0};
+    bool ok;
+    explicit NodeMask(int node) : ok(node >= 0 && node < 1024) {
+        if (ok) bits[node / (8 * sizeof(unsigned long))] |= 1ul << (node % (8 * sizeof(unsigned long)));
+    }
+};
+}  // namespace
+
 void prefer_gpu_node_for_this_thread(int device) {
     const int node = guess_gpu_numa_node(device);
-    if (node < 0 || node >= 1024) return;
-    unsigned long mask[16] = {0};
-    mask[node / (8 * sizeof(unsigned long))] |= 1ul << (node % (8 * sizeof(unsigned long)));
-    (void)::syscall(SYS_set_mempolicy, 1 /* MPOL_PREFERRED */, mask, sizeof mask * 8);
+    NodeMask mask(node);
+    if (!mask.ok) return;
+    (void)::syscall(SYS_set_mempolicy, 1 /* MPOL_PREFERRED */, mask.bits, sizeof mask.bits * 8);
     const char *c = std::getenv("INQ_NUMA_CPUS");
     if (!(c && c[0] == '0')) {
         char path[128], buf[4096] = {0};
@@ -86,10 +95,8 @@ void prefer_gpu_node_for_this_thread(int device) {
 }
 
 void prefer_numa_node(void *p, size_t len, int node) {
-    if (node < 0 || node >= 1024) return;
-    unsigned long mask[16] = {0};
-    mask[node / (8 * sizeof(unsigned long))] |= 1ul << (node % (8 * sizeof(unsigned long)));
-    (void)::syscall(SYS_mbind, p, len, 1 /* MPOL_PREFERRED */, mask, sizeof mask * 8, 0);  // best effort: placement only
+    NodeMask mask(node);
+    if (mask.ok) (void)::syscall(SYS_mbind, p, len, 1 /* MPOL_PREFERRED */, mask.bits, sizeof mask.bits * 8, 0);  // best effort: placement only
 }
 
 void SpanPipeline::release_buf(Item &it) {
@@ -188,19 +195,19 @@ void SpanPipeline::run() {
             it = free_.back();
             free_.pop_back();
         }
-        const auto t0 = std::chrono::steady_clock::now();
+        const auto t0 = Clock::now();
         std::swap(it->plan, ahead);
         std::future<bool> more = std::async(std::launch::async, [&] { return planner_.next(ahead); });  // joined by get() or by its destructor
         uint64_t nbytes = 0;
-        const auto t1 = std::chrono::steady_clock::now();
+        const auto t1 = Clock::now();
         if (!loader.total_bytes(it->plan, &nbytes, &e)) return fail(e);
         if (nbytes > (64ull << 30)) return fail("a span of the BAM exceeds 64 GiB (index without usable bins)");
         if (!fit(*it, (size_t)nbytes + 64)) return fail("cannot allocate the span buffer");
-        const auto t2 = std::chrono::steady_clock::now();
+        const auto t2 = Clock::now();
         if (!loader.load(it->plan, planner_.anchors(), it->buf, n_threads_, it->data, &e, &pool)) return fail(e);
         it->staged = false;
         if (verbose_) {
-            const auto t3 = std::chrono::steady_clock::now();
+            const auto t3 = Clock::now();
             {   // where the buffer's pages lie (a sample, asked of the kernel), and on which CPUs the readers ran
                 const size_t ps = 4096, n_s = 64;
                 void *pages[n_s];
@@ -214,7 +221,6 @@ void SpanPipeline::run() {
                 std::fprintf(stderr, "[inq loader] slot %d buffer pages by node (64 samples): %d %d %d %d; reader CPUs: %s\n", it->slot, on[0], on[1], on[2], on[3],
                              pool.last_cpus().c_str());
             }
-            auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
             std::fprintf(stderr, "[inq loader] @%.1f slot %d: plan %.2f ms, buffer %.2f ms (%s), read+tables %.2f ms (copy %.2f, block table + anchors %.2f) for %.1f MB, %zu segments, %zu anchors\n",
                          stamp_ms(), it->slot, ms(t0, t1), ms(t1, t2), it->pinned ? "pinned" : "pageable", ms(t2, t3), it->data.ms_read, it->data.ms_tables, nbytes / 1e6,
                          it->plan.segs.size(), it->data.anchors.size());
@@ -247,7 +253,7 @@ void SpanPipeline::run_uploads() {
     struct Flight {
         Item *it;
         bool begun;
-        std::chrono::steady_clock::time_point t0;
+        Clock::time_point t0;
     };
     std::deque<Flight> inflight;
     const size_t depth = stage_wait_ ? 2 : 1;
@@ -267,7 +273,7 @@ void SpanPipeline::run_uploads() {
         f.it->staged = f.begun && (!stage_wait_ || stage_wait_(f.it->slot));
         if (verbose_)
             std::fprintf(stderr, "[inq loader] @%.1f slot %d: upload %.2f ms for %.1f MB%s\n", stamp_ms(), f.it->slot,
-                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f.t0).count(), f.it->data.comp_bytes / 1e6,
+                         ms(f.t0, Clock::now()), f.it->data.comp_bytes / 1e6,
                          f.it->staged ? "" : " (not staged)");
         std::lock_guard<std::mutex> g(mu_);
         ready_.push_back(f.it);
@@ -290,7 +296,7 @@ void SpanPipeline::run_uploads() {
             }
         }
         if (it) {
-            const auto t0 = std::chrono::steady_clock::now();
+            const auto t0 = Clock::now();
             inq_span_t sp;
             fill_span(*it, &sp);
             if (register_ && !it->registered && !it->pinned && it->buf) {
@@ -372,8 +378,6 @@ void set_local_share(int sharers, int index) {
     g_sharers.store(sharers);
     g_share_index.store(index);
 }
-
-// fills p1 / p2 through the device front end; returns an exit status
 
 // The cores this process may really use: its affinity mask, cut by the cgroup's CPU quota when one is set (a container on a 256-thread
 // host is typically granted 16: std::thread::hardware_concurrency() says 256 there).
@@ -469,191 +473,172 @@ SpanPipeline *start_span_pipeline(const inq_call_args_t *args, const BamFile &ba
                             [&actx](int slot) { return !actx.timed_out() && inq_span_stage_wait(actx.ctx, slot) == INQ_OK; }, share_index);
 }
 
+namespace {
+// what the span loop of one file counts: from the moment the first span is handed to the device (the context is there, the span read
+// and uploaded) to the last flush - what the file costs once the process's fixed costs are behind it
+struct SpanLoop {
+    Clock::time_point t0{};
+    uint64_t spans = 0, comp_bytes = 0;
+};
+
+// the end of the span loop: the call's statistics for whoever asked (hooks.stats), and the INQ_TIMING lines
+void report_span_loop(const SpanLoop &loop, const SpanPipeline &pipe, int timing, Clock::time_point t_begin, double t_front, double t_dev,
+                      PartStats *stats) {
+    if (stats && loop.spans) {
+        stats->spans = loop.spans, stats->comp_bytes = loop.comp_bytes;
+        stats->span_loop_s = secs(loop.t0, Clock::now());
+        stats->wait_loader_s = t_front, stats->device_calls_s = t_dev;
+        stats->io_threads = pipe.io_threads();
+    }
+    if (!timing) return;
+    if (loop.spans) {
+        const double loop_s = secs(loop.t0, Clock::now());
+        std::fprintf(stderr, "[inq timing] span loop: %llu spans, %.1f MB compressed, %.4f s from the first span's call to the last flush = %.2f GB/s\n",
+                     (unsigned long long)loop.spans, loop.comp_bytes / 1e6, loop_s, loop.comp_bytes / 1e9 / std::max(loop_s, 1e-9));
+    }
+    std::fprintf(stderr, "[inq timing] spans done at %.3fs after the start of the device path\n", secs(t_begin, Clock::now()));
+    struct timespec pt;
+    const double proc = clock_gettime(CLOCK_PROCESS_CPUTIME_ID, &pt) == 0 ? (double)pt.tv_sec + (double)pt.tv_nsec * 1e-9 : 0.0;
+    const CpuByKind &k = cpu_by_kind();
+    std::fprintf(stderr,
+                 "[inq timing] cpu seconds so far: process %.3f | this thread (device calls) %.3f | reader pool %.3f (the loader's own share of the copies is "
+                 "under 'loader' until it ends) | loader %.3f, uploader %.3f (counted when they end) | the rest: the runtime's threads, the context thread\n",
+                 proc, thread_cpu_us() * 1e-6, k.readers_us.load() * 1e-6, k.loader_us.load() * 1e-6, k.uploader_us.load() * 1e-6);
+}
+
+// a pipeline the call started itself is deleted with the call - joining the loader, unmapping the span buffers - unless the call
+// ended clean in a process that is leaving (SessionHooks::process_is_leaving); one a session started ahead is the session's
+struct PipeDeleter {
+    bool owned;
+    const bool *leave;
+    void operator()(SpanPipeline *p) const {
+        if (owned && !*leave) delete p;
+    }
+};
+}  // namespace
+
+// fills p1 / p2 (or hooks.dev_p1 / dev_p2) through the device front end; returns an exit status
 int run_device_front(const inq_call_args_t *args, const CallView &V, AsyncCtx &actx, std::vector<double> &p1,
                             std::vector<double> &p2, char *errbuf, size_t errcap, double *t_front, double *t_dev,
                             const SessionHooks &hooks) {
-    using clk = std::chrono::steady_clock;
-    auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-    const int timing = std::getenv("INQ_TIMING") ? (std::getenv("INQ_TIMING")[0] == '2' ? 2 : 1) : 0;
-    const auto t_begin = clk::now();
-    bool &leak_all = actx.leak;
+    const int timing = timing_level();
+    const auto t_begin = Clock::now();
     inq_ctx_t *&ctx = actx.ctx;
     int &hrc = actx.hrc;
-    std::vector<double> b1, b2;
-    std::vector<uint8_t> bt;  // the tie flags of a flush (hooks.ties_out set)
-    {
-        // the CLI sets INQ_FAST_EXIT: it is about to leave the process, so the span buffers (unmapping a GB
-        // of touched pages takes ~0.1 s) and the device context are left to the operating system
-        const char *fast_env = std::getenv("INQ_FAST_EXIT");
-        const bool fast_exit = fast_env && fast_env[0] == '1';
-        struct PipeHolder {
-            SpanPipeline *p;
-            const bool &leak;
-            bool owned;
-            ~PipeHolder() {
-                if (owned && !leak) delete p;
-            }
-        } holder{hooks.early_pipe ? hooks.early_pipe
-                                  : start_span_pipeline(args, V.bam, V.targets, actx, hooks.slot_base, hooks.pool, hooks.sharers, hooks.share_index),
-                 leak_all, hooks.early_pipe == nullptr};
-        SpanPipeline &pipe = *holder.p;
-        bool joined = false;
-        // loci whose batches wait on the device (inq_call_span_deferred), in the order they were appended
-        // 50 000 loci per launch of the locus kernels: 0.69 of the HBM peak in the CLI's trace (53 500 loci, 240 us), 0.73 at
-        // 107 000 (452 us) against 0.83 for the same kernel in bench.py's steady loop - a launch here comes cold behind the
-        // gather that has just written its CIGARs - and twice the device memory to tear down at exit for 100 000
-        const size_t kFlushLoci = std::getenv("INQ_FLUSH_LOCI") ? (size_t)std::max(1l, std::atol(std::getenv("INQ_FLUSH_LOCI"))) : 50000;
-        constexpr uint64_t kFlushWords = 1ull << 31;    // ... or 8 GB of gathered CIGARs
-        std::vector<uint32_t> pending;
-        uint64_t pending_words = 0;
-        // the span loop by itself: from the moment the first span is handed to the device (the context is there, the span read and
-        // uploaded) to the last flush - what the file costs once the process's fixed costs are behind it
-        clk::time_point t_loop0{};
-        uint64_t loop_spans = 0, loop_comp_bytes = 0;
-        auto flush = [&]() -> int {
-            if (pending.empty()) return INQ_EXIT_OK;
-            const auto f0 = clk::now();
-            b1.assign(pending.size(), NAN);
-            b2.assign(pending.size(), NAN);
-            inq_result_t res;
-            std::memset(&res, 0, sizeof res);
-            res.phase1 = b1.data();
-            res.phase2 = b2.data();
-            double ms_call = 0;
-            uint8_t *flags = nullptr;
-            if (hooks.ties_out) bt.assign(pending.size(), 0), flags = bt.data();
-            // (rows that travel on from device memory stay there: pending[j] is the row's place in the caller's device arrays)
-            int rc2 = hooks.dev_p1 ? inq_call_flush_device_flags(ctx, hooks.dev_p1, hooks.dev_p2, hooks.dev_cap, pending.data(), pending.size(), nullptr,
-                                                                 &ms_call, flags)
-                                   : inq_call_flush_flags(ctx, &res, pending.size(), &ms_call, flags);
-            *t_dev += secs(f0, clk::now());
-            if (timing == 2)
-                std::fprintf(stderr, "[inq call] @%.1f %zu loci, %.1f MB of CIGARs: locus kernels %.3f ms | wall %.2f ms\n", stamp_ms(), pending.size(),
-                             pending_words * 4 / 1e6, ms_call, secs(f0, clk::now()) * 1e3);
-            if (rc2 != INQ_OK) {
-                std::string m = std::string("device call failed: ") + inq_strerror(rc2);
-                if (rc2 == INQ_ERR_HIP) m += std::string(" [") + inq_last_error(ctx) + "]";
-                set_err(errbuf, errcap, m);
-                return (rc2 == INQ_ERR_HIP || rc2 == INQ_ERR_NOMEM || rc2 == INQ_ERR_NO_DEVICE) ? INQ_EXIT_ERROR : INQ_EXIT_PANIC;
-            }
-            if (!hooks.dev_p1)
-                for (size_t j = 0; j < pending.size(); ++j) {
-                    p1[pending[j]] = b1[j];
-                    p2[pending[j]] = b2[j];
-                }
-            if (flags)
-                for (size_t j = 0; j < pending.size(); ++j) hooks.ties_out[pending[j]] = bt[j];
-            pending.clear();
-            pending_words = 0;
-            return INQ_EXIT_OK;
-        };
-        for (;;) {
-            SpanPipeline::Item *it = nullptr;
-            std::string ferr;
-            auto ta = clk::now();
-            int nb = pipe.next(it, &ferr);
-            auto tb = clk::now();
-            *t_front += secs(ta, tb);
-            if (nb < 0) {
-                set_err(errbuf, errcap, ferr);
-                return INQ_EXIT_PANIC;  // read errors are expect()/unwrap() panics in the reference (:294,346)
-            }
-            if (nb == 0) break;
-            if (!joined) {
-                actx.wait();
-                joined = true;
-                if (hrc == INQ_OK) inq_call_discard(ctx);  // a session's context: nothing of a file that failed half-way stays behind
-                if (hrc == INQ_OK) (void)inq_ctx_set_option(ctx, "batch_loci_hint", (int64_t)std::min<size_t>(kFlushLoci, V.targets.size()));
-            }
-            if (hrc != INQ_OK) {
-                set_err(errbuf, errcap, ctx_failure_message(actx));
-                return INQ_EXIT_ERROR;
-            }
-            inq_span_t sp;
-            SpanPipeline::fill_span(*it, &sp);
-            sp.minlen = V.minlen;
-            sp.support = V.support;
-            sp.unphased = V.unphased ? 1u : 0u;
-            // the span's batch is appended to the one on the device; the locus kernels run once enough loci wait (a span of
-            // SEQ-bearing records holds a few hundred loci, a launch wants tens of thousands) or the file is through
-            inq_span_stats_t stt;
-            if (loop_spans++ == 0) t_loop0 = clk::now();
-            loop_comp_bytes += sp.comp_bytes;
-            g_span_bytes_read.fetch_add(sp.comp_bytes, std::memory_order_relaxed);
-            int rc2 = inq_call_span_deferred(ctx, &sp, it->staged ? it->slot : -1, &stt);
-            *t_dev += secs(tb, clk::now());
-            if (timing == 2)
-                std::fprintf(stderr,
-                             "[inq span] @%.1f waited %.2f ms | loci %llu comp %.1f MB -> %.1f MB, %llu records, %llu pairs | upload %.2f inflate %.2f scan %.2f "
-                             "join %.2f ms | wall %.2f ms\n",
-                             stamp_ms(), secs(ta, tb) * 1e3, (unsigned long long)sp.n_loci, sp.comp_bytes / 1e6, stt.inflated_bytes / 1e6,
-                             (unsigned long long)stt.n_records, (unsigned long long)stt.n_pairs, stt.ms_upload, stt.ms_inflate,
-                             stt.ms_scan, stt.ms_join, secs(tb, clk::now()) * 1e3);
-            if (rc2 != INQ_OK) {
-                std::string m = std::string("device call failed: ") + inq_strerror(rc2);
-                if (rc2 == INQ_ERR_HIP) m += std::string(" [") + inq_last_error(ctx) + "]";
-                if (rc2 == INQ_ERR_BAM || rc2 == INQ_ERR_AUX || rc2 == INQ_ERR_INFLATE)
-                    m += " (status " + std::to_string(stt.front_status) + ", record " + std::to_string(stt.first_bad_record) +
-                         " of the span at file offset " + std::to_string(it->data.file_begin) + ")";
-                set_err(errbuf, errcap, m);
-                return (rc2 == INQ_ERR_HIP || rc2 == INQ_ERR_NOMEM || rc2 == INQ_ERR_NO_DEVICE) ? INQ_EXIT_ERROR : INQ_EXIT_PANIC;
-            }
-            pending.insert(pending.end(), it->plan.locus_index.begin(), it->plan.locus_index.end());
-            pending_words += stt.n_cigar_words;
-            pipe.release(it);
-            if (pending.size() >= kFlushLoci || pending_words >= kFlushWords) {
-                int frc = flush();
-                if (frc != INQ_EXIT_OK) return frc;
-            }
-            continue;
+    bool leave_pipe = false;  // only after a clean run: error paths tear down normally
+    std::unique_ptr<SpanPipeline, PipeDeleter> holder(
+        hooks.early_pipe ? hooks.early_pipe
+                         : start_span_pipeline(args, V.bam, V.targets, actx, hooks.slot_base, hooks.pool, hooks.sharers, hooks.share_index),
+        PipeDeleter{hooks.early_pipe == nullptr, &leave_pipe});
+    SpanPipeline &pipe = *holder;
+    bool joined = false;
+    // loci whose batches wait on the device (inq_call_span_deferred), in the order they were appended
+    // 50 000 loci per launch of the locus kernels: 0.69 of the HBM peak in the CLI's trace (53 500 loci, 240 us), 0.73 at
+    // 107 000 (452 us) against 0.83 for the same kernel in bench.py's steady loop - a launch here comes cold behind the
+    // gather that has just written its CIGARs - and twice the device memory to tear down at exit for 100 000
+    const size_t kFlushLoci = std::getenv("INQ_FLUSH_LOCI") ? (size_t)std::max(1l, std::atol(std::getenv("INQ_FLUSH_LOCI"))) : 50000;
+    constexpr uint64_t kFlushWords = 1ull << 31;    // ... or 8 GB of gathered CIGARs
+    std::vector<uint32_t> pending;
+    uint64_t pending_words = 0;
+    SpanLoop loop;
+    BatchRows br;
+    auto flush = [&]() -> int {
+        if (pending.empty()) return INQ_EXIT_OK;
+        const auto f0 = Clock::now();
+        br.begin(pending.size(), hooks.ties_out != nullptr);
+        double ms_call = 0;
+        // (rows that travel on from device memory stay there: pending[j] is the row's place in the caller's device arrays)
+        int rc2 = hooks.dev_p1 ? inq_call_flush_device_flags(ctx, hooks.dev_p1, hooks.dev_p2, hooks.dev_cap, pending.data(), pending.size(), nullptr,
+                                                             &ms_call, br.flags)
+                               : inq_call_flush_flags(ctx, &br.res, pending.size(), &ms_call, br.flags);
+        *t_dev += secs(f0, Clock::now());
+        if (timing == 2)
+            std::fprintf(stderr, "[inq call] @%.1f %zu loci, %.1f MB of CIGARs: locus kernels %.3f ms | wall %.2f ms\n", stamp_ms(), pending.size(),
+                         pending_words * 4 / 1e6, ms_call, secs(f0, Clock::now()) * 1e3);
+        if (rc2 != INQ_OK) return device_call_failed(rc2, ctx, errbuf, errcap);
+        br.scatter_to(pending.data(), hooks.dev_p1 ? nullptr : p1.data(), p2.data(), hooks.ties_out);
+        pending.clear();
+        pending_words = 0;
+        return INQ_EXIT_OK;
+    };
+    for (;;) {
+        SpanPipeline::Item *it = nullptr;
+        std::string ferr;
+        auto ta = Clock::now();
+        int nb = pipe.next(it, &ferr);
+        auto tb = Clock::now();
+        *t_front += secs(ta, tb);
+        if (nb < 0) {
+            set_err(errbuf, errcap, ferr);
+            return INQ_EXIT_PANIC;  // read errors are expect()/unwrap() panics in the reference (:294,346)
         }
-        if (!joined) actx.wait();
-        if (hrc == INQ_OK) {
+        if (nb == 0) break;
+        if (!joined) {
+            actx.wait();
+            joined = true;
+            if (hrc == INQ_OK) inq_call_discard(ctx);  // a session's context: nothing of a file that failed half-way stays behind
+            if (hrc == INQ_OK) (void)inq_ctx_set_option(ctx, "batch_loci_hint", (int64_t)std::min<size_t>(kFlushLoci, V.targets.size()));
+        }
+        if (hrc != INQ_OK) {
+            set_err(errbuf, errcap, ctx_failure_message(actx));
+            return INQ_EXIT_ERROR;
+        }
+        inq_span_t sp;
+        SpanPipeline::fill_span(*it, &sp);
+        V.opt.apply(sp);
+        // the span's batch is appended to the one on the device; the locus kernels run once enough loci wait (a span of
+        // SEQ-bearing records holds a few hundred loci, a launch wants tens of thousands) or the file is through
+        inq_span_stats_t stt;
+        if (loop.spans++ == 0) loop.t0 = Clock::now();
+        loop.comp_bytes += sp.comp_bytes;
+        g_span_bytes_read.fetch_add(sp.comp_bytes, std::memory_order_relaxed);
+        int rc2 = inq_call_span_deferred(ctx, &sp, it->staged ? it->slot : -1, &stt);
+        *t_dev += secs(tb, Clock::now());
+        if (timing == 2)
+            std::fprintf(stderr,
+                         "[inq span] @%.1f waited %.2f ms | loci %llu comp %.1f MB -> %.1f MB, %llu records, %llu pairs | upload %.2f inflate %.2f scan %.2f "
+                         "join %.2f ms | wall %.2f ms\n",
+                         stamp_ms(), secs(ta, tb) * 1e3, (unsigned long long)sp.n_loci, sp.comp_bytes / 1e6, stt.inflated_bytes / 1e6,
+                         (unsigned long long)stt.n_records, (unsigned long long)stt.n_pairs, stt.ms_upload, stt.ms_inflate,
+                         stt.ms_scan, stt.ms_join, secs(tb, Clock::now()) * 1e3);
+        if (rc2 != INQ_OK) {
+            std::string where;
+            if (rc2 == INQ_ERR_BAM || rc2 == INQ_ERR_AUX || rc2 == INQ_ERR_INFLATE)
+                where = " (status " + std::to_string(stt.front_status) + ", record " + std::to_string(stt.first_bad_record) +
+                        " of the span at file offset " + std::to_string(it->data.file_begin) + ")";
+            return device_call_failed(rc2, ctx, errbuf, errcap, where);
+        }
+        pending.insert(pending.end(), it->plan.locus_index.begin(), it->plan.locus_index.end());
+        pending_words += stt.n_cigar_words;
+        pipe.release(it);
+        if (pending.size() >= kFlushLoci || pending_words >= kFlushWords) {
             int frc = flush();
             if (frc != INQ_EXIT_OK) return frc;
         }
-        if (hooks.stats && loop_spans) {
-            hooks.stats->spans = loop_spans, hooks.stats->comp_bytes = loop_comp_bytes;
-            hooks.stats->span_loop_s = secs(t_loop0, clk::now());
-            hooks.stats->wait_loader_s = *t_front, hooks.stats->device_calls_s = *t_dev;
-            hooks.stats->io_threads = pipe.io_threads();
-        }
-        if (timing && loop_spans) {
-            const double loop_s = secs(t_loop0, clk::now());
-            std::fprintf(stderr, "[inq timing] span loop: %llu spans, %.1f MB compressed, %.4f s from the first span's call to the last flush = %.2f GB/s\n",
-                         (unsigned long long)loop_spans, loop_comp_bytes / 1e6, loop_s, loop_comp_bytes / 1e9 / std::max(loop_s, 1e-9));
-        }
-        leak_all = fast_exit;  // only after a clean run: error paths tear down normally
-        if (const char *probe = debug_env("INQ_EXIT_PROBE")) {
-            // experiment: what does the process's exit pay for?  1 = unmap the span buffers here (the pipeline's destructor) and
-            // time it, 2 = also destroy the device context (every hipFree) and time that; then the fast exit as usual
-            const auto e0 = clk::now();
-            leak_all = false;
-            if (holder.owned) {
-                delete holder.p;
-                holder.owned = false;
-            }
-            const auto e1 = clk::now();
-            std::fprintf(stderr, "[inq exit probe] span pipeline torn down (loader joined, host buffers unmapped): %.2f ms\n", secs(e0, e1) * 1e3);
-            if (probe[0] == '2') {
-                inq_ctx_destroy(ctx);
-                ctx = nullptr;
-                std::fprintf(stderr, "[inq exit probe] device context destroyed: %.2f ms\n", secs(e1, clk::now()) * 1e3);
-            }
-            leak_all = true;
-        }
-        if (timing) std::fprintf(stderr, "[inq timing] spans done at %.3fs after the start of the device path\n", secs(t_begin, clk::now()));
-        if (timing) {
-            struct timespec pt;
-            const double proc = clock_gettime(CLOCK_PROCESS_CPUTIME_ID, &pt) == 0 ? (double)pt.tv_sec + (double)pt.tv_nsec * 1e-9 : 0.0;
-            const CpuByKind &k = cpu_by_kind();
-            std::fprintf(stderr,
-                         "[inq timing] cpu seconds so far: process %.3f | this thread (device calls) %.3f | reader pool %.3f (the loader's own share of the copies is "
-                         "under 'loader' until it ends) | loader %.3f, uploader %.3f (counted when they end) | the rest: the runtime's threads, the context thread\n",
-                         proc, thread_cpu_us() * 1e-6, k.readers_us.load() * 1e-6, k.loader_us.load() * 1e-6, k.uploader_us.load() * 1e-6);
+    }
+    if (!joined) actx.wait();
+    if (hrc == INQ_OK) {
+        int frc = flush();
+        if (frc != INQ_EXIT_OK) return frc;
+    }
+    report_span_loop(loop, pipe, timing, t_begin, *t_front, *t_dev, hooks.stats);
+    leave_pipe = hooks.process_is_leaving;
+    if (const char *probe = debug_env("INQ_EXIT_PROBE")) {
+        // experiment: what does the process's exit pay for?  1 = unmap the span buffers here (the pipeline's destructor) and
+        // time it, 2 = also destroy the device context (every hipFree) and time that; then the exit as usual
+        const auto e0 = Clock::now();
+        leave_pipe = false;
+        holder.reset();
+        const auto e1 = Clock::now();
+        std::fprintf(stderr, "[inq exit probe] span pipeline torn down (loader joined, host buffers unmapped): %.2f ms\n", secs(e0, e1) * 1e3);
+        if (probe[0] == '2') {
+            inq_ctx_destroy(ctx);
+            ctx = nullptr;
+            std::fprintf(stderr, "[inq exit probe] device context destroyed: %.2f ms\n", secs(e1, Clock::now()) * 1e3);
         }
     }
-    if (timing) std::fprintf(stderr, "[inq timing] loader joined at %.3fs\n", secs(t_begin, clk::now()));
+    holder.reset();  // joins the loader of a pipeline made here (see PipeDeleter)
+    if (timing) std::fprintf(stderr, "[inq timing] loader joined at %.3fs\n", secs(t_begin, Clock::now()));
     if (hrc != INQ_OK) {  // no GPU is an error even for an empty target list
         set_err(errbuf, errcap, ctx_failure_message(actx));
         return INQ_EXIT_ERROR;
@@ -667,8 +652,7 @@ struct inq_spans {
     Prepared P;
     std::unique_ptr<SpanPipeline> pipe;
     SpanPipeline::Item *cur = nullptr;
-    uint32_t minlen = 5, support = 3;
-    bool unphased = false;
+    CallOptions opt;
 };
 
 extern "C" {
@@ -680,15 +664,9 @@ static int inq_spans_open_impl(const inq_call_args_t *args, uint64_t max_comp_by
     if (!out) return INQ_EXIT_ERROR;
     *out = nullptr;
     std::unique_ptr<inq_spans> S(new inq_spans());
-    std::string msg;
-    int rc = prepare(args, S->P, msg);
-    if (rc != INQ_EXIT_OK) {
-        set_err(errbuf, errcap, msg);
-        return rc;
-    }
-    S->minlen = args->minlen;
-    S->support = (uint32_t)std::min<uint64_t>(args->support, 0xffffffffull);
-    S->unphased = args->unphased != 0;
+    const int rc = prepare(args, S->P, errbuf, errcap);
+    if (rc != INQ_EXIT_OK) return rc;
+    S->opt = CallOptions(*args);
     S->pipe.reset(new SpanPipeline(args->bam, *S->P.bam, S->P.targets, max_comp_bytes ? max_comp_bytes : span_bytes_from_env(),
                                    (int)std::max<uint64_t>(1, std::min<uint64_t>(args->threads, 32)), false));
     *out = S.release();
@@ -709,9 +687,7 @@ static int inq_spans_next_impl(inq_spans_t *S, inq_span_t *sp, const uint32_t **
     if (rc == 0) return 0;
     SpanPipeline::Item *it = S->cur;
     SpanPipeline::fill_span(*it, sp);
-    sp->minlen = S->minlen;
-    sp->support = S->support;
-    sp->unphased = S->unphased ? 1u : 0u;
+    S->opt.apply(*sp);
     if (locus_index) *locus_index = it->plan.locus_index.data();
     if (file_begin) *file_begin = it->data.file_begin;
     return 1;
@@ -721,12 +697,7 @@ int inq_spans_open(const inq_call_args_t *args, uint64_t max_comp_bytes, inq_spa
     INQ_GUARD(inq_spans_open_impl(args, max_comp_bytes, out, errbuf, errcap), errbuf, errcap)
 }
 int inq_spans_next(inq_spans_t *S, inq_span_t *span, const uint32_t **locus_index, uint64_t *file_begin, char *errbuf, size_t errcap) {
-    try {
-        return inq_spans_next_impl(S, span, locus_index, file_begin, errbuf, errcap);
-    } catch (...) {
-        set_err(errbuf, errcap, "internal error");
-        return -INQ_EXIT_ERROR;
-    }
+    INQ_GUARD_AS(-INQ_EXIT_ERROR, inq_spans_next_impl(S, span, locus_index, file_begin, errbuf, errcap), errbuf, errcap)
 }
 uint64_t inq_spans_n_targets(const inq_spans_t *S) { return S ? S->P.targets.size() : 0; }
 void inq_spans_close(inq_spans_t *S) {

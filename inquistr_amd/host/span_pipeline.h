@@ -20,6 +20,7 @@ int guess_gpu_numa_node(int device);
 void prefer_gpu_node_for_this_thread(int device);
 void prefer_numa_node(void *p, size_t len, int node);
 double stamp_ms();  // milliseconds since the library was loaded (INQ_TIMING=2 stamps)
+inline int timing_level();  // driver_internal.h
 
 // Span buffers that outlive one file: a cohort run (inq_session) hands the buffers of file k to file k + 2 instead of unmapping
 // and re-faulting a GB of pages per file.
@@ -176,7 +177,7 @@ private:
     std::function<int()> numa_query_;  // the GPU's NUMA node, kNumaUnknown while the context is not there yet, -1 = do not place
     int device_ = 0;
     int io_group_offset_ = 0;  // which L3 domain the first reader thread is bound to: sharers of one host start at different ones
-    bool verbose_ = std::getenv("INQ_TIMING") && std::getenv("INQ_TIMING")[0] == '2';
+    bool verbose_ = timing_level() == 2;
     Item slots_[kSlotsPerSet];
     std::vector<Item *> free_;
     std::deque<Item *> ready_, loaded_;

@@ -228,6 +228,43 @@ def test_session_survives_a_file_that_fails_on_the_device(tmp_path, frontend):
         os.environ.update(env_before)
 
 
+def test_a_failed_device_call_reads_the_same_at_each_of_its_three_sites(tmp_path):
+    """The three places of the host driver a device call can fail in end the call with the reference's panic status and the same
+    sentence: one locus (tests/errclass.py), four reads, the third of them (record 2 of the file and of its only span) the bad one.
+    HP:C:3 on a read that passes the phased filter is seen by the locus kernels only: by inq_call_batch behind the host sweep, by the
+    flush behind the device front end.  HP typed `s` is seen by the device front end's scan: the span call, whose message also
+    says which record of which span (the host sweep panics on that one by itself, in other words).
+    The expected sentences are written out here as the driver printed them before the three sites shared their code."""
+    from tests import errclass
+
+    def case(name, hp):
+        recs = [py.Record(pos=4797 + k, cigar=[("M", 210), ("I", 12), ("M", 300)], hp=hp if k == 2 else ("C", 1 + k % 2), tid=0) for k in range(4)]
+        path = str(tmp_path / f"{name}.bam")
+        assert [r.pos for r in errclass.write_bam(path, recs)] == [4797, 4798, 4799, 4800]
+        return path
+
+    region = "%s:%d-%d" % errclass.LOCUS
+
+    def failure(bam, frontend):
+        with open(tmp_path / "out.inq", "w") as f, pytest.raises(call.CallError) as e:
+            call.genotype_repeats(bam, region, None, 5, 3, 1, False, None, None, out=f, frontend=frontend)
+        return e.value.status, e.value.message
+
+    phase = "device call failed: a read passing the phased filter has HP outside {0,1,2}"
+    hp3 = case("hp3", ("C", 3))
+    assert failure(hp3, "host") == (101, phase)    # site one: the host sweep's inq_call_batch
+    assert failure(hp3, "device") == (101, phase)  # site two: the flush behind the span loop
+    hps = case("hp_s", ("s", 1))
+    S = call.Spans(hps, region)
+    spans = list(S.spans())
+    S.close()
+    assert len(spans) == 1
+    aux = ("device call failed: HP aux of a fetched read is neither C nor i, or the SA aux of a kept read with a soft clip cannot be parsed "
+           "(the reference panics)")
+    # site three: the span call; status 8 = the scan's bit for an HP of another type
+    assert failure(hps, "device") == (101, f"{aux} (status 8, record 2 of the span at file offset {spans[0]['file_begin']})")
+
+
 def test_call_through_a_resident_server_equals_call(tmp_path, sock_dir):
     """`inquistr serve` keeps the device context; `inquistr call` with INQ_SERVER set hands it the arguments (relative paths made
     absolute) and its stdout: same bytes, same exit status and message as the call run by itself - also for a file the reference
