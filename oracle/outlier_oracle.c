@@ -61,7 +61,7 @@ void orc_outlier_rows(const float *values, const uint32_t *row_len, uint64_t n_r
             keep[r] = 3;
             continue;
         }
-        const uint64_t twice = best_key * 2u;
+        const uint64_t twice = best_key * 2u;  /* usize, wrapping: the reference's release profile has no overflow checks */
         const double eps = (double)(twice > 10u ? twice : 10u);  /* :115 */
         uint8_t *core = (uint8_t *)malloc(n);
         for (uint32_t i = 0; i < n; ++i) {

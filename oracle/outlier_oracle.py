@@ -11,7 +11,9 @@ least `min_points` neighbours is a core point, and what is neither a core point 
 stays `Noise`; which cluster an edge point lands in depends on visiting order, whether a point is noise
 does not.  `mode` (src/outlier.rs:132-145) breaks ties between equally frequent values by HashMap
 iteration order, which Rust randomises per process: the reference itself is ambiguous there; this
-restatement (and the kernel) take the smallest of the tied values.
+restatement (and the kernel) take the smallest of the tied values.  `2 * mode` (src/outlier.rs:115) is usize
+arithmetic: the reference's Cargo.toml sets no `overflow-checks`, so in the release build it ships as the
+product wraps modulo 2^64 (a debug build would panic); this restatement, the C one and the kernel wrap.
 """
 from __future__ import annotations
 
@@ -81,7 +83,7 @@ def mode(values: Sequence[np.float32]) -> int:
     counts = {}
     for v in values:
         if v > 0:
-            k = int(min(float(v), 2.0**64 - 1))  # `as usize` saturates
+            k = 2**64 - 1 if float(v) >= 2.0**64 else int(float(v))  # `as usize` saturates (at usize::MAX, which no f64 equals)
             counts[k] = counts.get(k, 0) + 1
     if not counts:
         raise ReferencePanic("No mode found for repeat")
@@ -91,7 +93,9 @@ def mode(values: Sequence[np.float32]) -> int:
 
 def dbscan_flags(values: Sequence[np.float32], mincluster: int) -> List[bool]:
     """src/outlier.rs:112-130 + [3P] dbscan 0.3.1 Model::run, as per-value "is noise" flags"""
-    eps = float(max(2 * mode(values), 10))
+    # src/outlier.rs:115: `2 * mode` in usize; the release profile has no overflow checks, so it wraps (mode = usize::MAX
+    # - an infinite value, or one of 2^64 and beyond - gives 2^64 - 2)
+    eps = float(max((2 * mode(values)) % (1 << 64), 10))
     v = [float(x) for x in values]
     n = len(v)
     core = [sum(1 for j in range(n) if abs(v[i] - v[j]) < eps) >= mincluster for i in range(n)]

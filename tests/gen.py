@@ -7,6 +7,8 @@ unmapped-but-placed reads, reads shared by neighbouring loci, empty loci, long C
 """
 from __future__ import annotations
 
+import dataclasses
+import functools
 import random
 from typing import List, Tuple
 
@@ -469,3 +471,305 @@ def row_walk_case(seed: int, unphased: bool = None, max_depth: int = None):
             recs[i] = py.Record(pos=pos, cigar=[(py.OPS[int(x) & 15], int(x) >> 4) for x in w], mapq=mapq, flag=flag, hp=hp, sa=sa)
         info["per_locus"] = [[recs[i] for i in idx] for idx in per_locus_idx]
     return batch, info
+
+
+# ---- cases shaped after the launch geometry of the work-list kernels (csrc/kernels.hip walk_part, csrc/deep_select.hip) ------
+# How many workgroups locus_call_mid_walk and locus_call_tail are launched with ("grid_medium", "grid_tail") decides how the three
+# work lists are dealt, how a locus of more than kWalkSplit reads is split over a group of workgroups and what slice of a locus of
+# more than kGridSelectMin reads a workgroup takes in every pass of the grid-wide select.  These batches put loci on every list.
+
+# the smallest depths on both sides of kMediumSlots * 64 (64 | 65 is the list threshold itself), kReduceInPlace, kWalkSplit and
+# kGridSelectMin, and a few between the last two: six loci on list 2, two of them the whole grid's
+LADDER_DEPTHS = (0, 1, 64, 65, 256, 257, 2048, 2049, 16384, 16385, 20000, 30000, 65536, 65537, 70001)
+LADDER_POOL = 70_001
+
+
+@functools.lru_cache(maxsize=2)
+def _ladder_layout(seed: int):
+    rng = random.Random(seed)
+    start, end = 900_000, 900_140
+    shapes = random_locus_reads(rng, start, end, 60, long_every=9)  # few shapes: ties everywhere
+    # ... and as many reads that cross every window of the ladder with an insertion or a soft clip of 6 / 8 / 20 bases every 30 - 60
+    # bases: their Calls are the sums of what lies inside a window - other sums in every window, the same sum as Span and as Clip
+    for _ in range(60):
+        cig, span = [], 0
+        while span < 620:
+            m = rng.choice([30, 45, 60])
+            cig += [("M", m), (rng.choice("IIIS"), rng.choice([6, 8, 20]))]
+            span += m
+        shapes.append(py.Record(pos=start - 260 - rng.randint(0, 20), cigar=cig + [("M", 50)], mapq=60, flag=rng.choice([0, 16])))
+    pool = [(shapes[rng.randrange(len(shapes))], rng.choice([9, 60, 60, 60]), rng.choice([None, 0, 1, 1, 2, 2]), k % 7 == 0) for k in range(LADDER_POOL)]
+    bb = BatchBuilder(minlen=5, support=3, unphased=False)
+    ids = [bb.add_read(r.pos, encode_cigar(r.cigar), mapq=mq, phase=ph, reverse=bool(r.flag & 0x10), is_2d=twod) for r, mq, ph, twod in pool]
+    order = sorted(range(len(ids)), key=lambda k: (bb._reads[ids[k]][2], k))  # file order: by position, then insertion
+    loci = []
+    for k, d in enumerate(LADDER_DEPTHS):
+        # every step-th read of the file order from a random first one: a shallow locus too draws from the whole range of
+        # positions (64 neighbours of the file order start within a base or two of each other and may all miss the window)
+        step = LADDER_POOL // max(d, 1)
+        off = rng.randint(0, LADDER_POOL - step * d)
+        sh = 14 * k - 98  # every locus its own window, the deeper the wider: no two see the same Calls
+        loci.append((d, start + sh, end + sh + 9 * k, [ids[i] for i in order[off : off + step * d : step]]))
+    rng.shuffle(loci)
+    for d, s, e, idx in loci:
+        bb.add_locus(s, e, idx)
+    return bb.build(), tuple(d for d, _, _, _ in loci)
+
+
+def depth_ladder_case(seed: int, unphased: bool, support: int):
+    """One locus at each depth of LADDER_DEPTHS, every one a file-ordered slice (every step-th read) of one pool of 70 001 reads
+    drawn from 120 shapes - random_locus_reads' and reads with an insertion or soft clip every few dozen bases -, with 2D reads,
+    mapq 9 / 60, phases none / 0 / 1 / 2; each locus has its own window, shifted and the deeper the wider.  The reads and the layout depend on
+    `seed` only and are built once; `unphased` and `support` are the batch's scalars.  Returns (Batch, depth of every locus)."""
+    base, depths = _ladder_layout(seed)
+    return dataclasses.replace(base, reads=base.reads.copy(), support=support, unphased=unphased), list(depths)
+
+
+def group_counts(batch: Batch, probe, locus: int):
+    """Per haplotype group of `locus` (1, 2): (its Calls, the spanning ones among them), from the per-pair outputs of an oracle run
+    of the batch (they do not depend on `support`).  Phased: the kept reads of HP 1 / 2.  Unphased: h1 = the lower half of the kept
+    Calls, ties in file order (src/call.rs:311-313), h2 the rest."""
+    p0, p1 = int(batch.locus_pair_off[locus]), int(batch.locus_pair_off[locus + 1])
+    bits = probe.pair_bits[p0:p1].astype(np.int64)
+    kept = (bits & 4) != 0
+    if batch.unphased:
+        at = np.nonzero(kept)[0]
+        at = at[np.argsort(probe.pair_call[p0:p1][at], kind="stable")]
+        grp = np.zeros(p1 - p0, dtype=np.int64)
+        grp[at[: at.shape[0] // 2]] = 1
+        grp[at[at.shape[0] // 2 :]] = 2
+    else:
+        grp = np.where(kept, batch.reads["phase"][batch.pair_read[p0:p1]].astype(np.int64), 0)
+    return {g: (int((grp == g).sum()), int(((grp == g) & ((bits & 1) == 0)).sum())) for g in (1, 2)}
+
+
+def clip_rule_support(batch: Batch, probe, locus: int):
+    """A `support` at which median_str_length's clip rule (src/call.rs:509-513) bites on `locus`: for the haplotype group that
+    holds more clipped Calls, more than its spanning Calls - so that half of its clipped Calls, the largest, ties at the threshold
+    included, join them - and no more than the group holds.  Returns (support, the group, its Calls, the spanning ones among them)."""
+    counts = group_counts(batch, probe, locus)
+    g = max(counts, key=lambda k: counts[k][0] - counts[k][1])
+    ng, ns = counts[g]
+    assert ng - ns >= 2, "the group needs clipped Calls for the rule to pick from"
+    return ns + (ng - ns) // 2, g, ng, ns
+
+
+@functools.lru_cache(maxsize=1)
+def _listed_pool():
+    rng = random.Random(4242)
+    start, end = 300_000, 300_120
+    shapes = random_locus_reads(rng, start, end, 40, long_every=9)
+    return start, end, [(shapes[rng.randrange(len(shapes))], rng.choice([9, 60, 60, 60]), rng.choice([None, 0, 1, 1, 2, 2]), k % 7 == 0) for k in range(700)]
+
+
+def all_listed_case(n_loci: int, depth: int, unphased: bool = False, support: int = 3) -> Batch:
+    """`n_loci` loci of depth .. depth + 3 reads each - every one on a work list when depth > 64 -, file-ordered slices of one pool
+    of 700 reads, windows shifted against each other."""
+    start, end, pool = _listed_pool()
+    assert depth + 3 <= len(pool)
+    bb = BatchBuilder(minlen=5, support=support, unphased=unphased)
+    ids = [bb.add_read(r.pos, encode_cigar(r.cigar), mapq=mq, phase=ph, reverse=bool(r.flag & 0x10), is_2d=twod) for r, mq, ph, twod in pool]
+    order = sorted(range(len(ids)), key=lambda k: (bb._reads[ids[k]][2], k))
+    for j in range(n_loci):
+        d = depth + j % 4
+        off = (37 * j) % (len(pool) - d + 1)
+        sh = j % 25 - 12
+        bb.add_locus(start + sh, end + sh, [ids[i] for i in order[off : off + d]])
+    return bb.build()
+
+
+# ---- rows for the 1-D DBSCAN of `inquiSTR outlier` (csrc/outlier.hip outlier_dbscan_kernel) ----------------------------------
+# The kernel has a size class per row width (up to 256, up to 2 048, up to 8 192 values).  What decides a value is whether
+# |x - y| < eps holds (strictly) and whether a point has at least `mincluster` neighbours, itself included: the rows put groups of
+# equal values exactly on both sides of both.
+
+DBSCAN_WRAP_ROW = (float("inf"), float("inf"), float("inf"), 12.0, 2.5e19)  # mode usize::MAX: 2 * mode wraps (src/outlier.rs:115)
+DBSCAN_PAD = 777.0  # behind a row's length: never read by the reference, and a kernel that reads it gets a value that matters
+
+
+def _dbscan_struct(rng: random.Random, n: int, mincluster: int, base: int, near: bool = False) -> List[float]:
+    """A dense cluster around `base` (its mode: eps = max(2 * base, 10)) whose largest value, top = base + 2, exactly two points
+    hold, nothing else above top - 1.  Where `mincluster` leaves room: replicas of [a body of mincluster + 2 points at F - 2, two
+    points at F, a satellite group of s equal values at F + off] far from one another (F steps by 10 eps + 1000), off in
+    {eps - 1, eps, eps + 1}, s in {mincluster - 3 .. mincluster + 1}.  At off = eps - 1 the satellites' neighbours are themselves
+    and the two points at F: core from s = mincluster - 2, an edge point below; from off = eps on they are on their own: core from
+    s = mincluster, noise below.  Then a lone far value.  Where mincluster is near the row's length: the dense cluster and one
+    satellite group of 1 - 3 values at top + off (`near`: off = eps - 1 - at the full width the two points at top then reach
+    everything and are the only core points, every other value is an edge point; one value fewer and all are noise)."""
+    eps, top = max(2 * base, 10), base + 2
+    if n < 8:
+        return [float(base)] * n
+    extra: List[float] = []
+    if mincluster > n // 3:
+        extra = [float(top + (eps - 1 if near else rng.choice([eps - 1, eps, eps + 1])))] * rng.choice([1, 2, 3])
+    else:
+        sizes = [s for s in (mincluster - 3, mincluster - 2, mincluster - 1, mincluster, mincluster + 1) if s >= 1]
+        first = [(s, o) for s, o in ((mincluster - 3, eps - 1), (mincluster - 2, eps - 1), (mincluster - 1, eps), (mincluster, eps)) if s >= 1]
+        rest = [(s, o) for s in sizes for o in (eps - 1, eps, eps + 1) if (s, o) not in first]
+        rng.shuffle(rest)
+        room = n - (2 * mincluster + 10) - 1  # the dense cluster keeps enough points for `base` to stay the mode; one lone value
+        F = top + 10 * eps + 1000
+        for s, o in first + rest:
+            need = mincluster + 2 + 2 + s
+            if need > room:
+                break
+            extra += [float(F - 2)] * (mincluster + 2) + [float(F)] * 2 + [float(F + o)] * s
+            room -= need
+            F += 10 * eps + 1000
+        extra.append(float(F + 5000))
+    n_dense = n - len(extra)
+    n_base = max(1, (n_dense - 2) * 7 // 10)
+    dense = [float(top)] * 2 + [float(base)] * n_base
+    dense += [base + rng.choice([-1.0, -0.5, 0.5, 1.0]) for _ in range(n_dense - len(dense))]
+    row = dense + extra
+    assert len(row) == n
+    rng.shuffle(row)
+    return row
+
+
+def dbscan_wrap_row(stride: int, mincluster: int) -> List[float]:
+    """A row whose flags depend on `2 * mode` wrapping (src/outlier.rs:115), scaled to `mincluster` >= 3: a values of 12 and b of
+    2.5e19 with a < b < mincluster = a + b, and up to three infinities.  2.5e19 and inf both cast to usize::MAX, the mode.  Wrapped,
+    eps is 2^64 - 2 = 1.8e19: the two groups do not reach each other, neither is a cluster, every value is noise.  Unwrapped (or
+    saturated) eps would be 3.7e19 (1.8e19 and a bit): the a + b finite values would all be neighbours and core points, and only
+    the infinities noise.  Below mincluster 3 no such row exists (DBSCAN_WRAP_ROW instead, which decides it at mincluster 2)."""
+    if mincluster < 3:
+        return list(DBSCAN_WRAP_ROW)
+    a = (mincluster - 1) // 2
+    b = mincluster - a
+    assert 1 <= a < b < mincluster <= stride
+    return [float("inf")] * min(3, stride - mincluster) + [12.0] * a + [2.5e19] * b
+
+
+def dbscan_rows(rng: random.Random, stride: int, n_rows: int, mincluster: int, first_kind: int = 0):
+    """Rows for inq_outlier_rows(method = dbscan) at width `stride`: (values f32 [n_rows, stride], lengths u32 [n_rows]).  Twelve kinds
+    in turn from `first_kind` on: _dbscan_struct at the full width and one value past a power of two, dbscan_wrap_row, a row
+    without a positive value (no mode), _dbscan_struct with NaN / +-inf / negative values thrown in at one value short of a power
+    of two, positive values all inside (0, 1) (the mode's key is 0); then one repeated value at the full width (the sort's all-ties
+    path), lengths 0 and 1, negative values only, and further _dbscan_struct rows of random length and of the full width with NaN
+    and the like.  Behind a row's length lies DBSCAN_PAD."""
+    pow2 = 1 << ((stride - 1).bit_length() - 1)  # the largest power of two below the width
+    vals = np.full((n_rows, stride), DBSCAN_PAD, dtype=np.float32)
+    lens = np.zeros(n_rows, dtype=np.uint32)
+    inf = float("inf")
+    for i in range(n_rows):
+        kind = (i + first_kind) % 12
+        base = (5, 12, 30, 200)[(i // 2 + i) % 4]
+        if kind == 0:
+            row = _dbscan_struct(rng, stride, mincluster, base, near=True)
+        elif kind == 1:
+            row = _dbscan_struct(rng, pow2 + 1, mincluster, base)
+        elif kind == 2:
+            row = dbscan_wrap_row(stride, mincluster)
+        elif kind == 3:
+            row = [rng.choice([0.0, -0.0, float("nan"), -1.0, -40.0]) for _ in range(pow2 - 1)] + [0.0]
+        elif kind == 4 or kind == 11:
+            row = _dbscan_struct(rng, pow2 - 1 if kind == 4 else stride, mincluster, base)
+            for _ in range(max(3, len(row) // 30)):
+                row[rng.randrange(len(row))] = rng.choice([float("nan"), inf, -inf, -3.0, -1e9, 0.0])
+        elif kind == 5:
+            row = [rng.choice([0.0, -2.0]) if rng.random() < 0.2 else rng.uniform(0.01, 0.99) for _ in range(stride)]
+        elif kind == 6:
+            row = [7.0] * stride
+        elif kind == 7:
+            row = []
+        elif kind == 8:
+            row = [12.0]
+        elif kind == 9:
+            row = [rng.choice([-5.0, -6.0, -inf]) for _ in range(pow2 // 2 + 3)]
+        else:
+            row = _dbscan_struct(rng, rng.randint(1, stride), mincluster, base)
+        vals[i, : len(row)] = row
+        lens[i] = len(row)
+    return vals, lens
+
+
+DBSCAN_CLASSES = ((256, 48), (257, 48), (2048, 12), (2049, 12), (8192, 6))  # (width, rows): both sides of every size class' edge
+
+
+def dbscan_minclusters(stride: int):
+    """1 (every finite value is a core point), usize::ilog2 of the width (what `inquiSTR outlier` passes), the width itself."""
+    return (1, stride.bit_length() - 1, stride)
+
+
+def dbscan_edge_points(values: np.ndarray, n: int, mincluster: int, flags: np.ndarray) -> int:
+    """How many values of the row are neither flagged as noise nor core points - neighbours of a core point without `mincluster`
+    neighbours of their own -, counted from the definition; 0 for a row with a value that is not a small finite number."""
+    v = np.where(np.isnan(values[:n]), 0.0, values[:n]).astype(np.float64)
+    if n == 0 or not np.isfinite(v).all() or np.abs(v).max() >= 2.0**23 or not (v > 0).any():
+        return 0
+    keys, counts = np.unique(np.floor(v[v > 0]), return_counts=True)
+    eps = max(2.0 * float(keys[np.argmax(counts)]), 10.0)  # (argmax: the first, so the smallest, of equally frequent keys)
+    s = np.sort(v)
+    neighbours = np.searchsorted(s, v + eps, "left") - np.searchsorted(s, v - eps, "right")  # exact: small numbers, |x - y| < eps
+    return int(((neighbours < mincluster) & (flags[:n] == 0)).sum())
+
+
+def dbscan_flags_by_definition(values: np.ndarray, n: int, mincluster: int, wrap: bool) -> np.ndarray:
+    """The noise flags of one row from the definition (src/outlier.rs:112-145, dbscan 0.3.1: neighbours at f64 distance < eps, a
+    core point has at least `mincluster` of them, noise is neither a core point nor the neighbour of one), with `2 * mode` wrapped
+    modulo 2^64 as the release build does or, `wrap` = False, not: what a kernel that widened or saturated it would give."""
+    v = np.where(np.isnan(values[:n]), 0.0, values[:n]).astype(np.float64)
+    counts = {}
+    for x in v[v > 0].tolist():
+        k = 2**64 - 1 if x >= 2.0**64 else int(x)
+        counts[k] = counts.get(k, 0) + 1
+    best = max(counts.values())
+    twice = 2 * min(k for k, c in counts.items() if c == best)
+    eps = float(max(twice % 2**64 if wrap else twice, 10))
+    core = np.zeros(n, dtype=bool)
+    near_core = np.zeros(n, dtype=bool)
+    with np.errstate(invalid="ignore"):  # inf - inf: NaN, no neighbour
+        for lo in range(0, n, 512):
+            core[lo : lo + 512] = (np.abs(v[lo : lo + 512, None] - v[None, :]) < eps).sum(axis=1) >= mincluster
+        for lo in range(0, n, 512):
+            near_core[lo : lo + 512] = ((np.abs(v[lo : lo + 512, None] - v[None, :]) < eps) & core[None, :]).any(axis=1)
+    return (~core & ~near_core).astype(np.uint8)
+
+
+def rows_decided_by_the_wrap(vals, lens, mincluster, flags, keep) -> int:
+    """How many kept rows of the reference's answer hold a flag that an unwrapped `2 * mode` would change (only a row with a value
+    of 2^63 or more can); asserts on the way that the wrapped definition is the reference's answer for those rows."""
+    n_rows = 0
+    for i in np.nonzero(keep == 1)[0]:
+        n = int(lens[i])
+        if not (np.nan_to_num(vals[i, :n], nan=0.0) >= 2.0**63).any():
+            continue
+        assert np.array_equal(dbscan_flags_by_definition(vals[i], n, mincluster, True), flags[i, :n]), (i, mincluster)
+        n_rows += int(not np.array_equal(dbscan_flags_by_definition(vals[i], n, mincluster, False), flags[i, :n]))
+    return n_rows
+
+
+def assert_dbscan_class_is_covered(stride: int, per_mincluster) -> None:
+    """per_mincluster: [(values, lengths, mincluster, reference flags, reference keep)] of one width.  From the reference alone: the
+    class has at least four kept rows, a flagged value, an unflagged value that is no core point, a row without a mode, and a row
+    whose flags differ from what an unwrapped `2 * mode` gives - under every mincluster from 3 on, in fact."""
+    kept = flagged = edge = no_mode = 0
+    for vals, lens, mincluster, flags, keep in per_mincluster:
+        kept = max(kept, int((keep == 1).sum()))
+        flagged += int(flags.sum())
+        no_mode += int((keep == 3).sum())
+        edge += sum(dbscan_edge_points(vals[i], int(lens[i]), mincluster, flags[i]) for i in np.nonzero(keep == 1)[0])
+        if mincluster >= 3:
+            assert rows_decided_by_the_wrap(vals, lens, mincluster, flags, keep) >= 1, (stride, mincluster)
+    assert kept >= 4 and flagged >= 1 and edge >= 1 and no_mode >= 1, (stride, kept, flagged, edge, no_mode)
+
+
+_DBSCAN_REF = {}
+
+
+def dbscan_class_reference(stride: int, n_rows: int):
+    """dbscan_rows at one width under each of dbscan_minclusters, with the C restatement's flags and row states (minsize 0: a row
+    without a positive value is kept and has no mode): [(values, lengths, mincluster, flags, keep)].  Under mincluster 1, where
+    every finite value is a core point whatever the row, the kinds start with the seventh: the narrow matrix of the widest class
+    holds the repeated value and the lengths 0 and 1 too.  Computed once per process."""
+    from oracle import outlier_oracle as oo
+
+    if stride not in _DBSCAN_REF:
+        per = []
+        for mincluster in dbscan_minclusters(stride):
+            vals, lens = dbscan_rows(random.Random(31 * stride + mincluster), stride, n_rows, mincluster, first_kind=6 if mincluster == 1 else 0)
+            flags, keep = oo.c_outlier_rows(vals, lens, "dbscan", minsize=0, mincluster=mincluster, threads=8)
+            per.append((vals, lens, mincluster, flags, keep))
+        _DBSCAN_REF[stride] = per
+    return _DBSCAN_REF[stride]

@@ -11,6 +11,7 @@ import pytest
 
 from inquistr_amd import call, hipcall
 from oracle import outlier_oracle as oo
+from tests import gen
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -171,3 +172,87 @@ def test_outlier_command_panics_like_the_reference(tmp_path):
     with pytest.raises(call.CallError) as e:
         call.outlier(tmp_path / "c.tsv", sample="A", subset=tmp_path / "subset.txt")
     assert e.value.status == 101
+
+
+@pytest.mark.parametrize("stride,n_rows", gen.DBSCAN_CLASSES)
+def test_dbscan_at_every_size_class(ctx, stride, n_rows):
+    """launch_outlier picks outlier_dbscan_kernel<256, 64>, <2048, 256> or <8192, 256> by the matrix' width: widths on both sides of
+    both edges and the widest (65.6 KB of LDS, a 13-stage bitonic sort, 16-bit indices and prefix counts), rows of gen.dbscan_rows
+    - groups of equal values placed exactly eps - 1, eps and eps + 1 from a cluster, of one fewer, exactly and one more than
+    `mincluster` values; NaN, +-inf, negative values; a mode key of 0; ragged lengths around a power of two; one repeated value -
+    under mincluster 1, ilog2(width) and the width.  From mincluster 3 on every matrix holds gen.dbscan_wrap_row, whose flags a
+    kernel that did not wrap `2 * mode` would get wrong (asserted from the reference by assert_dbscan_class_is_covered).  Flags and
+    row states equal the C restatement's exactly."""
+    per = gen.dbscan_class_reference(stride, n_rows)
+    gen.assert_dbscan_class_is_covered(stride, per)  # from the reference alone (without a GPU: tests/test_outlier_oracle.py)
+    for vals, lens, mincluster, want_flags, want_keep in per:
+        rc, flags, keep = ctx.outlier_rows(vals, lens, "dbscan", minsize=0, mincluster=mincluster)
+        assert rc == 0
+        assert np.array_equal(keep, want_keep), (stride, mincluster, keep.tolist(), want_keep.tolist())
+        bad = np.argwhere(flags != want_flags)
+        assert bad.size == 0, (stride, mincluster, bad[:8].tolist())
+
+
+@pytest.mark.parametrize("stride", [5, 257, 2049])
+def test_dbscan_wraps_twice_the_mode(ctx, stride):
+    """[inf, inf, inf, 12, 2.5e19] at mincluster 2, through each of the three kernels: the mode is usize::MAX, `2 * mode` wraps to
+    2^64 - 2 as in the reference's release build (src/outlier.rs:115), so 12 and 2.5e19 are no neighbours and all five values are
+    noise; a kernel that widened or saturated the product would make the two a cluster and flag the infinities only.  Beside it
+    the row whose mode, 2^63, wraps to 0: eps is the floor of 10 and 12 and 30 are noise."""
+    vals = np.full((2, stride), gen.DBSCAN_PAD, dtype=np.float32)
+    vals[0, :5] = gen.DBSCAN_WRAP_ROW
+    vals[1, :5] = [2.0**63] * 3 + [12, 30]
+    lens = np.array([5, 5], dtype=np.uint32)
+    want_flags, want_keep = oo.c_outlier_rows(vals, lens, "dbscan", minsize=10, mincluster=2)
+    assert want_keep.tolist() == [1, 1] and want_flags[:, :5].tolist() == [[1, 1, 1, 1, 1], [0, 0, 0, 1, 1]]
+    assert gen.dbscan_flags_by_definition(vals[0], 5, 2, False).tolist() == [1, 1, 1, 0, 0]
+    rc, flags, keep = ctx.outlier_rows(vals, lens, "dbscan", minsize=10, mincluster=2)
+    assert rc == 0 and keep.tolist() == [1, 1] and np.array_equal(flags, want_flags), flags[:, :5].tolist()
+
+
+def test_dbscan_rows_wider_than_the_widest_class(ctx):
+    """A matrix of 8 193 columns: the row that fills them is INQ_OUTLIER_ROW_TOO_WIDE and nothing of it is flagged; the rows beside
+    it that fit the widest class are computed as ever."""
+    rng = random.Random(8193)
+    stride, lens = 8193, np.array([8193, 8192, 10, 0], dtype=np.uint32)
+    vals, _ = gen.dbscan_rows(rng, stride, 4, 13)
+    vals[1, :8192] = vals[0, :8192]
+    vals[2, :10] = [12, 12, 13, 12, 400, 12, 11, 12, float("nan"), 12]
+    rc, flags, keep = ctx.outlier_rows(vals, lens, "dbscan", minsize=10, mincluster=3)
+    want_flags, want_keep = oo.c_outlier_rows(vals[1:], lens[1:], "dbscan", minsize=10, mincluster=3, threads=8)
+    assert rc == 0 and want_keep.tolist() == [1, 1, 2] and want_flags[1, :10].tolist() == [0, 0, 0, 0, 1, 0, 0, 0, 0, 0]
+    assert keep.tolist() == [4, 1, int(want_keep[1]), 2]
+    assert not flags[0].any() and not flags[3].any()
+    assert np.array_equal(flags[1:], want_flags)
+
+
+def test_outlier_command_refuses_dbscan_on_more_than_8192_values(tmp_path):
+    """`inquistr outlier --method dbscan` on a cohort file with 8 193 value columns: the error status and its message, and not one
+    line on standard output - the same file is fine for the z-score."""
+    names = "\t".join(f"S{k}_H{1 + k % 2}" for k in range(8193))
+    cells = "\t".join(["12"] * 8192 + ["500"])
+    p = tmp_path / "wide.tsv"
+    p.write_text(f"chromosome\tbegin\tend\t{names}\nchr1\t100\t200\t{cells}\n")
+    cli = os.path.join(ROOT, "inquistr_amd", "lib", "inquistr")
+    r = subprocess.run([cli, "outlier", str(p), "--method", "dbscan"], capture_output=True, text=True)
+    assert r.returncode == 1 and "more than 8192 values" in r.stderr and r.stdout == ""
+    with pytest.raises(call.CallError) as e, open(tmp_path / "o.txt", "w") as f:
+        call.outlier(p, method="dbscan", out=f)
+    assert e.value.status == 1 and "more than 8192 values" in e.value.message and (tmp_path / "o.txt").read_text() == ""
+    r = subprocess.run([cli, "outlier", str(p), "--method", "zscore"], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout == "chrom\tbegin\tend\toutliers\nchr1\t100\t200\tS8192\n"
+
+
+@pytest.mark.parametrize("stride", [257, 2049, 8193])
+def test_zscore_on_wide_rows_equals_the_c_restatement(ctx, stride):
+    """Rows wider than the LDS tile take the transposed copy: widths past 256, 2 048 and 8 192 values (the transpose's last tile
+    holds one column), ragged, against the sequential f32 sums of the C restatement."""
+    rng = random.Random(stride)
+    vals, lens = _random_matrix(rng, 130, stride)
+    lens[:3] = [stride, stride - 1, 0]
+    for cutoff, minsize in ((2.0, 10), (3.0, 0)):
+        rc, flags, keep = ctx.outlier_rows(vals, lens, "zscore", minsize=minsize, zscore_cutoff=cutoff, mincluster=3)
+        want_flags, want_keep = oo.c_outlier_rows(vals, lens, "zscore", minsize=minsize, cutoff=cutoff, threads=8)
+        assert rc == 0 and np.array_equal(keep, want_keep)
+        assert np.array_equal(flags, want_flags), np.argwhere(flags != want_flags)[:8].tolist()
+        assert (want_keep == 1).sum() > 50 and want_flags.any()

@@ -398,20 +398,11 @@ def test_very_deep_loci_at_the_edges_of_the_clip_rule(ctx, orc, seed, unphased):
     batch = build(1)
     oc, probe = orc.call_batch(batch, debug=True, threads=8)
     assert oc == 0
-    n0 = int(batch.locus_pair_off[1])
-    bits = probe.pair_bits[:n0].astype(np.int64)
-    kept = (bits & 4) != 0
-    if unphased:  # h1 = the lower half of the kept Calls
-        vals = np.sort(probe.pair_call[:n0][kept], kind="stable")
-        h1 = kept.sum() // 2
-        ng = int(h1)
+    ng, ns = gen.group_counts(batch, probe, 0)[1]  # h1: the kept reads of HP 1, or the lower half of the kept Calls
+    if unphased:
         ns = None  # which Calls are clipped depends on the split: take the supports around half of h1 instead
         supports = [1, max(1, ng // 2), ng - 1, ng, ng + 1]
-        del vals
     else:
-        phase = batch.reads["phase"][batch.pair_read[:n0]]
-        g1 = kept & (phase == 1)
-        ng, ns = int(g1.sum()), int((g1 & ((bits & 1) == 0)).sum())
         supports = [max(1, ns - 1), ns, ns + 1, ng, ng + 1]
     for support in supports:
         b = build(support)

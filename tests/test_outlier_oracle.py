@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import outlier_oracle as oo
+from tests import gen
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -25,6 +26,28 @@ def test_oracle_reproduces_the_reference_unit_tests(kat):
         else:
             got = oo.dbscan_outliers(vals, v["samples"], v["mincluster"])
         assert got == v["expect"], v["name"]
+
+
+WRAPPING_ROW = [float("inf"), float("inf"), float("inf"), 12.0, 2.5e19]
+
+
+def test_twice_the_mode_wraps_like_the_release_build():
+    """`max(2 * mode, 10)` (src/outlier.rs:115) is usize arithmetic without overflow checks in the reference's release
+    profile.  Three `inf` and 2.5e19 all cast to usize::MAX: the mode; twice that wraps to 2^64 - 2 = 1.8e19 as f64.
+    12 and 2.5e19 are then 2.5e19 apart - not neighbours - and each alone is no cluster of two; an infinite value is
+    not even its own neighbour (inf - inf is NaN).  All five are noise.  Without the wrap eps would be 3.7e19 and the
+    two finite values a cluster."""
+    row = [np.float32(x) for x in WRAPPING_ROW]
+    assert oo.mode(row) == 2**64 - 1
+    assert oo.dbscan_flags(row, 2) == [True] * 5
+    vals = np.array([WRAPPING_ROW], dtype=np.float32)
+    flags, keep = oo.c_outlier_rows(vals, [5], "dbscan", minsize=10, mincluster=2)
+    assert keep.tolist() == [1] and flags[0].tolist() == [1] * 5
+    # a mode of 2^63 wraps to 0, so eps is the floor of 10: 12 and 30 are noise (unwrapped, 2^64 would reach everything)
+    vals = np.array([[2.0**63] * 3 + [12, 30]], dtype=np.float32)
+    assert oo.dbscan_flags(list(vals[0]), 2) == [False, False, False, True, True]
+    flags, keep = oo.c_outlier_rows(vals, [5], "dbscan", minsize=10, mincluster=2)
+    assert keep.tolist() == [1] and flags[0].tolist() == [0, 0, 0, 1, 1]
 
 
 def test_parse_f32_follows_rust():
@@ -86,6 +109,15 @@ def test_c_restatement_agrees_with_the_python_one(method):
                 row[rng.randrange(n)] = rng.choice([base * 7.0, float("nan"), float("inf"), -4.0])
         vals[i, :n] = row
         lens[i] = n
+    # rows whose mode is usize::MAX, so that `2 * mode` wraps: the known-answer row (at mincluster = 5 noise with or without the wrap)
+    # and one in which only the wrap keeps the finite values from being a cluster of six
+    wide = [float("inf")] * 7 + [12.0] * 3 + [2.5e19] * 3
+    for i, row in ((n_rows - 2, WRAPPING_ROW), (n_rows - 1, wide)):
+        vals[i] = 0
+        vals[i, : len(row)] = row
+        lens[i] = len(row)
+    if method == "dbscan":
+        assert oo.dbscan_flags(list(vals[n_rows - 1, : len(wide)]), 5) == [True] * len(wide)
     flags, keep = oo.c_outlier_rows(vals, lens, method, minsize=10, cutoff=2.0, mincluster=5, threads=2)
     for i in range(n_rows):
         row = [np.float32(0) if np.isnan(x) else x for x in vals[i, : lens[i]]]
@@ -100,3 +132,32 @@ def test_c_restatement_agrees_with_the_python_one(method):
                 assert keep[i] == 3
                 continue
             assert keep[i] == 1 and list(flags[i, : lens[i]].astype(bool)) == want, i
+
+
+@pytest.mark.parametrize("stride,n_rows", gen.DBSCAN_CLASSES)
+def test_dbscan_rows_cover_every_size_class(stride, n_rows):
+    """What the wide-row GPU test relies on, from the reference alone: at every width kept rows, flagged values, edge points, a row
+    without a mode and a row that only a wrapping `2 * mode` answers as the reference does; over the three matrices of a width
+    every kind of row - lengths 0, 1, the width and both neighbours of a power of two, one repeated value at the full width, a row
+    that is skipped -; nothing flagged behind a row's length; and, on the narrowest class, the C restatement's answer is the
+    Python one's."""
+    per = gen.dbscan_class_reference(stride, n_rows)
+    gen.assert_dbscan_class_is_covered(stride, per)
+    pow2 = 1 << ((stride - 1).bit_length() - 1)
+    lengths, states, constant = set(), set(), False
+    for vals, lens, mincluster, flags, keep in per:
+        lengths |= set(lens.tolist())
+        states |= set(keep.tolist())
+        constant |= any(lens[i] == stride and (vals[i] == vals[i, 0]).all() for i in range(n_rows))
+        assert not flags[np.arange(stride)[None, :] >= lens[:, None]].any()
+        if mincluster >= 3:  # the wrap row: every value noise; unwrapped, only its infinities
+            want = np.array(gen.dbscan_wrap_row(stride, mincluster), dtype=np.float32)
+            at = [i for i in range(n_rows) if lens[i] == len(want) and np.array_equal(vals[i, : len(want)], want)]
+            assert at and all(keep[i] == 1 and flags[i, : len(want)].all() for i in at)
+            assert gen.dbscan_flags_by_definition(want, len(want), mincluster, False).tolist() == np.isinf(want).astype(int).tolist()
+        if stride == 256 and mincluster == 8:
+            for i in range(0, n_rows, 5):
+                row = [np.float32(0) if np.isnan(x) else x for x in vals[i, : lens[i]]]
+                if keep[i] == 1:
+                    assert list(flags[i, : lens[i]].astype(bool)) == oo.dbscan_flags(row, mincluster), i
+    assert {0, 1, stride, pow2 - 1, pow2, pow2 + 1} <= lengths and {0, 1, 2, 3} <= states and constant
