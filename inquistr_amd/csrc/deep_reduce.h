@@ -1,6 +1,8 @@
-// deep_reduce.h - the reduces of a locus with more than 256 offered reads that ONE workgroup does (device functions; the walk that
-// leaves the per-read Calls in the ctx scratch is locus_call_mid_walk in kernels.hip, the kernel that calls these is locus_call_tail
-// in deep_select.hip):
+// deep_reduce.h - first, the ONE copy of what every reduce of a locus' Calls to its two rows shares (the one in registers of
+// kernels.hip, the two below, the grid-wide select of deep_select.hip): the reference's rule as arithmetic on counts and keys, the
+// store of a locus' rows, the look-up of a work-list item.  Then the reduces of a locus with more than 256 offered reads that ONE
+// workgroup does (device functions; the walk that leaves the per-read Calls in the ctx scratch is locus_call_mid_walk in
+// kernels.hip, the kernel that calls these is locus_call_tail in deep_select.hip):
 //   sort_reduce_locus   up to 16 384 reads: 64-bit keys sorted by a bitonic network in LDS
 //   reduce_deep_select  beyond that (and Calls that do not fit a key): most-significant-byte-first radix select over the scratch
 // Reference semantics: median_str_length src/call.rs:497-522, the unphased split :308-322, the phased bins :341-369.
@@ -14,7 +16,127 @@
 namespace inq {
 
 __device__ __forceinline__ double qnan() { return __builtin_nan(""); }
+__device__ __forceinline__ uint64_t order_key(int64_t v) { return (uint64_t)v ^ (1ull << 63); }  // signed order as unsigned order
+__device__ __forceinline__ int64_t order_key_inv(uint64_t k) { return (int64_t)(k ^ (1ull << 63)); }
 
+// ---- the rule: arithmetic on counts and keys (no memory access, no barrier).  Keys may be absolute or rebased to the locus'
+// smallest Call: only their order is used.
+// :498-500: a haplotype group with fewer Calls than `support` has no median (its row is NaN)
+__device__ __forceinline__ bool group_live(uint32_t ng, uint32_t support) { return ng >= support; }
+// :509-513: of a group of ng Calls, ns of them spanning, the median takes every spanning Call and, when there are no more than
+// `support` of them, the largest `take` clipped ones (which of several equal clipped values does not change the multiset of values)
+struct GroupPlan {
+    bool live;
+    uint32_t take;
+    uint32_t nc;          // clipped Calls; >= take in a live group because ng >= support
+    uint32_t first_clip;  // rank, among the group's clipped Calls in ascending order, of the smallest one taken: the clip threshold
+    uint32_t M;           // chosen Calls; >= 1 in a live group because support >= 1
+};
+__device__ __forceinline__ GroupPlan plan_group(uint32_t ng, uint32_t ns, uint32_t support) {
+    GroupPlan p;
+    p.live = group_live(ng, support);
+    p.take = ns <= support ? support - ns : 0u;
+    p.nc = ng - ns;
+    p.first_clip = p.nc - p.take;
+    p.M = ns + p.take;
+    return p;
+}
+// The clip threshold from a select at rank first_clip of the group's clipped Calls, which found `below` of them smaller than the
+// key and `eq` equal to it: the clipped Calls larger than the key are all chosen, and `lump` of those equal to it.
+struct ClipThreshold {
+    uint64_t key;
+    uint32_t lump;
+};
+__device__ __forceinline__ ClipThreshold clip_threshold(const GroupPlan &p, uint64_t key, uint32_t below, uint32_t eq) {
+    return ClipThreshold{key, p.take - (p.nc - below - eq)};
+}
+// Is a Call of the group chosen?  (The `lump` clipped Calls equal to the threshold are counted by the caller: they have no names.)
+__device__ __forceinline__ bool call_chosen(bool clipped, uint64_t key, const GroupPlan &p, const ClipThreshold &t) {
+    return !clipped || (p.take > 0u && key > t.key);
+}
+// :515-520: the median of M chosen Calls from the two middle ones (vlo is not looked at when M is odd)
+__device__ __forceinline__ double median_finish(int64_t vlo, int64_t vhi, uint32_t M) {
+    return (M & 1u) ? (double)vhi : (double)(vlo + vhi) / 2.0;  // i64 add, then f64
+}
+// :311-313: the unphased split sorts the mcount kept Calls by (value, file order); h1 = the lower mcount / 2, h2 = the rest.  The
+// split value is the Call at this rank (mcount >= 1)
+__device__ __forceinline__ uint32_t split_rank(uint32_t mcount) {
+    const uint32_t kh = mcount / 2u;
+    return kh < mcount ? kh : mcount - 1u;
+}
+// ... and of the Calls equal to it, h1 still takes this many, the first in file order (`below`: Calls smaller than the split value)
+__device__ __forceinline__ uint32_t split_h1_equals(uint32_t mcount, uint32_t below) { return mcount / 2u - below; }
+// the split cuts through equal values of mixed kind (:312-314 ambiguity) iff some Call equal to the split value went to h1 and
+// both kinds are among the equal ones (flags: bit 0 a clipped, bit 1 a spanning Call equal to the split value)
+__device__ __forceinline__ bool split_is_tie(uint32_t mcount, uint32_t below, uint32_t flags) {
+    const uint32_t kh = mcount / 2u;
+    return kh >= 1u && kh < mcount && split_h1_equals(mcount, below) >= 1u && flags == 3u;
+}
+
+// ---- the rule's memory side
+// Per-thread tallies of haplotype groups 1 and 2: Calls and spanning Calls.  (Scalars, not arrays indexed by the group: those
+// would live in scratch or LDS.)
+struct GroupCounts {
+    uint32_t ng1 = 0, ng2 = 0, ns1 = 0, ns2 = 0;
+    __device__ __forceinline__ void add(uint32_t grp, uint32_t me) {  // grp is 1 or 2
+        const uint32_t span = (me & PM_CLIP) ? 0u : 1u;
+        if (grp == 1u) ng1++, ns1 += span;
+        else ng2++, ns2 += span;
+    }
+    // into a workgroup's eight LDS counters: [g] Calls, [4 + g] spanning Calls
+    __device__ __forceinline__ void flush(unsigned int *cnt) const {
+        if (ng1) atomicAdd(&cnt[1], ng1);
+        if (ns1) atomicAdd(&cnt[5], ns1);
+        if (ng2) atomicAdd(&cnt[2], ng2);
+        if (ns2) atomicAdd(&cnt[6], ns2);
+    }
+};
+
+// The unphased groups of elements [e0, e1), a thread's contiguous part of the store (contiguous parts: "the first r equal ones in
+// file order" is a prefix count; eq_before = Calls equal to the split value in front of e0).  Calls below the split value go to h1,
+// above to h2.  Rewrites the group bits of meta, tallies the groups in c and returns the tie flags of split_is_tie.
+__device__ __forceinline__ uint32_t assign_split_groups(const int64_t *val, uint8_t *meta, uint32_t e0, uint32_t e1, uint64_t split, uint32_t r,
+                                                        uint32_t eq_before, GroupCounts &c) {
+    uint32_t fl = 0;
+    for (uint32_t e = e0; e < e1; ++e) {
+        const uint32_t me = meta[e];
+        if (!(me & PM_KEPT)) continue;
+        const uint64_t key = order_key(val[e]);
+        uint32_t grp = key < split ? 1u : 2u;
+        if (key == split) {
+            grp = eq_before < r ? 1u : 2u;
+            ++eq_before;
+            fl |= (me & PM_CLIP) ? 1u : 2u;
+        }
+        meta[e] = (uint8_t)((me & ~(3u << PM_GRP_SHIFT)) | (grp << PM_GRP_SHIFT));
+        c.add(grp, me);
+    }
+    return fl;
+}
+
+// The two rows of locus j.  ONE thread calls it: the thread that writes phase1[j] is the one that stores locus_flags[j] (kernels.h)
+__device__ __forceinline__ void write_locus_rows(const KArgs &a, uint64_t j, double out1, double out2, bool tie) {
+    a.phase1[j] = out1;
+    a.phase2[j] = out2;
+    if (tie) {
+        atomicAdd((unsigned long long *)&a.status->ties, 1ull);
+        if (a.locus_flags) a.locus_flags[j] = INQ_LOCUS_TIE;
+    }
+}
+// A locus that cannot be called: NaN rows and a status bit.  ONE thread calls it.
+__device__ __forceinline__ void write_failed_rows(const KArgs &a, uint64_t j, uint32_t status) {
+    atomicOr(&a.status->err, status);
+    write_locus_rows(a, j, qnan(), qnan(), false);
+}
+
+// Item `item` of work list `kind` (its shards in order; cnt = the kind's shard lengths, item < their sum) -> the locus
+__device__ __forceinline__ uint64_t worklist_locus(const KArgs &a, const uint32_t *cnt, uint32_t kind, uint32_t item) {
+    uint32_t shard = 0, idx = item;
+    while (idx >= cnt[shard]) idx -= cnt[shard++];
+    return a.worklist[((uint64_t)kind * kListShards + shard) * a.shard_cap + idx];
+}
+
+// ---- one workgroup's radix select over the global store
 // Per-read results of one very deep locus (more reads than the LDS sort holds, or a Call beyond the sort key's 47 bits) stay
 // in the ctx's global scratch (L2-resident: 9 bytes per read) and are reduced there by ONE workgroup with a most-significant-
 // byte-first radix select: eight passes of a 256-bin histogram find the k-th smallest value of any subset, O(n) each.  About
@@ -22,7 +144,7 @@ __device__ __forceinline__ double qnan() { return __builtin_nan(""); }
 // haplotype): a 100 000-read locus costs ~25 000 element visits per thread.
 struct DeepStore {
     const int64_t *val;
-    unsigned char *meta;
+    uint8_t *meta;
 };
 struct SelectLds {
     unsigned int hist[256];
@@ -31,7 +153,6 @@ struct SelectLds {
     unsigned int k, below, eq, flags;
     unsigned int cnt[8];
 };
-__device__ __forceinline__ uint64_t order_key(int64_t v) { return (uint64_t)v ^ (1ull << 63); }  // signed order as unsigned order
 
 // k-th smallest (0-based) key among the elements for which pred(e, key) holds, plus `lump_cnt` extra elements of key
 // `lump_key`.  Block-uniform result; L.below = elements smaller than it, L.eq = elements equal to it (lump included).
@@ -69,55 +190,55 @@ __device__ __forceinline__ uint64_t radix_select(const DeepStore &S, uint32_t n,
     return L.prefix;
 }
 
-// median_str_length (src/call.rs:497-522) of haplotype group g (1 / 2) of the store
+// median_str_length (src/call.rs:497-522) of haplotype group g (1 / 2) of the store.  Contains workgroup barriers: every thread
+// calls it.
 __device__ __forceinline__ double deep_group_median(const DeepStore &S, uint32_t n, uint32_t g, uint32_t ng, uint32_t ns, uint32_t support, SelectLds &L) {
-    if (ng < support) return qnan();  // :498-500
+    const GroupPlan P = plan_group(ng, ns, support);
+    if (!P.live) return qnan();
     auto in_group = [&](uint32_t e) {
         const uint32_t me = S.meta[e];
         return (me & PM_KEPT) && ((me >> PM_GRP_SHIFT) & 3u) == g;
     };
-    const uint32_t take = ns <= support ? support - ns : 0u;  // :509-513: the largest `take` clipped Calls join the spanning ones
-    uint64_t t_key = 0;
-    uint32_t lump = 0;
-    if (take > 0u) {
-        const uint32_t nc = ng - ns;  // >= take because ng >= support
-        t_key = radix_select(S, n, [&](uint32_t e, uint64_t) { return in_group(e) && (S.meta[e] & PM_CLIP); }, nc - take, 0ull, 0u, L);
-        const uint32_t above = nc - L.below - L.eq;  // clipped Calls larger than the threshold value: all chosen
-        lump = take - above;                          // ... and this many equal to it (which ones does not change the values)
+    ClipThreshold T{0ull, 0u};
+    if (P.take > 0u) {
+        const uint64_t t_key = radix_select(S, n, [&](uint32_t e, uint64_t) { return in_group(e) && (S.meta[e] & PM_CLIP); }, P.first_clip, 0ull, 0u, L);
+        T = clip_threshold(P, t_key, L.below, L.eq);
         __syncthreads();
     }
-    const uint32_t M = ns + take;  // >= 1 because support >= 1
-    auto chosen = [&](uint32_t e, uint64_t key) { return in_group(e) && (!(S.meta[e] & PM_CLIP) || (take > 0u && key > t_key)); };
-    const int64_t vhi = (int64_t)(radix_select(S, n, chosen, M / 2u, t_key, lump, L) ^ (1ull << 63));
+    auto chosen = [&](uint32_t e, uint64_t key) { return in_group(e) && call_chosen((S.meta[e] & PM_CLIP) != 0u, key, P, T); };
+    const int64_t vhi = order_key_inv(radix_select(S, n, chosen, P.M / 2u, T.key, T.lump, L));
     __syncthreads();
-    if (M & 1u) return (double)vhi;  // :520
-    const int64_t vlo = (int64_t)(radix_select(S, n, chosen, M / 2u - 1u, t_key, lump, L) ^ (1ull << 63));
-    __syncthreads();
-    return (double)(vlo + vhi) / 2.0;  // :515-518
+    int64_t vlo = vhi;
+    if (!(P.M & 1u)) {
+        vlo = order_key_inv(radix_select(S, n, chosen, P.M / 2u - 1u, T.key, T.lump, L));
+        __syncthreads();
+    }
+    return median_finish(vlo, vhi, P.M);
 }
 
-// The whole reduce of one locus over the global store.
+// The whole reduce of one locus over the global store.  Contains workgroup barriers: every thread calls it.
 template <bool UNPHASED>
 __device__ __forceinline__ void reduce_deep_select(const KArgs &a, uint64_t j, uint64_t p0, uint32_t n, SelectLds &L) {
-    DeepStore S{a.sval + p0, (unsigned char *)(a.smeta + p0)};
+    DeepStore S{a.sval + p0, a.smeta + p0};
     bool tie = false;
-    if (UNPHASED) {  // src/call.rs:311-313: sort by (value, file order), h1 = the lower mcount / 2, h2 = the rest
-        if (threadIdx.x < 8) L.cnt[threadIdx.x] = 0u;
-        __syncthreads();
+    GroupCounts c;
+    if (threadIdx.x < 8) L.cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    if (UNPHASED) {
         uint32_t local = 0;
         for (uint32_t e = threadIdx.x; e < n; e += 256u) local += (S.meta[e] & PM_KEPT) ? 1u : 0u;
         if (local) atomicAdd(&L.cnt[0], local);
         __syncthreads();
-        const uint32_t mcount = L.cnt[0], ks = mcount / 2u;
+        const uint32_t mcount = L.cnt[0];
         __syncthreads();
         uint64_t split = ~0ull;
-        uint32_t r = 0;  // elements equal to the split value that still belong to h1 (the first r in file order)
+        uint32_t below = 0, r = 0;
         if (mcount) {
-            split = radix_select(S, n, [&](uint32_t e, uint64_t) { return (S.meta[e] & PM_KEPT) != 0; }, ks < mcount ? ks : mcount - 1u, 0ull, 0u, L);
-            r = ks - L.below;
+            split = radix_select(S, n, [&](uint32_t e, uint64_t) { return (S.meta[e] & PM_KEPT) != 0; }, split_rank(mcount), 0ull, 0u, L);
+            below = L.below;
+            r = split_h1_equals(mcount, below);
             __syncthreads();
         }
-        // groups: each thread owns a contiguous stretch so that "the first r equal ones in file order" is a prefix count
         const uint32_t chunk = (n + 255u) / 256u, e0 = min(n, threadIdx.x * chunk), e1 = min(n, e0 + chunk);
         uint32_t eq = 0;
         for (uint32_t e = e0; e < e1; ++e) eq += ((S.meta[e] & PM_KEPT) && order_key(S.val[e]) == split) ? 1u : 0u;
@@ -126,55 +247,24 @@ __device__ __forceinline__ void reduce_deep_select(const KArgs &a, uint64_t j, u
         __syncthreads();
         uint32_t eq_before = 0;
         for (uint32_t t = 0; t < threadIdx.x; ++t) eq_before += L.scan[t];
-        uint32_t fl = 0;
-        for (uint32_t e = e0; e < e1; ++e) {
-            uint32_t me = S.meta[e];
-            if (!(me & PM_KEPT)) continue;
-            const uint64_t key = order_key(S.val[e]);
-            uint32_t grp = key < split ? 1u : 2u;
-            if (key == split) {
-                grp = eq_before < r ? 1u : 2u;
-                ++eq_before;
-                fl |= (me & PM_CLIP) ? 1u : 2u;
-            }
-            S.meta[e] = (unsigned char)((me & ~(3u << PM_GRP_SHIFT)) | (grp << PM_GRP_SHIFT));
-        }
+        const uint32_t fl = assign_split_groups(S.val, S.meta, e0, e1, split, r, eq_before, c);
         if (fl) atomicOr(&L.flags, fl);
         __syncthreads();
-        // the split cuts through equal values iff some element equal to the split value went to h1 (:312-314 ambiguity)
-        tie = ks >= 1u && ks < mcount && r >= 1u && L.flags == 3u;
-    }
-    if (threadIdx.x < 8) L.cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    {
-        uint32_t c_ng[3] = {0, 0, 0}, c_ns[3] = {0, 0, 0};
+        tie = split_is_tie(mcount, below, L.flags);
+    } else {
         for (uint32_t e = threadIdx.x; e < n; e += 256u) {
             const uint32_t me = S.meta[e];
-            if (!(me & PM_KEPT)) continue;
             const uint32_t g = (me >> PM_GRP_SHIFT) & 3u;
-            if (g == 1u || g == 2u) {
-                c_ng[g]++;
-                if (!(me & PM_CLIP)) c_ns[g]++;
-            }
-        }
-        for (int g = 1; g <= 2; ++g) {
-            if (c_ng[g]) atomicAdd(&L.cnt[g], c_ng[g]);
-            if (c_ns[g]) atomicAdd(&L.cnt[4 + g], c_ns[g]);
+            if ((me & PM_KEPT) && (g == 1u || g == 2u)) c.add(g, me);
         }
     }
+    c.flush(L.cnt);
     __syncthreads();
     const uint32_t ng1 = L.cnt[1], ng2 = L.cnt[2], ns1 = L.cnt[5], ns2 = L.cnt[6];
     __syncthreads();
     const double out1 = deep_group_median(S, n, 1u, ng1, ns1, a.support, L);
     const double out2 = deep_group_median(S, n, 2u, ng2, ns2, a.support, L);
-    if (threadIdx.x == 0) {
-        a.phase1[j] = out1;
-        a.phase2[j] = out2;
-        if (tie) {
-            atomicAdd((unsigned long long *)&a.status->ties, 1ull);
-            if (a.locus_flags) a.locus_flags[j] = INQ_LOCUS_TIE;
-        }
-    }
+    if (threadIdx.x == 0) write_locus_rows(a, j, out1, out2, tie);
     __syncthreads();
 }
 
@@ -198,11 +288,12 @@ struct SortLds {
 
 __device__ __forceinline__ int64_t key_value(uint64_t k) { return (int64_t)((k >> 15) & ((1ull << 47) - 1ull)) - (int64_t)kKeyBias; }
 
-// median_str_length (src/call.rs:497-522) of the sorted range key[lo, hi).  Block-uniform result.
+// median_str_length (src/call.rs:497-522) of the sorted range key[lo, hi).  Block-uniform result.  Contains workgroup barriers:
+// every thread calls it.
 template <int CAP>
 __device__ __forceinline__ double median_of_sorted_range(SortLds<CAP> &L, uint32_t lo, uint32_t hi, uint32_t support) {
     const uint32_t ng = hi - lo;
-    if (ng < support) return qnan();  // :498-500
+    if (!group_live(ng, support)) return qnan();
     const uint32_t t = threadIdx.x;
     const uint32_t seglen = (ng + 255u) / 256u;
     const uint32_t s0 = min(hi, lo + t * seglen), s1 = min(hi, s0 + seglen);
@@ -216,13 +307,9 @@ __device__ __forceinline__ double median_of_sorted_range(SortLds<CAP> &L, uint32
         before_me += k < t ? c : 0u;
         ns += c;
     }
-    // chosen = every spanning Call, plus (when there are no more than `support` of them) the largest
-    // support - ns clipped ones (:509-513) = the LAST `take` clips of the ascending range; which of several
-    // equal clipped values is taken does not change the multiset of values
-    const uint32_t nc = ng - ns;
-    const uint32_t take = ns <= support ? support - ns : 0u;  // <= nc because ng >= support
-    const uint32_t first_clip = nc - take;                     // clips with clip-rank >= first_clip are chosen
-    const uint32_t M = ns + take;
+    // the clipped Calls taken are the LAST `take` clips of the ascending range: those with clip-rank >= first_clip
+    const GroupPlan P = plan_group(ng, ns, support);
+    const uint32_t first_clip = P.first_clip, M = P.M;
     uint32_t span_before = before_me;
     for (uint32_t e = s0; e < s1; ++e) {
         const uint64_t k = L.key[e];
@@ -237,7 +324,7 @@ __device__ __forceinline__ double median_of_sorted_range(SortLds<CAP> &L, uint32
         span_before += clip ? 0u : 1u;
     }
     __syncthreads();
-    const double out = (M & 1u) ? (double)L.pick[1] : (double)(L.pick[0] + L.pick[1]) / 2.0;  // :515-520
+    const double out = median_finish(L.pick[0], L.pick[1], M);
     __syncthreads();
     return out;
 }
@@ -318,14 +405,7 @@ __device__ __forceinline__ void sort_reduce_locus(const KArgs &a, uint64_t j, ui
     __syncthreads();
     const double out1 = median_of_sorted_range<CAP>(L, lo1, hi1, a.support);
     const double out2 = median_of_sorted_range<CAP>(L, lo2, hi2, a.support);
-    if (threadIdx.x == 0) {
-        a.phase1[j] = out1;
-        a.phase2[j] = out2;
-        if (UNPHASED && L.tie_span && L.tie_clip) {
-            atomicAdd((unsigned long long *)&a.status->ties, 1ull);
-            if (a.locus_flags) a.locus_flags[j] = INQ_LOCUS_TIE;
-        }
-    }
+    if (threadIdx.x == 0) write_locus_rows(a, j, out1, out2, UNPHASED && L.tie_span && L.tie_clip);
     __syncthreads();
 }
 

@@ -38,10 +38,6 @@ namespace inq {
 
 namespace {
 
-__device__ __forceinline__ double qnan_d() { return __builtin_nan(""); }
-__device__ __forceinline__ uint64_t okey(int64_t v) { return (uint64_t)v ^ (1ull << 63); }  // signed order as unsigned order
-__device__ __forceinline__ int64_t okey_inv(uint64_t k) { return (int64_t)(k ^ (1ull << 63)); }
-
 // device-scope loads of words other workgroups wrote with atomics (they bypass this CU's L1; the barrier's acquire has dealt with it
 // already: belt and braces for the few control words everything else hangs on)
 __device__ __forceinline__ uint32_t ld_u32(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -112,13 +108,9 @@ struct DeepLocus {
     Sel thr[3], hi[3];
 };
 static_assert(sizeof(Sel) % 128 == 0 && offsetof(DeepLocus, split) % 128 == 0 && sizeof(DeepLocus) % 128 == 0, "histograms on lines of their own");
-struct DeepHead {
-    uint32_t pad[32];
-};
 
 struct DeepArgs {
     KArgs k;
-    DeepHead *head;
     DeepLocus *loci;  // may be null: no locus of the batch can be that deep
     uint32_t cap;     // loci the scratch holds
 };
@@ -136,20 +128,20 @@ __device__ __forceinline__ KeySpace key_space(const DeepLocus &D) {
     return ks;
 }
 
-// what a group's selects look for (src/call.rs:497-513), from its counts
-struct GroupPlan {
-    bool live;      // ng >= support
-    uint32_t take;  // clipped Calls that join the spanning ones
-    uint32_t nc, M;
-};
+// what a group's selects look for, from its counts
 __device__ __forceinline__ GroupPlan plan_of(const DeepLocus &D, uint32_t g, uint32_t support) {
-    GroupPlan p;
-    const uint32_t ng = ld_u32(&D.ng[g]), ns = ld_u32(&D.ns[g]);
-    p.live = ng >= support;
-    p.take = ns <= support ? support - ns : 0u;
-    p.nc = ng - ns;
-    p.M = ns + p.take;
-    return p;
+    return plan_group(ld_u32(&D.ng[g]), ld_u32(&D.ns[g]), support);
+}
+// The finished selects of a locus, replayed from their histograms.  Both contain workgroup barriers (chain): every thread calls them.
+// The unphased split: .key (rebased) is the split value, .below the kept Calls smaller than it
+__device__ __forceinline__ SelOut split_of(const DeepLocus &D, const KeySpace &ks, uint32_t mcount, ChainLds &L) {
+    return chain(D.split, ks.top, -1, split_rank(mcount), 0ull, 0u, L);
+}
+// group g's clip threshold (rebased key), once its threshold select is through; {0, 0} for a group that takes no clipped Call
+__device__ __forceinline__ ClipThreshold threshold_of(const DeepLocus &D, uint32_t g, const GroupPlan &P, const KeySpace &ks, ChainLds &L) {
+    if (P.take == 0u) return ClipThreshold{0ull, 0u};
+    const SelOut T = chain(D.thr[g], ks.top, -1, P.first_clip, 0ull, 0u, L);
+    return clip_threshold(P, T.key, T.below, T.eq);
 }
 
 // ---------------------------------------------------------------- the phases (device functions of locus_call_tail)
@@ -211,7 +203,7 @@ __device__ __forceinline__ void deep_count_kept(const DeepArgs &a, const uint32_
         FOR_MY_SLICES(D) for_slice_elems(a, D, sl, [&](uint32_t, uint32_t me, int64_t v) {
             if (!(me & PM_KEPT)) return;
             ++local;
-            const uint64_t key = okey(v);
+            const uint64_t key = order_key(v);
             kmin = key < kmin ? key : kmin;
             kmax = key > kmax ? key : kmax;
         });
@@ -242,44 +234,38 @@ __device__ __forceinline__ void deep_select_pass(const DeepArgs &a, const uint32
         const KeySpace ks = key_space(D);
         if (pass > ks.top) continue;  // this locus' keys have no such byte
         for (uint32_t g = (WHICH == 0 ? 0u : 1u); g <= (WHICH == 0 ? 0u : 2u); ++g) {
-            uint32_t k0 = 0, lump = 0;
-            uint64_t t_key = 0;
-            bool use_t = false;
+            uint32_t k0 = 0;
+            GroupPlan P{};
+            ClipThreshold T{0ull, 0u};
             Sel *S;
             if (WHICH == 0) {
                 const uint32_t mcount = ld_u32(&D.mcount);
                 if (mcount == 0u) continue;
-                const uint32_t kh = mcount / 2u;
-                k0 = kh < mcount ? kh : mcount - 1u;
+                k0 = split_rank(mcount);
                 S = &D.split;
             } else {
-                const GroupPlan P = plan_of(D, g, a.k.support);
+                P = plan_of(D, g, a.k.support);
                 if (!P.live) continue;
                 if (WHICH == 1) {
                     if (P.take == 0u) continue;
-                    k0 = P.nc - P.take;
+                    k0 = P.first_clip;
                     S = &D.thr[g];
                 } else {
-                    if (P.take > 0u) {  // the threshold select is through: its value, and how many Calls equal to it are taken
-                        const SelOut T = chain(D.thr[g], ks.top, -1, P.nc - P.take, 0ull, 0u, L.ch);
-                        t_key = T.key;
-                        lump = P.take - (P.nc - T.below - T.eq);
-                        use_t = true;
-                    }
+                    T = threshold_of(D, g, P, ks, L.ch);  // the threshold select is through
                     k0 = P.M / 2u;
                     S = &D.hi[g];
                 }
             }
-            const SelOut st = chain(*S, ks.top, pass, k0, t_key, lump, L.ch);
+            const SelOut st = chain(*S, ks.top, pass, k0, T.key, T.lump, L.ch);
             const uint64_t prefix = st.key;
             L.hist[threadIdx.x] = 0u;
             __syncthreads();
             FOR_MY_SLICES(D) for_slice_elems(a, D, sl, [&](uint32_t, uint32_t me, int64_t v) {
                 if (!(me & PM_KEPT)) return;
                 if (WHICH != 0 && ((me >> PM_GRP_SHIFT) & 3u) != g) return;
-                const uint64_t key = okey(v) - ks.kmin;
+                const uint64_t key = order_key(v) - ks.kmin;
                 if (WHICH == 1 && !(me & PM_CLIP)) return;
-                if (WHICH == 2 && (me & PM_CLIP) && !(use_t && key > t_key)) return;
+                if (WHICH == 2 && !call_chosen((me & PM_CLIP) != 0u, key, P, T)) return;
                 if (pass != ks.top && (key >> (8 * (pass + 1))) != prefix) return;
                 atomicAdd(&L.hist[(key >> (8 * pass)) & 255u], 1u);
             });
@@ -296,11 +282,10 @@ __device__ __forceinline__ void deep_split_eq(const DeepArgs &a, const uint32_t 
         const uint32_t mcount = ld_u32(&D.mcount);
         if (mcount == 0u) continue;
         const KeySpace ks = key_space(D);
-        const uint32_t kh = mcount / 2u;
-        const uint64_t split = chain(D.split, ks.top, -1, kh < mcount ? kh : mcount - 1u, 0ull, 0u, ch).key + ks.kmin;
+        const uint64_t split = split_of(D, ks, mcount, ch).key + ks.kmin;
         FOR_MY_SLICES(D) {
             uint32_t local = 0;
-            for_slice_elems(a, D, sl, [&](uint32_t, uint32_t me, int64_t v) { local += ((me & PM_KEPT) && okey(v) == split) ? 1u : 0u; });
+            for_slice_elems(a, D, sl, [&](uint32_t, uint32_t me, int64_t v) { local += ((me & PM_KEPT) && order_key(v) == split) ? 1u : 0u; });
             for (int off = 32; off; off >>= 1) local += __shfl_xor(local, off);
             if ((threadIdx.x & 63u) == 0u && local) atomicAdd(&D.slice_eq[sl], local);
         }
@@ -323,13 +308,13 @@ __device__ __forceinline__ void deep_groups(const DeepArgs &a, const uint32_t nd
         const uint32_t mcount = UNPHASED ? ld_u32(&D.mcount) : 0u;
         if (UNPHASED && mcount) {
             const KeySpace ks = key_space(D);
-            const uint32_t kh = mcount / 2u;
-            const SelOut so = chain(D.split, ks.top, -1, kh < mcount ? kh : mcount - 1u, 0ull, 0u, ch);
+            const SelOut so = split_of(D, ks, mcount, ch);
             split = so.key + ks.kmin;
-            r = kh - so.below;  // kh >= below: the split value is the kh-th smallest
+            r = split_h1_equals(mcount, so.below);
         }
         __syncthreads();
-        uint32_t c_ng[3] = {0, 0, 0}, c_ns[3] = {0, 0, 0}, fl = 0;
+        GroupCounts c;
+        uint32_t fl = 0;
         uint64_t kmin = ~0ull, kmax = 0ull;
         bool any = false;
         FOR_MY_SLICES(D) {
@@ -346,34 +331,20 @@ __device__ __forceinline__ void deep_groups(const DeepArgs &a, const uint32_t nd
                 const uint32_t s_lo = sl * D.slice, s_hi = min(D.n, s_lo + D.slice);
                 const uint32_t part = (s_hi - s_lo + 255u) / 256u, e0 = min(s_hi, s_lo + threadIdx.x * part), e1 = min(s_hi, e0 + part);
                 uint32_t mine = 0;
-                for (uint32_t e = e0; e < e1; ++e) mine += ((a.k.smeta[D.p0 + e] & PM_KEPT) && okey(a.k.sval[D.p0 + e]) == split) ? 1u : 0u;
+                for (uint32_t e = e0; e < e1; ++e) mine += ((a.k.smeta[D.p0 + e] & PM_KEPT) && order_key(a.k.sval[D.p0 + e]) == split) ? 1u : 0u;
                 th_eq[threadIdx.x] = mine;
                 __syncthreads();
                 uint32_t eq_before = eq_front;
                 for (uint32_t t = 0; t < threadIdx.x; ++t) eq_before += th_eq[t];
                 __syncthreads();
-                for (uint32_t e = e0; e < e1; ++e) {
-                    const uint32_t me = a.k.smeta[D.p0 + e];
-                    if (!(me & PM_KEPT)) continue;
-                    const uint64_t key = okey(a.k.sval[D.p0 + e]);
-                    uint32_t grp = key < split ? 1u : 2u;
-                    if (key == split) {
-                        grp = eq_before < r ? 1u : 2u;
-                        ++eq_before;
-                        fl |= (me & PM_CLIP) ? 1u : 2u;
-                    }
-                    a.k.smeta[D.p0 + e] = (uint8_t)((me & ~(3u << PM_GRP_SHIFT)) | (grp << PM_GRP_SHIFT));
-                    c_ng[grp]++;
-                    if (!(me & PM_CLIP)) c_ns[grp]++;
-                }
+                fl |= assign_split_groups(a.k.sval + D.p0, a.k.smeta + D.p0, e0, e1, split, r, eq_before, c);
             } else {
                 for_slice_elems(a, D, sl, [&](uint32_t, uint32_t me, int64_t v) {
                     if (!(me & PM_KEPT)) return;
                     const uint32_t grp = (me >> PM_GRP_SHIFT) & 3u;
                     if (grp == 1u || grp == 2u) {
-                        c_ng[grp]++;
-                        if (!(me & PM_CLIP)) c_ns[grp]++;
-                        const uint64_t key = okey(v);
+                        c.add(grp, me);
+                        const uint64_t key = order_key(v);
                         kmin = key < kmin ? key : kmin;
                         kmax = key > kmax ? key : kmax;
                         any = true;
@@ -382,10 +353,7 @@ __device__ __forceinline__ void deep_groups(const DeepArgs &a, const uint32_t nd
             }
         }
         if (!UNPHASED) publish_key_range(D, kmin, kmax, any);  // (unphased: deep_count_kept did, over all kept Calls)
-        for (int g = 1; g <= 2; ++g) {
-            if (c_ng[g]) atomicAdd(&cnt[g], c_ng[g]);
-            if (c_ns[g]) atomicAdd(&cnt[4 + g], c_ns[g]);
-        }
+        c.flush(cnt);
         if (fl) atomicOr(&cnt[0], fl);
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -409,25 +377,19 @@ __device__ __forceinline__ void deep_lower(const DeepArgs &a, const uint32_t nd)
         for (uint32_t g = 1; g <= 2; ++g) {
             const GroupPlan P = plan_of(D, g, a.k.support);
             if (!P.live || (P.M & 1u)) continue;
-            uint64_t t_key = 0;
-            uint32_t lump = 0;
-            if (P.take > 0u) {
-                const SelOut T = chain(D.thr[g], ks.top, -1, P.nc - P.take, 0ull, 0u, ch);
-                t_key = T.key;
-                lump = P.take - (P.nc - T.below - T.eq);
-            }
-            const SelOut H = chain(D.hi[g], ks.top, -1, P.M / 2u, t_key, lump, ch);
+            const ClipThreshold T = threshold_of(D, g, P, ks, ch);
+            const SelOut H = chain(D.hi[g], ks.top, -1, P.M / 2u, T.key, T.lump, ch);
             if (H.below < P.M / 2u) continue;  // rank M / 2 - 1 holds the same value
             if (threadIdx.x == 0) best = 0ull;
             __syncthreads();
             unsigned long long mine = 0ull;
             FOR_MY_SLICES(D) for_slice_elems(a, D, sl, [&](uint32_t, uint32_t me, int64_t v) {
                 if (!(me & PM_KEPT) || ((me >> PM_GRP_SHIFT) & 3u) != g) return;
-                const uint64_t key = okey(v) - ks.kmin;
-                if ((me & PM_CLIP) && !(P.take > 0u && key > t_key)) return;
+                const uint64_t key = order_key(v) - ks.kmin;
+                if (!call_chosen((me & PM_CLIP) != 0u, key, P, T)) return;
                 if (key < H.key && key + 1ull > mine) mine = key + 1ull;  // + 1: 0 means "none"
             });
-            if (blockIdx.x == 0 && lump && t_key < H.key && t_key + 1ull > mine) mine = t_key + 1ull;  // the taken Calls equal to the threshold
+            if (blockIdx.x == 0 && T.lump && T.key < H.key && T.key + 1ull > mine) mine = T.key + 1ull;  // the taken Calls equal to the threshold
             if (mine) atomicMax(&best, mine);
             __syncthreads();
             if (threadIdx.x == 0 && best) atomicMax(&D.lo_max[g], best);
@@ -443,39 +405,21 @@ __device__ __forceinline__ void deep_final(const DeepArgs &a, const uint32_t nd)
     for (uint32_t d = blockIdx.x; d < nd; d += gridDim.x) {
         DeepLocus &D = a.loci[d];
         const KeySpace ks = key_space(D);
-        double out[3] = {qnan_d(), qnan_d(), qnan_d()};
+        double out[3] = {qnan(), qnan(), qnan()};
         for (uint32_t g = 1; g <= 2; ++g) {
             const GroupPlan P = plan_of(D, g, a.k.support);
-            if (!P.live) continue;  // :498-500
-            uint64_t t_key = 0;
-            uint32_t lump = 0;
-            if (P.take > 0u) {
-                const SelOut T = chain(D.thr[g], ks.top, -1, P.nc - P.take, 0ull, 0u, ch);
-                t_key = T.key;
-                lump = P.take - (P.nc - T.below - T.eq);
-            }
-            const SelOut H = chain(D.hi[g], ks.top, -1, P.M / 2u, t_key, lump, ch);
-            const int64_t vhi = okey_inv(H.key + ks.kmin);
-            if (P.M & 1u) out[g] = (double)vhi;  // :520
-            else {
-                const int64_t vlo = H.below < P.M / 2u ? vhi : okey_inv(ld_u64(&D.lo_max[g]) - 1ull + ks.kmin);
-                out[g] = (double)(vlo + vhi) / 2.0;  // :515-518: i64 add, then f64
-            }
-        }
-        if (threadIdx.x == 0) {
-            a.k.phase1[D.j] = out[1];
-            a.k.phase2[D.j] = out[2];
+            if (!P.live) continue;
+            const ClipThreshold T = threshold_of(D, g, P, ks, ch);
+            const SelOut H = chain(D.hi[g], ks.top, -1, P.M / 2u, T.key, T.lump, ch);
+            const int64_t vhi = order_key_inv(H.key + ks.kmin);
+            // the lower median is the upper one again unless exactly M / 2 chosen Calls lie below it (deep_lower)
+            const int64_t vlo = ((P.M & 1u) || H.below < P.M / 2u) ? vhi : order_key_inv(ld_u64(&D.lo_max[g]) - 1ull + ks.kmin);
+            out[g] = median_finish(vlo, vhi, P.M);
         }
         const uint32_t mcount = UNPHASED ? ld_u32(&D.mcount) : 0u;
-        if (UNPHASED && mcount) {  // the split cuts through equal values of mixed kind (:312-314 ambiguity)
-            const uint32_t kh = mcount / 2u;
-            const SelOut so = chain(D.split, ks.top, -1, kh < mcount ? kh : mcount - 1u, 0ull, 0u, ch);
-            const uint32_t r = kh - so.below;
-            if (threadIdx.x == 0 && kh >= 1u && kh < mcount && r >= 1u && ld_u32(&D.flags) == 3u) {  // (the thread that wrote phase1[D.j])
-                atomicAdd((unsigned long long *)&a.k.status->ties, 1ull);
-                if (a.k.locus_flags) a.k.locus_flags[D.j] = INQ_LOCUS_TIE;
-            }
-        }
+        bool tie = false;
+        if (UNPHASED && mcount) tie = split_is_tie(mcount, split_of(D, ks, mcount, ch).below, ld_u32(&D.flags));
+        if (threadIdx.x == 0) write_locus_rows(a.k, D.j, out[1], out[2], tie);
         __syncthreads();
     }
 }
@@ -556,10 +500,7 @@ __global__ __launch_bounds__(256) void locus_call_tail(DeepArgs a) {
     // item < total1: list 1 (257 .. kWalkSplit reads; up to kReduceInPlace the walk has reduced them already); the rest: list 2
     auto item_locus = [&](uint32_t item, uint64_t &j, uint64_t &p0, uint64_t &n) {
         const bool second = item >= total1;
-        const uint32_t *const c = second ? cnt2 : cnt;
-        uint32_t shard = 0, idx = second ? item - total1 : item;
-        while (idx >= c[shard]) idx -= c[shard++];
-        j = a.k.worklist[((uint64_t)(second ? 2 : 1) * kListShards + shard) * a.k.shard_cap + idx];
+        j = second ? worklist_locus(a.k, cnt2, 2u, item - total1) : worklist_locus(a.k, cnt, 1u, item);
         p0 = a.k.locus_pair_off[j];
         n = a.k.locus_pair_off[j + 1] - p0;
     };
@@ -591,9 +532,7 @@ __global__ __launch_bounds__(256) void locus_call_tail(DeepArgs a) {
                     const uint32_t slice = (uint32_t)(((n + gridDim.x - 1) / gridDim.x + 255u) / 256u * 256u);  // at most one slice per workgroup
                     D.j = j, D.p0 = p0, D.n = (uint32_t)n, D.slice = slice, D.n_slices = (uint32_t)((n + slice - 1) / slice);
                 } else {  // (the scratch is sized from n_pairs: cannot happen; such a locus stays NaN and is flagged)
-                    atomicOr(&st->err, ST_RANGE);
-                    a.k.phase1[j] = qnan_d();
-                    a.k.phase2[j] = qnan_d();
+                    write_failed_rows(a.k, j, ST_RANGE);
                 }
             }
             seen += selL.scan[0] + selL.scan[1] + selL.scan[2] + selL.scan[3];
@@ -614,11 +553,7 @@ __global__ __launch_bounds__(256) void locus_call_tail(DeepArgs a) {
         }
         if (n <= 16384u) sort_reduce_locus<UNPHASED, 16384>(a.k, j, p0, (uint32_t)n, sortL, &selL);
         else if (n <= 0xffffffffull) reduce_deep_select<UNPHASED>(a.k, j, p0, (uint32_t)n, selL);
-        else if (threadIdx.x == 0) {  // 2^32 reads at one locus: outside what the scratch indexing covers
-            atomicOr(&st->err, ST_RANGE);
-            a.k.phase1[j] = qnan_d();
-            a.k.phase2[j] = qnan_d();
-        }
+        else if (threadIdx.x == 0) write_failed_rows(a.k, j, ST_RANGE);  // 2^32 reads at one locus: outside what the scratch indexing covers
     }
     if (nd == 0u) return leave();
 
@@ -672,14 +607,13 @@ __global__ __launch_bounds__(256) void locus_call_tail(DeepArgs a) {
 
 size_t deep_select_scratch_bytes(uint64_t n_pairs) {
     const uint64_t cap = n_pairs / kGridSelectMin + 1u;
-    return sizeof(DeepHead) + (size_t)cap * sizeof(DeepLocus);
+    return (size_t)cap * sizeof(DeepLocus);
 }
 
 void launch_locus_tail(const KArgs &k, bool unphased, void *scratch, uint64_t n_pairs, uint32_t grid, hipStream_t s) {
     DeepArgs a;
     a.k = k;
-    a.head = reinterpret_cast<DeepHead *>(scratch);
-    a.loci = scratch ? reinterpret_cast<DeepLocus *>(reinterpret_cast<char *>(scratch) + sizeof(DeepHead)) : nullptr;
+    a.loci = reinterpret_cast<DeepLocus *>(scratch);  // an allocation of its own: aligned to DeepLocus' 128 bytes
     a.cap = scratch ? (uint32_t)(n_pairs / kGridSelectMin + 1u) : 0u;
     if (grid < 1u) grid = 1u;
     if (unphased) hipLaunchKernelGGL(locus_call_tail<true>, dim3(grid), dim3(256), 0, s, a);

@@ -128,30 +128,25 @@ __device__ __forceinline__ double median_in_lanes(const Masks<E> &g, const Masks
                                                   uint32_t support) {
     const int lane = o.lane;
     const uint32_t ng = g.count();
-    if (ng < support) return qnan();  // :498-500
+    if (!group_live(ng, support)) return qnan();
     Masks<E> cm, chosen;
 #pragma unroll
     for (int s = 0; s < E; ++s) {
         cm.m[s] = g.m[s] & clip.m[s];
         chosen.m[s] = g.m[s] & ~clip.m[s];
     }
-    const uint32_t ns = chosen.count();
-    if (ns <= support && cm.any()) {  // :509-513: add the largest (support - ns) clipped values
-        const uint32_t take = support - ns;
-        if (take > 0u) {
-            uint32_t drank[E];
-            o.rank_desc(cm, drank);
+    const GroupPlan P = plan_group(ng, chosen.count(), support);
+    if (P.take > 0u) {  // the largest `take` clipped values join (there are that many: GroupPlan)
+        uint32_t drank[E];
+        o.rank_desc(cm, drank);
 #pragma unroll
-            for (int s = 0; s < E; ++s) chosen.m[s] |= ballot64(((cm.m[s] >> lane) & 1ull) && drank[s] < take);
-        }
+        for (int s = 0; s < E; ++s) chosen.m[s] |= ballot64(((cm.m[s] >> lane) & 1ull) && drank[s] < P.take);
     }
-    const uint32_t M = chosen.count();  // >= 1 because support >= 1
     uint32_t arank[E];
     o.rank_asc(chosen, arank);
-    const int64_t vhi = o.pick(chosen, arank, M / 2u);
-    if (M & 1u) return (double)vhi;  // :520
-    const int64_t vlo = o.pick(chosen, arank, M / 2u - 1u);
-    return (double)(vlo + vhi) / 2.0;  // :515-518
+    const int64_t vhi = o.pick(chosen, arank, P.M / 2u);
+    const int64_t vlo = (P.M & 1u) ? vhi : o.pick(chosen, arank, P.M / 2u - 1u);
+    return median_finish(vlo, vhi, P.M);
 }
 
 // The two medians of one locus from the per-read (val, meta) held in registers.
@@ -176,9 +171,10 @@ __device__ __forceinline__ void reduce_locus_in_lanes(const int64_t (&val)[E], c
             // no soft-clipped call at this locus: every group member is "spanning", so the
             // within-group order is the global order and the medians can be read off `rank`
             auto med = [&](uint32_t base, uint32_t cnt) -> double {
-                if (cnt < support) return qnan();
-                if (cnt & 1u) return (double)o.pick(kept, rank, base + cnt / 2u);
-                return (double)(o.pick(kept, rank, base + cnt / 2u - 1u) + o.pick(kept, rank, base + cnt / 2u)) / 2.0;
+                if (!group_live(cnt, support)) return qnan();
+                const int64_t vhi = o.pick(kept, rank, base + cnt / 2u);
+                const int64_t vlo = (cnt & 1u) ? vhi : o.pick(kept, rank, base + cnt / 2u - 1u);
+                return median_finish(vlo, vhi, cnt);
             };
             out1 = med(0u, ks);
             out2 = med(ks, mcount - ks);
@@ -250,14 +246,7 @@ __device__ __forceinline__ void wave_locus(const KArgs &a, uint64_t j, uint64_t 
         reduce_locus_in_lanes<UNPHASED, true, E>(val, meta, lane, a.support, out1, out2, tie);
     else
         reduce_locus_in_lanes<UNPHASED, false, E>(val, meta, lane, a.support, out1, out2, tie);
-    if (lane == 0) {
-        a.phase1[j] = out1;
-        a.phase2[j] = out2;
-        if (tie) {
-            atomicAdd((unsigned long long *)&a.status->ties, 1ull);
-            if (a.locus_flags) a.locus_flags[j] = INQ_LOCUS_TIE;
-        }
-    }
+    if (lane == 0) write_locus_rows(a, j, out1, out2, tie);
     if (status) atomicOr(&a.status->err, status);  // per lane: index / phase errors belong to the lane's read
 }
 
@@ -283,11 +272,7 @@ __global__ __launch_bounds__(256) void locus_call_small(KArgs a) {
     const uint64_t n64 = p1 - p0;
     if (!status && a.max_reads_hint && n64 > a.max_reads_hint) status |= ST_HINT;  // the caller's promise is broken
     if (status) {
-        if (lane == 0) {
-            atomicOr(&a.status->err, status);
-            a.phase1[j] = qnan();
-            a.phase2[j] = qnan();
-        }
+        if (lane == 0) write_failed_rows(a, j, status);
         return;
     }
     if (n64 > 64ull) {  // deeper locus: listed for locus_call_mid_walk - medium (<= 256 reads), deep, or deeper than kWalkSplit
@@ -309,9 +294,7 @@ __device__ __forceinline__ void medium_part(const KArgs &a, WaveLds (&lds)[4], c
     uint32_t total = 0;
     for (int k = 0; k < kListShards; ++k) total += cnt[k];
     for (uint32_t item = blockIdx.x * 4u + wave; item < total; item += gridDim.x * 4u) {
-        uint32_t shard = 0, idx = item;
-        while (idx >= cnt[shard]) idx -= cnt[shard++];
-        const uint64_t j = a.worklist[(uint64_t)shard * a.shard_cap + idx];
+        const uint64_t j = worklist_locus(a, cnt, 0u, item);
         const uint64_t p0 = a.locus_pair_off[j];
         const int n = (int)(a.locus_pair_off[j + 1] - p0);
         wave_locus<UNPHASED, AUX, kMediumSlots>(a, j, p0, n, a.locus_start[j], a.locus_end[j], lane, lds[wave]);
@@ -383,9 +366,7 @@ __device__ __forceinline__ void walk_part(const KArgs &a, MidLds &lds, const uin
     uint32_t total = 0;
     for (int k = 0; k < kListShards; ++k) total += cnt[k];
     for (uint32_t item = blockIdx.x; item < total; item += gridDim.x) {
-        uint32_t shard = 0, idx = item;
-        while (idx >= cnt[shard]) idx -= cnt[shard++];
-        const uint64_t j = a.worklist[((uint64_t)kListShards + shard) * a.shard_cap + idx];
+        const uint64_t j = worklist_locus(a, cnt, 1u, item);
         const uint64_t p0 = a.locus_pair_off[j];
         const uint32_t n = (uint32_t)(a.locus_pair_off[j + 1] - p0);
         walk_locus<UNPHASED, AUX>(a, b, j, p0, n, 1u, 0u, lane, wave, lds.wave[wave]);
@@ -409,9 +390,7 @@ __device__ __forceinline__ void walk_part(const KArgs &a, MidLds &lds, const uin
     const uint32_t my_group = blockIdx.x / per_item, my_rank = blockIdx.x % per_item;
     if (my_group >= groups) return;  // (gridDim % per_item workgroups are left over)
     for (uint32_t item = my_group; item < total; item += groups) {
-        uint32_t shard = 0, idx = item;
-        while (idx >= cnt2[shard]) idx -= cnt2[shard++];
-        const uint64_t j = a.worklist[((uint64_t)2 * kListShards + shard) * a.shard_cap + idx];
+        const uint64_t j = worklist_locus(a, cnt2, 2u, item);
         const uint64_t p0 = a.locus_pair_off[j];
         const uint64_t n64 = a.locus_pair_off[j + 1] - p0;
         if (n64 > 0xffffffffull) continue;  // (flagged by the tail kernel: outside what the scratch indexing covers)

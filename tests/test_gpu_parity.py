@@ -203,6 +203,35 @@ def test_huge_values(ctx, orc, unphased):
 
 
 @pytest.mark.parametrize("unphased", [False, True])
+@pytest.mark.parametrize("depth", [300, 3000])
+def test_calls_beyond_the_sort_key(ctx, orc, unphased, depth):
+    """A Call of 2^46 or more does not fit the LDS sort's 47-bit key: the sort sees the overflow and the locus ends in one
+    workgroup's radix select.  Depth 300 is reduced in place by the workgroup that walked it, which leaves the deferred-row
+    marker for the tail kernel; depth 3000 overflows in the tail kernel's own sort."""
+    import random
+
+    rng = random.Random(13)
+    big = (1 << 28) - 1
+    n_big = 262_200  # consecutive insertions do not advance the reference: all of them start inside the window
+    start = 10_000
+    bb = B.BatchBuilder(minlen=5, support=3, unphased=unphased)
+    huge = bb.add_read(start - 110, B.encode_cigar([("M", 150)] + [("I", big)] * n_big + [("M", 200)]), phase=1)
+    # every third pair names the huge read (the pair list may name one read many times), the others a small read of their own
+    bb.add_locus(start, start + 100, [
+        huge if k % 3 == 0 else
+        bb.add_read(start - 110, B.encode_cigar([("M", 150), ("I", rng.choice([8, 8, 20, 31])), ("M", 200)]), phase=2)
+        for k in range(depth)])
+    batch = bb.build()
+    rc, got = ctx.call_batch(batch, debug=True)
+    oc, want = orc.call_batch(batch, debug=True)
+    assert rc == oc == 0
+    assert np.abs(want.pair_call).max() >= 1 << 46
+    assert max(want.phase1[0], want.phase2[0]) >= 1 << 46
+    _assert_same(got, want, f"beyond the sort key unphased={unphased} depth={depth}")
+    _other_variants(ctx, batch, want, f"beyond the sort key unphased={unphased} depth={depth}")
+
+
+@pytest.mark.parametrize("unphased", [False, True])
 def test_wide_windows_fill_the_lane_queue(ctx, orc, unphased):
     """Loci tens of kb wide with reads made of thousands of short ops: nearly every lane of every chunk
     starts inside the window, so the LDS window-lane queue drains many times per read (and in the middle
