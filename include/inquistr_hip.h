@@ -147,6 +147,21 @@ typedef struct inq_result {
  * counted in n_tie_loci (unphased only; a phased batch leaves every flag 0), so the flags of a batch sum to its n_tie_loci. */
 #define INQ_LOCUS_TIE 0x01u
 
+/* Per-locus read evidence (the *_evidence entry points below): what stands behind a row's two medians.  Counted on the device from
+ * the per-pair outputs above, behind the locus kernels.  phase1 is NaN exactly when n_group1 < support, phase2 when n_group2 < support
+ * (median_str_length, src/call.rs:498), and n_fetched >= n_kept >= n_group1 + n_group2 >= n_clip. */
+typedef struct inq_locus_evidence {
+    uint32_t n_fetched;  /* pairs with INQ_PAIR_FETCHED: what fetch() yields (src/call.rs:288,338)            */
+    uint32_t n_kept;     /* pairs with INQ_PAIR_KEPT: passed the read filter (:297-302 / :349-355);
+                            phased: reads with HP 0 included, which no group takes                          */
+    uint32_t n_group1;   /* Calls behind phase1. phased: kept reads with HP 1. unphased: n_kept / 2 (:314)  */
+    uint32_t n_group2;   /* Calls behind phase2. phased: kept reads with HP 2. unphased: n_kept - n_kept / 2 */
+    uint32_t n_clip;     /* Calls of group 1 or 2 that are Call::Clip (INQ_PAIR_CLIP)                       */
+    uint32_t reserved;   /* written as 0                                                                    */
+    int64_t call_min;    /* smallest / largest Call value over groups 1 and 2; both 0 when                  */
+    int64_t call_max;    /* n_group1 + n_group2 == 0                                                        */
+} inq_locus_evidence_t;
+
 typedef struct inq_ctx inq_ctx_t;
 
 /* Opens HIP device `device_id` (must be gfx950), creates the library's stream and
@@ -181,6 +196,16 @@ int inq_call_batch_device(inq_ctx_t *ctx, const inq_batch_t *batch, inq_result_t
 int inq_call_batch_flags(inq_ctx_t *ctx, const inq_batch_t *batch, inq_result_t *result, uint8_t *locus_flags);
 int inq_call_batch_device_flags(inq_ctx_t *ctx, const inq_batch_t *batch, inq_result_t *result, uint8_t *d_locus_flags,
                                 void *hip_stream);
+
+/* ... and with per-locus evidence: evidence[j] belongs to locus j of the batch; HOST memory of n_loci records for
+ * inq_call_batch_evidence (locus_flags may be NULL; per-pair outputs the caller did not ask for are kept in context scratch), DEVICE
+ * memory for the device form, which allocates nothing and therefore needs result->pair_call and result->pair_bits when d_evidence is
+ * given (INQ_ERR_ARG otherwise).  NULL = no evidence: exactly the *_flags entries, nothing more is enqueued or allocated.  Two launches
+ * behind the locus kernels write every byte of every record.  A batch that ends in a domain error leaves the evidence unspecified. */
+int inq_call_batch_evidence(inq_ctx_t *ctx, const inq_batch_t *batch, inq_result_t *result, uint8_t *locus_flags,
+                            inq_locus_evidence_t *evidence);
+int inq_call_batch_device_evidence(inq_ctx_t *ctx, const inq_batch_t *batch, inq_result_t *result, uint8_t *d_locus_flags,
+                                   inq_locus_evidence_t *d_evidence, void *hip_stream);
 
 /* Device-side status of the launches since the last inq_ctx_status() call: returns
  * INQ_OK or the first domain error (INQ_ERR_PHASE / _CIGAR_OP / _LOCUS / _RANGE /
@@ -358,6 +383,10 @@ int inq_call_flush_device(inq_ctx_t *ctx, double *d_phase1, double *d_phase2, ui
 int inq_call_flush_flags(inq_ctx_t *ctx, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags);
 int inq_call_flush_device_flags(inq_ctx_t *ctx, double *d_phase1, double *d_phase2, uint64_t cap, const uint32_t *index, uint64_t n_loci,
                                 uint64_t *n_tie_loci, double *ms_call, uint8_t *locus_flags);
+/* inq_call_flush_flags with per-locus evidence: evidence = HOST [n_loci], record j for the j-th locus of the flush (append order);
+ * NULL = exactly inq_call_flush_flags.  The per-pair arrays the counting needs live in context scratch sized from the batch's pairs. */
+int inq_call_flush_evidence(inq_ctx_t *ctx, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
+                            inq_locus_evidence_t *evidence);
 /* Row arrays in device memory for a host that does not link the HIP runtime itself: n f64, filled with quiet NaN (a locus no span
  * holds prints NaN NaN); plain synchronous copies in and out. */
 int inq_dev_alloc_rows(inq_ctx_t *ctx, uint64_t n, double **out);

@@ -43,6 +43,14 @@ typedef struct inq_call_args {
                               * reference itself may print differently), coordinates as given, in the .inq's row order, no header: the
                               * file is itself a valid -R input.  Created / truncated before any device work (a path that cannot be
                               * opened: exit status 1); empty for a phased call; its content is unspecified after a failed call. */
+    const char *evidence_path; /* --evidence: the per-locus read evidence (not a reference argument), NULL = none.  A header line
+                              * `chrom\tbegin\tend\tfetched\tkept\th1\th2\tclipped\tmin\tmax`, then exactly one line per .inq row, in the
+                              * .inq's row order, from the target's record (inq_locus_evidence_t of include/inquistr_hip.h; a target no span
+                              * holds: zeros): the reads fetch() yields, those that pass the read filter, the Calls behind each of the two medians,
+                              * how many of those are Clip, and their smallest and largest value (`.` `.` when h1 + h2 == 0).  Opened like
+                              * ties_path; content unspecified after a failed call.  inq_genotype_repeats and inq_genotype_repeats_devices
+                              * write it; every other entry that takes these arguments (inq_genotype_repeats_rows, inq_run_*, inq_session_*)
+                              * refuses them with exit status 1 when it is set. */
 } inq_call_args_t;
 
 #define INQ_EXIT_OK 0
@@ -227,6 +235,8 @@ int inq_outlier(const inq_outlier_args_t *args, int out_fd, char *errbuf, size_t
 size_t inq_host_format_f64(double v, char *buf, size_t cap);
 size_t inq_host_format_row(const char *chrom, uint32_t start, uint32_t end, double p1, double p2, char *buf, size_t cap);
 size_t inq_host_format_header(const char *sample, char *buf, size_t cap);
+/* one line of the evidence file (inq_call_args_t.evidence_path), without the newline; returns its length as snprintf does */
+size_t inq_host_format_evidence_row(const char *chrom, uint32_t start, uint32_t end, const inq_locus_evidence_t *evidence, char *buf, size_t cap);
 size_t inq_host_sample_name(const char *bam_path, char *buf, size_t cap);
 int inq_host_human_compare(const char *a, const char *b);
 /* RepeatIntervalIterator::from_string against a one-contig length table; 0 ok, 101 panic */

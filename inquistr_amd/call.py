@@ -62,6 +62,7 @@ HOST_ABI_SYMBOLS = (
     "inq_host_format_f64",
     "inq_host_format_row",
     "inq_host_format_header",
+    "inq_host_format_evidence_row",
     "inq_host_sample_name",
     "inq_host_human_compare",
     "inq_host_parse_region",
@@ -94,6 +95,7 @@ class CallArgsC(C.Structure):
         ("device", C.c_int32),
         ("reserved", C.c_int32),
         ("ties_path", C.c_char_p),
+        ("evidence_path", C.c_char_p),
     ]
 
 
@@ -222,6 +224,10 @@ def load():
         L.inq_host_format_row.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_char_p, C.c_size_t]
         L.inq_host_format_header.restype = C.c_size_t
         L.inq_host_format_header.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
+        from .hipcall import LocusEvidenceC
+
+        L.inq_host_format_evidence_row.restype = C.c_size_t
+        L.inq_host_format_evidence_row.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(LocusEvidenceC), C.c_char_p, C.c_size_t]
         L.inq_host_sample_name.restype = C.c_size_t
         L.inq_host_sample_name.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
         L.inq_host_human_compare.restype = C.c_int
@@ -306,7 +312,7 @@ class _Handle:
 
 
 def _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, reference, device=0,
-          frontend=None, ties=None) -> CallArgsC:
+          frontend=None, ties=None, evidence=None) -> CallArgsC:
     a = CallArgsC()
     a.bam = os.fspath(bamp).encode()
     a.region = region.encode() if region is not None else None
@@ -318,19 +324,21 @@ def _args(bamp, region, region_file, minlen, support, threads, unphased, sample_
     a.device = device
     a.reserved = FRONTENDS[frontend]
     a.ties_path = os.fspath(ties).encode() if ties is not None else None
+    a.evidence_path = os.fspath(evidence).encode() if evidence is not None else None
     return a
 
 
 def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str], minlen: int = 5, support: int = 3,
                      threads: int = 1, unphased: bool = False, sample_name: Optional[str] = None,
                      reference: Optional[str] = None, out=None, device: int = 0, frontend: Optional[str] = None,
-                     ties: Optional[str] = None) -> None:
+                     ties: Optional[str] = None, evidence: Optional[str] = None) -> None:
     """src/call.rs:76-86: same parameters, same output; raises CallError instead of exiting.
     frontend: "host" (BGZF inflate + record decode on CPU threads), "device" (inq_call_span: both on the GPU)
     or None (env INQ_FRONTEND, else the library default).
-    ties: path of the tie report (inquistr call --ties): the tie-ambiguous unphased loci as BED, in the rows' order."""
+    ties: path of the tie report (inquistr call --ties): the tie-ambiguous unphased loci as BED, in the rows' order.
+    evidence: path of the evidence file (inquistr call --evidence): one line per row with the read counts behind its two medians."""
     L = load()
-    a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, reference, device, frontend, ties)
+    a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, reference, device, frontend, ties, evidence)
     out = sys.stdout if out is None else out
     out.flush()
     _checked(L.inq_genotype_repeats, C.byref(a), out.fileno())
@@ -338,11 +346,11 @@ def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str
 
 def genotype_repeats_devices(bamp: str, region: Optional[str], region_file: Optional[str], devices, minlen: int = 5, support: int = 3,
                              threads: int = 1, unphased: bool = False, sample_name: Optional[str] = None, out=None,
-                             frontend: Optional[str] = None, ties: Optional[str] = None):
+                             frontend: Optional[str] = None, ties: Optional[str] = None, evidence: Optional[str] = None):
     """inq_genotype_repeats_devices: the same command on several HIP devices from this one process (one thread + one device
     context per entry of `devices`; an ordinal may repeat).  Returns the per-part statistics as a list of dicts."""
     L = load()
-    a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, None, 0, frontend, ties)
+    a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, None, 0, frontend, ties, evidence)
     ids = (C.c_int32 * len(devices))(*[int(d) for d in devices])
     st = (PartStatsC * len(devices))()
     out = sys.stdout if out is None else out

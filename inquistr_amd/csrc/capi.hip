@@ -14,6 +14,7 @@
 #include "../../include/inquistr_hip.h"
 #include "cigar_walk.h"
 #include "ctx.h"
+#include "evidence.h"
 #include "front_kernels.h"
 #include "kernels.h"
 
@@ -321,10 +322,13 @@ static int check_scalars(const inq_batch_t *b, const inq_result_t *r) {
 }
 
 // d_flags: DEVICE [n_loci] per-locus flags (INQ_LOCUS_TIE), or null - then nothing is added to the launch sequence
-static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, uint8_t *d_flags = nullptr) {
+// d_evidence: DEVICE [n_loci] per-locus evidence, or null - then nothing is added to the launch sequence and nothing is allocated
+static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, uint8_t *d_flags = nullptr,
+                         inq_locus_evidence_t *d_evidence = nullptr) {
     if (!c) return INQ_ERR_ARG;
     int rc = check_scalars(b, r);
     if (rc != INQ_OK) return rc;
+    if (d_evidence && b->n_pairs && (!r->pair_call || !r->pair_bits)) return INQ_ERR_ARG;  // the counting reads both
     if (((uintptr_t)b->cigar & 15u) || ((uintptr_t)b->reads & 15u)) return INQ_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
@@ -340,6 +344,9 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     const uint32_t hint = c->call_hint ? c->call_hint : c->max_reads_hint;
     const bool deep_possible = b->n_pairs > kGridSelectMin && !(hint && hint <= kGridSelectMin);
     if (deep_possible && (rc = ensure(c, c->deep, deep_select_scratch_bytes(b->n_pairs))) != INQ_OK) return rc;
+    // evidence: the slice list of the loci one wave does not count; no list and no second launch when the depth hint rules them out
+    const uint64_t ev_list_cap = d_evidence && b->n_pairs > kEvidenceWaveMax && !(hint && hint <= kEvidenceWaveMax) ? evidence_list_cap(b->n_pairs) : 0;
+    if (d_evidence && (rc = ensure(c, c->evwork, evidence_scratch_bytes(ev_list_cap))) != INQ_OK) return rc;
 
     KArgs a;
     a.cigar4 = (const uint4 *)b->cigar;
@@ -374,8 +381,24 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     EvTriple *ev;
     if ((rc = timing_begin(c, s, &ev)) != INQ_OK) return rc;
     if (d_flags) HIP_TRY(c, hipMemsetAsync(d_flags, 0, (size_t)b->n_loci, s));  // the kernels store tie loci only
+    if (d_evidence) HIP_TRY(c, hipMemsetAsync(c->evwork.p, 0, sizeof(EvidenceWork), s));  // the slice list starts empty
     launch_locus_call(a, b->unphased != 0, nt, grid_small, c->grid_medium, c->grid_tail, s, ev ? ev->e1 : nullptr, deep_possible ? c->deep.p : nullptr);
     HIP_TRY(c, hipGetLastError());
+    if (d_evidence) {
+        EvidenceArgs ea;
+        ea.locus_pair_off = b->locus_pair_off;
+        ea.pair_bits = r->pair_bits;
+        ea.pair_call = r->pair_call;
+        ea.pair_read = b->pair_read;
+        ea.read_words = (const uint32_t *)b->reads;
+        ea.n_reads = b->n_reads, ea.n_pairs = b->n_pairs, ea.n_loci = b->n_loci;
+        ea.evidence = d_evidence;
+        ea.work = (EvidenceWork *)c->evwork.p;
+        ea.list = (EvidenceSlice *)((char *)c->evwork.p + sizeof(EvidenceWork));
+        ea.list_cap = ev_list_cap;
+        launch_evidence(ea, b->unphased != 0, c->n_cus * 4u, s);
+        HIP_TRY(c, hipGetLastError());
+    }
     if (ev) HIP_TRY(c, hipEventRecord(ev->e2, s));
     return INQ_OK;
 }
@@ -385,7 +408,12 @@ int inq_call_batch_device(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, v
 }
 
 int inq_call_batch_device_flags(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *d_locus_flags, void *hip_stream) {
-    return guarded([&] { return enqueue_batch(c, b, r, hip_stream, d_locus_flags); });
+    return inq_call_batch_device_evidence(c, b, r, d_locus_flags, nullptr, hip_stream);
+}
+
+int inq_call_batch_device_evidence(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *d_locus_flags, inq_locus_evidence_t *d_evidence,
+                                   void *hip_stream) {
+    return guarded([&] { return enqueue_batch(c, b, r, hip_stream, d_locus_flags, d_evidence); });
 }
 
 int inq_ctx_status(inq_ctx_t *c, uint64_t *n_tie_loci) {
@@ -399,7 +427,7 @@ int inq_ctx_status(inq_ctx_t *c, uint64_t *n_tie_loci) {
     return status_to_code(c->h_status->err);
 }
 
-static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *h_flags) {
+static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *h_flags, inq_locus_evidence_t *h_evidence) {
     if (!c) return INQ_ERR_ARG;
     int rc = check_scalars(b, r);
     if (rc != INQ_OK) return rc;
@@ -435,18 +463,23 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
     }
     if ((rc = ensure(c, c->p1, (size_t)b->n_loci * 8)) != INQ_OK) return rc;
     if ((rc = ensure(c, c->p2, (size_t)b->n_loci * 8)) != INQ_OK) return rc;
-    if (r->pair_call && (rc = ensure(c, c->pcall, (size_t)b->n_pairs * 8)) != INQ_OK) return rc;
-    if (r->pair_bits && (rc = ensure(c, c->pbits, (size_t)b->n_pairs)) != INQ_OK) return rc;
+    // (the evidence is counted from the per-pair outputs: they are kept in scratch also when the caller does not want them)
+    const bool want_call = r->pair_call || h_evidence, want_bits = r->pair_bits || h_evidence;
+    if (want_call && (rc = ensure(c, c->pcall, (size_t)b->n_pairs * 8)) != INQ_OK) return rc;
+    if (want_bits && (rc = ensure(c, c->pbits, (size_t)b->n_pairs)) != INQ_OK) return rc;
     if (h_flags && (rc = ensure(c, c->lflags, (size_t)b->n_loci)) != INQ_OK) return rc;
+    if (h_evidence && (rc = ensure(c, c->levidence, (size_t)b->n_loci * sizeof(inq_locus_evidence_t))) != INQ_OK) return rc;
 
     DevBatch d = device_batch(c->cigar.p, c->reads.p, c->pair_read.p, c->off.p, c->lstart.p, c->lend.p, b->n_reads, b->n_cigar_words,
                               b->n_pairs, b->n_loci, b->minlen, b->support, b->unphased, c->p1.p, c->p2.p,
-                              r->pair_call ? c->pcall.p : nullptr, r->pair_bits ? c->pbits.p : nullptr);
+                              want_call ? c->pcall.p : nullptr, want_bits ? c->pbits.p : nullptr);
     const inq_result_t &dr = d.r;
     c->call_hint = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(max_reads, 1), 0xffffffffull);  // skips the deep-locus launches when no locus needs them
     uint8_t *d_flags = h_flags ? (uint8_t *)c->lflags.p : nullptr;
-    if ((rc = enqueue_batch(c, &d.b, &d.r, s, d_flags)) != INQ_OK) return rc;
+    inq_locus_evidence_t *d_evidence = h_evidence ? (inq_locus_evidence_t *)c->levidence.p : nullptr;
+    if ((rc = enqueue_batch(c, &d.b, &d.r, s, d_flags, d_evidence)) != INQ_OK) return rc;
     if (h_flags) HIP_TRY(c, hipMemcpyAsync(h_flags, d_flags, (size_t)b->n_loci, hipMemcpyDeviceToHost, s));
+    if (h_evidence) HIP_TRY(c, hipMemcpyAsync(h_evidence, d_evidence, (size_t)b->n_loci * sizeof(inq_locus_evidence_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(r->phase1, dr.phase1, (size_t)b->n_loci * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(r->phase2, dr.phase2, (size_t)b->n_loci * 8, hipMemcpyDeviceToHost, s));
     if (r->pair_call && b->n_pairs)
@@ -463,7 +496,11 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
 int inq_call_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r) { return inq_call_batch_flags(c, b, r, nullptr); }
 
 int inq_call_batch_flags(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *locus_flags) {
-    return guarded([&] { return call_batch_impl(c, b, r, locus_flags); });
+    return inq_call_batch_evidence(c, b, r, locus_flags, nullptr);
+}
+
+int inq_call_batch_evidence(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *locus_flags, inq_locus_evidence_t *evidence) {
+    return guarded([&] { return call_batch_impl(c, b, r, locus_flags, evidence); });
 }
 
 static int outlier_rows_impl(inq_ctx_t *c, const float *values, const uint32_t *row_len, uint64_t n_rows, uint32_t stride,
@@ -708,7 +745,8 @@ void inq_free_pinned(void *p) {
 
 }  // extern "C"
 
-int inq::call_batch_device_impl(inq_ctx *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, uint8_t *d_locus_flags) {
-    return enqueue_batch(c, b, r, hip_stream, d_locus_flags);
+int inq::call_batch_device_impl(inq_ctx *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, uint8_t *d_locus_flags,
+                                inq_locus_evidence_t *d_evidence) {
+    return enqueue_batch(c, b, r, hip_stream, d_locus_flags, d_evidence);
 }
 

@@ -564,7 +564,9 @@ struct FlushToDevice {
     uint64_t cap;           // entries of d1 / d2
 };
 // h_flags: HOST [n_loci] per-locus flags (INQ_LOCUS_TIE) in append order, brought down with the rows through the same staging; may be null
-int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_call, const FlushToDevice *dev = nullptr, uint8_t *h_flags = nullptr) {
+// h_evidence: HOST [n_loci] per-locus evidence in append order; may be null (and is, where the rows stay on the device)
+int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_call, const FlushToDevice *dev = nullptr, uint8_t *h_flags = nullptr,
+                    inq_locus_evidence_t *h_evidence = nullptr) {
     if (!c || !r) return INQ_ERR_ARG;
     SpanState *S;
     int rc;
@@ -590,9 +592,16 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     if ((rc = ensure(c, S->p2, nl * 8)) != INQ_OK) return rc;
     if (h_flags && (rc = ensure(c, c->lflags, nl)) != INQ_OK) return rc;
     uint8_t *const d_flags = h_flags ? (uint8_t *)c->lflags.p : nullptr;
+    // the evidence is counted from the per-pair outputs, which a flush otherwise does not produce: context scratch sized from the batch
+    if (h_evidence) {
+        if ((rc = ensure(c, c->pcall, A.n_pairs * 8)) != INQ_OK) return rc;
+        if ((rc = ensure(c, c->pbits, A.n_pairs)) != INQ_OK) return rc;
+        if ((rc = ensure(c, c->levidence, nl * sizeof(inq_locus_evidence_t))) != INQ_OK) return rc;
+    }
+    inq_locus_evidence_t *const d_evidence = h_evidence ? (inq_locus_evidence_t *)c->levidence.p : nullptr;
     if ((rc = ensure_row_staging(c, S, nl, 2 * nl + (h_flags ? (nl + 7) / 8 : 0))) != INQ_OK) return rc;  // the rows, then the flags
     DevBatch d = device_batch(A.cigar.p, A.reads.p, A.pair_read.p, A.off.p, A.lstart.p, A.lend.p, A.n_reads, A.n_units * 4, A.n_pairs, nl,
-                              A.minlen, A.support, A.unphased, S->p1.p, S->p2.p);
+                              A.minlen, A.support, A.unphased, S->p1.p, S->p2.p, h_evidence ? c->pcall.p : nullptr, h_evidence ? c->pbits.p : nullptr);
     inq_batch_t &db = d.b;
     inq_result_t &dr = d.r;
     c->call_hint = std::max<uint32_t>(A.max_reads, 1u);
@@ -603,7 +612,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     } spent{A};
     const uint64_t n_reads_all = A.n_reads, n_units_all = A.n_units, n_pairs_all = A.n_pairs;
     HIP_TRY(c, hipEventRecord(S->ev[4], s));
-    if ((rc = call_batch_device_impl(c, &db, &dr, s, d_flags)) != INQ_OK) return rc;
+    if ((rc = call_batch_device_impl(c, &db, &dr, s, d_flags, d_evidence)) != INQ_OK) return rc;
     HIP_TRY(c, hipEventRecord(S->ev[5], s));
     // measurement builds only (make DEBUG_ENV=1; tools/profile_cli_locus.sh): the shipped library reads nothing here
     if (const char *again = debug_env("INQ_CALL_AGAIN"); again && again[0] == '1') {
@@ -628,6 +637,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
         HIP_TRY(c, hipMemcpyAsync(S->h_rows + nl, dr.phase2, nl * 8, hipMemcpyDeviceToHost, s));
     }
     if (h_flags) HIP_TRY(c, hipMemcpyAsync(S->h_rows + 2 * nl, d_flags, nl, hipMemcpyDeviceToHost, s));
+    if (h_evidence) HIP_TRY(c, hipMemcpyAsync(h_evidence, d_evidence, nl * sizeof(inq_locus_evidence_t), hipMemcpyDeviceToHost, s));
     if ((rc = status_readback(c, &S->h->ks, s)) != INQ_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
     if (h_flags) std::memcpy(h_flags, S->h_rows + 2 * nl, nl);
@@ -802,7 +812,12 @@ int inq_call_flush(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *
 }
 
 int inq_call_flush_flags(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags) {
-    return guarded([&] { return call_flush_impl(c, result, n_loci, ms_call, nullptr, locus_flags); });
+    return inq_call_flush_evidence(c, result, n_loci, ms_call, locus_flags, nullptr);
+}
+
+int inq_call_flush_evidence(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
+                            inq_locus_evidence_t *evidence) {
+    return guarded([&] { return call_flush_impl(c, result, n_loci, ms_call, nullptr, locus_flags, evidence); });
 }
 
 int inq_call_flush_device(inq_ctx_t *c, double *d_phase1, double *d_phase2, uint64_t cap, const uint32_t *index, uint64_t n_loci, uint64_t *n_tie_loci,

@@ -74,6 +74,9 @@ ABI_SYMBOLS = (
     "inq_call_batch_device_flags",
     "inq_call_flush_flags",
     "inq_call_flush_device_flags",
+    "inq_call_batch_evidence",
+    "inq_call_batch_device_evidence",
+    "inq_call_flush_evidence",
 )
 
 
@@ -129,6 +132,25 @@ class SpanStatsC(C.Structure):
         ("ms_join", C.c_double),
         ("ms_call", C.c_double),
     ]
+
+
+class LocusEvidenceC(C.Structure):
+    """inq_locus_evidence_t"""
+
+    _fields_ = [
+        ("n_fetched", C.c_uint32),
+        ("n_kept", C.c_uint32),
+        ("n_group1", C.c_uint32),
+        ("n_group2", C.c_uint32),
+        ("n_clip", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("call_min", C.c_int64),
+        ("call_max", C.c_int64),
+    ]
+
+
+EVIDENCE_DTYPE = np.dtype([("n_fetched", "<u4"), ("n_kept", "<u4"), ("n_group1", "<u4"), ("n_group2", "<u4"), ("n_clip", "<u4"),
+                           ("reserved", "<u4"), ("call_min", "<i8"), ("call_max", "<i8")])
 
 
 def scan_bgzf(data) -> np.ndarray:
@@ -211,6 +233,12 @@ def load(path: Optional[str] = None):
     L.inq_call_batch_flags.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp]
     L.inq_call_batch_device_flags.restype = C.c_int
     L.inq_call_batch_device_flags.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp, vp]
+    L.inq_call_batch_evidence.restype = C.c_int
+    L.inq_call_batch_evidence.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp, vp]
+    L.inq_call_batch_device_evidence.restype = C.c_int
+    L.inq_call_batch_device_evidence.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp, vp, vp]
+    L.inq_call_flush_evidence.restype = C.c_int
+    L.inq_call_flush_evidence.argtypes = [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double), vp, vp]
     L.inq_ctx_status.restype = C.c_int
     L.inq_ctx_status.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.inq_ctx_timing_enable.restype = C.c_int
@@ -352,6 +380,27 @@ class Context:
             self._raise(rc)
         return rc, res, flags[: batch.n_loci]
 
+    def call_batch_evidence(self, batch: Batch, debug: bool = False, check: bool = True, flags: bool = True):
+        """inq_call_batch_evidence: (code, Result, per-locus flags or None, per-locus evidence as an EVIDENCE_DTYPE array)."""
+        res = Result.alloc(batch, debug=debug)
+        fl = np.full(max(batch.n_loci, 1), 0xFF, dtype=np.uint8) if flags else None
+        ev = np.full(max(batch.n_loci, 1) * EVIDENCE_DTYPE.itemsize, 0xFF, dtype=np.uint8)  # (0xFF: a byte the call did not write shows)
+        bc, rc_ = batch.as_c(), res.as_c()
+        rc = self._L.inq_call_batch_evidence(self._h, C.byref(bc), C.byref(rc_), fl.ctypes.data if flags else None, ev.ctypes.data)
+        res.n_tie_loci = int(rc_.n_tie_loci)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        return rc, res, (fl[: batch.n_loci] if flags else None), ev.view(EVIDENCE_DTYPE)[: batch.n_loci]
+
+    def call_batch_device_evidence(self, bc: InqBatchC, rc_: InqResultC, d_flags: Optional[int], d_evidence: Optional[int],
+                                   stream: Optional[int] = None, check: bool = True) -> int:
+        """inq_call_batch_device_evidence: every pointer is a device pointer (d_flags / d_evidence may be None); enqueue only."""
+        rc = self._L.inq_call_batch_device_evidence(self._h, C.byref(bc), C.byref(rc_), C.c_void_p(d_flags or 0), C.c_void_p(d_evidence or 0),
+                                                    C.c_void_p(stream or 0))
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        return rc
+
     def call_batch_device(self, bc: InqBatchC, rc_: InqResultC, stream: Optional[int] = None) -> None:
         """Device-resident entry: pointers in bc / rc_ are device pointers; enqueue only."""
         rc = self._L.inq_call_batch_device(self._h, C.byref(bc), C.byref(rc_), C.c_void_p(stream or 0))
@@ -475,6 +524,20 @@ class Context:
         if rc != INQ_OK and check:
             self._raise(rc)
         return rc, p1, p2, int(res.n_tie_loci), float(ms.value), flags[:n]
+
+    def call_flush_evidence(self, check: bool = True):
+        """inq_call_flush_evidence: as call_flush_flags, plus the per-locus evidence (EVIDENCE_DTYPE, append order) as a seventh element."""
+        n = self.deferred_loci
+        p1 = np.full(n, np.nan)
+        p2 = np.full(n, np.nan)
+        flags = np.full(max(n, 1), 0xFF, dtype=np.uint8)
+        ev = np.full(max(n, 1) * EVIDENCE_DTYPE.itemsize, 0xFF, dtype=np.uint8)
+        res = InqResultC(p1.ctypes.data, p2.ctypes.data, None, None, 0)
+        ms = C.c_double(0.0)
+        rc = self._L.inq_call_flush_evidence(self._h, C.byref(res), n, C.byref(ms), flags.ctypes.data, ev.ctypes.data)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        return rc, p1, p2, int(res.n_tie_loci), float(ms.value), flags[:n], ev.view(EVIDENCE_DTYPE)[:n]
 
     def span_fetch_batch(self, stats: "SpanStatsC", n_loci: int):
         """The batch the last call_span built on the device, as host arrays (cigar, reads, pair_read, locus_pair_off)."""

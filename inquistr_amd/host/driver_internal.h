@@ -299,23 +299,45 @@ struct SessionHooks {
     // collected, the locus kernels run without flags); ties_fd >= 0: a text call writes the report there, in the .inq's row order
     uint8_t *ties_out = nullptr;
     int ties_fd = -1;
+    // the evidence file (inq_call_args_t::evidence_path), on the same rails: the record of target k of the call -> evidence_out[k]
+    // (null: not collected, nothing is added to the launch sequence); evidence_fd >= 0: a text call writes the file there
+    inq_locus_evidence_t *evidence_out = nullptr;
+    int evidence_fd = -1;
     // the caller owns the context AND the process ends with this call (fast_exit()): a pipeline the call made itself is left to the
     // operating system after a clean run (unmapping a GB of touched pages takes ~0.1 s), as the caller then leaves its context
     bool process_is_leaving = false;
 };
 
-// the tie report's file: opened (created / truncated) before any device work, closed with the call
-struct TiesFile {
+// a file a call writes beside its .inq (the tie report, the evidence file): opened (created / truncated) before any device work,
+// closed with the call
+struct ReportFile {
     int fd = -1;
-    TiesFile() = default;
-    TiesFile(const TiesFile &) = delete;
-    TiesFile &operator=(const TiesFile &) = delete;
-    ~TiesFile() {
+    ReportFile() = default;
+    ReportFile(const ReportFile &) = delete;
+    ReportFile &operator=(const ReportFile &) = delete;
+    ~ReportFile() {
         if (fd >= 0) ::close(fd);
     }
-    // path may be null (no report): INQ_EXIT_OK; a path that cannot be opened: INQ_EXIT_ERROR and a message that names it
-    int open(const char *path, std::string &msg);
+    // path may be null (no file): INQ_EXIT_OK; a path that cannot be opened: INQ_EXIT_ERROR and a message that names `what` and it
+    int open(const char *path, const char *what, std::string &msg);
 };
+constexpr const char *kTiesWhat = "the tie report", *kEvidenceWhat = "the evidence file";
+// the two files of a text call (inq_call_args_t::ties_path, ::evidence_path)
+struct CallReports {
+    ReportFile ties, evidence;
+    int open(const inq_call_args_t &a, std::string &msg) {
+        const int rc = ties.open(a.ties_path, kTiesWhat, msg);
+        return rc != INQ_EXIT_OK ? rc : evidence.open(a.evidence_path, kEvidenceWhat, msg);
+    }
+    void to(SessionHooks &hooks) const { hooks.ties_fd = ties.fd, hooks.evidence_fd = evidence.fd; }
+};
+// an entry that returns rows or keeps its context for many files writes no evidence file and says so (INQ_EXIT_ERROR) instead of
+// ignoring the request
+inline int refuse_evidence(const inq_call_args_t *a, const char *who, std::string &msg) {
+    if (!a || !a->evidence_path) return INQ_EXIT_OK;
+    msg = std::string("--evidence (evidence_path) is not supported by ") + who + ": use inquistr call / inq_genotype_repeats";
+    return INQ_EXIT_ERROR;
+}
 
 // rows instead of text: the targets named by idx[] (positions in the parsed target list) are called, their rows go to p1 / p2
 struct RowsOut {
@@ -327,28 +349,32 @@ struct RowsOut {
     uint64_t dcap = 0;
 };
 
-// src[j] -> dst[index[j]]: rows and tie flags of a batch, a flush or a device part into their targets' places
+// src[j] -> dst[index[j]]: rows, tie flags and evidence of a batch, a flush or a device part into their targets' places
 template <class T>
 inline void scatter(const T *src, const uint32_t *index, size_t n, T *dst) {
     for (size_t j = 0; j < n; ++j) dst[index[j]] = src[j];
 }
-// the result buffers of one device call over n loci (rows start as NaN, flags as 0), and their way into the call's arrays
+// the result buffers of one device call over n loci (rows start as NaN, flags and evidence as 0), and their way into the call's arrays
 struct BatchRows {
     std::vector<double> b1, b2;
     std::vector<uint8_t> bt;
+    std::vector<inq_locus_evidence_t> be;
     inq_result_t res;
-    uint8_t *flags = nullptr;  // null: the call collects none
-    void begin(size_t n, bool want_flags) {
+    uint8_t *flags = nullptr;                 // null: the call collects none
+    inq_locus_evidence_t *evidence = nullptr;  // null: the call collects none
+    void begin(size_t n, bool want_flags, bool want_evidence) {
         b1.assign(n, NAN), b2.assign(n, NAN);
         std::memset(&res, 0, sizeof res);
         res.phase1 = b1.data(), res.phase2 = b2.data();
-        flags = nullptr;
+        flags = nullptr, evidence = nullptr;
         if (want_flags) bt.assign(n, 0), flags = bt.data();
+        if (want_evidence) be.assign(n, inq_locus_evidence_t{}), evidence = be.data();
     }
-    // p1 null: the rows went elsewhere (device memory); ties is asked for only where flags were
-    void scatter_to(const uint32_t *index, double *p1, double *p2, uint8_t *ties) const {
+    // p1 null: the rows went elsewhere (device memory); ties / ev are asked for only where flags / evidence were
+    void scatter_to(const uint32_t *index, double *p1, double *p2, uint8_t *ties, inq_locus_evidence_t *ev) const {
         if (p1) scatter(b1.data(), index, b1.size(), p1), scatter(b2.data(), index, b2.size(), p2);
         if (flags) scatter(flags, index, bt.size(), ties);
+        if (evidence) scatter(evidence, index, be.size(), ev);
     }
 };
 
@@ -365,25 +391,30 @@ int run_device_front(const inq_call_args_t *args, const CallView &V, AsyncCtx &a
                      char *errbuf, size_t errcap, double *t_front, double *t_dev, const SessionHooks &hooks = SessionHooks());
 int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, int out_fd, char *errbuf, size_t errcap, const RowsOut &rows,
                       std::chrono::steady_clock::time_point t_start, const SessionHooks &hooks = SessionHooks());
-// ties / ties_fd (may be null / < 0): the tie report of the same rows goes to ties_fd, in the same order
+// ties / ties_fd, evidence / evidence_fd (may be null / < 0): the tie report and the evidence file of the same rows go there, in the
+// same order
 int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, const std::string &sample, const double *p1, const double *p2,
-               int out_fd, char *errbuf, size_t errcap, const uint8_t *ties = nullptr, int ties_fd = -1);
+               int out_fd, char *errbuf, size_t errcap, const uint8_t *ties = nullptr, int ties_fd = -1,
+               const inq_locus_evidence_t *evidence = nullptr, int evidence_fd = -1);
 // the order of the .inq's rows: BED order for -t 1, (human_compare(chrom), start) for -t >= 2 (src/call.rs:33-38,141)
 std::vector<uint32_t> row_order(uint64_t threads, const std::vector<RepeatInterval> &targets);
 // the tie report: `chrom\tbegin\tend\n` for every target order[k] with a flag set
 int write_ties(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const uint8_t *ties, int fd, char *errbuf,
                size_t errcap);
+// the evidence file: the header, then one line for every target order[k]
+int write_evidence(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const inq_locus_evidence_t *evidence, int fd,
+                   char *errbuf, size_t errcap);
 int partition_prepared(Prepared &P, uint64_t world, uint32_t *order, uint64_t *cuts);
 
 struct OwnedArgs {
     inq_call_args_t a;
-    std::string bam, region, region_file, sample_name, reference, ties_path;
+    std::string bam, region, region_file, sample_name, reference, ties_path, evidence_path;
     explicit OwnedArgs(const inq_call_args_t &src) : a(src) {
         auto own = [](const char *&p, std::string &keep) {
             if (p) keep = p, p = keep.c_str();
         };
         own(a.bam, bam), own(a.region, region), own(a.region_file, region_file), own(a.sample_name, sample_name), own(a.reference, reference);
-        own(a.ties_path, ties_path);
+        own(a.ties_path, ties_path), own(a.evidence_path, evidence_path);
     }
     OwnedArgs(const OwnedArgs &) = delete;
 };

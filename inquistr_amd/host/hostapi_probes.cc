@@ -20,6 +20,12 @@ size_t inq_host_format_row(const char *chrom, uint32_t start, uint32_t end, doub
 size_t inq_host_format_header(const char *sample, char *buf, size_t cap) {
     return (size_t)std::snprintf(buf, cap, "%s", format_header(sample).c_str());
 }
+size_t inq_host_format_evidence_row(const char *chrom, uint32_t start, uint32_t end, const inq_locus_evidence_t *evidence, char *buf, size_t cap) {
+    if (!chrom || !evidence) return 0;
+    std::string s;
+    append_evidence_row(s, chrom, start, end, *evidence);
+    return (size_t)std::snprintf(buf, cap, "%s", s.c_str());
+}
 size_t inq_host_sample_name(const char *p, char *buf, size_t cap) {
     return (size_t)std::snprintf(buf, cap, "%s", sample_name_from_path(p).c_str());
 }

@@ -146,6 +146,17 @@ std::string format_header(const std::string &sample) {
     return "chromosome\tbegin\tend\t" + sample + "_H1\t" + sample + "_H2";
 }
 
+const char *const kEvidenceHeader = "chrom\tbegin\tend\tfetched\tkept\th1\th2\tclipped\tmin\tmax";
+
+void append_evidence_row(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_locus_evidence_t &e) {
+    out += chrom;
+    for (const uint32_t v : {start, end, e.n_fetched, e.n_kept, e.n_group1, e.n_group2, e.n_clip}) out += '\t', out += std::to_string(v);
+    if ((uint64_t)e.n_group1 + e.n_group2 == 0)
+        out += "\t.\t.";  // no Call behind either median: nothing to take extremes of
+    else
+        out += '\t', out += std::to_string(e.call_min), out += '\t', out += std::to_string(e.call_max);
+}
+
 static void erase_all(std::string &s, const std::string &pat) {
     size_t p = 0;
     while ((p = s.find(pat, p)) != std::string::npos) s.erase(p, pat.size());

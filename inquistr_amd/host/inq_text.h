@@ -3,6 +3,8 @@
 #include <cstdint>
 #include <string>
 
+#include "../../include/inquistr_hip.h"  // inq_locus_evidence_t
+
 namespace inqhost {
 
 // Rust `{}` of an f64 that is an integer, a half, or NaN (src/call.rs:57-65 prints phase1/phase2 so)
@@ -17,6 +19,9 @@ void append_row(std::string &out, const std::string &chrom, uint32_t start, uint
 void append_f64(std::string &out, double v);
 // src/call.rs:101
 std::string format_header(const std::string &sample);
+// the evidence file (inq_call_args_t::evidence_path; not a reference output): its header, and the line of one target
+extern const char *const kEvidenceHeader;
+void append_evidence_row(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_locus_evidence_t &e);
 // src/call.rs:91-100: file_stem, then every ".bam" and ".cram" removed
 std::string sample_name_from_path(const std::string &bam_path);
 // [3P] human_sort::compare as used by Genotype::cmp (src/call.rs:33-38): <0, 0, >0

@@ -30,6 +30,7 @@ static void usage(FILE *f) {
         "      --devices <N,N,...>          several HIP devices: the loci are split among them by BAM bytes, same output\n"
         "      --ctx-option <KEY=VALUE>     a device-context option (include/inquistr_hip.h, inq_ctx_set_option), repeatable\n"
         "      --ties <FILE>                write the loci whose unphased split is tie-ambiguous there, as BED (empty when phased)\n"
+        "      --evidence <FILE>            write the read evidence behind every row there: fetched, kept, h1, h2, clipped, min, max\n"
         "  -h, --help                       Print help\n",
         f);
 }
@@ -261,6 +262,7 @@ int main(int argc, char **argv) {
         else if (key == "--reference") a.reference = val();
         else if (key == "--device") a.device = (int32_t)num(val(), "--device");
         else if (key == "--ties") a.ties_path = val();
+        else if (key == "--evidence") a.evidence_path = val();
         else if (key == "--devices") {
             const std::string list = val();
             for (size_t b = 0; b <= list.size();) {
@@ -320,6 +322,10 @@ int main(int argc, char **argv) {
         return leave(rc, nullptr);
     }
     if (const char *server_env = std::getenv("INQ_SERVER"); server_env && *server_env) {
+        if (a.evidence_path) {  // a server's calls run on a session, which writes no evidence file: said here, before a server is looked for
+            std::fputs("error: '--evidence <FILE>' cannot be used with INQ_SERVER set: a server does not write the evidence file\n", stderr);
+            return 2;
+        }
         // INQ_SERVER=auto: this user's server for the device, started (detached; it leaves after INQ_SERVER_IDLE seconds without a
         // call, 120 by default) when none is running - the first call of a batch pays the start-up, the others find the context there
         std::string server_path = server_env;

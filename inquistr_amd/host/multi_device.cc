@@ -91,8 +91,9 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
         }
     const auto t_start = Clock::now();
     std::string msg;
-    TiesFile tf;
-    if (tf.open(args->ties_path, msg) != INQ_EXIT_OK) {
+    CallReports files;
+    const ReportFile &tf = files.ties, &ef = files.evidence;
+    if (files.open(*args, msg) != INQ_EXIT_OK) {
         set_err(errbuf, errcap, msg);
         return INQ_EXIT_ERROR;
     }
@@ -108,6 +109,7 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
     std::vector<PartStats> pst(n_devices);
     // the tie report: each part's flags are scattered like its rows (the parts' target sets are disjoint)
     std::vector<uint8_t> ties(tf.fd >= 0 ? P.targets.size() : 0, 0);
+    std::vector<inq_locus_evidence_t> evidence(ef.fd >= 0 ? P.targets.size() : 0, inq_locus_evidence_t{});  // ... and so is its evidence
     std::vector<double> p1, p2, part_s;
     std::vector<uint32_t> order;
     std::vector<uint64_t> cuts;
@@ -122,10 +124,13 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
         hooks.process_is_leaving = fast_exit();  // the contexts are this call's own, and so is the process's end (`call --devices`)
         std::vector<uint8_t> part_ties(tf.fd >= 0 ? n : 0, 0);
         if (tf.fd >= 0) hooks.ties_out = part_ties.data();
+        std::vector<inq_locus_evidence_t> part_evidence(ef.fd >= 0 ? n : 0, inq_locus_evidence_t{});
+        if (ef.fd >= 0) hooks.evidence_out = part_evidence.data();
         // (the runtime threads of this part prefer the NUMA node of ITS device: genotype_prepared's helpers bind per thread)
         const int prc = genotype_prepared(&oa.a, *actx[r], P, -1, err, cap, ro, t_start, hooks);
         actx[r]->leak = prc == INQ_EXIT_OK && hooks.process_is_leaving;  // only after a clean run: error paths tear down normally
         if (prc == INQ_EXIT_OK && tf.fd >= 0) scatter(part_ties.data(), idx, n, ties.data());
+        if (prc == INQ_EXIT_OK && ef.fd >= 0) scatter(part_evidence.data(), idx, n, evidence.data());
         return prc;
     };
     rc = run_parts(P, n_devices, fn, p1, p2, order, cuts, &part_rc, &part_s, errbuf, errcap);
@@ -142,7 +147,8 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
             o.front = pst[r].front, o.io_threads = pst[r].io_threads;
         }
     if (rc != INQ_EXIT_OK) return rc;
-    return write_rows(args->threads, P.targets, P.sample, p1.data(), p2.data(), out_fd, errbuf, errcap, tf.fd >= 0 ? ties.data() : nullptr, tf.fd);
+    return write_rows(args->threads, P.targets, P.sample, p1.data(), p2.data(), out_fd, errbuf, errcap, tf.fd >= 0 ? ties.data() : nullptr, tf.fd,
+                      ef.fd >= 0 ? evidence.data() : nullptr, ef.fd);
 }
 
 int inq_genotype_repeats_devices(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, inq_part_stats_t *stats,

@@ -86,11 +86,11 @@ int prepare(const inq_call_args_t *a, Prepared &P, std::string &msg, BedCache *b
     return INQ_EXIT_OK;
 }
 
-int TiesFile::open(const char *path, std::string &msg) {
+int ReportFile::open(const char *path, const char *what, std::string &msg) {
     if (!path) return INQ_EXIT_OK;
     fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
     if (fd >= 0) return INQ_EXIT_OK;
-    msg = std::string("cannot write the tie report ") + path + ": " + std::strerror(errno);
+    msg = std::string("cannot write ") + what + " " + path + ": " + std::strerror(errno);
     return INQ_EXIT_ERROR;
 }
 
@@ -133,6 +133,9 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
     // the tie report: per-target flags, collected only when someone asked for them (the locus kernels run without flags otherwise)
     const bool want_ties = hooks.ties_out || hooks.ties_fd >= 0;
     std::vector<uint8_t> ties(want_ties ? n : 0, 0);
+    // the evidence file, likewise: a target no batch or span holds keeps its zeros
+    const bool want_evidence = hooks.evidence_out || hooks.evidence_fd >= 0;
+    std::vector<inq_locus_evidence_t> evidence(want_evidence ? n : 0, inq_locus_evidence_t{});
     const bool rows_on_device = rows.active && rows.d1 && rows.d2;
     if (rows_on_device && rows.dcap < n) {
         set_err(errbuf, errcap, "device row arrays smaller than the target list");
@@ -141,8 +144,9 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
     auto emit = [&]() -> int {
         if (!rows.active)
             return write_rows(args->threads, V.targets, V.sample, p1.data(), p2.data(), out_fd, errbuf, errcap, want_ties ? ties.data() : nullptr,
-                              hooks.ties_fd);
+                              hooks.ties_fd, want_evidence ? evidence.data() : nullptr, hooks.evidence_fd);
         if (hooks.ties_out && n) std::memcpy(hooks.ties_out, ties.data(), n);
+        if (hooks.evidence_out && n) std::memcpy(hooks.evidence_out, evidence.data(), n * sizeof(inq_locus_evidence_t));
         if (rows_on_device) return INQ_EXIT_OK;  // (device front end: they are there; host sweep: written below)
         if (n) std::memcpy(rows.p1, p1.data(), n * sizeof(double)), std::memcpy(rows.p2, p2.data(), n * sizeof(double));
         return INQ_EXIT_OK;
@@ -164,6 +168,7 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
         dh.stats = ps;
         if (rows_on_device) dh.dev_p1 = rows.d1, dh.dev_p2 = rows.d2, dh.dev_cap = rows.dcap;
         dh.ties_out = want_ties ? ties.data() : nullptr;  // (indexed like p1 / p2)
+        dh.evidence_out = want_evidence ? evidence.data() : nullptr;
         int drc = run_device_front(args, V, actx, p1, p2, errbuf, errcap, &t_front, &t_dev, dh);
         if (drc != INQ_EXIT_OK) return drc;
         const auto t_run = Clock::now();
@@ -253,16 +258,16 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
             batch.locus_start = (const uint32_t *)put(batch.locus_start, batch.n_loci * 4, off, s4);
             batch.locus_end = (const uint32_t *)put(batch.locus_end, batch.n_loci * 4, off, s4);
         }
-        br.begin(batch.n_loci, want_ties);
+        br.begin(batch.n_loci, want_ties, want_evidence);
         auto tc = Clock::now();
-        int rc2 = want_ties ? inq_call_batch_flags(ctx, &batch, &br.res, br.flags) : inq_call_batch(ctx, &batch, &br.res);
+        int rc2 = inq_call_batch_evidence(ctx, &batch, &br.res, br.flags, br.evidence);  // (null flags / evidence: inq_call_batch)
         t_dev += secs(tb, Clock::now());
         if (timing == 2)
             std::fprintf(stderr, "[inq batch] loci %llu pairs %llu cigar %.1f MB  wait-ctx %.2f ms  call %.2f ms\n",
                          (unsigned long long)batch.n_loci, (unsigned long long)batch.n_pairs, batch.n_cigar_words * 4 / 1e6,
                          secs(tb, tc) * 1e3, secs(tc, Clock::now()) * 1e3);
         if (rc2 != INQ_OK) return device_call_failed(rc2, ctx, errbuf, errcap);
-        br.scatter_to(item.index.data(), p1.data(), p2.data(), ties.data());
+        br.scatter_to(item.index.data(), p1.data(), p2.data(), ties.data(), evidence.data());
         pfe.recycle(std::move(item));
     }
     if (!need_ctx()) return INQ_EXIT_ERROR;  // no GPU is an error even for an empty target list
@@ -360,8 +365,24 @@ int write_ties(const std::vector<uint32_t> &order, const std::vector<RepeatInter
     return INQ_EXIT_OK;
 }
 
+int write_evidence(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const inq_locus_evidence_t *evidence, int fd,
+                   char *errbuf, size_t errcap) {
+    std::string text = std::string(kEvidenceHeader) + '\n';
+    for (const uint32_t i : order) {
+        const RepeatInterval &t = targets[i];
+        append_evidence_row(text, t.chrom, t.start, t.end, evidence[i]);
+        text += '\n';
+    }
+    if (!write_all(fd, text)) {
+        set_err(errbuf, errcap, "Failed writing the evidence file.");
+        return INQ_EXIT_ERROR;
+    }
+    return INQ_EXIT_OK;
+}
+
 int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, const std::string &sample, const double *p1,
-                      const double *p2, int out_fd, char *errbuf, size_t errcap, const uint8_t *ties, int ties_fd) {
+                      const double *p2, int out_fd, char *errbuf, size_t errcap, const uint8_t *ties, int ties_fd,
+                      const inq_locus_evidence_t *evidence, int evidence_fd) {
     const size_t n = targets.size();
     const auto t_w0 = Clock::now();
     const std::vector<uint32_t> order = row_order(threads, targets);
@@ -418,6 +439,10 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
     if (ties && ties_fd >= 0) {  // the tie report, in the rows' order
         const int trc = write_ties(order, targets, ties, ties_fd, errbuf, errcap);
         if (trc != INQ_EXIT_OK) return trc;
+    }
+    if (evidence && evidence_fd >= 0) {  // the evidence file, one line per row
+        const int erc = write_evidence(order, targets, evidence, evidence_fd, errbuf, errcap);
+        if (erc != INQ_EXIT_OK) return erc;
     }
     if (timing_level())
         std::fprintf(stderr, "[inq output] %zu rows: order %.2f ms, bounds %.2f ms, text %.2f ms (%zu threads), write %.2f ms\n", n, ms(t_w0, t_w1), ms(t_w1, t_w1b), ms(t_w1b, t_w2),
@@ -515,8 +540,8 @@ void inq_frontend_close(inq_frontend_t *fe) { delete fe; }
 static int inq_genotype_repeats_impl(const inq_call_args_t *args, int out_fd, char *errbuf, size_t errcap, const RowsOut &rows = RowsOut()) {
     const auto t_start = Clock::now();
     std::string msg;
-    TiesFile tf;  // (a call that returns rows writes no file)
-    if (args && !rows.active && tf.open(args->ties_path, msg) != INQ_EXIT_OK) {
+    CallReports files;  // (a call that returns rows writes no file: the tie report is left out, the evidence file refused)
+    if (args && (rows.active ? refuse_evidence(args, "inq_genotype_repeats_rows", msg) : files.open(*args, msg)) != INQ_EXIT_OK) {
         set_err(errbuf, errcap, msg);
         return INQ_EXIT_ERROR;
     }
@@ -526,7 +551,7 @@ static int inq_genotype_repeats_impl(const inq_call_args_t *args, int out_fd, ch
     int rc = prepare(args, P, errbuf, errcap);
     if (rc != INQ_EXIT_OK) return rc;
     SessionHooks hooks;
-    hooks.ties_fd = tf.fd;
+    files.to(hooks);
     hooks.process_is_leaving = fast_exit();  // the context is this call's own, and so is the process's end (the CLI's `call`)
     rc = genotype_prepared(args, actx, P, out_fd, errbuf, errcap, rows, t_start, hooks);
     actx.leak = rc == INQ_EXIT_OK && hooks.process_is_leaving;  // only after a clean run: error paths tear down normally
@@ -665,6 +690,11 @@ struct inq_run {
 static int inq_run_open_impl(const inq_call_args_t *args, inq_run_t **out, char *errbuf, size_t errcap, inq_session *sess = nullptr) {
     if (!out || !args) return INQ_EXIT_ERROR;
     *out = nullptr;
+    std::string refused;
+    if (refuse_evidence(args, "a prepared run (inq_run_*)", refused) != INQ_EXIT_OK) {
+        set_err(errbuf, errcap, refused);
+        return INQ_EXIT_ERROR;
+    }
     std::unique_ptr<inq_run> R(new inq_run());
     R->args.reset(new OwnedArgs(*args));
     R->sess = sess;

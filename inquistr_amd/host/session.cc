@@ -16,7 +16,7 @@ struct StagedFile {
     int rc = INQ_EXIT_OK;
     std::string msg;
     std::unique_ptr<SpanPipeline> pipe;
-    std::unique_ptr<TiesFile> ties;  // the tie report (args->ties_path), opened when the file is staged
+    std::unique_ptr<ReportFile> ties;  // the tie report (args->ties_path), opened when the file is staged
     int slot_base = 0, front = 0;
     Clock::time_point t_start;
 };
@@ -26,8 +26,10 @@ void stage_file(inq_session *S, const inq_call_args_t *a, int slot_base, StagedF
     try {
         out.args.reset(new OwnedArgs(*a));
         out.slot_base = slot_base;
-        out.ties.reset(new TiesFile());
-        out.rc = out.ties->open(out.args->a.ties_path, out.msg);
+        out.rc = refuse_evidence(&out.args->a, "a session (inq_session_*, inquistr cohort / serve)", out.msg);
+        if (out.rc != INQ_EXIT_OK) return;
+        out.ties.reset(new ReportFile());
+        out.rc = out.ties->open(out.args->a.ties_path, kTiesWhat, out.msg);
         if (out.rc != INQ_EXIT_OK) return;
         out.rc = prepare(&out.args->a, out.P, out.msg, &S->bed_cache);
         if (out.rc != INQ_EXIT_OK) return;
