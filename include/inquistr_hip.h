@@ -162,6 +162,20 @@ typedef struct inq_locus_evidence {
     int64_t call_max;    /* n_group1 + n_group2 == 0                                                        */
 } inq_locus_evidence_t;
 
+/* The per-read Calls behind each row (the *_reads entry points below): one record per kept pair (INQ_PAIR_KEPT), compacted on the
+ * device from the per-pair outputs above, behind the locus kernels (and the evidence launches).  Per batch two arrays: kept_off[n_loci + 1]
+ * (u64, kept_off[0] = 0) and the records; locus j owns records [kept_off[j], kept_off[j + 1]), its kept pairs in file (pair) order,
+ * so kept_off[j + 1] - kept_off[j] is the evidence record's n_kept.  The Calls median_str_length is handed (src/call.rs:312-314 / :358)
+ * are, phased, the records of group 1 and of group 2; unphased, the records stable-sorted by value, the first len / 2 and the rest. */
+#define INQ_READ_CALL_CLIP 0x01u
+typedef struct inq_read_call {   /* 16 bytes, every byte written */
+    int64_t  call;      /* the Call's value (pair_call) */
+    uint32_t read;      /* index into the batch's reads[] (pair_read of the pair) */
+    uint8_t  group;     /* phased: the read's HP (0, 1, 2); unphased: 0 */
+    uint8_t  flags;     /* INQ_READ_CALL_CLIP = Call::Clip */
+    uint16_t reserved;  /* 0 */
+} inq_read_call_t;
+
 typedef struct inq_ctx inq_ctx_t;
 
 /* Opens HIP device `device_id` (must be gfx950), creates the library's stream and
@@ -206,6 +220,24 @@ int inq_call_batch_evidence(inq_ctx_t *ctx, const inq_batch_t *batch, inq_result
                             inq_locus_evidence_t *evidence);
 int inq_call_batch_device_evidence(inq_ctx_t *ctx, const inq_batch_t *batch, inq_result_t *result, uint8_t *d_locus_flags,
                                    inq_locus_evidence_t *d_evidence, void *hip_stream);
+
+/* ... and with the per-read Calls (inq_read_call_t above); locus_flags and evidence may be NULL.
+ * Device form: d_kept_off = DEVICE [n_loci + 1] u64, d_kept = DEVICE [n_pairs] records, 16-byte aligned; allocates no output and only
+ * enqueues: three launches (count per tile of inq_read_call_tile() pairs, scan of the tiles, scatter) behind the locus kernels and the
+ * evidence launches write every byte of d_kept_off and of the records [0, d_kept_off[n_loci]); records at and behind that are not
+ * written.  Like the evidence form it needs result->pair_call and result->pair_bits (INQ_ERR_ARG otherwise, nothing enqueued); one of
+ * the two pointers without the other is INQ_ERR_ARG; both NULL = exactly inq_call_batch_device_evidence.
+ * Host form: kept_off = HOST [n_loci + 1], brought down with the rows; per-pair outputs the caller did not ask for and the records
+ * stay in context scratch, the records until the context's next call: inq_read_calls_fetch copies the first n of them (n above the last
+ * call's total, kept_off[n_loci]: INQ_ERR_ARG; a call without the lists has a total of 0).  kept_off NULL = exactly
+ * inq_call_batch_evidence.  A batch that ends in a domain error leaves the lists unspecified. */
+int inq_call_batch_reads(inq_ctx_t *ctx, const inq_batch_t *batch, inq_result_t *result, uint8_t *locus_flags,
+                         inq_locus_evidence_t *evidence, uint64_t *kept_off);
+int inq_call_batch_device_reads(inq_ctx_t *ctx, const inq_batch_t *batch, inq_result_t *result, uint8_t *d_locus_flags,
+                                inq_locus_evidence_t *d_evidence, uint64_t *d_kept_off, inq_read_call_t *d_kept, void *hip_stream);
+int inq_read_calls_fetch(inq_ctx_t *ctx, inq_read_call_t *out, uint64_t n);
+/* pairs per workgroup of the compaction (a constant of the build) */
+uint32_t inq_read_call_tile(void);
 
 /* Device-side status of the launches since the last inq_ctx_status() call: returns
  * INQ_OK or the first domain error (INQ_ERR_PHASE / _CIGAR_OP / _LOCUS / _RANGE /
@@ -387,6 +419,10 @@ int inq_call_flush_device_flags(inq_ctx_t *ctx, double *d_phase1, double *d_phas
  * NULL = exactly inq_call_flush_flags.  The per-pair arrays the counting needs live in context scratch sized from the batch's pairs. */
 int inq_call_flush_evidence(inq_ctx_t *ctx, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
                             inq_locus_evidence_t *evidence);
+/* ... and with the per-read Calls: kept_off = HOST [n_loci + 1] in append order, NULL = exactly inq_call_flush_evidence; the records
+ * through inq_read_calls_fetch, their `read` indexing the deferred batch's reads as inq_span_fetch_batch returns them. */
+int inq_call_flush_reads(inq_ctx_t *ctx, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
+                         inq_locus_evidence_t *evidence, uint64_t *kept_off);
 /* Row arrays in device memory for a host that does not link the HIP runtime itself: n f64, filled with quiet NaN (a locus no span
  * holds prints NaN NaN); plain synchronous copies in and out. */
 int inq_dev_alloc_rows(inq_ctx_t *ctx, uint64_t n, double **out);

@@ -101,6 +101,18 @@ typedef struct inq_part_stats {
 } inq_part_stats_t;
 int inq_genotype_repeats_devices(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, inq_part_stats_t *stats,
                                  char *errbuf, size_t errcap);
+/* inq_genotype_repeats (n_devices == 0: the single device args->device; device_ids and stats are then not looked at) or
+ * inq_genotype_repeats_devices (n_devices >= 1) with the read-calls file (`inquistr call --read-calls`), which has an entry of its own
+ * because inq_call_args_t does not grow: read_calls_path NULL = exactly those two.  The file: a header line
+ * `chrom\tbegin\tend\th1\th2\tother`, then exactly one line per .inq row, in the .inq's row order.  h1 / h2 are the Calls
+ * median_str_length is handed for phase1 / phase2 (src/call.rs:312-314 / :358), comma-separated, ascending by (value, file order), a
+ * Clip with the suffix `c` (`-20,0,7,12c`), an empty list `.`.  Phased: the kept reads of HP 1 / HP 2, `other` those of HP 0.
+ * Unphased: the kept Calls stable-sorted by value (ties by file order: the tie rule of the device's reduces), the first len / 2 and
+ * the rest; `other` is `.`.  A target no batch or span holds: `.\t.\t.`.  Opened (created / truncated) before any device work, a
+ * path that cannot be opened: exit status 1 and nothing on out_fd; ties_path and evidence_path of args work beside it; content
+ * unspecified after a failed call.  The .inq text is that of the call without the file. */
+int inq_genotype_repeats_reads(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd,
+                               const char *read_calls_path, inq_part_stats_t *stats, char *errbuf, size_t errcap);
 /* How many processes (or device parts) share this host's cores with this one, and which of them it is (0 .. sharers - 1): sizes the
  * reader pool of every later call (granted cores / sharers, bound to L3 domains from a different start per sharer).  Default:
  * LOCAL_WORLD_SIZE / LOCAL_RANK of the environment (torch.distributed.run exports them), else 1 / 0.  sharers <= 0 = that default. */
@@ -237,6 +249,10 @@ size_t inq_host_format_row(const char *chrom, uint32_t start, uint32_t end, doub
 size_t inq_host_format_header(const char *sample, char *buf, size_t cap);
 /* one line of the evidence file (inq_call_args_t.evidence_path), without the newline; returns its length as snprintf does */
 size_t inq_host_format_evidence_row(const char *chrom, uint32_t start, uint32_t end, const inq_locus_evidence_t *evidence, char *buf, size_t cap);
+/* one line of the read-calls file (inq_genotype_repeats_reads) from the n records of a locus's kept reads in file order
+ * (inq_read_call_t of include/inquistr_hip.h), without the newline; returns its length as snprintf does */
+size_t inq_host_format_read_calls_row(const char *chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls, size_t n, int unphased,
+                                      char *buf, size_t cap);
 size_t inq_host_sample_name(const char *bam_path, char *buf, size_t cap);
 int inq_host_human_compare(const char *a, const char *b);
 /* RepeatIntervalIterator::from_string against a one-contig length table; 0 ok, 101 panic */

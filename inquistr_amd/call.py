@@ -24,6 +24,7 @@ HOST_ABI_SYMBOLS = (
     "inq_genotype_repeats",
     "inq_genotype_repeats_rows",
     "inq_genotype_repeats_devices",
+    "inq_genotype_repeats_reads",
     "inq_host_set_local_share",
     "inq_host_granted_cpus",
     "inq_host_ctx_option",
@@ -63,6 +64,7 @@ HOST_ABI_SYMBOLS = (
     "inq_host_format_row",
     "inq_host_format_header",
     "inq_host_format_evidence_row",
+    "inq_host_format_read_calls_row",
     "inq_host_sample_name",
     "inq_host_human_compare",
     "inq_host_parse_region",
@@ -152,6 +154,9 @@ def load():
         L.inq_genotype_repeats.argtypes = [C.POINTER(CallArgsC), C.c_int, C.c_char_p, C.c_size_t]
         L.inq_genotype_repeats_rows.restype = C.c_int
         L.inq_genotype_repeats_rows.argtypes = [C.POINTER(CallArgsC), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+        L.inq_genotype_repeats_reads.restype = C.c_int
+        L.inq_genotype_repeats_reads.argtypes = [C.POINTER(CallArgsC), C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.c_char_p, C.POINTER(PartStatsC),
+                                                 C.c_char_p, C.c_size_t]
         L.inq_genotype_repeats_devices.restype = C.c_int
         L.inq_genotype_repeats_devices.argtypes = [C.POINTER(CallArgsC), C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.POINTER(PartStatsC), C.c_char_p, C.c_size_t]
         L.inq_host_set_local_share.restype = None
@@ -228,6 +233,8 @@ def load():
 
         L.inq_host_format_evidence_row.restype = C.c_size_t
         L.inq_host_format_evidence_row.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(LocusEvidenceC), C.c_char_p, C.c_size_t]
+        L.inq_host_format_read_calls_row.restype = C.c_size_t
+        L.inq_host_format_read_calls_row.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t]
         L.inq_host_sample_name.restype = C.c_size_t
         L.inq_host_sample_name.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
         L.inq_host_human_compare.restype = C.c_int
@@ -331,17 +338,26 @@ def _args(bamp, region, region_file, minlen, support, threads, unphased, sample_
 def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str], minlen: int = 5, support: int = 3,
                      threads: int = 1, unphased: bool = False, sample_name: Optional[str] = None,
                      reference: Optional[str] = None, out=None, device: int = 0, frontend: Optional[str] = None,
-                     ties: Optional[str] = None, evidence: Optional[str] = None) -> None:
+                     ties: Optional[str] = None, evidence: Optional[str] = None, read_calls: Optional[str] = None, devices=None) -> None:
     """src/call.rs:76-86: same parameters, same output; raises CallError instead of exiting.
     frontend: "host" (BGZF inflate + record decode on CPU threads), "device" (inq_call_span: both on the GPU)
     or None (env INQ_FRONTEND, else the library default).
     ties: path of the tie report (inquistr call --ties): the tie-ambiguous unphased loci as BED, in the rows' order.
-    evidence: path of the evidence file (inquistr call --evidence): one line per row with the read counts behind its two medians."""
+    evidence: path of the evidence file (inquistr call --evidence): one line per row with the read counts behind its two medians.
+    read_calls: path of the read-calls file (inquistr call --read-calls): one line per row with the Calls behind its two medians.
+    devices: with read_calls, the HIP devices of inq_genotype_repeats_reads (None: the one device `device`)."""
     L = load()
     a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, reference, device, frontend, ties, evidence)
     out = sys.stdout if out is None else out
     out.flush()
-    _checked(L.inq_genotype_repeats, C.byref(a), out.fileno())
+    if read_calls is None and devices is None:
+        _checked(L.inq_genotype_repeats, C.byref(a), out.fileno())
+        return
+    devices = [] if devices is None else [int(d) for d in devices]
+    ids = (C.c_int32 * max(len(devices), 1))(*devices)
+    st = (PartStatsC * max(len(devices), 1))()
+    path = os.fspath(read_calls).encode() if read_calls is not None else None
+    _checked(L.inq_genotype_repeats_reads, C.byref(a), ids, len(devices), out.fileno(), path, st)
 
 
 def genotype_repeats_devices(bamp: str, region: Optional[str], region_file: Optional[str], devices, minlen: int = 5, support: int = 3,

@@ -17,6 +17,7 @@
 #include "evidence.h"
 #include "front_kernels.h"
 #include "kernels.h"
+#include "read_calls.h"
 
 using namespace inq;
 
@@ -323,12 +324,15 @@ static int check_scalars(const inq_batch_t *b, const inq_result_t *r) {
 
 // d_flags: DEVICE [n_loci] per-locus flags (INQ_LOCUS_TIE), or null - then nothing is added to the launch sequence
 // d_evidence: DEVICE [n_loci] per-locus evidence, or null - then nothing is added to the launch sequence and nothing is allocated
+// d_kept_off / d_kept: DEVICE [n_loci + 1] / [n_pairs] per-read Calls (both or neither), or null - then nothing is added and nothing allocated
 static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, uint8_t *d_flags = nullptr,
-                         inq_locus_evidence_t *d_evidence = nullptr) {
+                         inq_locus_evidence_t *d_evidence = nullptr, uint64_t *d_kept_off = nullptr, inq_read_call_t *d_kept = nullptr) {
     if (!c) return INQ_ERR_ARG;
     int rc = check_scalars(b, r);
     if (rc != INQ_OK) return rc;
     if (d_evidence && b->n_pairs && (!r->pair_call || !r->pair_bits)) return INQ_ERR_ARG;  // the counting reads both
+    if (!d_kept_off != !d_kept || ((uintptr_t)d_kept & 15u) || ((uintptr_t)d_kept_off & 7u)) return INQ_ERR_ARG;
+    if (d_kept && b->n_pairs && (!r->pair_call || !r->pair_bits)) return INQ_ERR_ARG;  // ... and so does the compaction
     if (((uintptr_t)b->cigar & 15u) || ((uintptr_t)b->reads & 15u)) return INQ_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
@@ -347,6 +351,7 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     // evidence: the slice list of the loci one wave does not count; no list and no second launch when the depth hint rules them out
     const uint64_t ev_list_cap = d_evidence && b->n_pairs > kEvidenceWaveMax && !(hint && hint <= kEvidenceWaveMax) ? evidence_list_cap(b->n_pairs) : 0;
     if (d_evidence && (rc = ensure(c, c->evwork, evidence_scratch_bytes(ev_list_cap))) != INQ_OK) return rc;
+    if (d_kept && b->n_pairs && (rc = ensure(c, c->rctiles, read_call_scratch_bytes(b->n_pairs))) != INQ_OK) return rc;
 
     KArgs a;
     a.cigar4 = (const uint4 *)b->cigar;
@@ -399,6 +404,22 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
         launch_evidence(ea, b->unphased != 0, c->n_cus * 4u, s);
         HIP_TRY(c, hipGetLastError());
     }
+    if (d_kept && !b->n_pairs) HIP_TRY(c, hipMemsetAsync(d_kept_off, 0, (size_t)(b->n_loci + 1) * 8, s));  // no pair: every list is empty
+    if (d_kept && b->n_pairs) {
+        ReadCallArgs ra;
+        ra.locus_pair_off = b->locus_pair_off;
+        ra.pair_bits = r->pair_bits;
+        ra.pair_call = r->pair_call;
+        ra.pair_read = b->pair_read;
+        ra.read_words = (const uint32_t *)b->reads;
+        ra.n_reads = b->n_reads, ra.n_pairs = b->n_pairs, ra.n_loci = b->n_loci;
+        ra.kept_off = d_kept_off;
+        ra.kept = d_kept;
+        ra.tile_base = (uint64_t *)c->rctiles.p;
+        ra.tile_count = (uint32_t *)(ra.tile_base + read_call_tiles(b->n_pairs) + 1);
+        launch_read_calls(ra, b->unphased != 0, s);
+        HIP_TRY(c, hipGetLastError());
+    }
     if (ev) HIP_TRY(c, hipEventRecord(ev->e2, s));
     return INQ_OK;
 }
@@ -413,7 +434,26 @@ int inq_call_batch_device_flags(inq_ctx_t *c, const inq_batch_t *b, inq_result_t
 
 int inq_call_batch_device_evidence(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *d_locus_flags, inq_locus_evidence_t *d_evidence,
                                    void *hip_stream) {
-    return guarded([&] { return enqueue_batch(c, b, r, hip_stream, d_locus_flags, d_evidence); });
+    return inq_call_batch_device_reads(c, b, r, d_locus_flags, d_evidence, nullptr, nullptr, hip_stream);
+}
+
+int inq_call_batch_device_reads(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *d_locus_flags, inq_locus_evidence_t *d_evidence,
+                                uint64_t *d_kept_off, inq_read_call_t *d_kept, void *hip_stream) {
+    return guarded([&] { return enqueue_batch(c, b, r, hip_stream, d_locus_flags, d_evidence, d_kept_off, d_kept); });
+}
+
+uint32_t inq_read_call_tile(void) { return kReadCallTile; }
+
+static int read_calls_fetch_impl(inq_ctx_t *c, inq_read_call_t *out, uint64_t n) {
+    if (!c || n > c->read_calls_total || (n && !out)) return INQ_ERR_ARG;
+    if (!n) return INQ_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(out, c->rckept.p, (size_t)n * sizeof(inq_read_call_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return INQ_OK;
+}
+int inq_read_calls_fetch(inq_ctx_t *c, inq_read_call_t *out, uint64_t n) {
+    return guarded([&] { return read_calls_fetch_impl(c, out, n); });
 }
 
 int inq_ctx_status(inq_ctx_t *c, uint64_t *n_tie_loci) {
@@ -427,8 +467,10 @@ int inq_ctx_status(inq_ctx_t *c, uint64_t *n_tie_loci) {
     return status_to_code(c->h_status->err);
 }
 
-static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *h_flags, inq_locus_evidence_t *h_evidence) {
+static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *h_flags, inq_locus_evidence_t *h_evidence,
+                           uint64_t *h_kept_off) {
     if (!c) return INQ_ERR_ARG;
+    c->read_calls_total = 0;  // (the records of the call before are no longer offered)
     int rc = check_scalars(b, r);
     if (rc != INQ_OK) return rc;
     // host-side shape checks: everything the grid and the kernels' indexing assume
@@ -442,7 +484,10 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
         }
     }
     r->n_tie_loci = 0;
-    if (b->n_loci == 0) return INQ_OK;
+    if (b->n_loci == 0) {
+        if (h_kept_off) h_kept_off[0] = 0;
+        return INQ_OK;
+    }
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     struct Up {
@@ -463,12 +508,15 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
     }
     if ((rc = ensure(c, c->p1, (size_t)b->n_loci * 8)) != INQ_OK) return rc;
     if ((rc = ensure(c, c->p2, (size_t)b->n_loci * 8)) != INQ_OK) return rc;
-    // (the evidence is counted from the per-pair outputs: they are kept in scratch also when the caller does not want them)
-    const bool want_call = r->pair_call || h_evidence, want_bits = r->pair_bits || h_evidence;
+    // (the evidence is counted and the lists are compacted from the per-pair outputs: they are kept in scratch also when the caller does
+    // not want them)
+    const bool want_call = r->pair_call || h_evidence || h_kept_off, want_bits = r->pair_bits || h_evidence || h_kept_off;
     if (want_call && (rc = ensure(c, c->pcall, (size_t)b->n_pairs * 8)) != INQ_OK) return rc;
     if (want_bits && (rc = ensure(c, c->pbits, (size_t)b->n_pairs)) != INQ_OK) return rc;
     if (h_flags && (rc = ensure(c, c->lflags, (size_t)b->n_loci)) != INQ_OK) return rc;
     if (h_evidence && (rc = ensure(c, c->levidence, (size_t)b->n_loci * sizeof(inq_locus_evidence_t))) != INQ_OK) return rc;
+    if (h_kept_off && (rc = ensure(c, c->rcoff, (size_t)(b->n_loci + 1) * 8)) != INQ_OK) return rc;
+    if (h_kept_off && (rc = ensure(c, c->rckept, (size_t)b->n_pairs * sizeof(inq_read_call_t))) != INQ_OK) return rc;
 
     DevBatch d = device_batch(c->cigar.p, c->reads.p, c->pair_read.p, c->off.p, c->lstart.p, c->lend.p, b->n_reads, b->n_cigar_words,
                               b->n_pairs, b->n_loci, b->minlen, b->support, b->unphased, c->p1.p, c->p2.p,
@@ -477,7 +525,10 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
     c->call_hint = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(max_reads, 1), 0xffffffffull);  // skips the deep-locus launches when no locus needs them
     uint8_t *d_flags = h_flags ? (uint8_t *)c->lflags.p : nullptr;
     inq_locus_evidence_t *d_evidence = h_evidence ? (inq_locus_evidence_t *)c->levidence.p : nullptr;
-    if ((rc = enqueue_batch(c, &d.b, &d.r, s, d_flags, d_evidence)) != INQ_OK) return rc;
+    uint64_t *d_kept_off = h_kept_off ? (uint64_t *)c->rcoff.p : nullptr;
+    if ((rc = enqueue_batch(c, &d.b, &d.r, s, d_flags, d_evidence, d_kept_off, h_kept_off ? (inq_read_call_t *)c->rckept.p : nullptr)) != INQ_OK)
+        return rc;
+    if (h_kept_off) HIP_TRY(c, hipMemcpyAsync(h_kept_off, d_kept_off, (size_t)(b->n_loci + 1) * 8, hipMemcpyDeviceToHost, s));
     if (h_flags) HIP_TRY(c, hipMemcpyAsync(h_flags, d_flags, (size_t)b->n_loci, hipMemcpyDeviceToHost, s));
     if (h_evidence) HIP_TRY(c, hipMemcpyAsync(h_evidence, d_evidence, (size_t)b->n_loci * sizeof(inq_locus_evidence_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(r->phase1, dr.phase1, (size_t)b->n_loci * 8, hipMemcpyDeviceToHost, s));
@@ -490,6 +541,8 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
     HIP_TRY(c, hipStreamSynchronize(s));  // the one synchronisation of the call
     purge_retired(c);  // the stream is idle: buffers this call outgrew go back now
     r->n_tie_loci = c->h_status->ties;
+    // (after a domain error the lists are unspecified: none is offered, whatever the offsets say)
+    if (h_kept_off && c->h_status->err == 0) c->read_calls_total = std::min<uint64_t>(h_kept_off[b->n_loci], b->n_pairs);
     return status_to_code(c->h_status->err);
 }
 
@@ -500,7 +553,12 @@ int inq_call_batch_flags(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, ui
 }
 
 int inq_call_batch_evidence(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *locus_flags, inq_locus_evidence_t *evidence) {
-    return guarded([&] { return call_batch_impl(c, b, r, locus_flags, evidence); });
+    return inq_call_batch_reads(c, b, r, locus_flags, evidence, nullptr);
+}
+
+int inq_call_batch_reads(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *locus_flags, inq_locus_evidence_t *evidence,
+                         uint64_t *kept_off) {
+    return guarded([&] { return call_batch_impl(c, b, r, locus_flags, evidence, kept_off); });
 }
 
 static int outlier_rows_impl(inq_ctx_t *c, const float *values, const uint32_t *row_len, uint64_t n_rows, uint32_t stride,
@@ -746,7 +804,7 @@ void inq_free_pinned(void *p) {
 }  // extern "C"
 
 int inq::call_batch_device_impl(inq_ctx *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, uint8_t *d_locus_flags,
-                                inq_locus_evidence_t *d_evidence) {
-    return enqueue_batch(c, b, r, hip_stream, d_locus_flags, d_evidence);
+                                inq_locus_evidence_t *d_evidence, uint64_t *d_kept_off, inq_read_call_t *d_kept) {
+    return enqueue_batch(c, b, r, hip_stream, d_locus_flags, d_evidence, d_kept_off, d_kept);
 }
 

@@ -42,11 +42,15 @@ struct inq_ctx {
     // per-locus evidence (evidence.hip): the records of a host-buffer call or a flush, the slice list of the deep loci; pcall / pbits
     // also hold the per-pair outputs of a call with evidence whose caller did not ask for them.  Allocated by calls with evidence only
     inq::DevBuf levidence, evwork;
+    // the per-read Calls (read_calls.hip): the tile arrays of the compaction; kept_off and the records of a host-buffer call or a flush,
+    // which stay until the context's next call (inq_read_calls_fetch).  Allocated by calls with the lists only
+    inq::DevBuf rctiles, rcoff, rckept;
+    uint64_t read_calls_total = 0;  // records of the last host-buffer call or flush (0: it had no lists)
     inq::DevBuf ovalues, olen, oflags, okeep, otrans;  // inq_outlier_rows
     // every DevBuf above, for inq_ctx_destroy (DevBuf frees nothing itself): a member missing here leaks
     auto bufs() {
         return std::array{&worklist, &sval, &smeta, &deep, &cigar, &reads, &pair_read, &off, &lstart, &lend, &p1, &p2, &pcall, &pbits, &lflags,
-                          &levidence, &evwork, &ovalues, &olen, &oflags, &okeep, &otrans};
+                          &levidence, &evwork, &rctiles, &rcoff, &rckept, &ovalues, &olen, &oflags, &okeep, &otrans};
     }
     uint32_t n_cus = 0;        // compute units of the device
     uint32_t grid_tail = 256;  // workgroups of the persistent locus_call_tail: they meet at grid barriers, so never more than n_cus
@@ -148,7 +152,7 @@ void retire(inq_ctx *c, void *p, size_t bytes);
 void purge_retired(inq_ctx *c);  // hipFree of everything retired (waits for the device: call where it is idle)
 // enqueue-only launch sequence of the locus kernels over a device-resident batch
 int call_batch_device_impl(inq_ctx *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, uint8_t *d_locus_flags = nullptr,
-                           inq_locus_evidence_t *d_evidence = nullptr);
+                           inq_locus_evidence_t *d_evidence = nullptr, uint64_t *d_kept_off = nullptr, inq_read_call_t *d_kept = nullptr);
 int status_to_code(uint32_t st);
 // The kernels' status travels with the results: enqueues DevStatus -> dst (page-locked), then clears err and ties on the same stream,
 // i.e. before the next call's kernels (the work-list counters stay).  No synchronisation: dst is valid once the caller has waited for s.

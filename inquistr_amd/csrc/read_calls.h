@@ -1,0 +1,32 @@
+// read_calls.h — the compaction kernels behind inq_read_call_t (read_calls.hip), launched by capi.hip behind the locus kernels
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/inquistr_hip.h"
+
+namespace inq {
+
+constexpr uint32_t kReadCallTile = 4096;  // pairs per workgroup of the count and the scatter launch: 16 B of pair_bits per lane
+
+struct ReadCallArgs {
+    const uint64_t *locus_pair_off;  // [n_loci + 1]
+    const uint8_t *pair_bits;        // [n_pairs] INQ_PAIR_*, as the locus kernels left them
+    const int64_t *pair_call;        // [n_pairs]
+    const uint32_t *pair_read;       // [n_pairs]
+    const uint32_t *read_words;      // inq_read_t as four words: word 3 = mapq | bits << 8 | phase << 16 | promise << 24  (phased only)
+    uint64_t n_reads, n_pairs, n_loci;
+    uint64_t *kept_off;              // [n_loci + 1]
+    inq_read_call_t *kept;           // [n_pairs]: records [0, kept_off[n_loci]) are written, 16-byte aligned
+    uint32_t *tile_count;            // [n_tiles]      context scratch
+    uint64_t *tile_base;             // [n_tiles + 1]  context scratch; the last entry is the total
+};
+
+inline uint64_t read_call_tiles(uint64_t n_pairs) { return (n_pairs + kReadCallTile - 1) / kReadCallTile; }
+// the tile arrays of a batch of n_pairs pairs: tile_base first (8-byte entries), tile_count behind it
+inline size_t read_call_scratch_bytes(uint64_t n_pairs) { return (size_t)(read_call_tiles(n_pairs) + 1) * 8 + (size_t)read_call_tiles(n_pairs) * 4; }
+
+// the three launches on s (a.n_pairs > 0; a batch without pairs is a fill of kept_off, done by the caller)
+void launch_read_calls(const ReadCallArgs &a, bool unphased, hipStream_t s);
+
+}  // namespace inq

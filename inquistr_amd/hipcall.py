@@ -77,6 +77,11 @@ ABI_SYMBOLS = (
     "inq_call_batch_evidence",
     "inq_call_batch_device_evidence",
     "inq_call_flush_evidence",
+    "inq_call_batch_reads",
+    "inq_call_batch_device_reads",
+    "inq_call_flush_reads",
+    "inq_read_calls_fetch",
+    "inq_read_call_tile",
 )
 
 
@@ -151,6 +156,24 @@ class LocusEvidenceC(C.Structure):
 
 EVIDENCE_DTYPE = np.dtype([("n_fetched", "<u4"), ("n_kept", "<u4"), ("n_group1", "<u4"), ("n_group2", "<u4"), ("n_clip", "<u4"),
                            ("reserved", "<u4"), ("call_min", "<i8"), ("call_max", "<i8")])
+
+
+READ_CALL_CLIP = 0x01
+
+
+class ReadCallC(C.Structure):
+    """inq_read_call_t"""
+
+    _fields_ = [
+        ("call", C.c_int64),
+        ("read", C.c_uint32),
+        ("group", C.c_uint8),
+        ("flags", C.c_uint8),
+        ("reserved", C.c_uint16),
+    ]
+
+
+READ_CALL_DTYPE = np.dtype([("call", "<i8"), ("read", "<u4"), ("group", "u1"), ("flags", "u1"), ("reserved", "<u2")])
 
 
 def scan_bgzf(data) -> np.ndarray:
@@ -239,6 +262,16 @@ def load(path: Optional[str] = None):
     L.inq_call_batch_device_evidence.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp, vp, vp]
     L.inq_call_flush_evidence.restype = C.c_int
     L.inq_call_flush_evidence.argtypes = [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double), vp, vp]
+    L.inq_call_batch_reads.restype = C.c_int
+    L.inq_call_batch_reads.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp, vp, vp]
+    L.inq_call_batch_device_reads.restype = C.c_int
+    L.inq_call_batch_device_reads.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp, vp, vp, vp, vp]
+    L.inq_call_flush_reads.restype = C.c_int
+    L.inq_call_flush_reads.argtypes = [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double), vp, vp, vp]
+    L.inq_read_calls_fetch.restype = C.c_int
+    L.inq_read_calls_fetch.argtypes = [vp, vp, C.c_uint64]
+    L.inq_read_call_tile.restype = C.c_uint32
+    L.inq_read_call_tile.argtypes = []
     L.inq_ctx_status.restype = C.c_int
     L.inq_ctx_status.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.inq_ctx_timing_enable.restype = C.c_int
@@ -401,6 +434,41 @@ class Context:
             self._raise(rc)
         return rc
 
+    def read_calls_fetch(self, n: int, check: bool = True):
+        """inq_read_calls_fetch: the first n records of the last call_batch_reads / call_flush_reads as a READ_CALL_DTYPE array
+        (check=False: (code, array))."""
+        out = np.full(max(n, 1) * READ_CALL_DTYPE.itemsize, 0xFF, dtype=np.uint8)
+        rc = self._L.inq_read_calls_fetch(self._h, out.ctypes.data, n)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        rec = out.view(READ_CALL_DTYPE)[:n]
+        return rec if check else (rc, rec)
+
+    def call_batch_reads(self, batch: Batch, debug: bool = False, check: bool = True, flags: bool = True, evidence: bool = True):
+        """inq_call_batch_reads: (code, Result, per-locus flags or None, per-locus evidence or None, kept_off [n_loci + 1], the records
+        as a READ_CALL_DTYPE array - fetched with read_calls_fetch when the call succeeded, else None)."""
+        res = Result.alloc(batch, debug=debug)
+        fl = np.full(max(batch.n_loci, 1), 0xFF, dtype=np.uint8) if flags else None
+        ev = np.full(max(batch.n_loci, 1) * EVIDENCE_DTYPE.itemsize, 0xFF, dtype=np.uint8) if evidence else None
+        off = np.full(batch.n_loci + 1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+        bc, rc_ = batch.as_c(), res.as_c()
+        rc = self._L.inq_call_batch_reads(self._h, C.byref(bc), C.byref(rc_), fl.ctypes.data if flags else None,
+                                          ev.ctypes.data if evidence else None, off.ctypes.data)
+        res.n_tie_loci = int(rc_.n_tie_loci)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        rec = self.read_calls_fetch(int(off[-1])) if rc == INQ_OK else None
+        return (rc, res, (fl[: batch.n_loci] if flags else None), (ev.view(EVIDENCE_DTYPE)[: batch.n_loci] if evidence else None), off, rec)
+
+    def call_batch_device_reads(self, bc: InqBatchC, rc_: InqResultC, d_flags: Optional[int], d_evidence: Optional[int],
+                                d_kept_off: Optional[int], d_kept: Optional[int], stream: Optional[int] = None, check: bool = True) -> int:
+        """inq_call_batch_device_reads: every pointer is a device pointer (each of the four may be None); enqueue only."""
+        rc = self._L.inq_call_batch_device_reads(self._h, C.byref(bc), C.byref(rc_), C.c_void_p(d_flags or 0), C.c_void_p(d_evidence or 0),
+                                                 C.c_void_p(d_kept_off or 0), C.c_void_p(d_kept or 0), C.c_void_p(stream or 0))
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        return rc
+
     def call_batch_device(self, bc: InqBatchC, rc_: InqResultC, stream: Optional[int] = None) -> None:
         """Device-resident entry: pointers in bc / rc_ are device pointers; enqueue only."""
         rc = self._L.inq_call_batch_device(self._h, C.byref(bc), C.byref(rc_), C.c_void_p(stream or 0))
@@ -538,6 +606,23 @@ class Context:
         if rc != INQ_OK and check:
             self._raise(rc)
         return rc, p1, p2, int(res.n_tie_loci), float(ms.value), flags[:n], ev.view(EVIDENCE_DTYPE)[:n]
+
+    def call_flush_reads(self, check: bool = True):
+        """inq_call_flush_reads: as call_flush_evidence, plus kept_off [n + 1] and the records (READ_CALL_DTYPE; None after a failed
+        call) as the eighth and ninth element; `read` indexes the reads span_fetch_batch returns."""
+        n = self.deferred_loci
+        p1 = np.full(n, np.nan)
+        p2 = np.full(n, np.nan)
+        flags = np.full(max(n, 1), 0xFF, dtype=np.uint8)
+        ev = np.full(max(n, 1) * EVIDENCE_DTYPE.itemsize, 0xFF, dtype=np.uint8)
+        off = np.full(n + 1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+        res = InqResultC(p1.ctypes.data, p2.ctypes.data, None, None, 0)
+        ms = C.c_double(0.0)
+        rc = self._L.inq_call_flush_reads(self._h, C.byref(res), n, C.byref(ms), flags.ctypes.data, ev.ctypes.data, off.ctypes.data)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        rec = self.read_calls_fetch(int(off[-1])) if rc == INQ_OK else None
+        return rc, p1, p2, int(res.n_tie_loci), float(ms.value), flags[:n], ev.view(EVIDENCE_DTYPE)[:n], off, rec
 
     def span_fetch_batch(self, stats: "SpanStatsC", n_loci: int):
         """The batch the last call_span built on the device, as host arrays (cigar, reads, pair_read, locus_pair_off)."""

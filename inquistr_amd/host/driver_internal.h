@@ -283,6 +283,9 @@ struct CallView {
     CallOptions opt;
 };
 
+// the per-read Calls of a call's targets: [k] = the records of target k's kept reads in file order (empty: no batch or span held it)
+using ReadCallLists = std::vector<std::vector<inq_read_call_t>>;
+
 // what a session adds to one call: a pipeline that was started ahead of it (its loader has been reading and uploading while the
 // previous file was being called), the buffer pool, the set of device staging slots
 struct SessionHooks {
@@ -303,6 +306,10 @@ struct SessionHooks {
     // (null: not collected, nothing is added to the launch sequence); evidence_fd >= 0: a text call writes the file there
     inq_locus_evidence_t *evidence_out = nullptr;
     int evidence_fd = -1;
+    // the read-calls file (inq_genotype_repeats_reads), likewise: the records of target k of the call -> (*read_calls_out)[k] (null: not
+    // collected, nothing is added to the launch sequence); read_calls_fd >= 0: a text call writes the file there
+    ReadCallLists *read_calls_out = nullptr;
+    int read_calls_fd = -1;
     // the caller owns the context AND the process ends with this call (fast_exit()): a pipeline the call made itself is left to the
     // operating system after a clean run (unmapping a GB of touched pages takes ~0.1 s), as the caller then leaves its context
     bool process_is_leaving = false;
@@ -321,15 +328,16 @@ struct ReportFile {
     // path may be null (no file): INQ_EXIT_OK; a path that cannot be opened: INQ_EXIT_ERROR and a message that names `what` and it
     int open(const char *path, const char *what, std::string &msg);
 };
-constexpr const char *kTiesWhat = "the tie report", *kEvidenceWhat = "the evidence file";
-// the two files of a text call (inq_call_args_t::ties_path, ::evidence_path)
+constexpr const char *kTiesWhat = "the tie report", *kEvidenceWhat = "the evidence file", *kReadCallsWhat = "the read-calls file";
+// the files of a text call (inq_call_args_t::ties_path, ::evidence_path; read_calls_path of inq_genotype_repeats_reads, else null)
 struct CallReports {
-    ReportFile ties, evidence;
-    int open(const inq_call_args_t &a, std::string &msg) {
-        const int rc = ties.open(a.ties_path, kTiesWhat, msg);
-        return rc != INQ_EXIT_OK ? rc : evidence.open(a.evidence_path, kEvidenceWhat, msg);
+    ReportFile ties, evidence, read_calls;
+    int open(const inq_call_args_t &a, const char *read_calls_path, std::string &msg) {
+        int rc = ties.open(a.ties_path, kTiesWhat, msg);
+        if (rc == INQ_EXIT_OK) rc = evidence.open(a.evidence_path, kEvidenceWhat, msg);
+        return rc != INQ_EXIT_OK ? rc : read_calls.open(read_calls_path, kReadCallsWhat, msg);
     }
-    void to(SessionHooks &hooks) const { hooks.ties_fd = ties.fd, hooks.evidence_fd = evidence.fd; }
+    void to(SessionHooks &hooks) const { hooks.ties_fd = ties.fd, hooks.evidence_fd = evidence.fd, hooks.read_calls_fd = read_calls.fd; }
 };
 // an entry that returns rows or keeps its context for many files writes no evidence file and says so (INQ_EXIT_ERROR) instead of
 // ignoring the request
@@ -349,6 +357,17 @@ struct RowsOut {
     uint64_t dcap = 0;
 };
 
+// what write_rows writes beside the .inq, each where its array is set and its fd >= 0, for the same rows in the same order
+struct RowReports {
+    const uint8_t *ties = nullptr;
+    int ties_fd = -1;
+    const inq_locus_evidence_t *evidence = nullptr;
+    int evidence_fd = -1;
+    const ReadCallLists *read_calls = nullptr;
+    int read_calls_fd = -1;
+    bool unphased = false;  // how the read-calls file splits a target's Calls
+};
+
 // src[j] -> dst[index[j]]: rows, tie flags and evidence of a batch, a flush or a device part into their targets' places
 template <class T>
 inline void scatter(const T *src, const uint32_t *index, size_t n, T *dst) {
@@ -360,18 +379,30 @@ struct BatchRows {
     std::vector<uint8_t> bt;
     std::vector<inq_locus_evidence_t> be;
     inq_result_t res;
+    std::vector<uint64_t> bk;          // kept_off of the per-read Calls
+    std::vector<inq_read_call_t> bc;  // ... and the records, fetched behind the call
     uint8_t *flags = nullptr;                 // null: the call collects none
     inq_locus_evidence_t *evidence = nullptr;  // null: the call collects none
-    void begin(size_t n, bool want_flags, bool want_evidence) {
+    uint64_t *kept_off = nullptr;              // null: the call collects none
+    void begin(size_t n, bool want_flags, bool want_evidence, bool want_read_calls = false) {
         b1.assign(n, NAN), b2.assign(n, NAN);
         std::memset(&res, 0, sizeof res);
         res.phase1 = b1.data(), res.phase2 = b2.data();
-        flags = nullptr, evidence = nullptr;
+        flags = nullptr, evidence = nullptr, kept_off = nullptr;
+        if (want_read_calls) bk.assign(n + 1, 0), kept_off = bk.data();
         if (want_flags) bt.assign(n, 0), flags = bt.data();
         if (want_evidence) be.assign(n, inq_locus_evidence_t{}), evidence = be.data();
     }
-    // p1 null: the rows went elsewhere (device memory); ties / ev are asked for only where flags / evidence were
-    void scatter_to(const uint32_t *index, double *p1, double *p2, uint8_t *ties, inq_locus_evidence_t *ev) const {
+    // the records behind a call that filled kept_off, out of the context's scratch (INQ_OK at once for a call without the lists)
+    int fetch_read_calls(inq_ctx_t *ctx) {
+        if (!kept_off) return INQ_OK;
+        bc.resize(bk.back());
+        return inq_read_calls_fetch(ctx, bc.data(), bc.size());
+    }
+    // p1 null: the rows went elsewhere (device memory); ties / ev / lists are asked for only where flags / evidence / kept_off were
+    void scatter_to(const uint32_t *index, double *p1, double *p2, uint8_t *ties, inq_locus_evidence_t *ev, ReadCallLists *lists = nullptr) const {
+        if (kept_off)
+            for (size_t j = 0; j + 1 < bk.size(); ++j) (*lists)[index[j]].assign(bc.begin() + bk[j], bc.begin() + bk[j + 1]);
         if (p1) scatter(b1.data(), index, b1.size(), p1), scatter(b2.data(), index, b2.size(), p2);
         if (flags) scatter(flags, index, bt.size(), ties);
         if (evidence) scatter(evidence, index, be.size(), ev);
@@ -391,11 +422,9 @@ int run_device_front(const inq_call_args_t *args, const CallView &V, AsyncCtx &a
                      char *errbuf, size_t errcap, double *t_front, double *t_dev, const SessionHooks &hooks = SessionHooks());
 int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, int out_fd, char *errbuf, size_t errcap, const RowsOut &rows,
                       std::chrono::steady_clock::time_point t_start, const SessionHooks &hooks = SessionHooks());
-// ties / ties_fd, evidence / evidence_fd (may be null / < 0): the tie report and the evidence file of the same rows go there, in the
-// same order
+// reports: the tie report, the evidence file and the read-calls file of the same rows, in the same order
 int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, const std::string &sample, const double *p1, const double *p2,
-               int out_fd, char *errbuf, size_t errcap, const uint8_t *ties = nullptr, int ties_fd = -1,
-               const inq_locus_evidence_t *evidence = nullptr, int evidence_fd = -1);
+               int out_fd, char *errbuf, size_t errcap, const RowReports &reports = RowReports());
 // the order of the .inq's rows: BED order for -t 1, (human_compare(chrom), start) for -t >= 2 (src/call.rs:33-38,141)
 std::vector<uint32_t> row_order(uint64_t threads, const std::vector<RepeatInterval> &targets);
 // the tie report: `chrom\tbegin\tend\n` for every target order[k] with a flag set
@@ -404,6 +433,11 @@ int write_ties(const std::vector<uint32_t> &order, const std::vector<RepeatInter
 // the evidence file: the header, then one line for every target order[k]
 int write_evidence(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const inq_locus_evidence_t *evidence, int fd,
                    char *errbuf, size_t errcap);
+// the read-calls file: the header, then one line for every target order[k]
+int write_read_calls(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const ReadCallLists &lists, bool unphased,
+                     int fd, char *errbuf, size_t errcap);
+// inq_genotype_repeats with the read-calls file (null: none), for inq_genotype_repeats_reads
+int genotype_single(const inq_call_args_t *args, int out_fd, const char *read_calls_path, char *errbuf, size_t errcap);
 int partition_prepared(Prepared &P, uint64_t world, uint32_t *order, uint64_t *cuts);
 
 struct OwnedArgs {

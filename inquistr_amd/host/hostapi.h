@@ -15,8 +15,7 @@
 namespace inq {
 
 struct HostApi {
-    decltype(&::inq_genotype_repeats) genotype_repeats;
-    decltype(&::inq_genotype_repeats_devices) genotype_repeats_devices;
+    decltype(&::inq_genotype_repeats_reads) genotype_repeats_reads;  // (inq_genotype_repeats and _devices are its two forms)
     decltype(&::inq_host_ctx_option) ctx_option;
     decltype(&::inq_combine) combine;
     decltype(&::inq_outlier) outlier;
@@ -54,8 +53,7 @@ inline const HostApi &host_api() {
             }
             return p;
         };
-        a.genotype_repeats = reinterpret_cast<decltype(a.genotype_repeats)>(sym("inq_genotype_repeats"));
-        a.genotype_repeats_devices = reinterpret_cast<decltype(a.genotype_repeats_devices)>(sym("inq_genotype_repeats_devices"));
+        a.genotype_repeats_reads = reinterpret_cast<decltype(a.genotype_repeats_reads)>(sym("inq_genotype_repeats_reads"));
         a.ctx_option = reinterpret_cast<decltype(a.ctx_option)>(sym("inq_host_ctx_option"));
         a.combine = reinterpret_cast<decltype(a.combine)>(sym("inq_combine"));
         a.outlier = reinterpret_cast<decltype(a.outlier)>(sym("inq_outlier"));

@@ -26,6 +26,13 @@ size_t inq_host_format_evidence_row(const char *chrom, uint32_t start, uint32_t 
     append_evidence_row(s, chrom, start, end, *evidence);
     return (size_t)std::snprintf(buf, cap, "%s", s.c_str());
 }
+size_t inq_host_format_read_calls_row(const char *chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls, size_t n, int unphased,
+                                      char *buf, size_t cap) {
+    if (!chrom || (n && !calls)) return 0;
+    std::string s;
+    append_read_calls_row(s, chrom, start, end, calls, n, unphased != 0);
+    return (size_t)std::snprintf(buf, cap, "%s", s.c_str());
+}
 size_t inq_host_sample_name(const char *p, char *buf, size_t cap) {
     return (size_t)std::snprintf(buf, cap, "%s", sample_name_from_path(p).c_str());
 }

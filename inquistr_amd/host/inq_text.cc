@@ -1,5 +1,6 @@
 #include "inq_text.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -155,6 +156,38 @@ void append_evidence_row(std::string &out, const std::string &chrom, uint32_t st
         out += "\t.\t.";  // no Call behind either median: nothing to take extremes of
     else
         out += '\t', out += std::to_string(e.call_min), out += '\t', out += std::to_string(e.call_max);
+}
+
+const char *const kReadCallsHeader = "chrom\tbegin\tend\th1\th2\tother";
+
+// one list of the file: the Calls comma-separated, a Clip with the suffix `c`; `.` for none
+static void append_call_list(std::string &out, const inq_read_call_t *const *first, const inq_read_call_t *const *last) {
+    out += '\t';
+    if (first == last) out += '.';
+    for (const inq_read_call_t *const *p = first; p != last; ++p) {
+        if (p != first) out += ',';
+        out += std::to_string((*p)->call);
+        if ((*p)->flags & INQ_READ_CALL_CLIP) out += 'c';
+    }
+}
+
+void append_read_calls_row(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls, size_t n,
+                           bool unphased) {
+    out += chrom;
+    for (const uint32_t v : {start, end}) out += '\t', out += std::to_string(v);
+    // ascending by (value, file order) - the records come in file order, so a stable sort by value: the tie rule of the reduces
+    auto by_value = [](const inq_read_call_t *a, const inq_read_call_t *b) { return a->call < b->call; };
+    std::vector<const inq_read_call_t *> g[3];  // h1, h2, other
+    for (size_t i = 0; i < n; ++i) g[unphased ? 0 : calls[i].group == 1 ? 0 : calls[i].group == 2 ? 1 : 2].push_back(calls + i);
+    for (auto &v : g) std::stable_sort(v.begin(), v.end(), by_value);
+    if (unphased) {  // src/call.rs:312-314: the sorted kept Calls are split at len / 2
+        const inq_read_call_t *const *all = g[0].data();
+        append_call_list(out, all, all + n / 2);
+        append_call_list(out, all + n / 2, all + n);
+        out += "\t.";
+        return;
+    }
+    for (const auto &v : g) append_call_list(out, v.data(), v.data() + v.size());
 }
 
 static void erase_all(std::string &s, const std::string &pat) {

@@ -2,8 +2,9 @@
 #pragma once
 #include <cstdint>
 #include <string>
+#include <vector>
 
-#include "../../include/inquistr_hip.h"  // inq_locus_evidence_t
+#include "../../include/inquistr_hip.h"  // inq_locus_evidence_t, inq_read_call_t
 
 namespace inqhost {
 
@@ -22,6 +23,11 @@ std::string format_header(const std::string &sample);
 // the evidence file (inq_call_args_t::evidence_path; not a reference output): its header, and the line of one target
 extern const char *const kEvidenceHeader;
 void append_evidence_row(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_locus_evidence_t &e);
+// the read-calls file (inq_genotype_repeats_reads; not a reference output): its header, and the line of one target from the records of its
+// kept reads in file order - h1 / h2 are the Calls median_str_length is handed for phase1 / phase2, ascending by (value, file order)
+extern const char *const kReadCallsHeader;
+void append_read_calls_row(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls, size_t n,
+                           bool unphased);
 // src/call.rs:91-100: file_stem, then every ".bam" and ".cram" removed
 std::string sample_name_from_path(const std::string &bam_path);
 // [3P] human_sort::compare as used by Genotype::cmp (src/call.rs:33-38): <0, 0, >0

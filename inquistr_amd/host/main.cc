@@ -31,6 +31,7 @@ static void usage(FILE *f) {
         "      --ctx-option <KEY=VALUE>     a device-context option (include/inquistr_hip.h, inq_ctx_set_option), repeatable\n"
         "      --ties <FILE>                write the loci whose unphased split is tie-ambiguous there, as BED (empty when phased)\n"
         "      --evidence <FILE>            write the read evidence behind every row there: fetched, kept, h1, h2, clipped, min, max\n"
+        "      --read-calls <FILE>          write the per-read Calls behind every row's two medians there: h1, h2, other\n"
         "  -h, --help                       Print help\n",
         f);
 }
@@ -231,6 +232,7 @@ int main(int argc, char **argv) {
     a.support = 3;
     a.threads = 1;
     std::string bam;
+    const char *read_calls_path = nullptr;  // --read-calls (not a field of inq_call_args_t: inq_genotype_repeats_reads takes it)
     std::vector<int32_t> devices;  // --devices: one part of the targets per entry (an ordinal may repeat: N parts on one GPU)
     std::vector<std::pair<std::string, long long>> ctx_options;  // --ctx-option key=value
     auto num = [&](const char *s, const char *flag) -> unsigned long long {
@@ -263,6 +265,7 @@ int main(int argc, char **argv) {
         else if (key == "--device") a.device = (int32_t)num(val(), "--device");
         else if (key == "--ties") a.ties_path = val();
         else if (key == "--evidence") a.evidence_path = val();
+        else if (key == "--read-calls") read_calls_path = val();
         else if (key == "--devices") {
             const std::string list = val();
             for (size_t b = 0; b <= list.size();) {
@@ -308,7 +311,7 @@ int main(int argc, char **argv) {
         char err[1024] = {0};
         ::setenv("INQ_FAST_EXIT", "1", 0);
         std::vector<inq_part_stats_t> st(devices.size());
-        int rc = inq::host_api().genotype_repeats_devices(&a, devices.data(), devices.size(), 1 /* stdout */, st.data(), err, sizeof err);
+        int rc = inq::host_api().genotype_repeats_reads(&a, devices.data(), devices.size(), 1 /* stdout */, read_calls_path, st.data(), err, sizeof err);
         complain(rc, err);
         if (std::getenv("INQ_TIMING"))
             for (size_t r = 0; r < st.size(); ++r)
@@ -324,6 +327,10 @@ int main(int argc, char **argv) {
     if (const char *server_env = std::getenv("INQ_SERVER"); server_env && *server_env) {
         if (a.evidence_path) {  // a server's calls run on a session, which writes no evidence file: said here, before a server is looked for
             std::fputs("error: '--evidence <FILE>' cannot be used with INQ_SERVER set: a server does not write the evidence file\n", stderr);
+            return 2;
+        }
+        if (read_calls_path) {  // ... and no read-calls file
+            std::fputs("error: '--read-calls <FILE>' cannot be used with INQ_SERVER set: a server does not write the read-calls file\n", stderr);
             return 2;
         }
         // INQ_SERVER=auto: this user's server for the device, started (detached; it leaves after INQ_SERVER_IDLE seconds without a
@@ -355,5 +362,5 @@ int main(int argc, char **argv) {
     }
     char err[1024] = {0};
     ::setenv("INQ_FAST_EXIT", "1", 0);  // this process ends with the call: see leave()
-    return leave(inq::host_api().genotype_repeats(&a, 1 /* stdout */, err, sizeof err), err);
+    return leave(inq::host_api().genotype_repeats_reads(&a, nullptr, 0, 1 /* stdout */, read_calls_path, nullptr, err, sizeof err), err);
 }

@@ -136,15 +136,23 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
     // the evidence file, likewise: a target no batch or span holds keeps its zeros
     const bool want_evidence = hooks.evidence_out || hooks.evidence_fd >= 0;
     std::vector<inq_locus_evidence_t> evidence(want_evidence ? n : 0, inq_locus_evidence_t{});
+    // the read-calls file, likewise: a target no batch or span holds keeps its empty list
+    const bool want_read_calls = hooks.read_calls_out || hooks.read_calls_fd >= 0;
+    ReadCallLists own_lists(want_read_calls && !hooks.read_calls_out ? n : 0);
+    ReadCallLists *const lists = !want_read_calls ? nullptr : hooks.read_calls_out ? hooks.read_calls_out : &own_lists;
     const bool rows_on_device = rows.active && rows.d1 && rows.d2;
     if (rows_on_device && rows.dcap < n) {
         set_err(errbuf, errcap, "device row arrays smaller than the target list");
         return INQ_EXIT_ERROR;
     }
     auto emit = [&]() -> int {
-        if (!rows.active)
-            return write_rows(args->threads, V.targets, V.sample, p1.data(), p2.data(), out_fd, errbuf, errcap, want_ties ? ties.data() : nullptr,
-                              hooks.ties_fd, want_evidence ? evidence.data() : nullptr, hooks.evidence_fd);
+        if (!rows.active) {
+            RowReports rr;
+            rr.ties = want_ties ? ties.data() : nullptr, rr.ties_fd = hooks.ties_fd;
+            rr.evidence = want_evidence ? evidence.data() : nullptr, rr.evidence_fd = hooks.evidence_fd;
+            rr.read_calls = lists, rr.read_calls_fd = hooks.read_calls_fd, rr.unphased = V.opt.unphased;
+            return write_rows(args->threads, V.targets, V.sample, p1.data(), p2.data(), out_fd, errbuf, errcap, rr);
+        }
         if (hooks.ties_out && n) std::memcpy(hooks.ties_out, ties.data(), n);
         if (hooks.evidence_out && n) std::memcpy(hooks.evidence_out, evidence.data(), n * sizeof(inq_locus_evidence_t));
         if (rows_on_device) return INQ_EXIT_OK;  // (device front end: they are there; host sweep: written below)
@@ -169,6 +177,7 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
         if (rows_on_device) dh.dev_p1 = rows.d1, dh.dev_p2 = rows.d2, dh.dev_cap = rows.dcap;
         dh.ties_out = want_ties ? ties.data() : nullptr;  // (indexed like p1 / p2)
         dh.evidence_out = want_evidence ? evidence.data() : nullptr;
+        dh.read_calls_out = lists;
         int drc = run_device_front(args, V, actx, p1, p2, errbuf, errcap, &t_front, &t_dev, dh);
         if (drc != INQ_EXIT_OK) return drc;
         const auto t_run = Clock::now();
@@ -258,16 +267,18 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
             batch.locus_start = (const uint32_t *)put(batch.locus_start, batch.n_loci * 4, off, s4);
             batch.locus_end = (const uint32_t *)put(batch.locus_end, batch.n_loci * 4, off, s4);
         }
-        br.begin(batch.n_loci, want_ties, want_evidence);
+        br.begin(batch.n_loci, want_ties, want_evidence, want_read_calls);
         auto tc = Clock::now();
-        int rc2 = inq_call_batch_evidence(ctx, &batch, &br.res, br.flags, br.evidence);  // (null flags / evidence: inq_call_batch)
+        // (null flags / evidence / kept_off: inq_call_batch)
+        int rc2 = inq_call_batch_reads(ctx, &batch, &br.res, br.flags, br.evidence, br.kept_off);
+        if (rc2 == INQ_OK) rc2 = br.fetch_read_calls(ctx);
         t_dev += secs(tb, Clock::now());
         if (timing == 2)
             std::fprintf(stderr, "[inq batch] loci %llu pairs %llu cigar %.1f MB  wait-ctx %.2f ms  call %.2f ms\n",
                          (unsigned long long)batch.n_loci, (unsigned long long)batch.n_pairs, batch.n_cigar_words * 4 / 1e6,
                          secs(tb, tc) * 1e3, secs(tc, Clock::now()) * 1e3);
         if (rc2 != INQ_OK) return device_call_failed(rc2, ctx, errbuf, errcap);
-        br.scatter_to(item.index.data(), p1.data(), p2.data(), ties.data(), evidence.data());
+        br.scatter_to(item.index.data(), p1.data(), p2.data(), ties.data(), evidence.data(), lists);
         pfe.recycle(std::move(item));
     }
     if (!need_ctx()) return INQ_EXIT_ERROR;  // no GPU is an error even for an empty target list
@@ -380,9 +391,30 @@ int write_evidence(const std::vector<uint32_t> &order, const std::vector<RepeatI
     return INQ_EXIT_OK;
 }
 
+int write_read_calls(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const ReadCallLists &lists, bool unphased,
+                     int fd, char *errbuf, size_t errcap) {
+    std::string text = std::string(kReadCallsHeader) + '\n';
+    for (const uint32_t i : order) {
+        const RepeatInterval &t = targets[i];
+        append_read_calls_row(text, t.chrom, t.start, t.end, lists[i].data(), lists[i].size(), unphased);
+        text += '\n';
+        if (text.size() >= (8u << 20)) {  // deep loci make long lines: written as it grows
+            if (!write_all(fd, text)) break;
+            text.clear();
+        }
+    }
+    if (!write_all(fd, text)) {
+        set_err(errbuf, errcap, "Failed writing the read-calls file.");
+        return INQ_EXIT_ERROR;
+    }
+    return INQ_EXIT_OK;
+}
+
 int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, const std::string &sample, const double *p1,
-                      const double *p2, int out_fd, char *errbuf, size_t errcap, const uint8_t *ties, int ties_fd,
-                      const inq_locus_evidence_t *evidence, int evidence_fd) {
+                      const double *p2, int out_fd, char *errbuf, size_t errcap, const RowReports &reports) {
+    const uint8_t *const ties = reports.ties;
+    const inq_locus_evidence_t *const evidence = reports.evidence;
+    const int ties_fd = reports.ties_fd, evidence_fd = reports.evidence_fd;
     const size_t n = targets.size();
     const auto t_w0 = Clock::now();
     const std::vector<uint32_t> order = row_order(threads, targets);
@@ -443,6 +475,10 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
     if (evidence && evidence_fd >= 0) {  // the evidence file, one line per row
         const int erc = write_evidence(order, targets, evidence, evidence_fd, errbuf, errcap);
         if (erc != INQ_EXIT_OK) return erc;
+    }
+    if (reports.read_calls && reports.read_calls_fd >= 0) {  // the read-calls file, one line per row
+        const int rrc = write_read_calls(order, targets, *reports.read_calls, reports.unphased, reports.read_calls_fd, errbuf, errcap);
+        if (rrc != INQ_EXIT_OK) return rrc;
     }
     if (timing_level())
         std::fprintf(stderr, "[inq output] %zu rows: order %.2f ms, bounds %.2f ms, text %.2f ms (%zu threads), write %.2f ms\n", n, ms(t_w0, t_w1), ms(t_w1, t_w1b), ms(t_w1b, t_w2),
@@ -537,11 +573,12 @@ static int inq_frontend_next_impl(inq_frontend_t *fe, inq_batch_t *batch, const 
 void inq_frontend_close(inq_frontend_t *fe) { delete fe; }
 
 
-static int inq_genotype_repeats_impl(const inq_call_args_t *args, int out_fd, char *errbuf, size_t errcap, const RowsOut &rows = RowsOut()) {
+static int inq_genotype_repeats_impl(const inq_call_args_t *args, int out_fd, char *errbuf, size_t errcap, const RowsOut &rows = RowsOut(),
+                                     const char *read_calls_path = nullptr) {
     const auto t_start = Clock::now();
     std::string msg;
     CallReports files;  // (a call that returns rows writes no file: the tie report is left out, the evidence file refused)
-    if (args && (rows.active ? refuse_evidence(args, "inq_genotype_repeats_rows", msg) : files.open(*args, msg)) != INQ_EXIT_OK) {
+    if (args && (rows.active ? refuse_evidence(args, "inq_genotype_repeats_rows", msg) : files.open(*args, read_calls_path, msg)) != INQ_EXIT_OK) {
         set_err(errbuf, errcap, msg);
         return INQ_EXIT_ERROR;
     }
@@ -557,6 +594,12 @@ static int inq_genotype_repeats_impl(const inq_call_args_t *args, int out_fd, ch
     actx.leak = rc == INQ_EXIT_OK && hooks.process_is_leaving;  // only after a clean run: error paths tear down normally
     return rc;
 }
+
+}  // extern "C"
+int inqhost::genotype_single(const inq_call_args_t *args, int out_fd, const char *read_calls_path, char *errbuf, size_t errcap) {
+    return inq_genotype_repeats_impl(args, out_fd, errbuf, errcap, RowsOut(), read_calls_path);
+}
+extern "C" {
 
 int inq_frontend_open(const inq_call_args_t *args, inq_frontend_t **out, char *errbuf, size_t errcap) {
     INQ_GUARD(inq_frontend_open_impl(args, out, errbuf, errcap), errbuf, errcap)

@@ -546,18 +546,20 @@ int run_device_front(const inq_call_args_t *args, const CallView &V, AsyncCtx &a
         if (pending.empty()) return INQ_EXIT_OK;
         const auto f0 = Clock::now();
         // (rows that stay on the device belong to a prepared run, which takes no evidence: run.cc inq_run_open_impl)
-        br.begin(pending.size(), hooks.ties_out != nullptr, hooks.evidence_out != nullptr && !hooks.dev_p1);
+        br.begin(pending.size(), hooks.ties_out != nullptr, hooks.evidence_out != nullptr && !hooks.dev_p1,
+                 hooks.read_calls_out != nullptr && !hooks.dev_p1);
         double ms_call = 0;
         // (rows that travel on from device memory stay there: pending[j] is the row's place in the caller's device arrays)
         int rc2 = hooks.dev_p1 ? inq_call_flush_device_flags(ctx, hooks.dev_p1, hooks.dev_p2, hooks.dev_cap, pending.data(), pending.size(), nullptr,
                                                              &ms_call, br.flags)
-                               : inq_call_flush_evidence(ctx, &br.res, pending.size(), &ms_call, br.flags, br.evidence);
+                               : inq_call_flush_reads(ctx, &br.res, pending.size(), &ms_call, br.flags, br.evidence, br.kept_off);
+        if (rc2 == INQ_OK) rc2 = br.fetch_read_calls(ctx);
         *t_dev += secs(f0, Clock::now());
         if (timing == 2)
             std::fprintf(stderr, "[inq call] @%.1f %zu loci, %.1f MB of CIGARs: locus kernels %.3f ms | wall %.2f ms\n", stamp_ms(), pending.size(),
                          pending_words * 4 / 1e6, ms_call, secs(f0, Clock::now()) * 1e3);
         if (rc2 != INQ_OK) return device_call_failed(rc2, ctx, errbuf, errcap);
-        br.scatter_to(pending.data(), hooks.dev_p1 ? nullptr : p1.data(), p2.data(), hooks.ties_out, hooks.evidence_out);
+        br.scatter_to(pending.data(), hooks.dev_p1 ? nullptr : p1.data(), p2.data(), hooks.ties_out, hooks.evidence_out, hooks.read_calls_out);
         pending.clear();
         pending_words = 0;
         return INQ_EXIT_OK;
