@@ -109,12 +109,12 @@ def genotype_repeats_distributed(bamp: str, region: Optional[str], region_file: 
     t_open = time.perf_counter()
     st, msg = 0, ""
     run = None
-    ties_out = None
+    ties_file = None
     order, cuts, digest = None, None, 0
     try:
         if ties is not None and rank == 0:  # created before any device work, as by the one-process call
             try:
-                ties_out = open(ties, "w")
+                ties_file = open(ties, "w")
             except OSError as e:
                 raise hostcall.CallError(1, f"cannot write the tie report {ties}: {e.strerror}")
         sess = _process_session(device) if (compute is None and session is None) else session
@@ -141,8 +141,8 @@ def genotype_repeats_distributed(bamp: str, region: Optional[str], region_file: 
     if st != 0:
         if run is not None:
             run.close()
-        if ties_out is not None:
-            ties_out.close()
+        if ties_file is not None:
+            ties_file.close()
         raise hostcall.CallError(st, msg)
     if stats is not None:
         stats["open_s"] = time.perf_counter() - t_open  # header + index + BED + the cut (+ the exchange's wait for the slowest rank)
@@ -214,8 +214,8 @@ def genotype_repeats_distributed(bamp: str, region: Optional[str], region_file: 
     st, msg, bad_rank = _exchange_status(st, msg, rank, world, group)
     if st != 0:
         run.close()
-        if ties_out is not None:
-            ties_out.close()
+        if ties_file is not None:
+            ties_file.close()
         if own_failure == 1 and compute is None and session is None:
             # an error exit of THIS rank's device work (HIP, memory, no device - not one of the reference's panics, which a session
             # survives): the process's session is given up, the next call makes a new context
@@ -274,11 +274,11 @@ def genotype_repeats_distributed(bamp: str, region: Optional[str], region_file: 
     t0 = time.perf_counter()
     try:
         run.write_inq(full1, full2, out)
-        if ties_out is not None:
-            run.write_ties(full_t, ties_out)
+        if ties_file is not None:
+            run.write_ties(full_t, ties_file)
     finally:
-        if ties_out is not None:
-            ties_out.close()
+        if ties_file is not None:
+            ties_file.close()
     if stats is not None:
         stats["output_s"] = time.perf_counter() - t0
         stats["rows"] = n

@@ -322,17 +322,13 @@ static int check_scalars(const inq_batch_t *b, const inq_result_t *r) {
     return INQ_OK;
 }
 
-// d_flags: DEVICE [n_loci] per-locus flags (INQ_LOCUS_TIE), or null - then nothing is added to the launch sequence
-// d_evidence: DEVICE [n_loci] per-locus evidence, or null - then nothing is added to the launch sequence and nothing is allocated
-// d_kept_off / d_kept: DEVICE [n_loci + 1] / [n_pairs] per-read Calls (both or neither), or null - then nothing is added and nothing allocated
-static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, uint8_t *d_flags = nullptr,
-                         inq_locus_evidence_t *d_evidence = nullptr, uint64_t *d_kept_off = nullptr, inq_read_call_t *d_kept = nullptr) {
+static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, const LocusExtras &x = LocusExtras()) {
     if (!c) return INQ_ERR_ARG;
     int rc = check_scalars(b, r);
     if (rc != INQ_OK) return rc;
-    if (d_evidence && b->n_pairs && (!r->pair_call || !r->pair_bits)) return INQ_ERR_ARG;  // the counting reads both
-    if (!d_kept_off != !d_kept || ((uintptr_t)d_kept & 15u) || ((uintptr_t)d_kept_off & 7u)) return INQ_ERR_ARG;
-    if (d_kept && b->n_pairs && (!r->pair_call || !r->pair_bits)) return INQ_ERR_ARG;  // ... and so does the compaction
+    if (x.evidence && b->n_pairs && (!r->pair_call || !r->pair_bits)) return INQ_ERR_ARG;  // the counting reads both
+    if (!x.kept_off != !x.kept || ((uintptr_t)x.kept & 15u) || ((uintptr_t)x.kept_off & 7u)) return INQ_ERR_ARG;
+    if (x.kept && b->n_pairs && (!r->pair_call || !r->pair_bits)) return INQ_ERR_ARG;  // ... and so does the compaction
     if (((uintptr_t)b->cigar & 15u) || ((uintptr_t)b->reads & 15u)) return INQ_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
@@ -349,9 +345,9 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     const bool deep_possible = b->n_pairs > kGridSelectMin && !(hint && hint <= kGridSelectMin);
     if (deep_possible && (rc = ensure(c, c->deep, deep_select_scratch_bytes(b->n_pairs))) != INQ_OK) return rc;
     // evidence: the slice list of the loci one wave does not count; no list and no second launch when the depth hint rules them out
-    const uint64_t ev_list_cap = d_evidence && b->n_pairs > kEvidenceWaveMax && !(hint && hint <= kEvidenceWaveMax) ? evidence_list_cap(b->n_pairs) : 0;
-    if (d_evidence && (rc = ensure(c, c->evwork, evidence_scratch_bytes(ev_list_cap))) != INQ_OK) return rc;
-    if (d_kept && b->n_pairs && (rc = ensure(c, c->rctiles, read_call_scratch_bytes(b->n_pairs))) != INQ_OK) return rc;
+    const uint64_t ev_list_cap = x.evidence && b->n_pairs > kEvidenceWaveMax && !(hint && hint <= kEvidenceWaveMax) ? evidence_list_cap(b->n_pairs) : 0;
+    if (x.evidence && (rc = ensure(c, c->evwork, evidence_scratch_bytes(ev_list_cap))) != INQ_OK) return rc;
+    if (x.kept && b->n_pairs && (rc = ensure(c, c->rctiles, read_call_scratch_bytes(b->n_pairs))) != INQ_OK) return rc;
 
     KArgs a;
     a.cigar4 = (const uint4 *)b->cigar;
@@ -378,46 +374,28 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     a.shard_cap = shard_cap;
     c->call_hint = 0;
     a.max_reads_hint = hint;
-    a.locus_flags = d_flags;
+    a.locus_flags = x.flags;
 
     // CIGAR words of a read referenced by one locus only are read exactly once: stream them past the
     // caches (nt).  Reads shared by neighbouring loci keep the default policy so the second locus hits L2.
     const bool nt = c->nt_loads < 0 ? (b->n_pairs <= b->n_reads) : (c->nt_loads != 0);
     EvTriple *ev;
     if ((rc = timing_begin(c, s, &ev)) != INQ_OK) return rc;
-    if (d_flags) HIP_TRY(c, hipMemsetAsync(d_flags, 0, (size_t)b->n_loci, s));  // the kernels store tie loci only
-    if (d_evidence) HIP_TRY(c, hipMemsetAsync(c->evwork.p, 0, sizeof(EvidenceWork), s));  // the slice list starts empty
+    if (x.flags) HIP_TRY(c, hipMemsetAsync(x.flags, 0, (size_t)b->n_loci, s));  // the kernels store tie loci only
+    if (x.evidence) HIP_TRY(c, hipMemsetAsync(c->evwork.p, 0, sizeof(EvidenceWork), s));  // the slice list starts empty
     launch_locus_call(a, b->unphased != 0, nt, grid_small, c->grid_medium, c->grid_tail, s, ev ? ev->e1 : nullptr, deep_possible ? c->deep.p : nullptr);
     HIP_TRY(c, hipGetLastError());
-    if (d_evidence) {
-        EvidenceArgs ea;
-        ea.locus_pair_off = b->locus_pair_off;
-        ea.pair_bits = r->pair_bits;
-        ea.pair_call = r->pair_call;
-        ea.pair_read = b->pair_read;
-        ea.read_words = (const uint32_t *)b->reads;
-        ea.n_reads = b->n_reads, ea.n_pairs = b->n_pairs, ea.n_loci = b->n_loci;
-        ea.evidence = d_evidence;
-        ea.work = (EvidenceWork *)c->evwork.p;
-        ea.list = (EvidenceSlice *)((char *)c->evwork.p + sizeof(EvidenceWork));
-        ea.list_cap = ev_list_cap;
-        launch_evidence(ea, b->unphased != 0, c->n_cus * 4u, s);
+    // what both kernels behind the locus kernels read: the batch's pairs, and what was just written for each
+    const PairView view{b->locus_pair_off, r->pair_bits, r->pair_call, b->pair_read, (const uint32_t *)b->reads, b->n_reads, b->n_pairs, b->n_loci};
+    if (x.evidence) {
+        EvidenceWork *const work = (EvidenceWork *)c->evwork.p;
+        launch_evidence(EvidenceArgs{view, x.evidence, work, (EvidenceSlice *)(work + 1), ev_list_cap}, b->unphased != 0, c->n_cus * 4u, s);
         HIP_TRY(c, hipGetLastError());
     }
-    if (d_kept && !b->n_pairs) HIP_TRY(c, hipMemsetAsync(d_kept_off, 0, (size_t)(b->n_loci + 1) * 8, s));  // no pair: every list is empty
-    if (d_kept && b->n_pairs) {
-        ReadCallArgs ra;
-        ra.locus_pair_off = b->locus_pair_off;
-        ra.pair_bits = r->pair_bits;
-        ra.pair_call = r->pair_call;
-        ra.pair_read = b->pair_read;
-        ra.read_words = (const uint32_t *)b->reads;
-        ra.n_reads = b->n_reads, ra.n_pairs = b->n_pairs, ra.n_loci = b->n_loci;
-        ra.kept_off = d_kept_off;
-        ra.kept = d_kept;
-        ra.tile_base = (uint64_t *)c->rctiles.p;
-        ra.tile_count = (uint32_t *)(ra.tile_base + read_call_tiles(b->n_pairs) + 1);
-        launch_read_calls(ra, b->unphased != 0, s);
+    if (x.kept && !b->n_pairs) HIP_TRY(c, hipMemsetAsync(x.kept_off, 0, (size_t)(b->n_loci + 1) * 8, s));  // no pair: every list is empty
+    if (x.kept && b->n_pairs) {
+        uint64_t *const tile_base = (uint64_t *)c->rctiles.p;
+        launch_read_calls(ReadCallArgs{view, x.kept_off, x.kept, (uint32_t *)(tile_base + read_call_tiles(b->n_pairs) + 1), tile_base}, b->unphased != 0, s);
         HIP_TRY(c, hipGetLastError());
     }
     if (ev) HIP_TRY(c, hipEventRecord(ev->e2, s));
@@ -439,7 +417,7 @@ int inq_call_batch_device_evidence(inq_ctx_t *c, const inq_batch_t *b, inq_resul
 
 int inq_call_batch_device_reads(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *d_locus_flags, inq_locus_evidence_t *d_evidence,
                                 uint64_t *d_kept_off, inq_read_call_t *d_kept, void *hip_stream) {
-    return guarded([&] { return enqueue_batch(c, b, r, hip_stream, d_locus_flags, d_evidence, d_kept_off, d_kept); });
+    return guarded([&] { return enqueue_batch(c, b, r, hip_stream, LocusExtras{d_locus_flags, d_evidence, d_kept_off, d_kept}); });
 }
 
 uint32_t inq_read_call_tile(void) { return kReadCallTile; }
@@ -467,10 +445,9 @@ int inq_ctx_status(inq_ctx_t *c, uint64_t *n_tie_loci) {
     return status_to_code(c->h_status->err);
 }
 
-static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *h_flags, inq_locus_evidence_t *h_evidence,
-                           uint64_t *h_kept_off) {
+static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, const HostExtras &h) {
     if (!c) return INQ_ERR_ARG;
-    c->read_calls_total = 0;  // (the records of the call before are no longer offered)
+    extras_reset(c);
     int rc = check_scalars(b, r);
     if (rc != INQ_OK) return rc;
     // host-side shape checks: everything the grid and the kernels' indexing assume
@@ -485,7 +462,7 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
     }
     r->n_tie_loci = 0;
     if (b->n_loci == 0) {
-        if (h_kept_off) h_kept_off[0] = 0;
+        extras_finish(c, 0, 0, h, 0);
         return INQ_OK;
     }
     HIP_TRY(c, hipSetDevice(c->device));
@@ -508,29 +485,19 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
     }
     if ((rc = ensure(c, c->p1, (size_t)b->n_loci * 8)) != INQ_OK) return rc;
     if ((rc = ensure(c, c->p2, (size_t)b->n_loci * 8)) != INQ_OK) return rc;
-    // (the evidence is counted and the lists are compacted from the per-pair outputs: they are kept in scratch also when the caller does
-    // not want them)
-    const bool want_call = r->pair_call || h_evidence || h_kept_off, want_bits = r->pair_bits || h_evidence || h_kept_off;
-    if (want_call && (rc = ensure(c, c->pcall, (size_t)b->n_pairs * 8)) != INQ_OK) return rc;
-    if (want_bits && (rc = ensure(c, c->pbits, (size_t)b->n_pairs)) != INQ_OK) return rc;
-    if (h_flags && (rc = ensure(c, c->lflags, (size_t)b->n_loci)) != INQ_OK) return rc;
-    if (h_evidence && (rc = ensure(c, c->levidence, (size_t)b->n_loci * sizeof(inq_locus_evidence_t))) != INQ_OK) return rc;
-    if (h_kept_off && (rc = ensure(c, c->rcoff, (size_t)(b->n_loci + 1) * 8)) != INQ_OK) return rc;
-    if (h_kept_off && (rc = ensure(c, c->rckept, (size_t)b->n_pairs * sizeof(inq_read_call_t))) != INQ_OK) return rc;
+    const bool want_call = r->pair_call || h.per_pair(), want_bits = r->pair_bits || h.per_pair();
+    if (r->pair_call && (rc = ensure(c, c->pcall, (size_t)b->n_pairs * 8)) != INQ_OK) return rc;
+    if (r->pair_bits && (rc = ensure(c, c->pbits, (size_t)b->n_pairs)) != INQ_OK) return rc;
+    LocusExtras x;
+    if ((rc = extras_prepare(c, b->n_loci, b->n_pairs, h, &x)) != INQ_OK) return rc;
 
     DevBatch d = device_batch(c->cigar.p, c->reads.p, c->pair_read.p, c->off.p, c->lstart.p, c->lend.p, b->n_reads, b->n_cigar_words,
                               b->n_pairs, b->n_loci, b->minlen, b->support, b->unphased, c->p1.p, c->p2.p,
                               want_call ? c->pcall.p : nullptr, want_bits ? c->pbits.p : nullptr);
     const inq_result_t &dr = d.r;
     c->call_hint = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(max_reads, 1), 0xffffffffull);  // skips the deep-locus launches when no locus needs them
-    uint8_t *d_flags = h_flags ? (uint8_t *)c->lflags.p : nullptr;
-    inq_locus_evidence_t *d_evidence = h_evidence ? (inq_locus_evidence_t *)c->levidence.p : nullptr;
-    uint64_t *d_kept_off = h_kept_off ? (uint64_t *)c->rcoff.p : nullptr;
-    if ((rc = enqueue_batch(c, &d.b, &d.r, s, d_flags, d_evidence, d_kept_off, h_kept_off ? (inq_read_call_t *)c->rckept.p : nullptr)) != INQ_OK)
-        return rc;
-    if (h_kept_off) HIP_TRY(c, hipMemcpyAsync(h_kept_off, d_kept_off, (size_t)(b->n_loci + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (h_flags) HIP_TRY(c, hipMemcpyAsync(h_flags, d_flags, (size_t)b->n_loci, hipMemcpyDeviceToHost, s));
-    if (h_evidence) HIP_TRY(c, hipMemcpyAsync(h_evidence, d_evidence, (size_t)b->n_loci * sizeof(inq_locus_evidence_t), hipMemcpyDeviceToHost, s));
+    if ((rc = enqueue_batch(c, &d.b, &d.r, s, x)) != INQ_OK) return rc;
+    if ((rc = extras_download(c, b->n_loci, h, x, h.flags, s)) != INQ_OK) return rc;  // (the flags: straight to the caller's array)
     HIP_TRY(c, hipMemcpyAsync(r->phase1, dr.phase1, (size_t)b->n_loci * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(r->phase2, dr.phase2, (size_t)b->n_loci * 8, hipMemcpyDeviceToHost, s));
     if (r->pair_call && b->n_pairs)
@@ -541,8 +508,7 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
     HIP_TRY(c, hipStreamSynchronize(s));  // the one synchronisation of the call
     purge_retired(c);  // the stream is idle: buffers this call outgrew go back now
     r->n_tie_loci = c->h_status->ties;
-    // (after a domain error the lists are unspecified: none is offered, whatever the offsets say)
-    if (h_kept_off && c->h_status->err == 0) c->read_calls_total = std::min<uint64_t>(h_kept_off[b->n_loci], b->n_pairs);
+    extras_finish(c, b->n_loci, b->n_pairs, h, c->h_status->err);
     return status_to_code(c->h_status->err);
 }
 
@@ -558,7 +524,7 @@ int inq_call_batch_evidence(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r,
 
 int inq_call_batch_reads(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, uint8_t *locus_flags, inq_locus_evidence_t *evidence,
                          uint64_t *kept_off) {
-    return guarded([&] { return call_batch_impl(c, b, r, locus_flags, evidence, kept_off); });
+    return guarded([&] { return call_batch_impl(c, b, r, HostExtras{locus_flags, evidence, kept_off}); });
 }
 
 static int outlier_rows_impl(inq_ctx_t *c, const float *values, const uint32_t *row_len, uint64_t n_rows, uint32_t stride,
@@ -803,8 +769,34 @@ void inq_free_pinned(void *p) {
 
 }  // extern "C"
 
-int inq::call_batch_device_impl(inq_ctx *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, uint8_t *d_locus_flags,
-                                inq_locus_evidence_t *d_evidence, uint64_t *d_kept_off, inq_read_call_t *d_kept) {
-    return enqueue_batch(c, b, r, hip_stream, d_locus_flags, d_evidence, d_kept_off, d_kept);
+int inq::call_batch_device_impl(inq_ctx *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, const LocusExtras &x) {
+    return enqueue_batch(c, b, r, hip_stream, x);
 }
 
+int inq::extras_prepare(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const HostExtras &h, LocusExtras *d) {
+    int rc;
+    if (h.flags && (rc = ensure(c, c->lflags, (size_t)n_loci)) != INQ_OK) return rc;
+    if (h.per_pair() && (rc = ensure(c, c->pcall, (size_t)n_pairs * 8)) != INQ_OK) return rc;
+    if (h.per_pair() && (rc = ensure(c, c->pbits, (size_t)n_pairs)) != INQ_OK) return rc;
+    if (h.evidence && (rc = ensure(c, c->levidence, (size_t)n_loci * sizeof(inq_locus_evidence_t))) != INQ_OK) return rc;
+    if (h.kept_off && (rc = ensure(c, c->rcoff, (size_t)(n_loci + 1) * 8)) != INQ_OK) return rc;
+    if (h.kept_off && (rc = ensure(c, c->rckept, (size_t)n_pairs * sizeof(inq_read_call_t))) != INQ_OK) return rc;
+    d->flags = h.flags ? (uint8_t *)c->lflags.p : nullptr;
+    d->evidence = h.evidence ? (inq_locus_evidence_t *)c->levidence.p : nullptr;
+    d->kept_off = h.kept_off ? (uint64_t *)c->rcoff.p : nullptr;
+    d->kept = h.kept_off ? (inq_read_call_t *)c->rckept.p : nullptr;
+    return INQ_OK;
+}
+
+int inq::extras_download(inq_ctx *c, uint64_t n_loci, const HostExtras &h, const LocusExtras &d, uint8_t *flags_dst, hipStream_t s) {
+    if (h.flags) HIP_TRY(c, hipMemcpyAsync(flags_dst, d.flags, (size_t)n_loci, hipMemcpyDeviceToHost, s));
+    if (h.evidence) HIP_TRY(c, hipMemcpyAsync(h.evidence, d.evidence, (size_t)n_loci * sizeof(inq_locus_evidence_t), hipMemcpyDeviceToHost, s));
+    if (h.kept_off) HIP_TRY(c, hipMemcpyAsync(h.kept_off, d.kept_off, (size_t)(n_loci + 1) * 8, hipMemcpyDeviceToHost, s));
+    return INQ_OK;
+}
+
+void inq::extras_finish(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const HostExtras &h, uint32_t err) {
+    if (!h.kept_off) return;
+    if (!n_loci) h.kept_off[0] = 0;  // (nothing was launched: no list, no record)
+    if (err == 0) c->read_calls_total = std::min<uint64_t>(h.kept_off[n_loci], n_pairs);
+}

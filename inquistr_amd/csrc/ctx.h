@@ -150,9 +150,36 @@ int ensure(inq_ctx *c, DevBuf &b, size_t bytes);
 int device_alloc(inq_ctx *c, void **out, size_t want, size_t exact, size_t *got);
 void retire(inq_ctx *c, void *p, size_t bytes);
 void purge_retired(inq_ctx *c);  // hipFree of everything retired (waits for the device: call where it is idle)
+// The per-locus side outputs of a call, as the launch sequence takes them: all DEVICE pointers.  Null = not asked for: nothing is added
+// to the launch sequence and nothing is allocated.  A further per-locus output is one more member here and in HostExtras.
+struct LocusExtras {
+    uint8_t *flags = nullptr;                  // [n_loci] INQ_LOCUS_TIE
+    inq_locus_evidence_t *evidence = nullptr;  // [n_loci]
+    uint64_t *kept_off = nullptr;              // [n_loci + 1] the per-read Calls: offsets ...
+    inq_read_call_t *kept = nullptr;           // [n_pairs] ... and records; both or neither
+};
+// ... and as a host-buffer call or a flush takes them: HOST pointers, [n_loci] / [n_loci] / [n_loci + 1] in the call's locus order, each
+// may be null.  The records behind kept_off stay in context scratch (inq_read_calls_fetch).
+struct HostExtras {
+    uint8_t *flags = nullptr;
+    inq_locus_evidence_t *evidence = nullptr;
+    uint64_t *kept_off = nullptr;
+    // the evidence is counted and the lists are compacted from the per-pair outputs: the call keeps those (pcall / pbits) also when
+    // its caller did not ask for them
+    bool per_pair() const { return evidence || kept_off; }
+};
+// The three steps of a host-buffer call or a flush around its launch sequence.  First of all extras_reset: the records of the call
+// before are no longer offered, however this one ends.
+inline void extras_reset(inq_ctx *c) { c->read_calls_total = 0; }
+// the context buffers behind what h asks for (and pcall / pbits where h.per_pair()), as device pointers
+int extras_prepare(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const HostExtras &h, LocusExtras *d);
+// enqueues the copies down on s; the flags go to flags_dst (the caller's array, or page-locked staging on their way there)
+int extras_download(inq_ctx *c, uint64_t n_loci, const HostExtras &h, const LocusExtras &d, uint8_t *flags_dst, hipStream_t s);
+// after the call's synchronisation, or at once for a call without loci: how many records inq_read_calls_fetch offers.  err: the
+// kernels' status word - after a domain error the lists are unspecified and none is offered, whatever the offsets say
+void extras_finish(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const HostExtras &h, uint32_t err);
 // enqueue-only launch sequence of the locus kernels over a device-resident batch
-int call_batch_device_impl(inq_ctx *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, uint8_t *d_locus_flags = nullptr,
-                           inq_locus_evidence_t *d_evidence = nullptr, uint64_t *d_kept_off = nullptr, inq_read_call_t *d_kept = nullptr);
+int call_batch_device_impl(inq_ctx *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, const LocusExtras &x = LocusExtras());
 int status_to_code(uint32_t st);
 // The kernels' status travels with the results: enqueues DevStatus -> dst (page-locked), then clears err and ties on the same stream,
 // i.e. before the next call's kernels (the work-list counters stay).  No synchronisation: dst is valid once the caller has waited for s.

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/inquistr_hip.h"
+#include "pair_view.h"
 
 namespace inq {
 
@@ -21,13 +22,7 @@ struct EvidenceWork {
     unsigned long long pad;
 };
 
-struct EvidenceArgs {
-    const uint64_t *locus_pair_off;  // [n_loci + 1]
-    const uint8_t *pair_bits;        // [n_pairs] INQ_PAIR_*, as the locus kernels left them
-    const int64_t *pair_call;        // [n_pairs]
-    const uint32_t *pair_read;       // [n_pairs]  (phased only)
-    const uint32_t *read_words;      // inq_read_t as four words: word 3 = mapq | bits << 8 | phase << 16 | promise << 24  (phased only)
-    uint64_t n_reads, n_pairs, n_loci;
+struct EvidenceArgs : PairView {  // (pair_read is read for a phased batch only)
     inq_locus_evidence_t *evidence;  // [n_loci]
     EvidenceWork *work;
     EvidenceSlice *list;             // [list_cap]

@@ -42,10 +42,8 @@ __device__ __forceinline__ void count_pair(const EvidenceArgs &a, uint64_t i, Pa
     if (!(bits & INQ_PAIR_KEPT)) return;
     p.fetched_kept += 1u << 16;
     if (!UNPHASED) {
-        // a kept read of a phased batch has an HP tag (:349); HP 0 is kept and belongs to no group.  (An index outside the
-        // descriptors is the locus kernels' INQ_ERR_INDEX: nothing is read through it here.)
-        const uint32_t r = a.pair_read[i];
-        const uint32_t phase = r < a.n_reads ? (a.read_words[4 * (uint64_t)r + 3] >> 16) & 0xffu : 0u;
+        // a kept read of a phased batch has an HP tag (:349); HP 0 is kept and belongs to no group
+        const uint32_t phase = phase_group(a, a.pair_read[i]);
         if (phase != 1u && phase != 2u) return;
         p.group12 += phase == 1u ? 1u : 1u << 16;
     }

@@ -4,18 +4,13 @@
 #include <stdint.h>
 
 #include "../../include/inquistr_hip.h"
+#include "pair_view.h"
 
 namespace inq {
 
 constexpr uint32_t kReadCallTile = 4096;  // pairs per workgroup of the count and the scatter launch: 16 B of pair_bits per lane
 
-struct ReadCallArgs {
-    const uint64_t *locus_pair_off;  // [n_loci + 1]
-    const uint8_t *pair_bits;        // [n_pairs] INQ_PAIR_*, as the locus kernels left them
-    const int64_t *pair_call;        // [n_pairs]
-    const uint32_t *pair_read;       // [n_pairs]
-    const uint32_t *read_words;      // inq_read_t as four words: word 3 = mapq | bits << 8 | phase << 16 | promise << 24  (phased only)
-    uint64_t n_reads, n_pairs, n_loci;
+struct ReadCallArgs : PairView {
     uint64_t *kept_off;              // [n_loci + 1]
     inq_read_call_t *kept;           // [n_pairs]: records [0, kept_off[n_loci]) are written, 16-byte aligned
     uint32_t *tile_count;            // [n_tiles]      context scratch

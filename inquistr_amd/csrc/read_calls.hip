@@ -154,10 +154,7 @@ __global__ __launch_bounds__(256) void read_call_scatter(ReadCallArgs a) {
 #pragma unroll
     for (uint32_t k = 0; k < kPerLane; ++k) {
         const uint32_t bits = sbits[k * kThreads + tid];
-        // phased: the read's HP, word 3 of its descriptor as evidence.hip reads it.  (An index outside the descriptors is the locus
-        // kernels' INQ_ERR_INDEX: nothing is read through it here.)
-        uint32_t group = 0;
-        if (!UNPHASED && (bits & INQ_PAIR_KEPT) && read[k] < a.n_reads) group = (a.read_words[4 * (uint64_t)read[k] + 3] >> 16) & 0xffu;
+        const uint32_t group = !UNPHASED && (bits & INQ_PAIR_KEPT) ? phase_group(a, read[k]) : 0u;  // phased: the read's HP
         tail[k] = group | ((bits & INQ_PAIR_CLIP) ? INQ_READ_CALL_CLIP : 0u) << 8;
     }
 #pragma unroll

@@ -563,13 +563,11 @@ struct FlushToDevice {
     const uint32_t *index;  // HOST, n_loci entries
     uint64_t cap;           // entries of d1 / d2
 };
-// h_flags: HOST [n_loci] per-locus flags (INQ_LOCUS_TIE) in append order, brought down with the rows through the same staging; may be null
-// h_evidence: HOST [n_loci] per-locus evidence in append order; may be null (and is, where the rows stay on the device)
-// h_kept_off: HOST [n_loci + 1] offsets of the per-read Calls in append order, the records stay in context scratch; may be null
-int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_call, const FlushToDevice *dev = nullptr, uint8_t *h_flags = nullptr,
-                    inq_locus_evidence_t *h_evidence = nullptr, uint64_t *h_kept_off = nullptr) {
+// h: the side outputs in append order; the flags come down with the rows through the same staging (where the rows stay on the device, h
+// holds the flags only)
+int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_call, const FlushToDevice *dev, const HostExtras &h) {
     if (!c || !r) return INQ_ERR_ARG;
-    c->read_calls_total = 0;  // (the records of the call before are no longer offered)
+    extras_reset(c);
     SpanState *S;
     int rc;
     if ((rc = span_state(c, &S)) != INQ_OK) return rc;
@@ -579,7 +577,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     if (n_loci != A.n_loci) return INQ_ERR_ARG;
     if (A.n_loci == 0) {
         A.reset();
-        if (h_kept_off) h_kept_off[0] = 0;
+        extras_finish(c, 0, 0, h, 0);
         return INQ_OK;
     }
     if (!dev && (!r->phase1 || !r->phase2)) return INQ_ERR_ARG;
@@ -593,24 +591,11 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     const uint64_t nl = A.n_loci;
     if ((rc = ensure(c, S->p1, nl * 8)) != INQ_OK) return rc;
     if ((rc = ensure(c, S->p2, nl * 8)) != INQ_OK) return rc;
-    if (h_flags && (rc = ensure(c, c->lflags, nl)) != INQ_OK) return rc;
-    uint8_t *const d_flags = h_flags ? (uint8_t *)c->lflags.p : nullptr;
-    // the evidence is counted and the per-read Calls are compacted from the per-pair outputs, which a flush otherwise does not produce:
-    // context scratch sized from the batch
-    const bool per_pair = h_evidence || h_kept_off;
-    if (per_pair) {
-        if ((rc = ensure(c, c->pcall, A.n_pairs * 8)) != INQ_OK) return rc;
-        if ((rc = ensure(c, c->pbits, A.n_pairs)) != INQ_OK) return rc;
-    }
-    if (h_evidence && (rc = ensure(c, c->levidence, nl * sizeof(inq_locus_evidence_t))) != INQ_OK) return rc;
-    if (h_kept_off) {
-        if ((rc = ensure(c, c->rcoff, (nl + 1) * 8)) != INQ_OK) return rc;
-        if ((rc = ensure(c, c->rckept, A.n_pairs * sizeof(inq_read_call_t))) != INQ_OK) return rc;
-    }
-    uint64_t *const d_kept_off = h_kept_off ? (uint64_t *)c->rcoff.p : nullptr;
-    inq_read_call_t *const d_kept = h_kept_off ? (inq_read_call_t *)c->rckept.p : nullptr;
-    inq_locus_evidence_t *const d_evidence = h_evidence ? (inq_locus_evidence_t *)c->levidence.p : nullptr;
-    if ((rc = ensure_row_staging(c, S, nl, 2 * nl + (h_flags ? (nl + 7) / 8 : 0))) != INQ_OK) return rc;  // the rows, then the flags
+    // (the evidence and the per-read Calls need the per-pair outputs, which a flush otherwise does not produce)
+    LocusExtras x;
+    if ((rc = extras_prepare(c, nl, A.n_pairs, h, &x)) != INQ_OK) return rc;
+    const bool per_pair = h.per_pair();
+    if ((rc = ensure_row_staging(c, S, nl, 2 * nl + (h.flags ? (nl + 7) / 8 : 0))) != INQ_OK) return rc;  // the rows, then the flags
     DevBatch d = device_batch(A.cigar.p, A.reads.p, A.pair_read.p, A.off.p, A.lstart.p, A.lend.p, A.n_reads, A.n_units * 4, A.n_pairs, nl,
                               A.minlen, A.support, A.unphased, S->p1.p, S->p2.p, per_pair ? c->pcall.p : nullptr, per_pair ? c->pbits.p : nullptr);
     inq_batch_t &db = d.b;
@@ -623,7 +608,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     } spent{A};
     const uint64_t n_reads_all = A.n_reads, n_units_all = A.n_units, n_pairs_all = A.n_pairs;
     HIP_TRY(c, hipEventRecord(S->ev[4], s));
-    if ((rc = call_batch_device_impl(c, &db, &dr, s, d_flags, d_evidence, d_kept_off, d_kept)) != INQ_OK) return rc;
+    if ((rc = call_batch_device_impl(c, &db, &dr, s, x)) != INQ_OK) return rc;
     HIP_TRY(c, hipEventRecord(S->ev[5], s));
     // measurement builds only (make DEBUG_ENV=1; tools/profile_cli_locus.sh): the shipped library reads nothing here
     if (const char *again = debug_env("INQ_CALL_AGAIN"); again && again[0] == '1') {
@@ -647,12 +632,10 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
         HIP_TRY(c, hipMemcpyAsync(S->h_rows, dr.phase1, nl * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(S->h_rows + nl, dr.phase2, nl * 8, hipMemcpyDeviceToHost, s));
     }
-    if (h_flags) HIP_TRY(c, hipMemcpyAsync(S->h_rows + 2 * nl, d_flags, nl, hipMemcpyDeviceToHost, s));
-    if (h_evidence) HIP_TRY(c, hipMemcpyAsync(h_evidence, d_evidence, nl * sizeof(inq_locus_evidence_t), hipMemcpyDeviceToHost, s));
-    if (h_kept_off) HIP_TRY(c, hipMemcpyAsync(h_kept_off, d_kept_off, (nl + 1) * 8, hipMemcpyDeviceToHost, s));
+    if ((rc = extras_download(c, nl, h, x, (uint8_t *)(S->h_rows + 2 * nl), s)) != INQ_OK) return rc;
     if ((rc = status_readback(c, &S->h->ks, s)) != INQ_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
-    if (h_flags) std::memcpy(h_flags, S->h_rows + 2 * nl, nl);
+    if (h.flags) std::memcpy(h.flags, S->h_rows + 2 * nl, nl);
     if (!dev) {
         std::memcpy(r->phase1, S->h_rows, nl * 8);
         std::memcpy(r->phase2, S->h_rows + nl, nl * 8);
@@ -673,7 +656,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     S->n_reads = n_reads_all, S->n_cigar_words = n_units_all * 4, S->n_pairs = n_pairs_all, S->n_loci = nl;
     S->last_from_acc = true;  // inq_span_fetch_batch reads the accumulated buffers (their contents stay until the next append)
     r->n_tie_loci = S->h->ks.ties;
-    if (h_kept_off && S->h->ks.err == 0) c->read_calls_total = std::min<uint64_t>(h_kept_off[nl], n_pairs_all);
+    extras_finish(c, nl, n_pairs_all, h, S->h->ks.err);
     return status_to_code(S->h->ks.err);  // (`spent` puts the counters back to zero, the buffers stay)
 }
 
@@ -835,7 +818,7 @@ int inq_call_flush_evidence(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci,
 
 int inq_call_flush_reads(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
                          inq_locus_evidence_t *evidence, uint64_t *kept_off) {
-    return guarded([&] { return call_flush_impl(c, result, n_loci, ms_call, nullptr, locus_flags, evidence, kept_off); });
+    return guarded([&] { return call_flush_impl(c, result, n_loci, ms_call, nullptr, HostExtras{locus_flags, evidence, kept_off}); });
 }
 
 int inq_call_flush_device(inq_ctx_t *c, double *d_phase1, double *d_phase2, uint64_t cap, const uint32_t *index, uint64_t n_loci, uint64_t *n_tie_loci,
@@ -849,7 +832,7 @@ int inq_call_flush_device_flags(inq_ctx_t *c, double *d_phase1, double *d_phase2
         inq_result_t r;
         std::memset(&r, 0, sizeof r);
         const FlushToDevice dev{d_phase1, d_phase2, index, cap};
-        const int rc = call_flush_impl(c, &r, n_loci, ms_call, &dev, locus_flags);
+        const int rc = call_flush_impl(c, &r, n_loci, ms_call, &dev, HostExtras{locus_flags});
         if (n_tie_loci) *n_tie_loci = r.n_tie_loci;
         return rc;
     });

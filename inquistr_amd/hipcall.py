@@ -210,6 +210,7 @@ class InqError(RuntimeError):
 
 
 _lib = None
+_SIDE_SUFFIXES = ("", "_flags", "_evidence", "_reads")  # the entries of a family: each takes the side outputs of the one before and its own
 
 
 def load(path: Optional[str] = None):
@@ -248,26 +249,17 @@ def load(path: Optional[str] = None):
     L.inq_ctx_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
     L.inq_ctx_destroy.restype = None
     L.inq_ctx_destroy.argtypes = [vp]
-    L.inq_call_batch.restype = C.c_int
-    L.inq_call_batch.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC)]
-    L.inq_call_batch_device.restype = C.c_int
-    L.inq_call_batch_device.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp]
-    L.inq_call_batch_flags.restype = C.c_int
-    L.inq_call_batch_flags.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp]
-    L.inq_call_batch_device_flags.restype = C.c_int
-    L.inq_call_batch_device_flags.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp, vp]
-    L.inq_call_batch_evidence.restype = C.c_int
-    L.inq_call_batch_evidence.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp, vp]
-    L.inq_call_batch_device_evidence.restype = C.c_int
-    L.inq_call_batch_device_evidence.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp, vp, vp]
-    L.inq_call_flush_evidence.restype = C.c_int
-    L.inq_call_flush_evidence.argtypes = [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double), vp, vp]
-    L.inq_call_batch_reads.restype = C.c_int
-    L.inq_call_batch_reads.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp, vp, vp]
-    L.inq_call_batch_device_reads.restype = C.c_int
-    L.inq_call_batch_device_reads.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC), vp, vp, vp, vp, vp]
-    L.inq_call_flush_reads.restype = C.c_int
-    L.inq_call_flush_reads.argtypes = [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double), vp, vp, vp]
+    # The three families of calls with per-locus side outputs: a member takes the family's arguments, then one pointer for each side
+    # output it adds (flags | evidence | kept_off, and kept for the device form), then - the device form - the stream.
+    for family, head, widths, tail in (
+        ("inq_call_batch", [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC)], (0, 1, 2, 3), []),
+        ("inq_call_batch_device", [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC)], (0, 1, 2, 4), [vp]),
+        ("inq_call_flush", [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double)], (0, 1, 2, 3), []),
+    ):
+        for suffix, n_side in zip(_SIDE_SUFFIXES, widths):
+            fn = getattr(L, family + suffix)
+            fn.restype = C.c_int
+            fn.argtypes = head + [vp] * n_side + tail
     L.inq_read_calls_fetch.restype = C.c_int
     L.inq_read_calls_fetch.argtypes = [vp, vp, C.c_uint64]
     L.inq_read_call_tile.restype = C.c_uint32
@@ -314,10 +306,6 @@ def load(path: Optional[str] = None):
     L.inq_call_span_staged.argtypes = [vp, C.POINTER(SpanC), C.c_int, C.POINTER(InqResultC), C.POINTER(SpanStatsC)]
     L.inq_call_span_deferred.restype = C.c_int
     L.inq_call_span_deferred.argtypes = [vp, C.POINTER(SpanC), C.c_int, C.POINTER(SpanStatsC)]
-    L.inq_call_flush.restype = C.c_int
-    L.inq_call_flush.argtypes = [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double)]
-    L.inq_call_flush_flags.restype = C.c_int
-    L.inq_call_flush_flags.argtypes = [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double), vp]
     L.inq_call_flush_device_flags.restype = C.c_int
     L.inq_call_flush_device_flags.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double), vp]
     L.inq_call_deferred_loci.restype = C.c_uint64
@@ -392,44 +380,56 @@ class Context:
         detail = self._L.inq_last_error(self._h).decode()
         raise InqError(rc, strerror(rc) + (f" [{detail}]" if detail and rc == -8 else ""))
 
-    def call_batch(self, batch: Batch, debug: bool = False, check: bool = True) -> Tuple[int, Result]:
-        """Host-buffer entry (inq_call_batch).  Returns (code, Result); raises on error if check."""
-        res = Result.alloc(batch, debug=debug)
-        bc, rc_ = batch.as_c(), res.as_c()
-        rc = self._L.inq_call_batch(self._h, C.byref(bc), C.byref(rc_))
-        res.n_tie_loci = int(rc_.n_tie_loci)
+    @staticmethod
+    def _side_arrays(n: int, flags: bool, evidence: bool, kept_off: bool):
+        """The arrays of a call of n loci for the side outputs asked for (else None), every byte 0xFF: one the call did not write shows."""
+        fl = np.full(max(n, 1), 0xFF, dtype=np.uint8) if flags else None
+        ev = np.full(max(n, 1) * EVIDENCE_DTYPE.itemsize, 0xFF, dtype=np.uint8) if evidence else None
+        off = np.full(n + 1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if kept_off else None
+        return fl, ev, off
+
+    def _side_call(self, entry: str, head, n: int, width: int, check: bool, flags: bool = True, evidence: bool = True):
+        """Calls `entry`, the member of its family that takes `width` side outputs, with `head` and the arrays of _side_arrays; raises on
+        error if check.  Returns (code, flags, evidence, kept_off, records), each cut to the n loci, None where not taken; the records are
+        fetched behind a successful call with the lists."""
+        fl, ev, off = self._side_arrays(n, flags and width >= 1, evidence and width >= 2, width >= 3)
+        side = [None if a is None else a.ctypes.data for a in (fl, ev, off)][:width]
+        rc = getattr(self._L, entry)(self._h, *head, *side)
         if rc != INQ_OK and check:
             self._raise(rc)
+        rec = self.read_calls_fetch(int(off[-1])) if off is not None and rc == INQ_OK else None
+        return rc, (None if fl is None else fl[:n]), (None if ev is None else ev.view(EVIDENCE_DTYPE)[:n]), off, rec
+
+    def _batch_call(self, entry: str, batch: Batch, debug: bool, width: int, check: bool, **which):
+        res = Result.alloc(batch, debug=debug)
+        bc, rc_ = batch.as_c(), res.as_c()
+        try:
+            return (res,) + self._side_call(entry, (C.byref(bc), C.byref(rc_)), batch.n_loci, width, check, **which)
+        finally:
+            res.n_tie_loci = int(rc_.n_tie_loci)
+
+    def call_batch(self, batch: Batch, debug: bool = False, check: bool = True) -> Tuple[int, Result]:
+        """Host-buffer entry (inq_call_batch).  Returns (code, Result); raises on error if check."""
+        res, rc = self._batch_call("inq_call_batch", batch, debug, 0, check)[:2]
         return rc, res
 
     def call_batch_flags(self, batch: Batch, debug: bool = False, check: bool = True) -> Tuple[int, Result, np.ndarray]:
         """inq_call_batch_flags: (code, Result, per-locus flags as uint8 [n_loci], INQ_LOCUS_TIE where a locus is tie-ambiguous)."""
-        res = Result.alloc(batch, debug=debug)
-        flags = np.full(max(batch.n_loci, 1), 0xFF, dtype=np.uint8)  # (0xFF: a byte the call did not write shows)
-        bc, rc_ = batch.as_c(), res.as_c()
-        rc = self._L.inq_call_batch_flags(self._h, C.byref(bc), C.byref(rc_), flags.ctypes.data)
-        res.n_tie_loci = int(rc_.n_tie_loci)
-        if rc != INQ_OK and check:
-            self._raise(rc)
-        return rc, res, flags[: batch.n_loci]
+        res, rc, fl = self._batch_call("inq_call_batch_flags", batch, debug, 1, check)[:3]
+        return rc, res, fl
 
     def call_batch_evidence(self, batch: Batch, debug: bool = False, check: bool = True, flags: bool = True):
         """inq_call_batch_evidence: (code, Result, per-locus flags or None, per-locus evidence as an EVIDENCE_DTYPE array)."""
-        res = Result.alloc(batch, debug=debug)
-        fl = np.full(max(batch.n_loci, 1), 0xFF, dtype=np.uint8) if flags else None
-        ev = np.full(max(batch.n_loci, 1) * EVIDENCE_DTYPE.itemsize, 0xFF, dtype=np.uint8)  # (0xFF: a byte the call did not write shows)
-        bc, rc_ = batch.as_c(), res.as_c()
-        rc = self._L.inq_call_batch_evidence(self._h, C.byref(bc), C.byref(rc_), fl.ctypes.data if flags else None, ev.ctypes.data)
-        res.n_tie_loci = int(rc_.n_tie_loci)
-        if rc != INQ_OK and check:
-            self._raise(rc)
-        return rc, res, (fl[: batch.n_loci] if flags else None), ev.view(EVIDENCE_DTYPE)[: batch.n_loci]
+        res, rc, fl, ev = self._batch_call("inq_call_batch_evidence", batch, debug, 2, check, flags=flags)[:4]
+        return rc, res, fl, ev
 
     def call_batch_device_evidence(self, bc: InqBatchC, rc_: InqResultC, d_flags: Optional[int], d_evidence: Optional[int],
                                    stream: Optional[int] = None, check: bool = True) -> int:
         """inq_call_batch_device_evidence: every pointer is a device pointer (d_flags / d_evidence may be None); enqueue only."""
-        rc = self._L.inq_call_batch_device_evidence(self._h, C.byref(bc), C.byref(rc_), C.c_void_p(d_flags or 0), C.c_void_p(d_evidence or 0),
-                                                    C.c_void_p(stream or 0))
+        return self._device_call("inq_call_batch_device_evidence", bc, rc_, (d_flags, d_evidence), stream, check)
+
+    def _device_call(self, entry: str, bc: InqBatchC, rc_: InqResultC, side, stream: Optional[int], check: bool) -> int:
+        rc = getattr(self._L, entry)(self._h, C.byref(bc), C.byref(rc_), *[C.c_void_p(p or 0) for p in side], C.c_void_p(stream or 0))
         if rc != INQ_OK and check:
             self._raise(rc)
         return rc
@@ -447,33 +447,17 @@ class Context:
     def call_batch_reads(self, batch: Batch, debug: bool = False, check: bool = True, flags: bool = True, evidence: bool = True):
         """inq_call_batch_reads: (code, Result, per-locus flags or None, per-locus evidence or None, kept_off [n_loci + 1], the records
         as a READ_CALL_DTYPE array - fetched with read_calls_fetch when the call succeeded, else None)."""
-        res = Result.alloc(batch, debug=debug)
-        fl = np.full(max(batch.n_loci, 1), 0xFF, dtype=np.uint8) if flags else None
-        ev = np.full(max(batch.n_loci, 1) * EVIDENCE_DTYPE.itemsize, 0xFF, dtype=np.uint8) if evidence else None
-        off = np.full(batch.n_loci + 1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
-        bc, rc_ = batch.as_c(), res.as_c()
-        rc = self._L.inq_call_batch_reads(self._h, C.byref(bc), C.byref(rc_), fl.ctypes.data if flags else None,
-                                          ev.ctypes.data if evidence else None, off.ctypes.data)
-        res.n_tie_loci = int(rc_.n_tie_loci)
-        if rc != INQ_OK and check:
-            self._raise(rc)
-        rec = self.read_calls_fetch(int(off[-1])) if rc == INQ_OK else None
-        return (rc, res, (fl[: batch.n_loci] if flags else None), (ev.view(EVIDENCE_DTYPE)[: batch.n_loci] if evidence else None), off, rec)
+        res, rc, fl, ev, off, rec = self._batch_call("inq_call_batch_reads", batch, debug, 3, check, flags=flags, evidence=evidence)
+        return rc, res, fl, ev, off, rec
 
     def call_batch_device_reads(self, bc: InqBatchC, rc_: InqResultC, d_flags: Optional[int], d_evidence: Optional[int],
                                 d_kept_off: Optional[int], d_kept: Optional[int], stream: Optional[int] = None, check: bool = True) -> int:
         """inq_call_batch_device_reads: every pointer is a device pointer (each of the four may be None); enqueue only."""
-        rc = self._L.inq_call_batch_device_reads(self._h, C.byref(bc), C.byref(rc_), C.c_void_p(d_flags or 0), C.c_void_p(d_evidence or 0),
-                                                 C.c_void_p(d_kept_off or 0), C.c_void_p(d_kept or 0), C.c_void_p(stream or 0))
-        if rc != INQ_OK and check:
-            self._raise(rc)
-        return rc
+        return self._device_call("inq_call_batch_device_reads", bc, rc_, (d_flags, d_evidence, d_kept_off, d_kept), stream, check)
 
     def call_batch_device(self, bc: InqBatchC, rc_: InqResultC, stream: Optional[int] = None) -> None:
         """Device-resident entry: pointers in bc / rc_ are device pointers; enqueue only."""
-        rc = self._L.inq_call_batch_device(self._h, C.byref(bc), C.byref(rc_), C.c_void_p(stream or 0))
-        if rc != INQ_OK:
-            self._raise(rc)
+        self._device_call("inq_call_batch_device", bc, rc_, (), stream, True)
 
     def bgzf_inflate(self, comp, blocks: np.ndarray, check: bool = True):
         """inq_bgzf_inflate on host buffers: returns (code, inflated bytes as uint8 array, per-block status)."""
@@ -568,61 +552,33 @@ class Context:
     def deferred_loci(self) -> int:
         return int(self._L.inq_call_deferred_loci(self._h))
 
-    def call_flush(self, check: bool = True):
-        """inq_call_flush: (code, phase1, phase2, n_tie_loci, ms_call) for every locus deferred since the last flush."""
+    def _flush_call(self, entry: str, width: int, check: bool):
+        """(code, phase1, phase2, n_tie_loci, ms_call) of `entry` for every locus deferred since the last flush, then the first `width`
+        of flags, evidence, kept_off + records."""
         n = self.deferred_loci
         p1 = np.full(n, np.nan)
         p2 = np.full(n, np.nan)
         res = InqResultC(p1.ctypes.data, p2.ctypes.data, None, None, 0)
         ms = C.c_double(0.0)
-        rc = self._L.inq_call_flush(self._h, C.byref(res), n, C.byref(ms))
-        if rc != INQ_OK and check:
-            self._raise(rc)
-        return rc, p1, p2, int(res.n_tie_loci), float(ms.value)
+        rc, fl, ev, off, rec = self._side_call(entry, (C.byref(res), n, C.byref(ms)), n, width, check)
+        return (rc, p1, p2, int(res.n_tie_loci), float(ms.value)) + (fl, ev, off, rec)[: width + (width == 3)]
+
+    def call_flush(self, check: bool = True):
+        """inq_call_flush: (code, phase1, phase2, n_tie_loci, ms_call) for every locus deferred since the last flush."""
+        return self._flush_call("inq_call_flush", 0, check)
 
     def call_flush_flags(self, check: bool = True):
         """inq_call_flush_flags: as call_flush, plus the per-locus flags (uint8, append order) as a sixth element."""
-        n = self.deferred_loci
-        p1 = np.full(n, np.nan)
-        p2 = np.full(n, np.nan)
-        flags = np.full(max(n, 1), 0xFF, dtype=np.uint8)
-        res = InqResultC(p1.ctypes.data, p2.ctypes.data, None, None, 0)
-        ms = C.c_double(0.0)
-        rc = self._L.inq_call_flush_flags(self._h, C.byref(res), n, C.byref(ms), flags.ctypes.data)
-        if rc != INQ_OK and check:
-            self._raise(rc)
-        return rc, p1, p2, int(res.n_tie_loci), float(ms.value), flags[:n]
+        return self._flush_call("inq_call_flush_flags", 1, check)
 
     def call_flush_evidence(self, check: bool = True):
         """inq_call_flush_evidence: as call_flush_flags, plus the per-locus evidence (EVIDENCE_DTYPE, append order) as a seventh element."""
-        n = self.deferred_loci
-        p1 = np.full(n, np.nan)
-        p2 = np.full(n, np.nan)
-        flags = np.full(max(n, 1), 0xFF, dtype=np.uint8)
-        ev = np.full(max(n, 1) * EVIDENCE_DTYPE.itemsize, 0xFF, dtype=np.uint8)
-        res = InqResultC(p1.ctypes.data, p2.ctypes.data, None, None, 0)
-        ms = C.c_double(0.0)
-        rc = self._L.inq_call_flush_evidence(self._h, C.byref(res), n, C.byref(ms), flags.ctypes.data, ev.ctypes.data)
-        if rc != INQ_OK and check:
-            self._raise(rc)
-        return rc, p1, p2, int(res.n_tie_loci), float(ms.value), flags[:n], ev.view(EVIDENCE_DTYPE)[:n]
+        return self._flush_call("inq_call_flush_evidence", 2, check)
 
     def call_flush_reads(self, check: bool = True):
         """inq_call_flush_reads: as call_flush_evidence, plus kept_off [n + 1] and the records (READ_CALL_DTYPE; None after a failed
         call) as the eighth and ninth element; `read` indexes the reads span_fetch_batch returns."""
-        n = self.deferred_loci
-        p1 = np.full(n, np.nan)
-        p2 = np.full(n, np.nan)
-        flags = np.full(max(n, 1), 0xFF, dtype=np.uint8)
-        ev = np.full(max(n, 1) * EVIDENCE_DTYPE.itemsize, 0xFF, dtype=np.uint8)
-        off = np.full(n + 1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
-        res = InqResultC(p1.ctypes.data, p2.ctypes.data, None, None, 0)
-        ms = C.c_double(0.0)
-        rc = self._L.inq_call_flush_reads(self._h, C.byref(res), n, C.byref(ms), flags.ctypes.data, ev.ctypes.data, off.ctypes.data)
-        if rc != INQ_OK and check:
-            self._raise(rc)
-        rec = self.read_calls_fetch(int(off[-1])) if rc == INQ_OK else None
-        return rc, p1, p2, int(res.n_tie_loci), float(ms.value), flags[:n], ev.view(EVIDENCE_DTYPE)[:n], off, rec
+        return self._flush_call("inq_call_flush_reads", 3, check)
 
     def span_fetch_batch(self, stats: "SpanStatsC", n_loci: int):
         """The batch the last call_span built on the device, as host arrays (cigar, reads, pair_read, locus_pair_off)."""

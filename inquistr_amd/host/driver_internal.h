@@ -286,6 +286,44 @@ struct CallView {
 // the per-read Calls of a call's targets: [k] = the records of target k's kept reads in file order (empty: no batch or span held it)
 using ReadCallLists = std::vector<std::vector<inq_read_call_t>>;
 
+// src[j] -> dst[index[j]]: rows and reports of a batch, a flush or a device part into their targets' places
+template <class T>
+inline void scatter(const T *src, const uint32_t *index, size_t n, T *dst) {
+    for (size_t j = 0; j < n; ++j) dst[index[j]] = src[j];
+}
+
+// The per-target reports of a call, beside its rows: the tie report (inq_call_args_t::ties_path), the evidence file (::evidence_path), the
+// read-calls file (inq_genotype_repeats_reads).  One value at every layer; a further report is one more member of each of the three
+// structs, a line in begin / scatter_from, a row in write_rows' table and a pointer in BatchRows::call / flush.
+struct ReportSet {  // which of them are collected: what is not adds nothing to the launch sequence
+    bool ties = false, evidence = false, read_calls = false;
+};
+struct ReportFds {  // where a text call writes them, in the .inq's row order (-1: no file)
+    int ties = -1, evidence = -1, read_calls = -1;
+    ReportSet wanted() const { return ReportSet{ties >= 0, evidence >= 0, read_calls >= 0}; }
+};
+// ... of a set of targets (a call's, a device part's, one device call's loci): [k] belongs to target k of the set.  A target no batch or
+// span holds keeps what begin put there: no flag, zeros, an empty list.
+struct TargetReports {
+    ReportSet has;
+    std::vector<uint8_t> ties;                   // INQ_LOCUS_TIE
+    std::vector<inq_locus_evidence_t> evidence;
+    ReadCallLists read_calls;                    // the records of the target's kept reads in file order
+    void begin(size_t n, ReportSet which) {
+        has = which;
+        ties.assign(which.ties ? n : 0, 0);
+        evidence.assign(which.evidence ? n : 0, inq_locus_evidence_t{});
+        read_calls.assign(which.read_calls ? n : 0, std::vector<inq_read_call_t>());
+    }
+    // what part collected (nothing this one does not), part's k-th -> target idx[k]; the lists are moved out of part
+    void scatter_from(TargetReports &part, const uint32_t *idx, size_t n) {
+        if (part.has.ties) scatter(part.ties.data(), idx, n, ties.data());
+        if (part.has.evidence) scatter(part.evidence.data(), idx, n, evidence.data());
+        if (part.has.read_calls)
+            for (size_t k = 0; k < n; ++k) read_calls[idx[k]] = std::move(part.read_calls[k]);
+    }
+};
+
 // what a session adds to one call: a pipeline that was started ahead of it (its loader has been reading and uploading while the
 // previous file was being called), the buffer pool, the set of device staging slots
 struct SessionHooks {
@@ -298,18 +336,10 @@ struct SessionHooks {
     // rows stay on the device (inq_run_rows_device): row of target k of the call -> dev_p1[k], dev_p2[k]
     double *dev_p1 = nullptr, *dev_p2 = nullptr;
     uint64_t dev_cap = 0;
-    // the tie report (inq_call_args_t::ties_path): per-target flags (INQ_LOCUS_TIE) of target k of the call -> ties_out[k] (null: not
-    // collected, the locus kernels run without flags); ties_fd >= 0: a text call writes the report there, in the .inq's row order
-    uint8_t *ties_out = nullptr;
-    int ties_fd = -1;
-    // the evidence file (inq_call_args_t::evidence_path), on the same rails: the record of target k of the call -> evidence_out[k]
-    // (null: not collected, nothing is added to the launch sequence); evidence_fd >= 0: a text call writes the file there
-    inq_locus_evidence_t *evidence_out = nullptr;
-    int evidence_fd = -1;
-    // the read-calls file (inq_genotype_repeats_reads), likewise: the records of target k of the call -> (*read_calls_out)[k] (null: not
-    // collected, nothing is added to the launch sequence); read_calls_fd >= 0: a text call writes the file there
-    ReadCallLists *read_calls_out = nullptr;
-    int read_calls_fd = -1;
+    // the reports: of target k of the call -> (*reports)[k], begun by the caller with what it wants collected (null: the call collects
+    // what report_fds asks for into one of its own); a text call writes each file whose fd is set
+    TargetReports *reports = nullptr;
+    ReportFds report_fds;
     // the caller owns the context AND the process ends with this call (fast_exit()): a pipeline the call made itself is left to the
     // operating system after a clean run (unmapping a GB of touched pages takes ~0.1 s), as the caller then leaves its context
     bool process_is_leaving = false;
@@ -337,7 +367,8 @@ struct CallReports {
         if (rc == INQ_EXIT_OK) rc = evidence.open(a.evidence_path, kEvidenceWhat, msg);
         return rc != INQ_EXIT_OK ? rc : read_calls.open(read_calls_path, kReadCallsWhat, msg);
     }
-    void to(SessionHooks &hooks) const { hooks.ties_fd = ties.fd, hooks.evidence_fd = evidence.fd, hooks.read_calls_fd = read_calls.fd; }
+    ReportFds fds() const { return ReportFds{ties.fd, evidence.fd, read_calls.fd}; }
+    void to(SessionHooks &hooks) const { hooks.report_fds = fds(); }
 };
 // an entry that returns rows or keeps its context for many files writes no evidence file and says so (INQ_EXIT_ERROR) instead of
 // ignoring the request
@@ -357,55 +388,52 @@ struct RowsOut {
     uint64_t dcap = 0;
 };
 
-// what write_rows writes beside the .inq, each where its array is set and its fd >= 0, for the same rows in the same order
+// what write_rows writes beside the .inq, each where it was collected and its fd is set, for the same rows in the same order
 struct RowReports {
-    const uint8_t *ties = nullptr;
-    int ties_fd = -1;
-    const inq_locus_evidence_t *evidence = nullptr;
-    int evidence_fd = -1;
-    const ReadCallLists *read_calls = nullptr;
-    int read_calls_fd = -1;
+    const TargetReports *reports = nullptr;
+    ReportFds fds;
     bool unphased = false;  // how the read-calls file splits a target's Calls
 };
 
-// src[j] -> dst[index[j]]: rows, tie flags and evidence of a batch, a flush or a device part into their targets' places
-template <class T>
-inline void scatter(const T *src, const uint32_t *index, size_t n, T *dst) {
-    for (size_t j = 0; j < n; ++j) dst[index[j]] = src[j];
-}
-// the result buffers of one device call over n loci (rows start as NaN, flags and evidence as 0), and their way into the call's arrays
+// the result buffers of one device call over n loci (rows start as NaN), its reports, and their way into the call's arrays
 struct BatchRows {
     std::vector<double> b1, b2;
-    std::vector<uint8_t> bt;
-    std::vector<inq_locus_evidence_t> be;
     inq_result_t res;
-    std::vector<uint64_t> bk;          // kept_off of the per-read Calls
+    TargetReports rep;                // of the call's loci, in the call's order
+    std::vector<uint64_t> bk;         // kept_off of the per-read Calls
     std::vector<inq_read_call_t> bc;  // ... and the records, fetched behind the call
-    uint8_t *flags = nullptr;                 // null: the call collects none
-    inq_locus_evidence_t *evidence = nullptr;  // null: the call collects none
-    uint64_t *kept_off = nullptr;              // null: the call collects none
-    void begin(size_t n, bool want_flags, bool want_evidence, bool want_read_calls = false) {
+    void begin(size_t n, ReportSet which) {
         b1.assign(n, NAN), b2.assign(n, NAN);
         std::memset(&res, 0, sizeof res);
         res.phase1 = b1.data(), res.phase2 = b2.data();
-        flags = nullptr, evidence = nullptr, kept_off = nullptr;
-        if (want_read_calls) bk.assign(n + 1, 0), kept_off = bk.data();
-        if (want_flags) bt.assign(n, 0), flags = bt.data();
-        if (want_evidence) be.assign(n, inq_locus_evidence_t{}), evidence = be.data();
+        rep.begin(n, which);
+        if (which.read_calls) bk.assign(n + 1, 0);
     }
-    // the records behind a call that filled kept_off, out of the context's scratch (INQ_OK at once for a call without the lists)
+    // what the device call takes (null: not collected)
+    uint8_t *flags() { return rep.has.ties ? rep.ties.data() : nullptr; }
+    inq_locus_evidence_t *evidence() { return rep.has.evidence ? rep.evidence.data() : nullptr; }
+    uint64_t *kept_off() { return rep.has.read_calls ? bk.data() : nullptr; }
+    // the host-buffer call / the flush of the n deferred loci with what begin asked for, the lists fetched behind it
+    int call(inq_ctx_t *ctx, const inq_batch_t &batch) {
+        const int rc = inq_call_batch_reads(ctx, &batch, &res, flags(), evidence(), kept_off());
+        return rc != INQ_OK ? rc : fetch_read_calls(ctx);
+    }
+    int flush(inq_ctx_t *ctx, uint64_t n, double *ms_call) {
+        const int rc = inq_call_flush_reads(ctx, &res, n, ms_call, flags(), evidence(), kept_off());
+        return rc != INQ_OK ? rc : fetch_read_calls(ctx);
+    }
+    // the records behind a call that filled kept_off, out of the context's scratch, cut into the loci's lists
     int fetch_read_calls(inq_ctx_t *ctx) {
-        if (!kept_off) return INQ_OK;
+        if (!rep.has.read_calls) return INQ_OK;
         bc.resize(bk.back());
-        return inq_read_calls_fetch(ctx, bc.data(), bc.size());
+        const int rc = inq_read_calls_fetch(ctx, bc.data(), bc.size());
+        for (size_t j = 0; rc == INQ_OK && j + 1 < bk.size(); ++j) rep.read_calls[j].assign(bc.begin() + bk[j], bc.begin() + bk[j + 1]);
+        return rc;
     }
-    // p1 null: the rows went elsewhere (device memory); ties / ev / lists are asked for only where flags / evidence / kept_off were
-    void scatter_to(const uint32_t *index, double *p1, double *p2, uint8_t *ties, inq_locus_evidence_t *ev, ReadCallLists *lists = nullptr) const {
-        if (kept_off)
-            for (size_t j = 0; j + 1 < bk.size(); ++j) (*lists)[index[j]].assign(bc.begin() + bk[j], bc.begin() + bk[j + 1]);
+    // p1 null: the rows went elsewhere (device memory)
+    void scatter_to(const uint32_t *index, double *p1, double *p2, TargetReports *out) {
         if (p1) scatter(b1.data(), index, b1.size(), p1), scatter(b2.data(), index, b2.size(), p2);
-        if (flags) scatter(flags, index, bt.size(), ties);
-        if (evidence) scatter(evidence, index, be.size(), ev);
+        out->scatter_from(rep, index, b1.size());
     }
 };
 
@@ -427,15 +455,14 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
                int out_fd, char *errbuf, size_t errcap, const RowReports &reports = RowReports());
 // the order of the .inq's rows: BED order for -t 1, (human_compare(chrom), start) for -t >= 2 (src/call.rs:33-38,141)
 std::vector<uint32_t> row_order(uint64_t threads, const std::vector<RepeatInterval> &targets);
-// the tie report: `chrom\tbegin\tend\n` for every target order[k] with a flag set
+// One file beside the .inq: `header` (may be empty), then what row(text, i) appends for every target i = order[k] - its line, or nothing -,
+// written in pieces of 8 MB (deep loci make long lines).  what: the file's name in "Failed writing <what>."
+using ReportRow = std::function<void(std::string &text, uint32_t i)>;
+int write_report(const std::vector<uint32_t> &order, const std::string &header, const ReportRow &row, const char *what, int fd, char *errbuf,
+                 size_t errcap);
+// the tie report: `chrom\tbegin\tend\n` for every target order[k] with a flag set (no header)
 int write_ties(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const uint8_t *ties, int fd, char *errbuf,
                size_t errcap);
-// the evidence file: the header, then one line for every target order[k]
-int write_evidence(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const inq_locus_evidence_t *evidence, int fd,
-                   char *errbuf, size_t errcap);
-// the read-calls file: the header, then one line for every target order[k]
-int write_read_calls(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const ReadCallLists &lists, bool unphased,
-                     int fd, char *errbuf, size_t errcap);
 // inq_genotype_repeats with the read-calls file (null: none), for inq_genotype_repeats_reads
 int genotype_single(const inq_call_args_t *args, int out_fd, const char *read_calls_path, char *errbuf, size_t errcap);
 int partition_prepared(Prepared &P, uint64_t world, uint32_t *order, uint64_t *cuts);

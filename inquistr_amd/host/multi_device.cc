@@ -92,7 +92,6 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
     const auto t_start = Clock::now();
     std::string msg;
     CallReports files;
-    const ReportFile &tf = files.ties, &ef = files.evidence, &rf = files.read_calls;
     if (files.open(*args, read_calls_path, msg) != INQ_EXIT_OK) {
         set_err(errbuf, errcap, msg);
         return INQ_EXIT_ERROR;
@@ -107,10 +106,9 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
     int rc = prepare(args, P, errbuf, errcap);
     if (rc != INQ_EXIT_OK) return rc;
     std::vector<PartStats> pst(n_devices);
-    // the tie report: each part's flags are scattered like its rows (the parts' target sets are disjoint)
-    std::vector<uint8_t> ties(tf.fd >= 0 ? P.targets.size() : 0, 0);
-    std::vector<inq_locus_evidence_t> evidence(ef.fd >= 0 ? P.targets.size() : 0, inq_locus_evidence_t{});  // ... and so is its evidence
-    ReadCallLists lists(rf.fd >= 0 ? P.targets.size() : 0);  // ... and its lists
+    // the reports: each part's are scattered like its rows (the parts' target sets are disjoint)
+    TargetReports reports;
+    reports.begin(P.targets.size(), files.fds().wanted());
     std::vector<double> p1, p2, part_s;
     std::vector<uint32_t> order;
     std::vector<uint64_t> cuts;
@@ -123,19 +121,13 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
         SessionHooks hooks;
         hooks.sharers = (int)n_devices, hooks.share_index = (int)r, hooks.stats = &pst[r];
         hooks.process_is_leaving = fast_exit();  // the contexts are this call's own, and so is the process's end (`call --devices`)
-        std::vector<uint8_t> part_ties(tf.fd >= 0 ? n : 0, 0);
-        if (tf.fd >= 0) hooks.ties_out = part_ties.data();
-        std::vector<inq_locus_evidence_t> part_evidence(ef.fd >= 0 ? n : 0, inq_locus_evidence_t{});
-        if (ef.fd >= 0) hooks.evidence_out = part_evidence.data();
-        ReadCallLists part_lists(rf.fd >= 0 ? n : 0);
-        if (rf.fd >= 0) hooks.read_calls_out = &part_lists;
+        TargetReports part;
+        part.begin(n, reports.has);
+        hooks.reports = &part;
         // (the runtime threads of this part prefer the NUMA node of ITS device: genotype_prepared's helpers bind per thread)
         const int prc = genotype_prepared(&oa.a, *actx[r], P, -1, err, cap, ro, t_start, hooks);
         actx[r]->leak = prc == INQ_EXIT_OK && hooks.process_is_leaving;  // only after a clean run: error paths tear down normally
-        if (prc == INQ_EXIT_OK && tf.fd >= 0) scatter(part_ties.data(), idx, n, ties.data());
-        if (prc == INQ_EXIT_OK && ef.fd >= 0) scatter(part_evidence.data(), idx, n, evidence.data());
-        if (prc == INQ_EXIT_OK && rf.fd >= 0)
-            for (uint64_t k = 0; k < n; ++k) lists[idx[k]] = std::move(part_lists[k]);
+        if (prc == INQ_EXIT_OK) reports.scatter_from(part, idx, n);
         return prc;
     };
     rc = run_parts(P, n_devices, fn, p1, p2, order, cuts, &part_rc, &part_s, errbuf, errcap);
@@ -152,11 +144,8 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
             o.front = pst[r].front, o.io_threads = pst[r].io_threads;
         }
     if (rc != INQ_EXIT_OK) return rc;
-    RowReports rr;
-    rr.ties = tf.fd >= 0 ? ties.data() : nullptr, rr.ties_fd = tf.fd;
-    rr.evidence = ef.fd >= 0 ? evidence.data() : nullptr, rr.evidence_fd = ef.fd;
-    rr.read_calls = rf.fd >= 0 ? &lists : nullptr, rr.read_calls_fd = rf.fd, rr.unphased = args->unphased != 0;
-    return write_rows(args->threads, P.targets, P.sample, p1.data(), p2.data(), out_fd, errbuf, errcap, rr);
+    return write_rows(args->threads, P.targets, P.sample, p1.data(), p2.data(), out_fd, errbuf, errcap,
+                      RowReports{&reports, files.fds(), args->unphased != 0});
 }
 
 static int genotype_reads_impl(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,

@@ -130,31 +130,19 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
     const CallView V{*P.bam, rows.active ? sub : P.targets, P.sample, CallOptions(*args)};
     const size_t n = V.targets.size();
     std::vector<double> p1(n, NAN), p2(n, NAN);
-    // the tie report: per-target flags, collected only when someone asked for them (the locus kernels run without flags otherwise)
-    const bool want_ties = hooks.ties_out || hooks.ties_fd >= 0;
-    std::vector<uint8_t> ties(want_ties ? n : 0, 0);
-    // the evidence file, likewise: a target no batch or span holds keeps its zeros
-    const bool want_evidence = hooks.evidence_out || hooks.evidence_fd >= 0;
-    std::vector<inq_locus_evidence_t> evidence(want_evidence ? n : 0, inq_locus_evidence_t{});
-    // the read-calls file, likewise: a target no batch or span holds keeps its empty list
-    const bool want_read_calls = hooks.read_calls_out || hooks.read_calls_fd >= 0;
-    ReadCallLists own_lists(want_read_calls && !hooks.read_calls_out ? n : 0);
-    ReadCallLists *const lists = !want_read_calls ? nullptr : hooks.read_calls_out ? hooks.read_calls_out : &own_lists;
+    // the reports, collected only where someone asked for them (the locus kernels run without flags otherwise, and so on)
+    TargetReports own_reports;
+    if (!hooks.reports) own_reports.begin(n, hooks.report_fds.wanted());
+    TargetReports *const reports = hooks.reports ? hooks.reports : &own_reports;
     const bool rows_on_device = rows.active && rows.d1 && rows.d2;
     if (rows_on_device && rows.dcap < n) {
         set_err(errbuf, errcap, "device row arrays smaller than the target list");
         return INQ_EXIT_ERROR;
     }
     auto emit = [&]() -> int {
-        if (!rows.active) {
-            RowReports rr;
-            rr.ties = want_ties ? ties.data() : nullptr, rr.ties_fd = hooks.ties_fd;
-            rr.evidence = want_evidence ? evidence.data() : nullptr, rr.evidence_fd = hooks.evidence_fd;
-            rr.read_calls = lists, rr.read_calls_fd = hooks.read_calls_fd, rr.unphased = V.opt.unphased;
-            return write_rows(args->threads, V.targets, V.sample, p1.data(), p2.data(), out_fd, errbuf, errcap, rr);
-        }
-        if (hooks.ties_out && n) std::memcpy(hooks.ties_out, ties.data(), n);
-        if (hooks.evidence_out && n) std::memcpy(hooks.evidence_out, evidence.data(), n * sizeof(inq_locus_evidence_t));
+        if (!rows.active)
+            return write_rows(args->threads, V.targets, V.sample, p1.data(), p2.data(), out_fd, errbuf, errcap,
+                              RowReports{reports, hooks.report_fds, V.opt.unphased});
         if (rows_on_device) return INQ_EXIT_OK;  // (device front end: they are there; host sweep: written below)
         if (n) std::memcpy(rows.p1, p1.data(), n * sizeof(double)), std::memcpy(rows.p2, p2.data(), n * sizeof(double));
         return INQ_EXIT_OK;
@@ -175,9 +163,7 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
         SessionHooks dh = hooks;
         dh.stats = ps;
         if (rows_on_device) dh.dev_p1 = rows.d1, dh.dev_p2 = rows.d2, dh.dev_cap = rows.dcap;
-        dh.ties_out = want_ties ? ties.data() : nullptr;  // (indexed like p1 / p2)
-        dh.evidence_out = want_evidence ? evidence.data() : nullptr;
-        dh.read_calls_out = lists;
+        dh.reports = reports;  // (indexed like p1 / p2)
         int drc = run_device_front(args, V, actx, p1, p2, errbuf, errcap, &t_front, &t_dev, dh);
         if (drc != INQ_EXIT_OK) return drc;
         const auto t_run = Clock::now();
@@ -267,18 +253,16 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
             batch.locus_start = (const uint32_t *)put(batch.locus_start, batch.n_loci * 4, off, s4);
             batch.locus_end = (const uint32_t *)put(batch.locus_end, batch.n_loci * 4, off, s4);
         }
-        br.begin(batch.n_loci, want_ties, want_evidence, want_read_calls);
+        br.begin(batch.n_loci, reports->has);
         auto tc = Clock::now();
-        // (null flags / evidence / kept_off: inq_call_batch)
-        int rc2 = inq_call_batch_reads(ctx, &batch, &br.res, br.flags, br.evidence, br.kept_off);
-        if (rc2 == INQ_OK) rc2 = br.fetch_read_calls(ctx);
+        const int rc2 = br.call(ctx, batch);
         t_dev += secs(tb, Clock::now());
         if (timing == 2)
             std::fprintf(stderr, "[inq batch] loci %llu pairs %llu cigar %.1f MB  wait-ctx %.2f ms  call %.2f ms\n",
                          (unsigned long long)batch.n_loci, (unsigned long long)batch.n_pairs, batch.n_cigar_words * 4 / 1e6,
                          secs(tb, tc) * 1e3, secs(tc, Clock::now()) * 1e3);
         if (rc2 != INQ_OK) return device_call_failed(rc2, ctx, errbuf, errcap);
-        br.scatter_to(item.index.data(), p1.data(), p2.data(), ties.data(), evidence.data(), lists);
+        br.scatter_to(item.index.data(), p1.data(), p2.data(), reports);
         pfe.recycle(std::move(item));
     }
     if (!need_ctx()) return INQ_EXIT_ERROR;  // no GPU is an error even for an empty target list
@@ -361,60 +345,35 @@ std::vector<uint32_t> row_order(uint64_t threads, const std::vector<RepeatInterv
     return order;
 }
 
+int write_report(const std::vector<uint32_t> &order, const std::string &header, const ReportRow &row, const char *what, int fd, char *errbuf,
+                 size_t errcap) {
+    std::string text = header;
+    bool ok = true;
+    for (size_t k = 0; k < order.size() && ok; ++k) {
+        row(text, order[k]);
+        if (text.size() >= (8u << 20)) ok = write_all(fd, text), text.clear();
+    }
+    if (!ok || !write_all(fd, text)) {
+        set_err(errbuf, errcap, std::string("Failed writing ") + what + ".");
+        return INQ_EXIT_ERROR;
+    }
+    return INQ_EXIT_OK;
+}
+
+static ReportRow tie_row(const std::vector<RepeatInterval> &targets, const uint8_t *ties) {
+    return [&targets, ties](std::string &text, uint32_t i) {
+        const RepeatInterval &t = targets[i];
+        if (ties[i] & INQ_LOCUS_TIE) text += t.chrom + '\t' + std::to_string(t.start) + '\t' + std::to_string(t.end) + '\n';
+    };
+}
+
 int write_ties(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const uint8_t *ties, int fd, char *errbuf,
                size_t errcap) {
-    std::string text;
-    for (const uint32_t i : order)
-        if (ties[i] & INQ_LOCUS_TIE) {
-            const RepeatInterval &t = targets[i];
-            text += t.chrom + '\t' + std::to_string(t.start) + '\t' + std::to_string(t.end) + '\n';
-        }
-    if (!write_all(fd, text)) {
-        set_err(errbuf, errcap, "Failed writing the tie report.");
-        return INQ_EXIT_ERROR;
-    }
-    return INQ_EXIT_OK;
-}
-
-int write_evidence(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const inq_locus_evidence_t *evidence, int fd,
-                   char *errbuf, size_t errcap) {
-    std::string text = std::string(kEvidenceHeader) + '\n';
-    for (const uint32_t i : order) {
-        const RepeatInterval &t = targets[i];
-        append_evidence_row(text, t.chrom, t.start, t.end, evidence[i]);
-        text += '\n';
-    }
-    if (!write_all(fd, text)) {
-        set_err(errbuf, errcap, "Failed writing the evidence file.");
-        return INQ_EXIT_ERROR;
-    }
-    return INQ_EXIT_OK;
-}
-
-int write_read_calls(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const ReadCallLists &lists, bool unphased,
-                     int fd, char *errbuf, size_t errcap) {
-    std::string text = std::string(kReadCallsHeader) + '\n';
-    for (const uint32_t i : order) {
-        const RepeatInterval &t = targets[i];
-        append_read_calls_row(text, t.chrom, t.start, t.end, lists[i].data(), lists[i].size(), unphased);
-        text += '\n';
-        if (text.size() >= (8u << 20)) {  // deep loci make long lines: written as it grows
-            if (!write_all(fd, text)) break;
-            text.clear();
-        }
-    }
-    if (!write_all(fd, text)) {
-        set_err(errbuf, errcap, "Failed writing the read-calls file.");
-        return INQ_EXIT_ERROR;
-    }
-    return INQ_EXIT_OK;
+    return write_report(order, std::string(), tie_row(targets, ties), kTiesWhat, fd, errbuf, errcap);
 }
 
 int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, const std::string &sample, const double *p1,
                       const double *p2, int out_fd, char *errbuf, size_t errcap, const RowReports &reports) {
-    const uint8_t *const ties = reports.ties;
-    const inq_locus_evidence_t *const evidence = reports.evidence;
-    const int ties_fd = reports.ties_fd, evidence_fd = reports.evidence_fd;
     const size_t n = targets.size();
     const auto t_w0 = Clock::now();
     const std::vector<uint32_t> order = row_order(threads, targets);
@@ -468,17 +427,33 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
         set_err(errbuf, errcap, "Failed writing the result.");
         return INQ_EXIT_PANIC;
     }
-    if (ties && ties_fd >= 0) {  // the tie report, in the rows' order
-        const int trc = write_ties(order, targets, ties, ties_fd, errbuf, errcap);
-        if (trc != INQ_EXIT_OK) return trc;
-    }
-    if (evidence && evidence_fd >= 0) {  // the evidence file, one line per row
-        const int erc = write_evidence(order, targets, evidence, evidence_fd, errbuf, errcap);
-        if (erc != INQ_EXIT_OK) return erc;
-    }
-    if (reports.read_calls && reports.read_calls_fd >= 0) {  // the read-calls file, one line per row
-        const int rrc = write_read_calls(order, targets, *reports.read_calls, reports.unphased, reports.read_calls_fd, errbuf, errcap);
-        if (rrc != INQ_EXIT_OK) return rrc;
+    if (const TargetReports *const tr = reports.reports) {  // each file that was collected and has somewhere to go, in the rows' order
+        const bool unphased = reports.unphased;
+        const struct {
+            bool on;
+            int fd;
+            std::string header;
+            const char *what;
+            ReportRow row;  // one line per row; the tie report: per flagged row
+        } files[] = {
+            {tr->has.ties, reports.fds.ties, std::string(), kTiesWhat, tie_row(targets, tr->ties.data())},
+            {tr->has.evidence, reports.fds.evidence, std::string(kEvidenceHeader) + '\n', kEvidenceWhat,
+             [&targets, tr](std::string &text, uint32_t i) {
+                 append_evidence_row(text, targets[i].chrom, targets[i].start, targets[i].end, tr->evidence[i]);
+                 text += '\n';
+             }},
+            {tr->has.read_calls, reports.fds.read_calls, std::string(kReadCallsHeader) + '\n', kReadCallsWhat,
+             [&targets, tr, unphased](std::string &text, uint32_t i) {
+                 const std::vector<inq_read_call_t> &l = tr->read_calls[i];
+                 append_read_calls_row(text, targets[i].chrom, targets[i].start, targets[i].end, l.data(), l.size(), unphased);
+                 text += '\n';
+             }},
+        };
+        for (const auto &f : files) {
+            if (!f.on || f.fd < 0) continue;
+            const int frc = write_report(order, f.header, f.row, f.what, f.fd, errbuf, errcap);
+            if (frc != INQ_EXIT_OK) return frc;
+        }
     }
     if (timing_level())
         std::fprintf(stderr, "[inq output] %zu rows: order %.2f ms, bounds %.2f ms, text %.2f ms (%zu threads), write %.2f ms\n", n, ms(t_w0, t_w1), ms(t_w1, t_w1b), ms(t_w1b, t_w2),
@@ -720,8 +695,8 @@ struct inq_run {
     inq_session *sess = nullptr;
     double *d1 = nullptr, *d2 = nullptr;
     uint64_t dcap = 0;
-    // the tie flags of the last rows call (collected when the run was opened with ties_path set)
-    std::vector<uint8_t> ties;
+    // the reports of the last rows call: the tie flags, collected when the run was opened with ties_path set
+    TargetReports reports;
     bool have_ties = false;
     AsyncCtx *ctx_of_rows() { return sess ? &sess->actx : actx.get(); }
     ~inq_run() {
@@ -778,9 +753,12 @@ static int run_rows_on(inq_run_t *r, AsyncCtx &actx, RowsOut ro, const uint32_t 
     SessionHooks hooks;
     if (r->sess) hooks.pool = &r->sess->pool;  // the session's span buffers
     r->have_ties = false;
-    if (r->args->a.ties_path) r->ties.assign(n_index, 0), hooks.ties_out = r->ties.data();
+    ReportSet which;
+    which.ties = r->args->a.ties_path != nullptr;
+    r->reports.begin(n_index, which);
+    hooks.reports = &r->reports;
     const int rc = genotype_prepared(&r->args->a, actx, r->P, -1, errbuf, errcap, ro, t_start, hooks);
-    r->have_ties = rc == INQ_EXIT_OK && hooks.ties_out;
+    r->have_ties = rc == INQ_EXIT_OK && which.ties;
     return rc;
 }
 static int inq_run_rows_impl(inq_run_t *r, const uint32_t *target_index, uint64_t n_index, double *phase1, double *phase2, char *errbuf,
@@ -846,8 +824,8 @@ int inq_run_write_inq(inq_run_t *r, const double *phase1, const double *phase2, 
     INQ_GUARD(write_rows(r->args->a.threads, r->P.targets, r->P.sample, phase1, phase2, out_fd, errbuf, errcap), errbuf, errcap)
 }
 int inq_run_tie_flags(const inq_run_t *r, uint8_t *flags, uint64_t n) {
-    if (!r || !r->have_ties || n != r->ties.size() || (n && !flags)) return INQ_EXIT_ERROR;
-    if (n) std::memcpy(flags, r->ties.data(), n);
+    if (!r || !r->have_ties || n != r->reports.ties.size() || (n && !flags)) return INQ_EXIT_ERROR;
+    if (n) std::memcpy(flags, r->reports.ties.data(), n);
     return INQ_EXIT_OK;
 }
 int inq_run_write_ties(inq_run_t *r, const uint8_t *flags, uint64_t n_rows, int fd, char *errbuf, size_t errcap) {

@@ -51,7 +51,7 @@ int run_staged(inq_session *S, StagedFile &f, int out_fd, char *errbuf, size_t e
     hooks.pool = &S->pool;
     hooks.slot_base = f.slot_base;
     hooks.front = f.front;
-    hooks.ties_fd = f.ties ? f.ties->fd : -1;
+    hooks.report_fds.ties = f.ties ? f.ties->fd : -1;
     int rc = genotype_prepared(&f.args->a, S->actx, f.P, out_fd, errbuf, errcap, RowsOut(), f.t_start, hooks);
     f.pipe.reset();  // joins the loader, hands the span buffers back to the pool
     return rc;

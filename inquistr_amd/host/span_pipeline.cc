@@ -517,7 +517,7 @@ struct PipeDeleter {
 };
 }  // namespace
 
-// fills p1 / p2 (or hooks.dev_p1 / dev_p2) through the device front end; returns an exit status
+// fills p1 / p2 (or hooks.dev_p1 / dev_p2) and *hooks.reports (set by genotype_prepared) through the device front end; returns an exit status
 int run_device_front(const inq_call_args_t *args, const CallView &V, AsyncCtx &actx, std::vector<double> &p1,
                             std::vector<double> &p2, char *errbuf, size_t errcap, double *t_front, double *t_dev,
                             const SessionHooks &hooks) {
@@ -545,21 +545,21 @@ int run_device_front(const inq_call_args_t *args, const CallView &V, AsyncCtx &a
     auto flush = [&]() -> int {
         if (pending.empty()) return INQ_EXIT_OK;
         const auto f0 = Clock::now();
-        // (rows that stay on the device belong to a prepared run, which takes no evidence: run.cc inq_run_open_impl)
-        br.begin(pending.size(), hooks.ties_out != nullptr, hooks.evidence_out != nullptr && !hooks.dev_p1,
-                 hooks.read_calls_out != nullptr && !hooks.dev_p1);
+        // rows that stay on the device take flags only (they belong to a prepared run, which takes no evidence: run.cc inq_run_open_impl)
+        ReportSet which = hooks.reports->has;
+        if (hooks.dev_p1) which.evidence = which.read_calls = false;
+        br.begin(pending.size(), which);
         double ms_call = 0;
         // (rows that travel on from device memory stay there: pending[j] is the row's place in the caller's device arrays)
-        int rc2 = hooks.dev_p1 ? inq_call_flush_device_flags(ctx, hooks.dev_p1, hooks.dev_p2, hooks.dev_cap, pending.data(), pending.size(), nullptr,
-                                                             &ms_call, br.flags)
-                               : inq_call_flush_reads(ctx, &br.res, pending.size(), &ms_call, br.flags, br.evidence, br.kept_off);
-        if (rc2 == INQ_OK) rc2 = br.fetch_read_calls(ctx);
+        const int rc2 = hooks.dev_p1 ? inq_call_flush_device_flags(ctx, hooks.dev_p1, hooks.dev_p2, hooks.dev_cap, pending.data(), pending.size(),
+                                                                   nullptr, &ms_call, br.flags())
+                                     : br.flush(ctx, pending.size(), &ms_call);
         *t_dev += secs(f0, Clock::now());
         if (timing == 2)
             std::fprintf(stderr, "[inq call] @%.1f %zu loci, %.1f MB of CIGARs: locus kernels %.3f ms | wall %.2f ms\n", stamp_ms(), pending.size(),
                          pending_words * 4 / 1e6, ms_call, secs(f0, Clock::now()) * 1e3);
         if (rc2 != INQ_OK) return device_call_failed(rc2, ctx, errbuf, errcap);
-        br.scatter_to(pending.data(), hooks.dev_p1 ? nullptr : p1.data(), p2.data(), hooks.ties_out, hooks.evidence_out, hooks.read_calls_out);
+        br.scatter_to(pending.data(), hooks.dev_p1 ? nullptr : p1.data(), p2.data(), hooks.reports);
         pending.clear();
         pending_words = 0;
         return INQ_EXIT_OK;
