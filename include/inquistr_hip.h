@@ -176,6 +176,17 @@ typedef struct inq_read_call {   /* 16 bytes, every byte written */
     uint16_t reserved;  /* 0 */
 } inq_read_call_t;
 
+/* Who a record of the per-read Calls is: the read's origin (position, strand, MAPQ) and, through name_len, its name (QNAME).  Produced by
+ * the device front end only (inq_call_span_deferred_names / inq_call_flush_origins below): its records exist nowhere but in the inflated
+ * bytes of a span slot, so the names are gathered on the device, at span time into the deferred batch and at flush time for the kept
+ * records.  A caller of the host-buffer entries owns its batch and needs none of this: `read` indexes its own reads. */
+typedef struct inq_read_origin {  /* 8 bytes, every byte written; one per record of inq_read_calls_fetch, same order */
+    int32_t  pos;       /* inq_read_t.pos */
+    uint8_t  mapq;
+    uint8_t  bits;      /* INQ_READ_* of the descriptor (REVERSE is what the table prints) */
+    uint16_t name_len;  /* 0 .. 254: bytes of the name, no terminator */
+} inq_read_origin_t;
+
 typedef struct inq_ctx inq_ctx_t;
 
 /* Opens HIP device `device_id` (must be gfx950), creates the library's stream and
@@ -423,6 +434,27 @@ int inq_call_flush_evidence(inq_ctx_t *ctx, inq_result_t *result, uint64_t n_loc
  * through inq_read_calls_fetch, their `read` indexing the deferred batch's reads as inq_span_fetch_batch returns them. */
 int inq_call_flush_reads(inq_ctx_t *ctx, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
                          inq_locus_evidence_t *evidence, uint64_t *kept_off);
+/* The names (QNAME) and origins of the reads behind those records.  A read's name is bytes [0, max(l_read_name, 1) - 1) of the record's
+ * name field, as they stand (a NUL inside is the reader's to cut at; for l_read_name == 0 no name byte is read).
+ * inq_call_span_deferred_names is inq_call_span_deferred that also gathers the names of the span's placed records into the deferred
+ * batch (one scan of the lengths and one copy launch behind the CIGAR gather).  All spans of one batch with names or all without:
+ * mixing is INQ_ERR_ARG at the offending append, which appends nothing.  inq_call_span / inq_call_span_staged produce no per-pair outputs
+ * and take no names.
+ * inq_call_flush_origins is inq_call_flush_reads plus, behind the compaction, one inq_read_origin_t per kept record and the kept
+ * records' names back to back in record order; *name_bytes receives their total.  kept_off NULL or name_bytes NULL, or a batch
+ * appended without names, is INQ_ERR_ARG (the batch stays).  Both stay in context scratch until the context's next call:
+ * inq_read_origins_fetch copies the first n origins and the first name_bytes bytes of the names (the name of record k begins at the
+ * sum of name_len of the records in front of it); n or name_bytes above the last flush's totals is INQ_ERR_ARG, and a flush without
+ * origins has totals of 0.
+ * inq_span_fetch_names (test / debug, beside inq_span_fetch_batch): the names of ALL reads of the batch the last flush ran on,
+ * name_off[n_reads + 1] and the bytes (cap_bytes below the total, or a batch without names: INQ_ERR_ARG). */
+int inq_call_span_deferred_names(inq_ctx_t *ctx, const inq_span_t *span, int slot, inq_span_stats_t *stats);
+int inq_call_flush_origins(inq_ctx_t *ctx, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
+                           inq_locus_evidence_t *evidence, uint64_t *kept_off, uint64_t *name_bytes);
+int inq_read_origins_fetch(inq_ctx_t *ctx, inq_read_origin_t *origins, uint64_t n, uint8_t *names, uint64_t name_bytes);
+int inq_span_fetch_names(inq_ctx_t *ctx, uint64_t *name_off /* [n_reads + 1] */, uint8_t *names, uint64_t cap_bytes);
+/* segments (names) per workgroup of the byte gather (a constant of the build) */
+uint32_t inq_read_name_tile(void);
 /* Row arrays in device memory for a host that does not link the HIP runtime itself: n f64, filled with quiet NaN (a locus no span
  * holds prints NaN NaN); plain synchronous copies in and out. */
 int inq_dev_alloc_rows(inq_ctx_t *ctx, uint64_t n, double **out);

@@ -113,6 +113,23 @@ int inq_genotype_repeats_devices(const inq_call_args_t *args, const int32_t *dev
  * unspecified after a failed call.  The .inq text is that of the call without the file. */
 int inq_genotype_repeats_reads(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd,
                                const char *read_calls_path, inq_part_stats_t *stats, char *errbuf, size_t errcap);
+/* ... and with the read table (`inquistr call --read-table`), the widest entry of the family: read_table_path NULL = exactly
+ * inq_genotype_repeats_reads.  The file names the reads behind each row: a header line
+ * `chrom\tbegin\tend\tgroup\tcall\tkind\tread\tpos\tstrand\tmapq`, then one line per KEPT read of every target, targets in the .inq's row
+ * order, inside a target in the order of the read-calls lists - the lines of h1 in that list's order (ascending by value, ties by file
+ * order), then h2, then other; unphased the h1 / h2 split is the len / 2 one and `other` does not occur; a target without a kept read
+ * contributes no line.  group = h1 / h2 / other, call = the Call's value, kind = Span / Clip, read = the QNAME, pos = SAM POS
+ * (core.pos + 1), strand = `-` for flag 0x10, else `+`, mapq = the read's MAPQ.  Per target and group the `call` values (a Clip with the suffix
+ * `c`) joined by commas are the read-calls column.  The QNAME is bytes [0, l_read_name - 1) of the record's name field cut at the first
+ * NUL, an empty one (l_read_name <= 1, a leading NUL) printed as `*`; the bytes are written as they stand - SAM restricts a QNAME to
+ * [!-?A-~], so a valid file puts no tab or newline there.  Secondary and supplementary records of one read share a name; pos and strand
+ * tell them apart.  Both front ends produce it: the host sweep keeps its batches' names (inq_frontend_read_names), the device front end
+ * gathers them on the GPU (inq_call_span_deferred_names, inq_call_flush_origins of include/inquistr_hip.h).  Opened like the
+ * read-calls file, beside it and the two files of args in any combination; content unspecified after a failed call.  The .inq text and
+ * the other files are those of the call without the table.  The other entries that take these arguments - inq_genotype_repeats_rows,
+ * inq_run_*, inq_session_* - have no way to be handed the path: they write no table. */
+int inq_genotype_repeats_table(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,
+                               const char *read_table_path, inq_part_stats_t *stats, char *errbuf, size_t errcap);
 /* How many processes (or device parts) share this host's cores with this one, and which of them it is (0 .. sharers - 1): sizes the
  * reader pool of every later call (granted cores / sharers, bound to L3 domains from a different start per sharer).  Default:
  * LOCAL_WORLD_SIZE / LOCAL_RANK of the environment (torch.distributed.run exports them), else 1 / 0.  sharers <= 0 = that default. */
@@ -204,6 +221,10 @@ const char *inq_frontend_sample(const inq_frontend_t *fe);
  * status negated.  locus_index[j] = position of batch locus j in the target list. */
 int inq_frontend_next(inq_frontend_t *fe, inq_batch_t *batch, const uint32_t **locus_index, char *errbuf,
                       size_t errcap);
+/* The names (QNAME, without terminator, as they stand) of the reads of the batch the last inq_frontend_next handed out:
+ * name_off[n_reads + 1] and the bytes, read i's name = names[name_off[i] .. name_off[i + 1]); its position, strand and MAPQ are in
+ * batch->reads[i].  Valid until the next inq_frontend_next.  0, or 1 when no batch is out. */
+int inq_frontend_read_names(const inq_frontend_t *fe, const uint64_t **name_off, const uint8_t **names, uint64_t *n_reads);
 void inq_frontend_set_batch_words(inq_frontend_t *fe, uint64_t max_cigar_words);
 void inq_frontend_close(inq_frontend_t *fe);
 
@@ -253,6 +274,11 @@ size_t inq_host_format_evidence_row(const char *chrom, uint32_t start, uint32_t 
  * (inq_read_call_t of include/inquistr_hip.h), without the newline; returns its length as snprintf does */
 size_t inq_host_format_read_calls_row(const char *chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls, size_t n, int unphased,
                                       char *buf, size_t cap);
+/* the lines of the read table (inq_genotype_repeats_table) of one target, each with its newline, from the n records of its kept reads
+ * in file order, their origins in the same order and their names back to back (inq_read_origin_t of include/inquistr_hip.h); returns the
+ * text's length as snprintf does (n == 0: no line) */
+size_t inq_host_format_read_table_rows(const char *chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
+                                       const inq_read_origin_t *origins, const uint8_t *names, size_t n, int unphased, char *buf, size_t cap);
 size_t inq_host_sample_name(const char *bam_path, char *buf, size_t cap);
 int inq_host_human_compare(const char *a, const char *b);
 /* RepeatIntervalIterator::from_string against a one-contig length table; 0 ok, 101 panic */

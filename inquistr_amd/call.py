@@ -25,6 +25,7 @@ HOST_ABI_SYMBOLS = (
     "inq_genotype_repeats_rows",
     "inq_genotype_repeats_devices",
     "inq_genotype_repeats_reads",
+    "inq_genotype_repeats_table",
     "inq_host_set_local_share",
     "inq_host_granted_cpus",
     "inq_host_ctx_option",
@@ -58,6 +59,7 @@ HOST_ABI_SYMBOLS = (
     "inq_frontend_target",
     "inq_frontend_sample",
     "inq_frontend_next",
+    "inq_frontend_read_names",
     "inq_frontend_set_batch_words",
     "inq_frontend_close",
     "inq_host_format_f64",
@@ -65,6 +67,7 @@ HOST_ABI_SYMBOLS = (
     "inq_host_format_header",
     "inq_host_format_evidence_row",
     "inq_host_format_read_calls_row",
+    "inq_host_format_read_table_rows",
     "inq_host_sample_name",
     "inq_host_human_compare",
     "inq_host_parse_region",
@@ -157,6 +160,9 @@ def load():
         L.inq_genotype_repeats_reads.restype = C.c_int
         L.inq_genotype_repeats_reads.argtypes = [C.POINTER(CallArgsC), C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.c_char_p, C.POINTER(PartStatsC),
                                                  C.c_char_p, C.c_size_t]
+        L.inq_genotype_repeats_table.restype = C.c_int
+        L.inq_genotype_repeats_table.argtypes = [C.POINTER(CallArgsC), C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.c_char_p, C.c_char_p,
+                                                 C.POINTER(PartStatsC), C.c_char_p, C.c_size_t]
         L.inq_genotype_repeats_devices.restype = C.c_int
         L.inq_genotype_repeats_devices.argtypes = [C.POINTER(CallArgsC), C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.POINTER(PartStatsC), C.c_char_p, C.c_size_t]
         L.inq_host_set_local_share.restype = None
@@ -219,6 +225,8 @@ def load():
         L.inq_frontend_sample.argtypes = [vp]
         L.inq_frontend_next.restype = C.c_int
         L.inq_frontend_next.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(C.POINTER(C.c_uint32)), C.c_char_p, C.c_size_t]
+        L.inq_frontend_read_names.restype = C.c_int
+        L.inq_frontend_read_names.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]
         L.inq_frontend_set_batch_words.restype = None
         L.inq_frontend_set_batch_words.argtypes = [vp, C.c_uint64]
         L.inq_frontend_close.restype = None
@@ -235,6 +243,9 @@ def load():
         L.inq_host_format_evidence_row.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(LocusEvidenceC), C.c_char_p, C.c_size_t]
         L.inq_host_format_read_calls_row.restype = C.c_size_t
         L.inq_host_format_read_calls_row.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t]
+        L.inq_host_format_read_table_rows.restype = C.c_size_t
+        L.inq_host_format_read_table_rows.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                                      C.c_char_p, C.c_size_t]
         L.inq_host_sample_name.restype = C.c_size_t
         L.inq_host_sample_name.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
         L.inq_host_human_compare.restype = C.c_int
@@ -338,26 +349,29 @@ def _args(bamp, region, region_file, minlen, support, threads, unphased, sample_
 def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str], minlen: int = 5, support: int = 3,
                      threads: int = 1, unphased: bool = False, sample_name: Optional[str] = None,
                      reference: Optional[str] = None, out=None, device: int = 0, frontend: Optional[str] = None,
-                     ties: Optional[str] = None, evidence: Optional[str] = None, read_calls: Optional[str] = None, devices=None) -> None:
+                     ties: Optional[str] = None, evidence: Optional[str] = None, read_calls: Optional[str] = None, devices=None,
+                     read_table: Optional[str] = None) -> None:
     """src/call.rs:76-86: same parameters, same output; raises CallError instead of exiting.
     frontend: "host" (BGZF inflate + record decode on CPU threads), "device" (inq_call_span: both on the GPU)
     or None (env INQ_FRONTEND, else the library default).
     ties: path of the tie report (inquistr call --ties): the tie-ambiguous unphased loci as BED, in the rows' order.
     evidence: path of the evidence file (inquistr call --evidence): one line per row with the read counts behind its two medians.
     read_calls: path of the read-calls file (inquistr call --read-calls): one line per row with the Calls behind its two medians.
-    devices: with read_calls, the HIP devices of inq_genotype_repeats_reads (None: the one device `device`)."""
+    read_table: path of the read table (inquistr call --read-table): one line per kept read with its Call, group, name, pos, strand, mapq.
+    devices: with read_calls or read_table, the HIP devices of inq_genotype_repeats_table (None: the one device `device`)."""
     L = load()
     a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, reference, device, frontend, ties, evidence)
     out = sys.stdout if out is None else out
     out.flush()
-    if read_calls is None and devices is None:
+    if read_calls is None and read_table is None and devices is None:
         _checked(L.inq_genotype_repeats, C.byref(a), out.fileno())
         return
     devices = [] if devices is None else [int(d) for d in devices]
     ids = (C.c_int32 * max(len(devices), 1))(*devices)
     st = (PartStatsC * max(len(devices), 1))()
     path = os.fspath(read_calls).encode() if read_calls is not None else None
-    _checked(L.inq_genotype_repeats_reads, C.byref(a), ids, len(devices), out.fileno(), path, st)
+    table = os.fspath(read_table).encode() if read_table is not None else None
+    _checked(L.inq_genotype_repeats_table, C.byref(a), ids, len(devices), out.fileno(), path, table, st)
 
 
 def genotype_repeats_devices(bamp: str, region: Optional[str], region_file: Optional[str], devices, minlen: int = 5, support: int = 3,
@@ -618,8 +632,18 @@ class FrontEnd(_Handle):
             out.append((c.value.decode(), s.value, e.value))
         return out
 
+    def read_names(self):
+        """inq_frontend_read_names: the names of the reads of the batch batches() handed out last, as a list of bytes (read i's QNAME
+        without terminator, as it stands in the record); its pos, strand and mapq are in the batch's reads[i]."""
+        off, names, n = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint8)(), C.c_uint64(0)
+        if self._L.inq_frontend_read_names(self._h, C.byref(off), C.byref(names), C.byref(n)) != 0:
+            raise CallError(1, "no batch is out")
+        o = _copy_array(off, int(n.value) + 1, np.uint64)
+        raw = _copy_array(names, int(o[-1]), np.uint8).tobytes()
+        return [raw[int(o[i]) : int(o[i + 1])] for i in range(int(n.value))]
+
     def batches(self) -> Iterator[Tuple[Batch, np.ndarray]]:
-        """Yields (Batch copy, locus_index) until the BAM is exhausted."""
+        """Yields (Batch copy, locus_index) until the BAM is exhausted (read_names(): the names of the batch just yielded)."""
         arr = _copy_array
         while True:
             bc = InqBatchC()

@@ -407,6 +407,27 @@ struct LoadUnits {
     const unsigned long long *n_valid;
     __device__ uint64_t operator()(uint64_t i) const { return i < *n_valid ? ((uint64_t)reads[i].n_cigar + 3u) / 4u : 0u; }
 };
+// bytes of record i's name without its terminator, max(l_read_name, 1) - 1, cut to what the inflated bytes hold behind the name's
+// start; 0 for records at and behind *n_valid
+struct LoadNameLen {
+    const uint8_t *u;
+    uint64_t u_bytes;
+    const uint64_t *rec_off;
+    const unsigned long long *n_valid;
+    __device__ uint64_t operator()(uint64_t i) const {
+        if (i >= *n_valid) return 0u;
+        const uint64_t x = rec_off[i];
+        if (x >= u_bytes || u_bytes - x <= 36u) return 0u;  // (36: block_size + the fixed fields in front of the name)
+        const uint64_t l = u[x + 12], len = l > 1u ? l - 1u : 0u, room = u_bytes - x - 36u;
+        return len < room ? len : room;
+    }
+};
+// name_len of origin k, 0 at and behind min(*n_kept, n)
+struct LoadOriginLen {
+    const inq_read_origin_t *origins;
+    const uint64_t *n_kept;
+    __device__ uint64_t operator()(uint64_t k) const { return k < *n_kept ? origins[k].name_len : 0u; }
+};
 struct LoadI64 {
     const int64_t *in;
     __device__ int64_t operator()(uint64_t i) const { return in[i]; }
@@ -572,6 +593,13 @@ void launch_scan_u32_to_u64(const uint32_t *in, uint64_t *out, uint64_t n, uint6
 void launch_scan_cigar_units(const inq_read_t *reads, const unsigned long long *n_valid, uint64_t *out, uint64_t n, uint64_t *tmp,
                              hipStream_t s) {
     run_scan<SumOp, LoadUnits, true>(LoadUnits{reads, n_valid}, out, n, tmp, s);
+}
+void launch_scan_name_len(const uint8_t *u, uint64_t u_bytes, const uint64_t *rec_off, const unsigned long long *n_valid, uint64_t *out,
+                          uint64_t n, uint64_t *tmp, hipStream_t s) {
+    run_scan<SumOp, LoadNameLen, true>(LoadNameLen{u, u_bytes, rec_off, n_valid}, out, n, tmp, s);
+}
+void launch_scan_origin_len(const inq_read_origin_t *origins, const uint64_t *n_kept, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s) {
+    run_scan<SumOp, LoadOriginLen, true>(LoadOriginLen{origins, n_kept}, out, n, tmp, s);
 }
 void launch_scan_max_i64(const int64_t *in, int64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s) {
     run_scan<MaxOp, LoadI64, false>(LoadI64{in}, out, n, (int64_t *)tmp, s);

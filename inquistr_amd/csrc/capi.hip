@@ -329,6 +329,7 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     if (x.evidence && b->n_pairs && (!r->pair_call || !r->pair_bits)) return INQ_ERR_ARG;  // the counting reads both
     if (!x.kept_off != !x.kept || ((uintptr_t)x.kept & 15u) || ((uintptr_t)x.kept_off & 7u)) return INQ_ERR_ARG;
     if (x.kept && b->n_pairs && (!r->pair_call || !r->pair_bits)) return INQ_ERR_ARG;  // ... and so does the compaction
+    if (x.origins && (!x.kept || !x.origin_off || !x.name_off || ((uintptr_t)x.origins & 7u))) return INQ_ERR_ARG;  // who the records are
     if (((uintptr_t)b->cigar & 15u) || ((uintptr_t)b->reads & 15u)) return INQ_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
@@ -398,6 +399,13 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
         launch_read_calls(ReadCallArgs{view, x.kept_off, x.kept, (uint32_t *)(tile_base + read_call_tiles(b->n_pairs) + 1), tile_base}, b->unphased != 0, s);
         HIP_TRY(c, hipGetLastError());
     }
+    if (x.origins && !b->n_pairs) HIP_TRY(c, hipMemsetAsync(x.origin_off, 0, 8, s));  // no record, no name byte
+    if (x.origins && b->n_pairs) {  // behind the scatter: an origin per record it wrote, then where each record's name will go
+        const uint64_t *const n_kept = x.kept_off + b->n_loci;
+        launch_read_origins(ReadOriginArgs{x.kept, n_kept, view.read_words, b->n_reads, x.name_off, x.origins, b->n_pairs}, s);
+        launch_scan_origin_len(x.origins, n_kept, x.origin_off, b->n_pairs, x.origin_off + b->n_pairs + 1, s);
+        HIP_TRY(c, hipGetLastError());
+    }
     if (ev) HIP_TRY(c, hipEventRecord(ev->e2, s));
     return INQ_OK;
 }
@@ -432,6 +440,21 @@ static int read_calls_fetch_impl(inq_ctx_t *c, inq_read_call_t *out, uint64_t n)
 }
 int inq_read_calls_fetch(inq_ctx_t *c, inq_read_call_t *out, uint64_t n) {
     return guarded([&] { return read_calls_fetch_impl(c, out, n); });
+}
+
+uint32_t inq_read_name_tile(void) { return kReadNameTile; }
+
+static int read_origins_fetch_impl(inq_ctx_t *c, inq_read_origin_t *origins, uint64_t n, uint8_t *names, uint64_t name_bytes) {
+    if (!c || n > c->read_origins_total || name_bytes > c->read_names_total || (n && !origins) || (name_bytes && !names)) return INQ_ERR_ARG;
+    if (!n && !name_bytes) return INQ_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n) HIP_TRY(c, hipMemcpyAsync(origins, c->rorigins.p, (size_t)n * sizeof(inq_read_origin_t), hipMemcpyDeviceToHost, c->stream));
+    if (name_bytes) HIP_TRY(c, hipMemcpyAsync(names, c->rnames.p, (size_t)name_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return INQ_OK;
+}
+int inq_read_origins_fetch(inq_ctx_t *c, inq_read_origin_t *origins, uint64_t n, uint8_t *names, uint64_t name_bytes) {
+    return guarded([&] { return read_origins_fetch_impl(c, origins, n, names, name_bytes); });
 }
 
 int inq_ctx_status(inq_ctx_t *c, uint64_t *n_tie_loci) {
@@ -785,6 +808,13 @@ int inq::extras_prepare(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const Hos
     d->evidence = h.evidence ? (inq_locus_evidence_t *)c->levidence.p : nullptr;
     d->kept_off = h.kept_off ? (uint64_t *)c->rcoff.p : nullptr;
     d->kept = h.kept_off ? (inq_read_call_t *)c->rckept.p : nullptr;
+    if (h.name_bytes) {  // (the batch's own names, LocusExtras::name_off, are the caller's to set: only a deferred batch has them)
+        if (!h.kept_off) return INQ_ERR_ARG;
+        if ((rc = ensure(c, c->rorigins, (size_t)n_pairs * sizeof(inq_read_origin_t))) != INQ_OK) return rc;
+        if ((rc = ensure(c, c->rnameoff, (size_t)(n_pairs + 1 + scan_tmp_words(std::max<uint64_t>(n_pairs, 1))) * 8)) != INQ_OK) return rc;
+        d->origins = (inq_read_origin_t *)c->rorigins.p;
+        d->origin_off = (uint64_t *)c->rnameoff.p;
+    }
     return INQ_OK;
 }
 
@@ -795,8 +825,26 @@ int inq::extras_download(inq_ctx *c, uint64_t n_loci, const HostExtras &h, const
     return INQ_OK;
 }
 
+int inq::extras_names(inq_ctx *c, uint64_t n_pairs, const HostExtras &h, const LocusExtras &d, uint64_t n_kept, const uint8_t *batch_names,
+                      uint64_t batch_name_bytes, uint64_t n_reads, uint64_t *total, hipStream_t s) {
+    *total = 0;
+    if (!h.name_bytes || !n_pairs || !n_kept) return INQ_OK;
+    // (the scan's total sits behind the last element; nothing else is in flight on s: a plain 8-byte copy)
+    HIP_TRY(c, hipMemcpyAsync(total, d.origin_off + n_pairs, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (!*total) return INQ_OK;
+    const int rc = ensure(c, c->rnames, (size_t)*total);
+    if (rc != INQ_OK) return rc;
+    launch_name_copy(NameCopyArgs{batch_names, batch_name_bytes, d.name_off, n_reads, 0, d.kept, (uint8_t *)c->rnames.p, *total, d.origin_off,
+                                  std::min(n_kept, n_pairs)}, s);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return INQ_OK;
+}
+
 void inq::extras_finish(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const HostExtras &h, uint32_t err) {
     if (!h.kept_off) return;
     if (!n_loci) h.kept_off[0] = 0;  // (nothing was launched: no list, no record)
     if (err == 0) c->read_calls_total = std::min<uint64_t>(h.kept_off[n_loci], n_pairs);
+    if (h.name_bytes && err == 0) c->read_origins_total = c->read_calls_total, c->read_names_total = *h.name_bytes;
 }

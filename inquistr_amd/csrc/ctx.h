@@ -46,11 +46,16 @@ struct inq_ctx {
     // which stay until the context's next call (inq_read_calls_fetch).  Allocated by calls with the lists only
     inq::DevBuf rctiles, rcoff, rckept;
     uint64_t read_calls_total = 0;  // records of the last host-buffer call or flush (0: it had no lists)
+    // the names and origins of those records (read_names.hip; inq_call_flush_origins): one origin per record, the scan of their name
+    // lengths with its tile totals, the names back to back.  They stay until the context's next call (inq_read_origins_fetch).
+    // Allocated by flushes with origins only
+    inq::DevBuf rorigins, rnameoff, rnames;
+    uint64_t read_origins_total = 0, read_names_total = 0;  // origins and name bytes of the last flush (0: it had no origins)
     inq::DevBuf ovalues, olen, oflags, okeep, otrans;  // inq_outlier_rows
     // every DevBuf above, for inq_ctx_destroy (DevBuf frees nothing itself): a member missing here leaks
     auto bufs() {
         return std::array{&worklist, &sval, &smeta, &deep, &cigar, &reads, &pair_read, &off, &lstart, &lend, &p1, &p2, &pcall, &pbits, &lflags,
-                          &levidence, &evwork, &rctiles, &rcoff, &rckept, &ovalues, &olen, &oflags, &okeep, &otrans};
+                          &levidence, &evwork, &rctiles, &rcoff, &rckept, &rorigins, &rnameoff, &rnames, &ovalues, &olen, &oflags, &okeep, &otrans};
     }
     uint32_t n_cus = 0;        // compute units of the device
     uint32_t grid_tail = 256;  // workgroups of the persistent locus_call_tail: they meet at grid barriers, so never more than n_cus
@@ -157,6 +162,11 @@ struct LocusExtras {
     inq_locus_evidence_t *evidence = nullptr;  // [n_loci]
     uint64_t *kept_off = nullptr;              // [n_loci + 1] the per-read Calls: offsets ...
     inq_read_call_t *kept = nullptr;           // [n_pairs] ... and records; both or neither
+    // the origins of those records (needs kept): one per record, and origin_off[n_pairs + 1 + scan_tmp_words(n_pairs)], the exclusive
+    // scan of their name lengths (origin_off[n_pairs] = the total) with the scan's tile totals behind it; name_off: the batch's names
+    inq_read_origin_t *origins = nullptr;
+    uint64_t *origin_off = nullptr;
+    const uint64_t *name_off = nullptr;        // [n_reads + 1]
 };
 // ... and as a host-buffer call or a flush takes them: HOST pointers, [n_loci] / [n_loci] / [n_loci + 1] in the call's locus order, each
 // may be null.  The records behind kept_off stay in context scratch (inq_read_calls_fetch).
@@ -164,17 +174,22 @@ struct HostExtras {
     uint8_t *flags = nullptr;
     inq_locus_evidence_t *evidence = nullptr;
     uint64_t *kept_off = nullptr;
+    uint64_t *name_bytes = nullptr;  // a flush with origins (needs kept_off): receives the bytes of the kept records' names
     // the evidence is counted and the lists are compacted from the per-pair outputs: the call keeps those (pcall / pbits) also when
     // its caller did not ask for them
     bool per_pair() const { return evidence || kept_off; }
 };
 // The three steps of a host-buffer call or a flush around its launch sequence.  First of all extras_reset: the records of the call
 // before are no longer offered, however this one ends.
-inline void extras_reset(inq_ctx *c) { c->read_calls_total = 0; }
+inline void extras_reset(inq_ctx *c) { c->read_calls_total = c->read_origins_total = c->read_names_total = 0; }
 // the context buffers behind what h asks for (and pcall / pbits where h.per_pair()), as device pointers
 int extras_prepare(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const HostExtras &h, LocusExtras *d);
 // enqueues the copies down on s; the flags go to flags_dst (the caller's array, or page-locked staging on their way there)
 int extras_download(inq_ctx *c, uint64_t n_loci, const HostExtras &h, const LocusExtras &d, uint8_t *flags_dst, hipStream_t s);
+// a flush with origins, after its synchronisation (n_kept = kept_off[n_loci] is known then): the bytes of the kept records' names come
+// down (*total), c->rnames is sized from them, the copy launch runs and is waited for.  Without origins, pairs or records: nothing
+int extras_names(inq_ctx *c, uint64_t n_pairs, const HostExtras &h, const LocusExtras &d, uint64_t n_kept, const uint8_t *batch_names,
+                 uint64_t batch_name_bytes, uint64_t n_reads, uint64_t *total, hipStream_t s);
 // after the call's synchronisation, or at once for a call without loci: how many records inq_read_calls_fetch offers.  err: the
 // kernels' status word - after a domain error the lists are unspecified and none is offered, whatever the offsets say
 void extras_finish(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const HostExtras &h, uint32_t err);

@@ -104,6 +104,12 @@ void launch_scan_u32_to_u64(const uint32_t *in, uint64_t *out, uint64_t n, uint6
 // CIGAR sizes: units(i) = ceil(n_cigar / 4) for i < *n_valid, else 0
 void launch_scan_cigar_units(const inq_read_t *reads, const unsigned long long *n_valid, uint64_t *out, uint64_t n, uint64_t *tmp,
                              hipStream_t s);
+// read names (read_names.hip copies what these place): bytes of record i's name, max(l_read_name, 1) - 1 read at rec_off[i] + 12 and cut
+// to the inflated bytes, for i < *n_valid, else 0 ...
+void launch_scan_name_len(const uint8_t *u, uint64_t u_bytes, const uint64_t *rec_off, const unsigned long long *n_valid, uint64_t *out,
+                          uint64_t n, uint64_t *tmp, hipStream_t s);
+// ... and name_len of origin k for k < *n_kept (DEVICE), else 0
+void launch_scan_origin_len(const inq_read_origin_t *origins, const uint64_t *n_kept, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s);
 void launch_scan_max_i64(const int64_t *in, int64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s);
 inline uint64_t scan_tmp_words(uint64_t n) { return (n + 4095) / 4096 + 2; }
 

@@ -24,4 +24,37 @@ inline size_t read_call_scratch_bytes(uint64_t n_pairs) { return (size_t)(read_c
 // the three launches on s (a.n_pairs > 0; a batch without pairs is a fill of kept_off, done by the caller)
 void launch_read_calls(const ReadCallArgs &a, bool unphased, hipStream_t s);
 
+// ---- read_names.hip: the names and origins of the kept reads (inq_read_origin_t)
+constexpr uint32_t kReadNameLanes = 8;                    // lanes that share one segment of the byte gather
+constexpr uint32_t kReadNameTile = 256 / kReadNameLanes;  // segments per workgroup (inq_read_name_tile)
+constexpr uint32_t kReadNameMax = 254;                    // l_read_name is a byte and counts the terminator
+
+// The segmented byte gather: segment i copies dst_off[i + 1] - dst_off[i] bytes from src + src_off[r] + src_add to dst + dst_off[i],
+// r = index[i].read, or i where index is null.  dst_off is an exclusive prefix sum ([n + 1]).  A segment is cut to [dst, dst + dst_bytes)
+// and to [src, src + src_bytes); r >= n_src copies nothing.
+struct NameCopyArgs {
+    const uint8_t *src;
+    uint64_t src_bytes;
+    const uint64_t *src_off;       // [n_src]
+    uint64_t n_src, src_add;
+    const inq_read_call_t *index;  // [n] or null
+    uint8_t *dst;
+    uint64_t dst_bytes;
+    const uint64_t *dst_off;       // [n + 1]
+    uint64_t n;
+};
+void launch_name_copy(const NameCopyArgs &a, hipStream_t s);  // n == 0 launches nothing
+
+// one inq_read_origin_t per record the compaction wrote, k < min(*n_kept, n_pairs): reads[kept[k].read] and that read's name length
+struct ReadOriginArgs {
+    const inq_read_call_t *kept;
+    const uint64_t *n_kept;      // DEVICE: kept_off[n_loci]
+    const uint32_t *read_words;  // inq_read_t as four words (PairView::read_words)
+    uint64_t n_reads;
+    const uint64_t *name_off;    // [n_reads + 1] the batch's names
+    inq_read_origin_t *origins;  // [n_pairs], 8-byte aligned
+    uint64_t n_pairs;
+};
+void launch_read_origins(const ReadOriginArgs &a, hipStream_t s);
+
 }  // namespace inq

@@ -14,6 +14,7 @@
 #include "ctx.h"
 #include "deflate_probe.h"
 #include "front_kernels.h"
+#include "read_calls.h"
 
 namespace inq {
 
@@ -21,15 +22,18 @@ struct SpanState {
     DevBuf tok;  // the workgroup inflate's token scratch
     DevBuf comp, blocks, u, block_status, anchors, anchor_cnt, anchor_base, rec_off, reads, info, key, endkey, pmax, cig_off, cigar,
         anchor_stop, ltid, lstart, lend, locus_cnt, locus_off, pair_read, p1, p2, tmp;
+    DevBuf name_off;  // [n_records + 1] of a span appended with names: where each record's name begins among the span's (read_names.hip)
     auto bufs() {  // every DevBuf above, for span_state_destroy
         return std::array{&tok, &comp, &blocks, &u, &block_status, &anchors, &anchor_cnt, &anchor_base, &rec_off, &reads, &info, &key, &endkey,
-                          &pmax, &cig_off, &cigar, &anchor_stop, &ltid, &lstart, &lend, &locus_cnt, &locus_off, &pair_read, &p1, &p2, &tmp};
+                          &pmax, &cig_off, &cigar, &anchor_stop, &ltid, &lstart, &lend, &locus_cnt, &locus_off, &pair_read, &p1, &p2, &tmp,
+                          &name_off};
     }
     FrontStatus *d_st = nullptr;
     struct Host {  // pinned readback area
         FrontStatus st;
         DevStatus ks;
         uint64_t count;  // what a stage of call_span_impl reads back to size the next one
+        uint64_t name_bytes;  // ... and, for a span appended with names, the bytes of its names
         unsigned long long init_n_valid;
     } *h = nullptr;
     // pinned staging of the rows: the caller's result arrays are ordinary memory, and the FIRST copy to or from pageable
@@ -69,14 +73,20 @@ struct SpanState {
     // the batch the last inq_call_span built
     uint64_t n_reads = 0, n_cigar_words = 0, n_pairs = 0, n_loci = 0;
     bool last_from_acc = false;
+    bool last_names = false;  // that batch was appended with names (inq_span_fetch_names) ...
+    uint64_t n_name_bytes = 0;  // ... this many bytes of them
     // inq_call_span_deferred: the batches of several spans appended to one (CIGAR units, reads, pairs, loci so far), called
     // together by inq_call_flush - a span of SEQ-bearing records holds a few hundred loci, far too few to fill the chip
     struct Acc {
         DevBuf cigar, reads, pair_read, off, lstart, lend;
+        // a batch appended with names (inq_call_span_deferred_names): the names of its reads back to back, name_off[n_reads + 1]
+        DevBuf names, name_off;
         uint64_t n_units = 0, n_reads = 0, n_pairs = 0, n_loci = 0, n_spans = 0;
         uint32_t minlen = 0, support = 0, unphased = 0, max_reads = 0;
-        auto bufs() { return std::array{&cigar, &reads, &pair_read, &off, &lstart, &lend}; }
-        void reset() { *this = Acc{cigar, reads, pair_read, off, lstart, lend}; }  // the batch is gone, its buffers stay
+        uint64_t n_name_bytes = 0;
+        bool with_names = false;  // every span of the batch, or none
+        auto bufs() { return std::array{&cigar, &reads, &pair_read, &off, &lstart, &lend, &names, &name_off}; }
+        void reset() { *this = Acc{cigar, reads, pair_read, off, lstart, lend, names, name_off}; }  // the batch is gone, its buffers stay
     } acc;
 };
 
@@ -290,8 +300,9 @@ int bgzf_inflate_impl(inq_ctx *c, const uint8_t *comp, uint64_t comp_bytes, cons
 }
 
 // defer: the span's batch is appended to S->acc instead of being called (r may be null then)
-int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_stats_t *stats, int slot, bool defer = false) {
-    if (!c || !sp || (!r && !defer) || slot >= INQ_SPAN_SLOTS) return INQ_ERR_ARG;
+// names: with the names of the span's placed records (deferred only)
+int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_stats_t *stats, int slot, bool defer = false, bool names = false) {
+    if (!c || !sp || (!r && !defer) || slot >= INQ_SPAN_SLOTS || (names && !defer)) return INQ_ERR_ARG;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (sp->reserved || sp->unphased > 1) return INQ_ERR_ARG;
     if (sp->n_loci && (!sp->locus_tid || !sp->locus_start || !sp->locus_end || (!defer && (!r->phase1 || !r->phase2)))) return INQ_ERR_ARG;
@@ -320,6 +331,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     const uint64_t nl = sp->n_loci, na = sp->n_anchors;
     SpanState::Acc &A = S->acc;
     if (defer && A.n_spans && (A.minlen != sp->minlen || A.support != sp->support || A.unphased != sp->unphased)) return INQ_ERR_ARG;
+    if (defer && A.n_spans && A.with_names != names) return INQ_ERR_ARG;  // all spans of a batch with names, or all without
     const SpanState::Stage *staged = nullptr;
     if (slot >= 0) {  // the span inq_span_stage put there, and nothing else
         const SpanState::Stage &g = S->stage[slot];
@@ -395,8 +407,9 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
         return INQ_OK;
     };
     // the readback that ends each of the stages 1 - 3: one count and the front status come down, the stream drains
-    auto read_count = [&](const uint64_t *d_count, uint64_t *count) -> int {
+    auto read_count = [&](const uint64_t *d_count, uint64_t *count, const uint64_t *d_name_bytes = nullptr) -> int {
         HIP_TRY(c, hipMemcpyAsync(&S->h->count, d_count, 8, hipMemcpyDeviceToHost, s));
+        if (d_name_bytes) HIP_TRY(c, hipMemcpyAsync(&S->h->name_bytes, d_name_bytes, 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(&S->h->st, S->d_st, sizeof(FrontStatus), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
         *count = S->h->count;
@@ -414,6 +427,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     if ((rc = ensure(c, S->endkey, n_rec * 8)) != INQ_OK) return rc;
     if ((rc = ensure(c, S->pmax, n_rec * 8)) != INQ_OK) return rc;
     if ((rc = ensure(c, S->cig_off, (n_rec + 1) * 8)) != INQ_OK) return rc;
+    if (names && (rc = ensure(c, S->name_off, (n_rec + 1) * 8)) != INQ_OK) return rc;
     if ((rc = ensure(c, S->tmp, scan_tmp_words(std::max<uint64_t>(std::max(std::max(na, nl), n_rec), 1)) * 8)) != INQ_OK) return rc;
     a.rec_off = (uint64_t *)S->rec_off.p;
     a.n_records = n_rec;
@@ -428,8 +442,12 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     launch_chain_fill(a, s);
     launch_record_parse(a, s);
     launch_scan_cigar_units(a.reads, &S->d_st->n_valid, a.cig_off, n_rec, (uint64_t *)S->tmp.p, s);
+    uint64_t *const span_name_off = names ? (uint64_t *)S->name_off.p : nullptr;
+    if (names)  // where each placed record's name begins among the span's, and their total: it comes down with the CIGAR size
+        launch_scan_name_len(a.u, a.u_bytes, a.rec_off, &S->d_st->n_valid, span_name_off, n_rec, (uint64_t *)S->tmp.p, s);
     HIP_TRY(c, hipGetLastError());
-    if ((rc = read_count(a.cig_off + n_rec, &n_units)) != INQ_OK) return rc;
+    if ((rc = read_count(a.cig_off + n_rec, &n_units, names ? span_name_off + n_rec : nullptr)) != INQ_OK) return rc;
+    const uint64_t name_bytes = names ? S->h->name_bytes : 0;
     const uint64_t n_valid = S->h->st.n_valid;
     clock.at("parse done");
     if (n_valid > n_rec || n_valid >= 0xfffffff0ull || n_units >= 0xffffffffull) {
@@ -456,6 +474,11 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
         clock.at("  batch CIGAR buffer ready");
         if ((rc = ensure_keep(c, A.reads, (A.n_reads + n_valid) * sizeof(inq_read_t), A.n_reads * sizeof(inq_read_t), s, res_reads)) != INQ_OK) return rc;
         clock.at("  batch read buffer ready");
+        if (names) {
+            // (of the first span of a batch nothing is kept: name_off[0] is written with the span's offsets)
+            if ((rc = ensure_keep(c, A.names, A.n_name_bytes + name_bytes, A.n_name_bytes, s)) != INQ_OK) return rc;
+            if ((rc = ensure_keep(c, A.name_off, (A.n_reads + n_valid + 1) * 8, A.n_spans ? (A.n_reads + 1) * 8 : 0, s)) != INQ_OK) return rc;
+        }
         a.cigar = (uint32_t *)A.cigar.p + A.n_units * 4;
         a.unit_base = (uint32_t)A.n_units;
         a.read_base = (uint32_t)A.n_reads;
@@ -466,6 +489,13 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     a.n_cigar_units = n_units;
     a.gather_nt = c->gather_nt ? 1u : 0u;
     launch_cigar_gather(a, n_valid, s);
+    if (names) {
+        // the names of the placed records, out of the inflated bytes (rec_off[i] + 36) into the batch behind the names that are there;
+        // name_off[read_base + i] = the batch's bytes so far + the span's offset, [read_base + n_valid] = where the next span's begin
+        launch_offset_copy((uint64_t *)A.name_off.p + A.n_reads, span_name_off, n_valid + 1, A.n_name_bytes, s);
+        launch_name_copy(NameCopyArgs{a.u, a.u_bytes, a.rec_off, n_valid, 36, nullptr, (uint8_t *)A.names.p + A.n_name_bytes, name_bytes,
+                                      span_name_off, n_valid}, s);
+    }
     if (defer && n_valid)  // the descriptors, CIGAR offsets already counted from the start of the accumulated buffer
         HIP_TRY(c, hipMemcpyAsync((inq_read_t *)A.reads.p + A.n_reads, a.reads, n_valid * sizeof(inq_read_t), hipMemcpyDeviceToDevice, s));
     launch_scan_max_i64(a.endkey, a.pmax, n_valid, (uint64_t *)S->tmp.p, s);
@@ -521,7 +551,8 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
         HIP_TRY(c, hipStreamSynchronize(s));  // the span's slot and the scan buffers are free again when this returns
         fill_stats();
         if ((rc = front_fail(S->h->st)) != INQ_OK) return rc;
-        if (A.n_spans == 0) A.minlen = sp->minlen, A.support = sp->support, A.unphased = sp->unphased, A.max_reads = 0;
+        if (A.n_spans == 0) A.minlen = sp->minlen, A.support = sp->support, A.unphased = sp->unphased, A.max_reads = 0, A.with_names = names;
+        A.n_name_bytes += name_bytes;
         A.max_reads = std::max<uint32_t>(A.max_reads, S->h->st.max_reads);
         A.n_units += n_units, A.n_reads += n_valid, A.n_pairs += n_pairs, A.n_loci += nl, ++A.n_spans;
         clock.at("appended to the deferred batch");
@@ -550,6 +581,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     S->n_pairs = n_pairs;
     S->n_loci = nl;
     S->last_from_acc = false;
+    S->last_names = false, S->n_name_bytes = 0;
     fill_stats();
     r->n_tie_loci = S->h->ks.ties;
     if ((rc = front_fail(S->h->st)) != INQ_OK) return rc;
@@ -575,6 +607,10 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     r->n_tie_loci = 0;
     if (ms_call) *ms_call = 0.0;
     if (n_loci != A.n_loci) return INQ_ERR_ARG;
+    if (h.name_bytes) {  // origins: of the records behind kept_off, out of a batch that was appended with names (an empty one has none to lack)
+        if (!h.kept_off || (A.n_spans && !A.with_names)) return INQ_ERR_ARG;
+        *h.name_bytes = 0;
+    }
     if (A.n_loci == 0) {
         A.reset();
         extras_finish(c, 0, 0, h, 0);
@@ -594,6 +630,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     // (the evidence and the per-read Calls need the per-pair outputs, which a flush otherwise does not produce)
     LocusExtras x;
     if ((rc = extras_prepare(c, nl, A.n_pairs, h, &x)) != INQ_OK) return rc;
+    if (h.name_bytes) x.name_off = (const uint64_t *)A.name_off.p;
     const bool per_pair = h.per_pair();
     if ((rc = ensure_row_staging(c, S, nl, 2 * nl + (h.flags ? (nl + 7) / 8 : 0))) != INQ_OK) return rc;  // the rows, then the flags
     DevBatch d = device_batch(A.cigar.p, A.reads.p, A.pair_read.p, A.off.p, A.lstart.p, A.lend.p, A.n_reads, A.n_units * 4, A.n_pairs, nl,
@@ -606,7 +643,8 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
         SpanState::Acc &a;
         ~Spent() { a.reset(); }
     } spent{A};
-    const uint64_t n_reads_all = A.n_reads, n_units_all = A.n_units, n_pairs_all = A.n_pairs;
+    const uint64_t n_reads_all = A.n_reads, n_units_all = A.n_units, n_pairs_all = A.n_pairs, n_name_bytes_all = A.n_name_bytes;
+    const bool with_names = A.with_names;
     HIP_TRY(c, hipEventRecord(S->ev[4], s));
     if ((rc = call_batch_device_impl(c, &db, &dr, s, x)) != INQ_OK) return rc;
     HIP_TRY(c, hipEventRecord(S->ev[5], s));
@@ -636,6 +674,9 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     if ((rc = status_readback(c, &S->h->ks, s)) != INQ_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
     if (h.flags) std::memcpy(h.flags, S->h_rows + 2 * nl, nl);
+    if (h.name_bytes && S->h->ks.err == 0 &&  // the kept records' names, now that their number is known
+        (rc = extras_names(c, n_pairs_all, h, x, h.kept_off[nl], (const uint8_t *)A.names.p, n_name_bytes_all, n_reads_all, h.name_bytes, s)) != INQ_OK)
+        return rc;
     if (!dev) {
         std::memcpy(r->phase1, S->h_rows, nl * 8);
         std::memcpy(r->phase2, S->h_rows + nl, nl * 8);
@@ -655,6 +696,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     }
     S->n_reads = n_reads_all, S->n_cigar_words = n_units_all * 4, S->n_pairs = n_pairs_all, S->n_loci = nl;
     S->last_from_acc = true;  // inq_span_fetch_batch reads the accumulated buffers (their contents stay until the next append)
+    S->last_names = with_names, S->n_name_bytes = n_name_bytes_all;
     r->n_tie_loci = S->h->ks.ties;
     extras_finish(c, nl, n_pairs_all, h, S->h->ks.err);
     return status_to_code(S->h->ks.err);  // (`spent` puts the counters back to zero, the buffers stay)
@@ -769,6 +811,18 @@ int fetch_batch_impl(inq_ctx *c, uint32_t *cigar, inq_read_t *reads, uint32_t *p
     return INQ_OK;
 }
 
+// the names of the batch the last flush ran on (their contents stay until the next append, like the batch's other arrays)
+int fetch_names_impl(inq_ctx *c, uint64_t *name_off, uint8_t *names, uint64_t cap_bytes) {
+    if (!c || !c->span) return INQ_ERR_ARG;
+    SpanState *S = c->span;
+    if (!S->last_from_acc || !S->last_names || cap_bytes < S->n_name_bytes) return INQ_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (name_off) HIP_TRY(c, hipMemcpy(name_off, S->acc.name_off.p, (S->n_reads + 1) * 8, hipMemcpyDeviceToHost));
+    if (names && S->n_name_bytes) HIP_TRY(c, hipMemcpy(names, S->acc.names.p, S->n_name_bytes, hipMemcpyDeviceToHost));
+    return INQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -803,6 +857,10 @@ int inq_call_span_deferred(inq_ctx_t *c, const inq_span_t *span, int slot, inq_s
     return guarded([&] { return call_span_impl(c, span, nullptr, stats, slot < 0 ? -1 : slot, true); });
 }
 
+int inq_call_span_deferred_names(inq_ctx_t *c, const inq_span_t *span, int slot, inq_span_stats_t *stats) {
+    return guarded([&] { return call_span_impl(c, span, nullptr, stats, slot < 0 ? -1 : slot, true, true); });
+}
+
 int inq_call_flush(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call) {
     return inq_call_flush_flags(c, result, n_loci, ms_call, nullptr);
 }
@@ -819,6 +877,14 @@ int inq_call_flush_evidence(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci,
 int inq_call_flush_reads(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
                          inq_locus_evidence_t *evidence, uint64_t *kept_off) {
     return guarded([&] { return call_flush_impl(c, result, n_loci, ms_call, nullptr, HostExtras{locus_flags, evidence, kept_off}); });
+}
+
+int inq_call_flush_origins(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
+                           inq_locus_evidence_t *evidence, uint64_t *kept_off, uint64_t *name_bytes) {
+    return guarded([&] {
+        if (!kept_off || !name_bytes) return (int)INQ_ERR_ARG;
+        return call_flush_impl(c, result, n_loci, ms_call, nullptr, HostExtras{locus_flags, evidence, kept_off, name_bytes});
+    });
 }
 
 int inq_call_flush_device(inq_ctx_t *c, double *d_phase1, double *d_phase2, uint64_t cap, const uint32_t *index, uint64_t n_loci, uint64_t *n_tie_loci,
@@ -880,6 +946,10 @@ void inq_call_discard(inq_ctx_t *c) {
 
 int inq_span_fetch_batch(inq_ctx_t *c, uint32_t *cigar, inq_read_t *reads, uint32_t *pair_read, uint64_t *locus_pair_off) {
     return guarded([&] { return fetch_batch_impl(c, cigar, reads, pair_read, locus_pair_off); });
+}
+
+int inq_span_fetch_names(inq_ctx_t *c, uint64_t *name_off, uint8_t *names, uint64_t cap_bytes) {
+    return guarded([&] { return fetch_names_impl(c, name_off, names, cap_bytes); });
 }
 
 }  // extern "C"

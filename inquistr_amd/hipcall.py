@@ -82,6 +82,11 @@ ABI_SYMBOLS = (
     "inq_call_flush_reads",
     "inq_read_calls_fetch",
     "inq_read_call_tile",
+    "inq_call_span_deferred_names",
+    "inq_call_flush_origins",
+    "inq_read_origins_fetch",
+    "inq_span_fetch_names",
+    "inq_read_name_tile",
 )
 
 
@@ -176,6 +181,20 @@ class ReadCallC(C.Structure):
 READ_CALL_DTYPE = np.dtype([("call", "<i8"), ("read", "<u4"), ("group", "u1"), ("flags", "u1"), ("reserved", "<u2")])
 
 
+class ReadOriginC(C.Structure):
+    """inq_read_origin_t"""
+
+    _fields_ = [
+        ("pos", C.c_int32),
+        ("mapq", C.c_uint8),
+        ("bits", C.c_uint8),
+        ("name_len", C.c_uint16),
+    ]
+
+
+ORIGIN_DTYPE = np.dtype([("pos", "<i4"), ("mapq", "u1"), ("bits", "u1"), ("name_len", "<u2")])
+
+
 def scan_bgzf(data) -> np.ndarray:
     """Walks the BGZF headers of `data` (whole blocks): the block table inq_bgzf_inflate / inq_call_span take
     (payload offset and length, ISIZE, dense output offsets)."""
@@ -210,7 +229,8 @@ class InqError(RuntimeError):
 
 
 _lib = None
-_SIDE_SUFFIXES = ("", "_flags", "_evidence", "_reads")  # the entries of a family: each takes the side outputs of the one before and its own
+# the entries of a family: each takes the side outputs of the one before and its own (`_origins`: the flush family only)
+_SIDE_SUFFIXES = ("", "_flags", "_evidence", "_reads", "_origins")
 
 
 def load(path: Optional[str] = None):
@@ -250,11 +270,11 @@ def load(path: Optional[str] = None):
     L.inq_ctx_destroy.restype = None
     L.inq_ctx_destroy.argtypes = [vp]
     # The three families of calls with per-locus side outputs: a member takes the family's arguments, then one pointer for each side
-    # output it adds (flags | evidence | kept_off, and kept for the device form), then - the device form - the stream.
+    # output it adds (flags | evidence | kept_off, and kept for the device form | name_bytes), then - the device form - the stream.
     for family, head, widths, tail in (
         ("inq_call_batch", [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC)], (0, 1, 2, 3), []),
         ("inq_call_batch_device", [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC)], (0, 1, 2, 4), [vp]),
-        ("inq_call_flush", [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double)], (0, 1, 2, 3), []),
+        ("inq_call_flush", [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double)], (0, 1, 2, 3, 4), []),
     ):
         for suffix, n_side in zip(_SIDE_SUFFIXES, widths):
             fn = getattr(L, family + suffix)
@@ -264,6 +284,14 @@ def load(path: Optional[str] = None):
     L.inq_read_calls_fetch.argtypes = [vp, vp, C.c_uint64]
     L.inq_read_call_tile.restype = C.c_uint32
     L.inq_read_call_tile.argtypes = []
+    L.inq_read_origins_fetch.restype = C.c_int
+    L.inq_read_origins_fetch.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
+    L.inq_read_name_tile.restype = C.c_uint32
+    L.inq_read_name_tile.argtypes = []
+    L.inq_call_span_deferred_names.restype = C.c_int
+    L.inq_call_span_deferred_names.argtypes = [vp, C.POINTER(SpanC), C.c_int, C.POINTER(SpanStatsC)]
+    L.inq_span_fetch_names.restype = C.c_int
+    L.inq_span_fetch_names.argtypes = [vp, vp, vp, C.c_uint64]
     L.inq_ctx_status.restype = C.c_int
     L.inq_ctx_status.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.inq_ctx_timing_enable.restype = C.c_int
@@ -381,24 +409,30 @@ class Context:
         raise InqError(rc, strerror(rc) + (f" [{detail}]" if detail and rc == -8 else ""))
 
     @staticmethod
-    def _side_arrays(n: int, flags: bool, evidence: bool, kept_off: bool):
+    def _side_arrays(n: int, flags: bool, evidence: bool, kept_off: bool, name_bytes: bool = False):
         """The arrays of a call of n loci for the side outputs asked for (else None), every byte 0xFF: one the call did not write shows."""
         fl = np.full(max(n, 1), 0xFF, dtype=np.uint8) if flags else None
         ev = np.full(max(n, 1) * EVIDENCE_DTYPE.itemsize, 0xFF, dtype=np.uint8) if evidence else None
         off = np.full(n + 1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if kept_off else None
-        return fl, ev, off
+        nb = np.full(1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if name_bytes else None
+        return fl, ev, off, nb
 
     def _side_call(self, entry: str, head, n: int, width: int, check: bool, flags: bool = True, evidence: bool = True):
         """Calls `entry`, the member of its family that takes `width` side outputs, with `head` and the arrays of _side_arrays; raises on
         error if check.  Returns (code, flags, evidence, kept_off, records), each cut to the n loci, None where not taken; the records are
-        fetched behind a successful call with the lists."""
-        fl, ev, off = self._side_arrays(n, flags and width >= 1, evidence and width >= 2, width >= 3)
-        side = [None if a is None else a.ctypes.data for a in (fl, ev, off)][:width]
+        fetched behind a successful call with the lists.  width 4 (a flush with origins) adds a sixth element: (origins, names,
+        name_bytes) fetched the same way, (None, None, name_bytes) after a failed call."""
+        fl, ev, off, nb = self._side_arrays(n, flags and width >= 1, evidence and width >= 2, width >= 3, width >= 4)
+        side = [None if a is None else a.ctypes.data for a in (fl, ev, off, nb)][:width]
         rc = getattr(self._L, entry)(self._h, *head, *side)
         if rc != INQ_OK and check:
             self._raise(rc)
         rec = self.read_calls_fetch(int(off[-1])) if off is not None and rc == INQ_OK else None
-        return rc, (None if fl is None else fl[:n]), (None if ev is None else ev.view(EVIDENCE_DTYPE)[:n]), off, rec
+        out = (rc, (None if fl is None else fl[:n]), (None if ev is None else ev.view(EVIDENCE_DTYPE)[:n]), off, rec)
+        if nb is not None:
+            who = self.read_origins_fetch(int(off[-1]), int(nb[0])) if rc == INQ_OK else (None, None)
+            out += (who + (int(nb[0]),),)
+        return out
 
     def _batch_call(self, entry: str, batch: Batch, debug: bool, width: int, check: bool, **which):
         res = Result.alloc(batch, debug=debug)
@@ -443,6 +477,21 @@ class Context:
             self._raise(rc)
         rec = out.view(READ_CALL_DTYPE)[:n]
         return rec if check else (rc, rec)
+
+    def read_origins_fetch(self, n: int, name_bytes: int, check: bool = True):
+        """inq_read_origins_fetch: the first n origins (ORIGIN_DTYPE) and the first name_bytes bytes of the names (uint8) of the last
+        call_flush_origins; record k's name begins at the sum of name_len in front of it (check=False: (code, origins, names))."""
+        org = np.full(max(n, 1) * ORIGIN_DTYPE.itemsize, 0xFF, dtype=np.uint8)
+        names = np.full(max(name_bytes, 1), 0xFF, dtype=np.uint8)
+        rc = self._L.inq_read_origins_fetch(self._h, org.ctypes.data, n, names.ctypes.data, name_bytes)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        got = (org.view(ORIGIN_DTYPE)[:n], names[:name_bytes])
+        return got if check else (rc,) + got
+
+    @property
+    def read_name_tile(self) -> int:
+        return int(self._L.inq_read_name_tile())
 
     def call_batch_reads(self, batch: Batch, debug: bool = False, check: bool = True, flags: bool = True, evidence: bool = True):
         """inq_call_batch_reads: (code, Result, per-locus flags or None, per-locus evidence or None, kept_off [n_loci + 1], the records
@@ -523,9 +572,12 @@ class Context:
         return rc
 
     def call_span_deferred(self, comp, blocks, anchors, anchor_stop, locus_tid, locus_start, locus_end, minlen: int = 5, support: int = 3,
-                           unphased: bool = False, check: bool = True, stage_slot: Optional[int] = None, prestaged: bool = False):
+                           unphased: bool = False, check: bool = True, stage_slot: Optional[int] = None, prestaged: bool = False,
+                           names: bool = False):
         """inq_call_span_deferred: appends the span's batch to the deferred one; returns (code, stats).  Rows: call_flush().
-        prestaged: the span already sits in stage_slot (span_stage_begin + span_stage_wait): it is not staged again."""
+        prestaged: the span already sits in stage_slot (span_stage_begin + span_stage_wait): it is not staged again.
+        names: inq_call_span_deferred_names - the names of the span's placed records are gathered into the batch too (every span of
+        a batch, or none)."""
         comp = np.frombuffer(comp, dtype=np.uint8)
         blocks = np.ascontiguousarray(blocks, dtype=BGZF_BLOCK_DTYPE)
         anchors = np.ascontiguousarray(anchors, dtype=np.uint64)
@@ -540,7 +592,8 @@ class Context:
         if stage_slot is not None and not prestaged:
             rc = self._L.inq_span_stage(self._h, C.byref(sp), stage_slot)
         if rc == INQ_OK:
-            rc = self._L.inq_call_span_deferred(self._h, C.byref(sp), -1 if stage_slot is None else stage_slot, C.byref(stats))
+            entry = self._L.inq_call_span_deferred_names if names else self._L.inq_call_span_deferred
+            rc = entry(self._h, C.byref(sp), -1 if stage_slot is None else stage_slot, C.byref(stats))
         if rc != INQ_OK and check:
             self._raise(rc)
         return rc, stats
@@ -554,14 +607,14 @@ class Context:
 
     def _flush_call(self, entry: str, width: int, check: bool):
         """(code, phase1, phase2, n_tie_loci, ms_call) of `entry` for every locus deferred since the last flush, then the first `width`
-        of flags, evidence, kept_off + records."""
+        of flags, evidence, kept_off + records, origins + names + name_bytes."""
         n = self.deferred_loci
         p1 = np.full(n, np.nan)
         p2 = np.full(n, np.nan)
         res = InqResultC(p1.ctypes.data, p2.ctypes.data, None, None, 0)
         ms = C.c_double(0.0)
-        rc, fl, ev, off, rec = self._side_call(entry, (C.byref(res), n, C.byref(ms)), n, width, check)
-        return (rc, p1, p2, int(res.n_tie_loci), float(ms.value)) + (fl, ev, off, rec)[: width + (width == 3)]
+        rc, fl, ev, off, rec, *who = self._side_call(entry, (C.byref(res), n, C.byref(ms)), n, width, check)
+        return (rc, p1, p2, int(res.n_tie_loci), float(ms.value)) + (fl, ev, off, rec)[: width + (width >= 3)] + (who[0] if who else ())
 
     def call_flush(self, check: bool = True):
         """inq_call_flush: (code, phase1, phase2, n_tie_loci, ms_call) for every locus deferred since the last flush."""
@@ -579,6 +632,23 @@ class Context:
         """inq_call_flush_reads: as call_flush_evidence, plus kept_off [n + 1] and the records (READ_CALL_DTYPE; None after a failed
         call) as the eighth and ninth element; `read` indexes the reads span_fetch_batch returns."""
         return self._flush_call("inq_call_flush_reads", 3, check)
+
+    def call_flush_origins(self, check: bool = True):
+        """inq_call_flush_origins: as call_flush_reads, plus the origins of the records (ORIGIN_DTYPE, same order), their names back to
+        back (uint8) and the names' total as the tenth to twelfth element (None, None, total after a failed call)."""
+        return self._flush_call("inq_call_flush_origins", 4, check)
+
+    def span_fetch_names(self, n_reads: int, cap_bytes: Optional[int] = None, check: bool = True):
+        """inq_span_fetch_names: (name_off u64 [n_reads + 1], names uint8) of ALL reads of the batch the last flush ran on, n_reads from
+        the appended spans' stats; cap_bytes: room for the names (default: 255 per read).  check=False: (code, name_off, names)."""
+        cap = 255 * n_reads + 1 if cap_bytes is None else cap_bytes
+        off = np.full(n_reads + 1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+        names = np.full(max(cap, 1), 0xFF, dtype=np.uint8)
+        rc = self._L.inq_span_fetch_names(self._h, off.ctypes.data, names.ctypes.data, cap)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        got = (off, names[: int(off[-1])] if rc == INQ_OK else names[:0])
+        return got if check else (rc,) + got
 
     def span_fetch_batch(self, stats: "SpanStatsC", n_loci: int):
         """The batch the last call_span built on the device, as host arrays (cigar, reads, pair_read, locus_pair_off)."""

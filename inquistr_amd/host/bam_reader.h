@@ -124,6 +124,9 @@ struct BamRec {
     char sa_type = 0;   // 0 = absent
     const char *sa = nullptr;  // NUL-terminated when sa_type == 'Z'
     uint64_t voffset = 0;      // virtual offset of the record (identity for de-duplication)
+    // QNAME: bytes [0, max(l_read_name, 1) - 1) of the name field, as they stand, into the reader's record buffer (the read table)
+    const uint8_t *name = nullptr;
+    uint32_t name_len = 0;
 };
 
 class BamFile {

@@ -286,6 +286,12 @@ struct CallView {
 // the per-read Calls of a call's targets: [k] = the records of target k's kept reads in file order (empty: no batch or span held it)
 using ReadCallLists = std::vector<std::vector<inq_read_call_t>>;
 
+// who those reads are, for the read table: [k] = the origins of target k's records, in the records' order, and their names back to back
+struct ReadIdentities {
+    std::vector<inq_read_origin_t> origins;
+    std::vector<uint8_t> names;
+};
+
 // src[j] -> dst[index[j]]: rows and reports of a batch, a flush or a device part into their targets' places
 template <class T>
 inline void scatter(const T *src, const uint32_t *index, size_t n, T *dst) {
@@ -293,14 +299,15 @@ inline void scatter(const T *src, const uint32_t *index, size_t n, T *dst) {
 }
 
 // The per-target reports of a call, beside its rows: the tie report (inq_call_args_t::ties_path), the evidence file (::evidence_path), the
-// read-calls file (inq_genotype_repeats_reads).  One value at every layer; a further report is one more member of each of the three
+// read-calls file (inq_genotype_repeats_reads), the read table (inq_genotype_repeats_table; it needs the read-calls lists, which are
+// then collected with it).  One value at every layer; a further report is one more member of each of the three
 // structs, a line in begin / scatter_from, a row in write_rows' table and a pointer in BatchRows::call / flush.
 struct ReportSet {  // which of them are collected: what is not adds nothing to the launch sequence
-    bool ties = false, evidence = false, read_calls = false;
+    bool ties = false, evidence = false, read_calls = false, read_table = false;
 };
 struct ReportFds {  // where a text call writes them, in the .inq's row order (-1: no file)
-    int ties = -1, evidence = -1, read_calls = -1;
-    ReportSet wanted() const { return ReportSet{ties >= 0, evidence >= 0, read_calls >= 0}; }
+    int ties = -1, evidence = -1, read_calls = -1, read_table = -1;
+    ReportSet wanted() const { return ReportSet{ties >= 0, evidence >= 0, read_calls >= 0 || read_table >= 0, read_table >= 0}; }
 };
 // ... of a set of targets (a call's, a device part's, one device call's loci): [k] belongs to target k of the set.  A target no batch or
 // span holds keeps what begin put there: no flag, zeros, an empty list.
@@ -309,11 +316,13 @@ struct TargetReports {
     std::vector<uint8_t> ties;                   // INQ_LOCUS_TIE
     std::vector<inq_locus_evidence_t> evidence;
     ReadCallLists read_calls;                    // the records of the target's kept reads in file order
+    std::vector<ReadIdentities> read_table;      // ... and who each of them is
     void begin(size_t n, ReportSet which) {
         has = which;
         ties.assign(which.ties ? n : 0, 0);
         evidence.assign(which.evidence ? n : 0, inq_locus_evidence_t{});
         read_calls.assign(which.read_calls ? n : 0, std::vector<inq_read_call_t>());
+        read_table.assign(which.read_table ? n : 0, ReadIdentities());
     }
     // what part collected (nothing this one does not), part's k-th -> target idx[k]; the lists are moved out of part
     void scatter_from(TargetReports &part, const uint32_t *idx, size_t n) {
@@ -321,6 +330,8 @@ struct TargetReports {
         if (part.has.evidence) scatter(part.evidence.data(), idx, n, evidence.data());
         if (part.has.read_calls)
             for (size_t k = 0; k < n; ++k) read_calls[idx[k]] = std::move(part.read_calls[k]);
+        if (part.has.read_table)
+            for (size_t k = 0; k < n; ++k) read_table[idx[k]] = std::move(part.read_table[k]);
     }
 };
 
@@ -358,16 +369,22 @@ struct ReportFile {
     // path may be null (no file): INQ_EXIT_OK; a path that cannot be opened: INQ_EXIT_ERROR and a message that names `what` and it
     int open(const char *path, const char *what, std::string &msg);
 };
-constexpr const char *kTiesWhat = "the tie report", *kEvidenceWhat = "the evidence file", *kReadCallsWhat = "the read-calls file";
-// the files of a text call (inq_call_args_t::ties_path, ::evidence_path; read_calls_path of inq_genotype_repeats_reads, else null)
+constexpr const char *kTiesWhat = "the tie report", *kEvidenceWhat = "the evidence file", *kReadCallsWhat = "the read-calls file",
+                      *kReadTableWhat = "the read table";
+// the paths of the files that are no field of inq_call_args_t (it does not grow): what the widest entry of the family takes
+struct ReportPaths {
+    const char *read_calls = nullptr, *read_table = nullptr;
+};
+// the files of a text call (inq_call_args_t::ties_path, ::evidence_path; `more` of inq_genotype_repeats_table, else nulls)
 struct CallReports {
-    ReportFile ties, evidence, read_calls;
-    int open(const inq_call_args_t &a, const char *read_calls_path, std::string &msg) {
+    ReportFile ties, evidence, read_calls, read_table;
+    int open(const inq_call_args_t &a, const ReportPaths &more, std::string &msg) {
         int rc = ties.open(a.ties_path, kTiesWhat, msg);
         if (rc == INQ_EXIT_OK) rc = evidence.open(a.evidence_path, kEvidenceWhat, msg);
-        return rc != INQ_EXIT_OK ? rc : read_calls.open(read_calls_path, kReadCallsWhat, msg);
+        if (rc == INQ_EXIT_OK) rc = read_calls.open(more.read_calls, kReadCallsWhat, msg);
+        return rc != INQ_EXIT_OK ? rc : read_table.open(more.read_table, kReadTableWhat, msg);
     }
-    ReportFds fds() const { return ReportFds{ties.fd, evidence.fd, read_calls.fd}; }
+    ReportFds fds() const { return ReportFds{ties.fd, evidence.fd, read_calls.fd, read_table.fd}; }
     void to(SessionHooks &hooks) const { hooks.report_fds = fds(); }
 };
 // an entry that returns rows or keeps its context for many files writes no evidence file and says so (INQ_EXIT_ERROR) instead of
@@ -402,6 +419,8 @@ struct BatchRows {
     TargetReports rep;                // of the call's loci, in the call's order
     std::vector<uint64_t> bk;         // kept_off of the per-read Calls
     std::vector<inq_read_call_t> bc;  // ... and the records, fetched behind the call
+    std::vector<inq_read_origin_t> bo;  // the read table: the records' origins ...
+    std::vector<uint8_t> bn;            // ... and names, fetched with them (a flush) or looked up in the batch the host owns (a call)
     void begin(size_t n, ReportSet which) {
         b1.assign(n, NAN), b2.assign(n, NAN);
         std::memset(&res, 0, sizeof res);
@@ -413,14 +432,51 @@ struct BatchRows {
     uint8_t *flags() { return rep.has.ties ? rep.ties.data() : nullptr; }
     inq_locus_evidence_t *evidence() { return rep.has.evidence ? rep.evidence.data() : nullptr; }
     uint64_t *kept_off() { return rep.has.read_calls ? bk.data() : nullptr; }
-    // the host-buffer call / the flush of the n deferred loci with what begin asked for, the lists fetched behind it
-    int call(inq_ctx_t *ctx, const inq_batch_t &batch) {
-        const int rc = inq_call_batch_reads(ctx, &batch, &res, flags(), evidence(), kept_off());
-        return rc != INQ_OK ? rc : fetch_read_calls(ctx);
+    // the host-buffer call / the flush of the n deferred loci with what begin asked for, the lists fetched behind it.  The read table:
+    // `read` indexes a batch the host owns (owner: the sweep's batch with its names), or one that exists on the device only, whose
+    // flush gathers origins and names there (the spans were appended with names)
+    int call(inq_ctx_t *ctx, const inq_batch_t &batch, const HostBatch *owner = nullptr) {
+        int rc = inq_call_batch_reads(ctx, &batch, &res, flags(), evidence(), kept_off());
+        if (rc == INQ_OK) rc = fetch_read_calls(ctx);
+        if (rc != INQ_OK || !rep.has.read_table) return rc;
+        if (!owner || owner->name_off.size() != owner->reads.size() + 1) return INQ_ERR_ARG;
+        bo.resize(bc.size());
+        bn.clear();
+        for (size_t k = 0; k < bc.size(); ++k) {
+            const uint32_t r = bc[k].read;  // (the call succeeded: every index lies inside the batch)
+            const inq_read_t &rd = owner->reads[r];
+            const uint64_t at = owner->name_off[r], len = owner->name_off[r + 1] - at;
+            bo[k] = inq_read_origin_t{rd.pos, rd.mapq, rd.bits, (uint16_t)len};
+            bn.insert(bn.end(), owner->names.begin() + at, owner->names.begin() + at + len);
+        }
+        cut_read_table();
+        return INQ_OK;
     }
     int flush(inq_ctx_t *ctx, uint64_t n, double *ms_call) {
-        const int rc = inq_call_flush_reads(ctx, &res, n, ms_call, flags(), evidence(), kept_off());
-        return rc != INQ_OK ? rc : fetch_read_calls(ctx);
+        if (!rep.has.read_table) {
+            const int rc = inq_call_flush_reads(ctx, &res, n, ms_call, flags(), evidence(), kept_off());
+            return rc != INQ_OK ? rc : fetch_read_calls(ctx);
+        }
+        uint64_t name_bytes = 0;
+        int rc = inq_call_flush_origins(ctx, &res, n, ms_call, flags(), evidence(), kept_off(), &name_bytes);
+        if (rc == INQ_OK) rc = fetch_read_calls(ctx);
+        if (rc != INQ_OK) return rc;
+        bo.resize(bc.size()), bn.resize(name_bytes);
+        if ((rc = inq_read_origins_fetch(ctx, bo.data(), bo.size(), bn.data(), bn.size())) != INQ_OK) return rc;
+        cut_read_table();
+        return INQ_OK;
+    }
+    // bo / bn, in the records' order, cut into the loci's shares
+    void cut_read_table() {
+        size_t at = 0;
+        for (size_t j = 0; j + 1 < bk.size(); ++j) {
+            ReadIdentities &t = rep.read_table[j];
+            t.origins.assign(bo.begin() + bk[j], bo.begin() + bk[j + 1]);
+            size_t bytes = 0;
+            for (const inq_read_origin_t &o : t.origins) bytes += o.name_len;
+            t.names.assign(bn.begin() + at, bn.begin() + at + bytes);
+            at += bytes;
+        }
     }
     // the records behind a call that filled kept_off, out of the context's scratch, cut into the loci's lists
     int fetch_read_calls(inq_ctx_t *ctx) {
@@ -463,8 +519,8 @@ int write_report(const std::vector<uint32_t> &order, const std::string &header, 
 // the tie report: `chrom\tbegin\tend\n` for every target order[k] with a flag set (no header)
 int write_ties(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const uint8_t *ties, int fd, char *errbuf,
                size_t errcap);
-// inq_genotype_repeats with the read-calls file (null: none), for inq_genotype_repeats_reads
-int genotype_single(const inq_call_args_t *args, int out_fd, const char *read_calls_path, char *errbuf, size_t errcap);
+// inq_genotype_repeats with the read-calls file and the read table (null: none), for inq_genotype_repeats_table
+int genotype_single(const inq_call_args_t *args, int out_fd, const ReportPaths &more, char *errbuf, size_t errcap);
 int partition_prepared(Prepared &P, uint64_t world, uint32_t *order, uint64_t *cuts);
 
 struct OwnedArgs {

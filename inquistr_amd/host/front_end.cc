@@ -15,6 +15,8 @@ void HostBatch::clear() {
     locus_start.clear();
     locus_end.clear();
     locus_index.clear();
+    names.clear();
+    name_off.clear();
 }
 
 void HostBatch::view(inq_batch_t *b, uint32_t minlen, uint32_t support, bool unphased) const {
@@ -58,6 +60,8 @@ bool FrontEnd::begin_group(std::string *err) {
     edges_.clear();
     cig_.clear();
     reads_.clear();
+    names_.clear();
+    name_off_.assign(keep_names_ ? 1 : 0, 0);
     lo_ = 0;
     flushed_ = 0;
     group_eof_ = false;
@@ -119,6 +123,10 @@ int FrontEnd::add_read(const BamRec &r, bool has_clip, std::string *err, bool *p
     cig_.insert(cig_.end(), r.cigar, r.cigar + r.n_cigar);
     while (cig_.size() & 3) cig_.push_back(0u);  // 0M padding to the next 16-byte boundary
     reads_.push_back(rd);
+    if (keep_names_) {
+        names_.insert(names_.end(), r.name, r.name + r.name_len);
+        name_off_.push_back(names_.size());
+    }
     return (int)reads_.size() - 1;
 }
 
@@ -145,9 +153,16 @@ void FrontEnd::emit(size_t from, size_t to, HostBatch &out) {
         out.reads.swap(reads_);
         cig_.clear();
         reads_.clear();
+        if (keep_names_) {
+            out.names.swap(names_);
+            out.name_off.swap(name_off_);
+            names_.clear();
+            name_off_.assign(1, 0);
+        }
         edges_.clear();
     } else {
         remap.assign(reads_.size(), 0xffffffffu);
+        if (keep_names_) out.name_off.assign(1, 0);
         for (const Edge &e : edges_) {
             if (e.locus < from || e.locus >= to) continue;
             if (remap[e.read] == 0xffffffffu) {
@@ -158,6 +173,10 @@ void FrontEnd::emit(size_t from, size_t to, HostBatch &out) {
                 const size_t n4 = ((size_t)rd.n_cigar + 3) / 4 * 4;
                 out.cigar.insert(out.cigar.end(), src, src + n4);
                 out.reads.push_back(rd);
+                if (keep_names_) {
+                    out.names.insert(out.names.end(), names_.begin() + name_off_[e.read], names_.begin() + name_off_[e.read + 1]);
+                    out.name_off.push_back(out.names.size());
+                }
             }
             out.pair_read[bucket_[e.locus - from]++] = remap[e.read];
         }
@@ -174,6 +193,8 @@ void FrontEnd::compact(size_t keep_from) {
     std::vector<uint32_t> remap(reads_.size(), 0xffffffffu);
     std::vector<uint32_t> ncig;
     std::vector<inq_read_t> nreads;
+    std::vector<uint8_t> nnames;
+    std::vector<uint64_t> nname_off(keep_names_ ? 1 : 0, 0);
     size_t w = 0;
     for (const Edge &e0 : edges_) {
         if (e0.locus < keep_from) continue;
@@ -186,6 +207,10 @@ void FrontEnd::compact(size_t keep_from) {
             const size_t n4 = ((size_t)rd.n_cigar + 3) / 4 * 4;
             ncig.insert(ncig.end(), src, src + n4);
             nreads.push_back(rd);
+            if (keep_names_) {
+                nnames.insert(nnames.end(), names_.begin() + name_off_[e.read], names_.begin() + name_off_[e.read + 1]);
+                nname_off.push_back(nnames.size());
+            }
         }
         e.read = remap[e.read];
         edges_[w++] = e;
@@ -193,6 +218,8 @@ void FrontEnd::compact(size_t keep_from) {
     edges_.resize(w);
     cig_.swap(ncig);
     reads_.swap(nreads);
+    names_.swap(nnames);
+    name_off_.swap(nname_off);
 }
 
 int FrontEnd::next(HostBatch &out, std::string *err, bool *panic) {

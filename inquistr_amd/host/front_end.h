@@ -24,6 +24,9 @@ struct HostBatch {
     std::vector<uint64_t> locus_pair_off;
     std::vector<uint32_t> locus_start, locus_end;
     std::vector<uint32_t> locus_index;  // index into the target list
+    // the names of the reads back to back, name_off[n_reads + 1]; both empty unless the front end keeps names (the read table)
+    std::vector<uint8_t> names;
+    std::vector<uint64_t> name_off;
     void clear();
     void view(inq_batch_t *b, uint32_t minlen, uint32_t support, bool unphased) const;
 };
@@ -32,6 +35,7 @@ class FrontEnd {
 public:
     FrontEnd(BamFile &bam, const std::vector<RepeatInterval> &targets, bool unphased);
     void set_max_batch_words(uint64_t w) { max_words_ = w ? w : max_words_; }
+    void set_keep_names(bool on) { keep_names_ = on; }  // before the first next(): every batch then carries its reads' names
     // 1 = batch produced, 0 = done, -1 = error (err = message; panic = reference would panic)
     int next(HostBatch &out, std::string *err, bool *panic);
 
@@ -60,6 +64,9 @@ private:
     // contig-local store
     std::vector<uint32_t> cig_;
     std::vector<inq_read_t> reads_;
+    bool keep_names_ = false;
+    std::vector<uint8_t> names_;      // keep_names_: the names of reads_ back to back ...
+    std::vector<uint64_t> name_off_;  // ... and where each begins, [reads_.size() + 1]
     // (locus of the group, read of the store) in file order; grouped by locus (stable) when a batch is emitted
     struct Edge {
         uint32_t locus, read;

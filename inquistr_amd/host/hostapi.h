@@ -15,7 +15,7 @@
 namespace inq {
 
 struct HostApi {
-    decltype(&::inq_genotype_repeats_reads) genotype_repeats_reads;  // (inq_genotype_repeats and _devices are its two forms)
+    decltype(&::inq_genotype_repeats_table) genotype_repeats_table;  // (inq_genotype_repeats, _devices and _reads are its forms)
     decltype(&::inq_host_ctx_option) ctx_option;
     decltype(&::inq_combine) combine;
     decltype(&::inq_outlier) outlier;
@@ -53,7 +53,7 @@ inline const HostApi &host_api() {
             }
             return p;
         };
-        a.genotype_repeats_reads = reinterpret_cast<decltype(a.genotype_repeats_reads)>(sym("inq_genotype_repeats_reads"));
+        a.genotype_repeats_table = reinterpret_cast<decltype(a.genotype_repeats_table)>(sym("inq_genotype_repeats_table"));
         a.ctx_option = reinterpret_cast<decltype(a.ctx_option)>(sym("inq_host_ctx_option"));
         a.combine = reinterpret_cast<decltype(a.combine)>(sym("inq_combine"));
         a.outlier = reinterpret_cast<decltype(a.outlier)>(sym("inq_outlier"));

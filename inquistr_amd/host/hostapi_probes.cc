@@ -33,6 +33,19 @@ size_t inq_host_format_read_calls_row(const char *chrom, uint32_t start, uint32_
     append_read_calls_row(s, chrom, start, end, calls, n, unphased != 0);
     return (size_t)std::snprintf(buf, cap, "%s", s.c_str());
 }
+size_t inq_host_format_read_table_rows(const char *chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
+                                       const inq_read_origin_t *origins, const uint8_t *names, size_t n, int unphased, char *buf, size_t cap) {
+    if (!chrom || (n && (!calls || !origins))) return 0;
+    std::string s;
+    append_read_table_rows(s, chrom, start, end, calls, origins, names, n, unphased != 0);
+    // (the text may hold any byte a name does but NUL: copied as bytes, terminated like snprintf's)
+    if (cap) {
+        const size_t m = std::min(s.size(), cap - 1);
+        std::memcpy(buf, s.data(), m);
+        buf[m] = 0;
+    }
+    return s.size();
+}
 size_t inq_host_sample_name(const char *p, char *buf, size_t cap) {
     return (size_t)std::snprintf(buf, cap, "%s", sample_name_from_path(p).c_str());
 }

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 namespace inqhost {
 
@@ -171,23 +172,52 @@ static void append_call_list(std::string &out, const inq_read_call_t *const *fir
     }
 }
 
+// the three lists of a target - h1, h2, other - from the records of its kept reads in file order, each list in the file's order
+static void split_read_calls(const inq_read_call_t *calls, size_t n, bool unphased, std::vector<const inq_read_call_t *> (&g)[3]) {
+    // ascending by (value, file order) - the records come in file order, so a stable sort by value: the tie rule of the reduces
+    auto by_value = [](const inq_read_call_t *a, const inq_read_call_t *b) { return a->call < b->call; };
+    for (size_t i = 0; i < n; ++i) g[unphased ? 0 : calls[i].group == 1 ? 0 : calls[i].group == 2 ? 1 : 2].push_back(calls + i);
+    for (auto &v : g) std::stable_sort(v.begin(), v.end(), by_value);
+    if (unphased) {  // src/call.rs:312-314: the sorted kept Calls are split at len / 2
+        g[1].assign(g[0].begin() + n / 2, g[0].end());
+        g[0].resize(n / 2);
+    }
+}
+
 void append_read_calls_row(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls, size_t n,
                            bool unphased) {
     out += chrom;
     for (const uint32_t v : {start, end}) out += '\t', out += std::to_string(v);
-    // ascending by (value, file order) - the records come in file order, so a stable sort by value: the tie rule of the reduces
-    auto by_value = [](const inq_read_call_t *a, const inq_read_call_t *b) { return a->call < b->call; };
-    std::vector<const inq_read_call_t *> g[3];  // h1, h2, other
-    for (size_t i = 0; i < n; ++i) g[unphased ? 0 : calls[i].group == 1 ? 0 : calls[i].group == 2 ? 1 : 2].push_back(calls + i);
-    for (auto &v : g) std::stable_sort(v.begin(), v.end(), by_value);
-    if (unphased) {  // src/call.rs:312-314: the sorted kept Calls are split at len / 2
-        const inq_read_call_t *const *all = g[0].data();
-        append_call_list(out, all, all + n / 2);
-        append_call_list(out, all + n / 2, all + n);
-        out += "\t.";
-        return;
-    }
+    std::vector<const inq_read_call_t *> g[3];  // h1, h2, other (`.` for an unphased call: the list is empty)
+    split_read_calls(calls, n, unphased, g);
     for (const auto &v : g) append_call_list(out, v.data(), v.data() + v.size());
+}
+
+const char *const kReadTableHeader = "chrom\tbegin\tend\tgroup\tcall\tkind\tread\tpos\tstrand\tmapq";
+
+void append_read_table_rows(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
+                            const inq_read_origin_t *origins, const uint8_t *names, size_t n, bool unphased) {
+    if (!n) return;
+    std::vector<const inq_read_call_t *> g[3];
+    split_read_calls(calls, n, unphased, g);
+    std::vector<size_t> name_at(n + 1, 0);  // where record k's name begins
+    for (size_t k = 0; k < n; ++k) name_at[k + 1] = name_at[k] + origins[k].name_len;
+    const std::string locus = chrom + '\t' + std::to_string(start) + '\t' + std::to_string(end) + '\t';
+    static const char *const kGroup[3] = {"h1", "h2", "other"};
+    for (int q = 0; q < 3; ++q)
+        for (const inq_read_call_t *rec : g[q]) {
+            const size_t k = (size_t)(rec - calls);
+            const inq_read_origin_t &o = origins[k];
+            out += locus, out += kGroup[q], out += '\t', out += std::to_string(rec->call);
+            out += (rec->flags & INQ_READ_CALL_CLIP) ? "\tClip\t" : "\tSpan\t";
+            const char *name = (const char *)names + name_at[k];
+            const size_t len = o.name_len ? ::strnlen(name, o.name_len) : 0;  // cut at the first NUL
+            if (len) out.append(name, len);
+            else out += '*';
+            out += '\t', out += std::to_string((int64_t)o.pos + 1);  // SAM POS
+            out += (o.bits & INQ_READ_REVERSE) ? "\t-\t" : "\t+\t";
+            out += std::to_string((unsigned)o.mapq), out += '\n';
+        }
 }
 
 static void erase_all(std::string &s, const std::string &pat) {

@@ -28,6 +28,14 @@ void append_evidence_row(std::string &out, const std::string &chrom, uint32_t st
 extern const char *const kReadCallsHeader;
 void append_read_calls_row(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls, size_t n,
                            bool unphased);
+// the read table (inq_genotype_repeats_table; not a reference output): its header, and the lines of one target - one per kept read, in the
+// order of the read-calls lists (h1 in that list's order, then h2, then other) - from the records, their origins (same order) and
+// their names back to back (record k's name: name_len bytes behind the names of the records in front of it).  A name is cut at its
+// first NUL, an empty one printed as `*`; the bytes go out as they stand (SAM keeps tab and newline out of a QNAME: [!-?A-~]).
+// Every line ends in a newline; a target without a kept read appends nothing.
+extern const char *const kReadTableHeader;
+void append_read_table_rows(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
+                            const inq_read_origin_t *origins, const uint8_t *names, size_t n, bool unphased);
 // src/call.rs:91-100: file_stem, then every ".bam" and ".cram" removed
 std::string sample_name_from_path(const std::string &bam_path);
 // [3P] human_sort::compare as used by Genotype::cmp (src/call.rs:33-38): <0, 0, >0

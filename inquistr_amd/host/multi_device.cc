@@ -79,7 +79,7 @@ int run_parts(Prepared &P, size_t world, const PartFn &fn, std::vector<double> &
 extern "C" {
 
 static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, inq_part_stats_t *stats,
-                                 char *errbuf, size_t errcap, const char *read_calls_path = nullptr) {
+                                 char *errbuf, size_t errcap, const ReportPaths &more = ReportPaths()) {
     if (!args || !device_ids || n_devices == 0 || n_devices > 64) {
         set_err(errbuf, errcap, "device list: between 1 and 64 HIP device ordinals");
         return INQ_EXIT_ERROR;
@@ -92,7 +92,7 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
     const auto t_start = Clock::now();
     std::string msg;
     CallReports files;
-    if (files.open(*args, read_calls_path, msg) != INQ_EXIT_OK) {
+    if (files.open(*args, more, msg) != INQ_EXIT_OK) {
         set_err(errbuf, errcap, msg);
         return INQ_EXIT_ERROR;
     }
@@ -148,14 +148,19 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
                       RowReports{&reports, files.fds(), args->unphased != 0});
 }
 
-static int genotype_reads_impl(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,
+static int genotype_table_impl(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const ReportPaths &more,
                                inq_part_stats_t *stats, char *errbuf, size_t errcap) {
-    if (n_devices == 0) return genotype_single(args, out_fd, read_calls_path, errbuf, errcap);
-    return genotype_devices_impl(args, device_ids, n_devices, out_fd, stats, errbuf, errcap, read_calls_path);
+    if (n_devices == 0) return genotype_single(args, out_fd, more, errbuf, errcap);
+    return genotype_devices_impl(args, device_ids, n_devices, out_fd, stats, errbuf, errcap, more);
+}
+int inq_genotype_repeats_table(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,
+                               const char *read_table_path, inq_part_stats_t *stats, char *errbuf, size_t errcap) {
+    INQ_GUARD(genotype_table_impl(args, device_ids, n_devices, out_fd, ReportPaths{read_calls_path, read_table_path}, stats, errbuf, errcap), errbuf,
+              errcap)
 }
 int inq_genotype_repeats_reads(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,
                                inq_part_stats_t *stats, char *errbuf, size_t errcap) {
-    INQ_GUARD(genotype_reads_impl(args, device_ids, n_devices, out_fd, read_calls_path, stats, errbuf, errcap), errbuf, errcap)
+    return inq_genotype_repeats_table(args, device_ids, n_devices, out_fd, read_calls_path, nullptr, stats, errbuf, errcap);
 }
 
 int inq_genotype_repeats_devices(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, inq_part_stats_t *stats,

@@ -211,7 +211,7 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
         }
     } pin;
     const int n_workers = (int)std::max<uint64_t>(1, std::min<uint64_t>(args->threads > 1 ? args->threads - 1 : 1, 64));
-    ParallelFrontEnd pfe(args->bam, V.bam, V.targets, V.opt.unphased, n_workers);
+    ParallelFrontEnd pfe(args->bam, V.bam, V.targets, V.opt.unphased, n_workers, 0, reports->has.read_table);
     auto t_ctx = Clock::now();
     BatchRows br;
     for (;;) {
@@ -255,7 +255,7 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
         }
         br.begin(batch.n_loci, reports->has);
         auto tc = Clock::now();
-        const int rc2 = br.call(ctx, batch);
+        const int rc2 = br.call(ctx, batch, &item.batch);
         t_dev += secs(tb, Clock::now());
         if (timing == 2)
             std::fprintf(stderr, "[inq batch] loci %llu pairs %llu cigar %.1f MB  wait-ctx %.2f ms  call %.2f ms\n",
@@ -448,6 +448,14 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
                  append_read_calls_row(text, targets[i].chrom, targets[i].start, targets[i].end, l.data(), l.size(), unphased);
                  text += '\n';
              }},
+            {tr->has.read_table, reports.fds.read_table, std::string(kReadTableHeader) + '\n', kReadTableWhat,
+             [&targets, tr, unphased](std::string &text, uint32_t i) {  // one line per kept read: none for a target without one
+                 const std::vector<inq_read_call_t> &l = tr->read_calls[i];
+                 const ReadIdentities &w = tr->read_table[i];
+                 if (w.origins.size() == l.size())
+                     append_read_table_rows(text, targets[i].chrom, targets[i].start, targets[i].end, l.data(), w.origins.data(), w.names.data(),
+                                            l.size(), unphased);
+             }},
         };
         for (const auto &f : files) {
             if (!f.on || f.fd < 0) continue;
@@ -472,6 +480,7 @@ struct inq_frontend {
     std::string bam_path;
     CallOptions opt;
     uint64_t threads = 1, max_words = 0;
+    const HostBatch *current = nullptr;  // the batch the last inq_frontend_next handed out (inq_frontend_read_names)
 };
 
 // target i of a prepared call, for the two handles that show their list (0, or -1 past its end)
@@ -495,6 +504,7 @@ static int inq_frontend_open_impl(const inq_call_args_t *args, inq_frontend_t **
     F->threads = args->threads;
     F->bam_path = args->bam;
     if (F->threads <= 1) F->fe.reset(new FrontEnd(*F->P.bam, F->P.targets, F->opt.unphased));
+    if (F->fe) F->fe->set_keep_names(true);  // every batch this handle hands out names its reads (inq_frontend_read_names)
     *out = F.release();
     return INQ_EXIT_OK;
 }
@@ -518,10 +528,11 @@ static int inq_frontend_next_impl(inq_frontend_t *fe, inq_batch_t *batch, const 
     if (!fe || !batch) return -INQ_EXIT_ERROR;
     std::string err;
     bool panic = false;
+    fe->current = nullptr;
     if (fe->threads > 1) {  // batches arrive in completion order; locus_index says where each row belongs
         if (!fe->pfe)
             fe->pfe.reset(new ParallelFrontEnd(fe->bam_path, *fe->P.bam, fe->P.targets, fe->opt.unphased,
-                                               (int)std::min<uint64_t>(fe->threads, 64), fe->max_words));
+                                               (int)std::min<uint64_t>(fe->threads, 64), fe->max_words, true));
         fe->pfe->recycle(std::move(fe->item));
         fe->item = ParallelFrontEnd::Item();
         int rc = fe->pfe->next(fe->item, &err, &panic);
@@ -532,6 +543,7 @@ static int inq_frontend_next_impl(inq_frontend_t *fe, inq_batch_t *batch, const 
         if (rc == 0) return 0;
         fe->item.batch.view(batch, fe->opt.minlen, fe->opt.support, fe->opt.unphased);
         if (locus_index) *locus_index = fe->item.index.data();
+        fe->current = &fe->item.batch;
         return 1;
     }
     int rc = fe->fe->next(fe->batch, &err, &panic);
@@ -542,18 +554,27 @@ static int inq_frontend_next_impl(inq_frontend_t *fe, inq_batch_t *batch, const 
     if (rc == 0) return 0;
     fe->batch.view(batch, fe->opt.minlen, fe->opt.support, fe->opt.unphased);
     if (locus_index) *locus_index = fe->batch.locus_index.data();
+    fe->current = &fe->batch;
     return 1;
+}
+
+int inq_frontend_read_names(const inq_frontend_t *fe, const uint64_t **name_off, const uint8_t **names, uint64_t *n_reads) {
+    if (!fe || !fe->current || fe->current->name_off.size() != fe->current->reads.size() + 1) return INQ_EXIT_ERROR;
+    if (name_off) *name_off = fe->current->name_off.data();
+    if (names) *names = fe->current->names.data();
+    if (n_reads) *n_reads = fe->current->reads.size();
+    return INQ_EXIT_OK;
 }
 
 void inq_frontend_close(inq_frontend_t *fe) { delete fe; }
 
 
 static int inq_genotype_repeats_impl(const inq_call_args_t *args, int out_fd, char *errbuf, size_t errcap, const RowsOut &rows = RowsOut(),
-                                     const char *read_calls_path = nullptr) {
+                                     const ReportPaths &more = ReportPaths()) {
     const auto t_start = Clock::now();
     std::string msg;
     CallReports files;  // (a call that returns rows writes no file: the tie report is left out, the evidence file refused)
-    if (args && (rows.active ? refuse_evidence(args, "inq_genotype_repeats_rows", msg) : files.open(*args, read_calls_path, msg)) != INQ_EXIT_OK) {
+    if (args && (rows.active ? refuse_evidence(args, "inq_genotype_repeats_rows", msg) : files.open(*args, more, msg)) != INQ_EXIT_OK) {
         set_err(errbuf, errcap, msg);
         return INQ_EXIT_ERROR;
     }
@@ -571,8 +592,8 @@ static int inq_genotype_repeats_impl(const inq_call_args_t *args, int out_fd, ch
 }
 
 }  // extern "C"
-int inqhost::genotype_single(const inq_call_args_t *args, int out_fd, const char *read_calls_path, char *errbuf, size_t errcap) {
-    return inq_genotype_repeats_impl(args, out_fd, errbuf, errcap, RowsOut(), read_calls_path);
+int inqhost::genotype_single(const inq_call_args_t *args, int out_fd, const ReportPaths &more, char *errbuf, size_t errcap) {
+    return inq_genotype_repeats_impl(args, out_fd, errbuf, errcap, RowsOut(), more);
 }
 extern "C" {
 
