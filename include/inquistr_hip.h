@@ -187,6 +187,29 @@ typedef struct inq_read_origin {  /* 8 bytes, every byte written; one per record
     uint16_t name_len;  /* 0 .. 254: bytes of the name, no terminator */
 } inq_read_origin_t;
 
+/* The bases behind a Call: which part of the read's SEQ lies over the locus window.  Per (locus, read) pair take the window the locus
+ * kernels build, se = start - 10 and ee = end + 10 (both u32), and walk the read's CIGAR as the batch holds it (a long CIGAR from
+ * CG:B,I already swapped in).  The reference cursor r starts at pos, the query cursor at 0; arithmetic is 64-bit and never wraps.
+ * For a reference coordinate x,
+ *     Q(x) =  sum over I and S ops       len * [r_op < x]
+ *           + sum over M, = and X ops    clamp(x - r_op, 0, len)
+ * with r_op the reference cursor in front of the op; D and N move r only, H, P and op codes above 8 move nothing.  Then
+ *     q_beg = min(Q(se), l_seq),  q_end = min(Q(ee - 1), l_seq),  n_bases = q_end - q_beg,
+ * and the slice is SEQ bases [q_beg, q_end).  A window with ee - 1 <= se as integers - those of width 0, empty or wrapped, start < 9
+ * among them, and start = 9, whose se is 2^32 - 1 (no entry that calls accepts a start below 10) -, or a read index or descriptor
+ * outside the batch, gives (0, 0); l_seq == 0 (SEQ `*`) gives n_bases 0; a CIGAR whose query length disagrees with l_seq
+ * is only ever cut, never read past.
+ * An I or S op is in the slice exactly when se <= r_op <= ee - 2, which is exactly when call_from_cigar (src/call.rs:388-401,
+ * start < reference_position < end) would count it, whatever minlen; the M bases are those at reference coordinates [se, ee - 1).
+ * So n_bases = matched bases in the window + inserted + clipped bases in the window; a read that starts inside the window has
+ * q_beg = 0, its leading soft clip included, and one that ends inside it runs to l_seq.
+ * Bases stay as the BAM stores them: reference-forward, 4-bit codes (`=ACMGRSVTWYHKDBN`).  A slice is packed two bases to a byte,
+ * re-aligned so that its first base is the high nibble of its first byte; a last odd low nibble is 0: (n_bases + 1) / 2 bytes. */
+typedef struct inq_read_seq {  /* 8 bytes, every byte written; one per record of inq_read_calls_fetch, same order */
+    uint32_t q_beg;    /* 0-based offset into SEQ as stored */
+    uint32_t n_bases;
+} inq_read_seq_t;
+
 typedef struct inq_ctx inq_ctx_t;
 
 /* Opens HIP device `device_id` (must be gfx950), creates the library's stream and
@@ -455,6 +478,32 @@ int inq_read_origins_fetch(inq_ctx_t *ctx, inq_read_origin_t *origins, uint64_t 
 int inq_span_fetch_names(inq_ctx_t *ctx, uint64_t *name_off /* [n_reads + 1] */, uint8_t *names, uint64_t cap_bytes);
 /* segments (names) per workgroup of the byte gather (a constant of the build) */
 uint32_t inq_read_name_tile(void);
+/* The bases behind those records (inq_read_seq_t above).
+ * inq_call_span_deferred_seqs is inq_call_span_deferred_names that also cuts, for every pair of the span, the slice of the read's SEQ
+ * over the locus window, out of the slot's inflated bytes into the deferred batch (the window walk behind the join, a scan of the
+ * byte lengths whose total comes down with the append's last readback, the packed gather and one further stream wait).  All spans of
+ * one batch with sequences or all without: mixing is INQ_ERR_ARG at the offending append, which appends nothing.
+ * inq_call_flush_seqs is inq_call_flush_origins plus one inq_read_seq_t per kept record and the kept records' packed slices back to
+ * back in record order, record k's (n_bases + 1) / 2 bytes beginning at the sum of those in front of it; *seq_bytes receives their
+ * total.  seq_bytes NULL = exactly inq_call_flush_origins; with it, a batch appended without sequences is INQ_ERR_ARG (the batch
+ * stays).  Both stay in context scratch until the context's next call: inq_read_seqs_fetch copies the first n records and the first
+ * seq_bytes packed bytes; n or seq_bytes above the last flush's totals is INQ_ERR_ARG, and a flush without sequences has totals of 0.
+ * inq_span_fetch_seqs (test / debug, beside inq_span_fetch_names): q_beg, n_bases, seq_off[n_pairs + 1] and the packed bytes of ALL
+ * pairs of the batch the last flush ran on (each array may be NULL; cap_bytes below the total, or a batch without sequences:
+ * INQ_ERR_ARG).
+ * inq_seq_windows: the window walk alone over a host-buffer batch (uploaded like inq_call_batch's; minlen, support and unphased are
+ * not read): q_beg[n_pairs] and n_bases[n_pairs].  l_seq[n_reads] cuts both as the contract says, NULL = no cut but at 2^32 - 1, what the results hold.  The result does not
+ * depend on inq_read_t.promise. */
+int inq_call_span_deferred_seqs(inq_ctx_t *ctx, const inq_span_t *span, int slot, inq_span_stats_t *stats);
+int inq_call_flush_seqs(inq_ctx_t *ctx, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
+                        inq_locus_evidence_t *evidence, uint64_t *kept_off, uint64_t *name_bytes, uint64_t *seq_bytes);
+int inq_read_seqs_fetch(inq_ctx_t *ctx, inq_read_seq_t *seqs, uint64_t n, uint8_t *packed, uint64_t seq_bytes);
+int inq_span_fetch_seqs(inq_ctx_t *ctx, uint32_t *q_beg, uint32_t *n_bases, uint64_t *seq_off /* [n_pairs + 1] */, uint8_t *packed,
+                        uint64_t cap_bytes);
+int inq_seq_windows(inq_ctx_t *ctx, const inq_batch_t *batch, const uint32_t *l_seq /* [n_reads] */, uint32_t *q_beg,
+                    uint32_t *n_bases /* [n_pairs] */);
+/* pairs per workgroup and turn of the window walk (a constant of the build) */
+uint32_t inq_seq_window_tile(void);
 /* Row arrays in device memory for a host that does not link the HIP runtime itself: n f64, filled with quiet NaN (a locus no span
  * holds prints NaN NaN); plain synchronous copies in and out. */
 int inq_dev_alloc_rows(inq_ctx_t *ctx, uint64_t n, double **out);

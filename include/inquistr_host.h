@@ -130,6 +130,20 @@ int inq_genotype_repeats_reads(const inq_call_args_t *args, const int32_t *devic
  * inq_run_*, inq_session_* - have no way to be handed the path: they write no table. */
 int inq_genotype_repeats_table(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,
                                const char *read_table_path, inq_part_stats_t *stats, char *errbuf, size_t errcap);
+/* ... and with the read-seqs file (`inquistr call --read-seqs`), the widest entry of the family: read_seqs_path NULL = exactly
+ * inq_genotype_repeats_table.  The file gives the bases behind each Call: a header line
+ * `chrom\tbegin\tend\tgroup\tcall\tkind\tread\tqbeg\tlen\tseq`, then one line per KEPT read, targets, groups and order EXACTLY those of
+ * the read table, so line k of one file is line k of the other and columns 1 - 7 agree.  qbeg and len are q_beg and n_bases of
+ * inq_read_seq_t in include/inquistr_hip.h: the part of the read's SEQ, as the BAM stores it (reference-forward), that lies over the
+ * locus window - the matched bases at reference coordinates [start - 10, end + 9) and every insertion and soft clip the Call could
+ * count there.  seq = those bases as `=ACMGRSVTWYHKDBN`, `*` when len is 0 (SEQ `*`, or a read that only deletes across the window).
+ * Both front ends produce it: the host sweep keeps its batches' packed SEQ (inq_frontend_read_seqs) and cuts with inq_host_seq_window,
+ * the device front end cuts on the GPU while a span's inflated bytes exist (inq_call_span_deferred_seqs, inq_call_flush_seqs).  Opened
+ * like the read table, beside it and the other files in any combination; content unspecified after a failed call.  The .inq text and
+ * the other files are those of the call without it.  The other entries that take these arguments - inq_genotype_repeats_rows,
+ * inq_run_*, inq_session_* - have no way to be handed the path: they write no such file. */
+int inq_genotype_repeats_seqs(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,
+                              const char *read_table_path, const char *read_seqs_path, inq_part_stats_t *stats, char *errbuf, size_t errcap);
 /* How many processes (or device parts) share this host's cores with this one, and which of them it is (0 .. sharers - 1): sizes the
  * reader pool of every later call (granted cores / sharers, bound to L3 domains from a different start per sharer).  Default:
  * LOCAL_WORLD_SIZE / LOCAL_RANK of the environment (torch.distributed.run exports them), else 1 / 0.  sharers <= 0 = that default. */
@@ -225,6 +239,12 @@ int inq_frontend_next(inq_frontend_t *fe, inq_batch_t *batch, const uint32_t **l
  * name_off[n_reads + 1] and the bytes, read i's name = names[name_off[i] .. name_off[i + 1]); its position, strand and MAPQ are in
  * batch->reads[i].  Valid until the next inq_frontend_next.  0, or 1 when no batch is out. */
 int inq_frontend_read_names(const inq_frontend_t *fe, const uint64_t **name_off, const uint8_t **names, uint64_t *n_reads);
+/* ... and their SEQ as the BAM stores it (4-bit codes, two to a byte): l_seq[n_reads], seq_off[n_reads + 1] and the bytes, read i's
+ * (l_seq[i] + 1) / 2 bytes from seqs + seq_off[i].  Valid until the next inq_frontend_next.  0, or 1 when no batch is out or the
+ * handle does not keep sequences: inq_frontend_set_keep_seqs(fe, 1) before the first inq_frontend_next (SEQ is most of a record; a
+ * handle that is not asked keeps none). */
+void inq_frontend_set_keep_seqs(inq_frontend_t *fe, int on);
+int inq_frontend_read_seqs(const inq_frontend_t *fe, const uint32_t **l_seq, const uint64_t **seq_off, const uint8_t **seqs, uint64_t *n_reads);
 void inq_frontend_set_batch_words(inq_frontend_t *fe, uint64_t max_cigar_words);
 void inq_frontend_close(inq_frontend_t *fe);
 
@@ -279,6 +299,16 @@ size_t inq_host_format_read_calls_row(const char *chrom, uint32_t start, uint32_
  * text's length as snprintf does (n == 0: no line) */
 size_t inq_host_format_read_table_rows(const char *chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
                                        const inq_read_origin_t *origins, const uint8_t *names, size_t n, int unphased, char *buf, size_t cap);
+/* ... and of the read-seqs file (inq_genotype_repeats_seqs): the same lines in columns chrom .. read, then qbeg, len and seq, from the
+ * records' inq_read_seq_t in the same order and their packed slices back to back ((n_bases + 1) / 2 bytes each, first base in the high
+ * nibble); the bases as `=ACMGRSVTWYHKDBN`, `*` for an empty slice */
+size_t inq_host_format_read_seq_rows(const char *chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
+                                     const inq_read_origin_t *origins, const uint8_t *names, const inq_read_seq_t *seqs, const uint8_t *packed,
+                                     size_t n, int unphased, char *buf, size_t cap);
+/* The slice contract of inq_read_seq_t, as include/inquistr_hip.h states it, restated as a plain sequential walk of n_cigar packed ops (len << 4 | op) from
+ * pos: what the host sweep cuts its slices with.  0, or 1 for a null pointer. */
+int inq_host_seq_window(const uint32_t *cigar, uint32_t n_cigar, int32_t pos, uint32_t l_seq, uint32_t start, uint32_t end, uint32_t *q_beg,
+                        uint32_t *n_bases);
 size_t inq_host_sample_name(const char *bam_path, char *buf, size_t cap);
 int inq_host_human_compare(const char *a, const char *b);
 /* RepeatIntervalIterator::from_string against a one-contig length table; 0 ok, 101 panic */

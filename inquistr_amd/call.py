@@ -26,6 +26,7 @@ HOST_ABI_SYMBOLS = (
     "inq_genotype_repeats_devices",
     "inq_genotype_repeats_reads",
     "inq_genotype_repeats_table",
+    "inq_genotype_repeats_seqs",
     "inq_host_set_local_share",
     "inq_host_granted_cpus",
     "inq_host_ctx_option",
@@ -60,6 +61,8 @@ HOST_ABI_SYMBOLS = (
     "inq_frontend_sample",
     "inq_frontend_next",
     "inq_frontend_read_names",
+    "inq_frontend_read_seqs",
+    "inq_frontend_set_keep_seqs",
     "inq_frontend_set_batch_words",
     "inq_frontend_close",
     "inq_host_format_f64",
@@ -68,6 +71,8 @@ HOST_ABI_SYMBOLS = (
     "inq_host_format_evidence_row",
     "inq_host_format_read_calls_row",
     "inq_host_format_read_table_rows",
+    "inq_host_format_read_seq_rows",
+    "inq_host_seq_window",
     "inq_host_sample_name",
     "inq_host_human_compare",
     "inq_host_parse_region",
@@ -163,6 +168,9 @@ def load():
         L.inq_genotype_repeats_table.restype = C.c_int
         L.inq_genotype_repeats_table.argtypes = [C.POINTER(CallArgsC), C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.c_char_p, C.c_char_p,
                                                  C.POINTER(PartStatsC), C.c_char_p, C.c_size_t]
+        L.inq_genotype_repeats_seqs.restype = C.c_int
+        L.inq_genotype_repeats_seqs.argtypes = [C.POINTER(CallArgsC), C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p,
+                                                C.POINTER(PartStatsC), C.c_char_p, C.c_size_t]
         L.inq_genotype_repeats_devices.restype = C.c_int
         L.inq_genotype_repeats_devices.argtypes = [C.POINTER(CallArgsC), C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.POINTER(PartStatsC), C.c_char_p, C.c_size_t]
         L.inq_host_set_local_share.restype = None
@@ -227,6 +235,11 @@ def load():
         L.inq_frontend_next.argtypes = [vp, C.POINTER(InqBatchC), C.POINTER(C.POINTER(C.c_uint32)), C.c_char_p, C.c_size_t]
         L.inq_frontend_read_names.restype = C.c_int
         L.inq_frontend_read_names.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint64)]
+        L.inq_frontend_read_seqs.restype = C.c_int
+        L.inq_frontend_read_seqs.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint8)),
+                                             C.POINTER(C.c_uint64)]
+        L.inq_frontend_set_keep_seqs.restype = None
+        L.inq_frontend_set_keep_seqs.argtypes = [vp, C.c_int]
         L.inq_frontend_set_batch_words.restype = None
         L.inq_frontend_set_batch_words.argtypes = [vp, C.c_uint64]
         L.inq_frontend_close.restype = None
@@ -246,6 +259,12 @@ def load():
         L.inq_host_format_read_table_rows.restype = C.c_size_t
         L.inq_host_format_read_table_rows.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
                                                       C.c_char_p, C.c_size_t]
+        L.inq_host_format_read_seq_rows.restype = C.c_size_t
+        L.inq_host_format_read_seq_rows.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_size_t, C.c_int, C.c_char_p, C.c_size_t]
+        L.inq_host_seq_window.restype = C.c_int
+        L.inq_host_seq_window.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                          C.POINTER(C.c_uint32)]
         L.inq_host_sample_name.restype = C.c_size_t
         L.inq_host_sample_name.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
         L.inq_host_human_compare.restype = C.c_int
@@ -350,7 +369,7 @@ def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str
                      threads: int = 1, unphased: bool = False, sample_name: Optional[str] = None,
                      reference: Optional[str] = None, out=None, device: int = 0, frontend: Optional[str] = None,
                      ties: Optional[str] = None, evidence: Optional[str] = None, read_calls: Optional[str] = None, devices=None,
-                     read_table: Optional[str] = None) -> None:
+                     read_table: Optional[str] = None, read_seqs: Optional[str] = None) -> None:
     """src/call.rs:76-86: same parameters, same output; raises CallError instead of exiting.
     frontend: "host" (BGZF inflate + record decode on CPU threads), "device" (inq_call_span: both on the GPU)
     or None (env INQ_FRONTEND, else the library default).
@@ -358,12 +377,13 @@ def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str
     evidence: path of the evidence file (inquistr call --evidence): one line per row with the read counts behind its two medians.
     read_calls: path of the read-calls file (inquistr call --read-calls): one line per row with the Calls behind its two medians.
     read_table: path of the read table (inquistr call --read-table): one line per kept read with its Call, group, name, pos, strand, mapq.
-    devices: with read_calls or read_table, the HIP devices of inq_genotype_repeats_table (None: the one device `device`)."""
+    read_seqs: path of the read-seqs file (inquistr call --read-seqs): the table's lines with the read's bases over the locus window.
+    devices: with read_calls, read_table or read_seqs, the HIP devices of inq_genotype_repeats_seqs (None: the one device `device`)."""
     L = load()
     a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, reference, device, frontend, ties, evidence)
     out = sys.stdout if out is None else out
     out.flush()
-    if read_calls is None and read_table is None and devices is None:
+    if read_calls is None and read_table is None and read_seqs is None and devices is None:
         _checked(L.inq_genotype_repeats, C.byref(a), out.fileno())
         return
     devices = [] if devices is None else [int(d) for d in devices]
@@ -371,7 +391,8 @@ def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str
     st = (PartStatsC * max(len(devices), 1))()
     path = os.fspath(read_calls).encode() if read_calls is not None else None
     table = os.fspath(read_table).encode() if read_table is not None else None
-    _checked(L.inq_genotype_repeats_table, C.byref(a), ids, len(devices), out.fileno(), path, table, st)
+    seqs = os.fspath(read_seqs).encode() if read_seqs is not None else None
+    _checked(L.inq_genotype_repeats_seqs, C.byref(a), ids, len(devices), out.fileno(), path, table, seqs, st)
 
 
 def genotype_repeats_devices(bamp: str, region: Optional[str], region_file: Optional[str], devices, minlen: int = 5, support: int = 3,
@@ -614,11 +635,13 @@ class FrontEnd(_Handle):
     _CLOSE = "inq_frontend_close"
 
     def __init__(self, bamp, region=None, region_file=None, minlen=5, support=3, threads=1, unphased=False,
-                 sample_name=None, max_batch_words: int = 0):
+                 sample_name=None, max_batch_words: int = 0, keep_seqs: bool = False):
         self._args = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, None)
         self._open("inq_frontend_open", C.byref(self._args))
         if max_batch_words:
             self._L.inq_frontend_set_batch_words(self._h, max_batch_words)
+        if keep_seqs:  # every batch then carries its reads' packed SEQ (read_seqs())
+            self._L.inq_frontend_set_keep_seqs(self._h, 1)
 
     @property
     def sample(self) -> str:
@@ -641,6 +664,15 @@ class FrontEnd(_Handle):
         o = _copy_array(off, int(n.value) + 1, np.uint64)
         raw = _copy_array(names, int(o[-1]), np.uint8).tobytes()
         return [raw[int(o[i]) : int(o[i + 1])] for i in range(int(n.value))]
+
+    def read_seqs(self):
+        """inq_frontend_read_seqs: (l_seq u32 [n_reads], seq_off u64 [n_reads + 1], the packed SEQ bytes uint8) of the reads of the batch
+        batches() handed out last."""
+        ls, off, seqs, n = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint8)(), C.c_uint64(0)
+        if self._L.inq_frontend_read_seqs(self._h, C.byref(ls), C.byref(off), C.byref(seqs), C.byref(n)) != 0:
+            raise CallError(1, "no batch is out")
+        o = _copy_array(off, int(n.value) + 1, np.uint64)
+        return _copy_array(ls, int(n.value), np.uint32), o, _copy_array(seqs, int(o[-1]), np.uint8)
 
     def batches(self) -> Iterator[Tuple[Batch, np.ndarray]]:
         """Yields (Batch copy, locus_index) until the BAM is exhausted (read_names(): the names of the batch just yielded)."""

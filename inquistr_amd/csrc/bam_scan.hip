@@ -428,6 +428,17 @@ struct LoadOriginLen {
     const uint64_t *n_kept;
     __device__ uint64_t operator()(uint64_t k) const { return k < *n_kept ? origins[k].name_len : 0u; }
 };
+// packed bytes of pair p's slice, (n_bases + 1) / 2
+struct LoadSeqBytes {
+    const uint32_t *n_bases;
+    __device__ uint64_t operator()(uint64_t p) const { return ((uint64_t)n_bases[p] + 1u) / 2u; }
+};
+// ... and of record k's, 0 at and behind min(*n_kept, n)
+struct LoadSeqRecBytes {
+    const inq_read_seq_t *recs;
+    const uint64_t *n_kept;
+    __device__ uint64_t operator()(uint64_t k) const { return k < *n_kept ? ((uint64_t)recs[k].n_bases + 1u) / 2u : 0u; }
+};
 struct LoadI64 {
     const int64_t *in;
     __device__ int64_t operator()(uint64_t i) const { return in[i]; }
@@ -600,6 +611,12 @@ void launch_scan_name_len(const uint8_t *u, uint64_t u_bytes, const uint64_t *re
 }
 void launch_scan_origin_len(const inq_read_origin_t *origins, const uint64_t *n_kept, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s) {
     run_scan<SumOp, LoadOriginLen, true>(LoadOriginLen{origins, n_kept}, out, n, tmp, s);
+}
+void launch_scan_seq_bytes(const uint32_t *n_bases, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s) {
+    run_scan<SumOp, LoadSeqBytes, true>(LoadSeqBytes{n_bases}, out, n, tmp, s);
+}
+void launch_scan_seq_rec_bytes(const inq_read_seq_t *recs, const uint64_t *n_kept, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s) {
+    run_scan<SumOp, LoadSeqRecBytes, true>(LoadSeqRecBytes{recs, n_kept}, out, n, tmp, s);
 }
 void launch_scan_max_i64(const int64_t *in, int64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s) {
     run_scan<MaxOp, LoadI64, false>(LoadI64{in}, out, n, (int64_t *)tmp, s);

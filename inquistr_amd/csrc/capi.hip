@@ -18,6 +18,7 @@
 #include "front_kernels.h"
 #include "kernels.h"
 #include "read_calls.h"
+#include "read_seqs.h"
 
 using namespace inq;
 
@@ -330,6 +331,7 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     if (!x.kept_off != !x.kept || ((uintptr_t)x.kept & 15u) || ((uintptr_t)x.kept_off & 7u)) return INQ_ERR_ARG;
     if (x.kept && b->n_pairs && (!r->pair_call || !r->pair_bits)) return INQ_ERR_ARG;  // ... and so does the compaction
     if (x.origins && (!x.kept || !x.origin_off || !x.name_off || ((uintptr_t)x.origins & 7u))) return INQ_ERR_ARG;  // who the records are
+    if (x.seq_recs && (!x.kept || !x.kept_pair || !x.seq_rec_off || !x.seq_qbeg || !x.seq_len || ((uintptr_t)x.seq_recs & 7u))) return INQ_ERR_ARG;
     if (((uintptr_t)b->cigar & 15u) || ((uintptr_t)b->reads & 15u)) return INQ_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
@@ -396,7 +398,8 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     if (x.kept && !b->n_pairs) HIP_TRY(c, hipMemsetAsync(x.kept_off, 0, (size_t)(b->n_loci + 1) * 8, s));  // no pair: every list is empty
     if (x.kept && b->n_pairs) {
         uint64_t *const tile_base = (uint64_t *)c->rctiles.p;
-        launch_read_calls(ReadCallArgs{view, x.kept_off, x.kept, (uint32_t *)(tile_base + read_call_tiles(b->n_pairs) + 1), tile_base}, b->unphased != 0, s);
+        launch_read_calls(ReadCallArgs{view, x.kept_off, x.kept, (uint32_t *)(tile_base + read_call_tiles(b->n_pairs) + 1), tile_base, x.kept_pair},
+                          b->unphased != 0, s);
         HIP_TRY(c, hipGetLastError());
     }
     if (x.origins && !b->n_pairs) HIP_TRY(c, hipMemsetAsync(x.origin_off, 0, 8, s));  // no record, no name byte
@@ -404,6 +407,13 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
         const uint64_t *const n_kept = x.kept_off + b->n_loci;
         launch_read_origins(ReadOriginArgs{x.kept, n_kept, view.read_words, b->n_reads, x.name_off, x.origins, b->n_pairs}, s);
         launch_scan_origin_len(x.origins, n_kept, x.origin_off, b->n_pairs, x.origin_off + b->n_pairs + 1, s);
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (x.seq_recs && !b->n_pairs) HIP_TRY(c, hipMemsetAsync(x.seq_rec_off, 0, 8, s));  // no record, no base
+    if (x.seq_recs && b->n_pairs) {  // behind the scatter: the slice of the pair each record came from, then where its packed bytes will go
+        const uint64_t *const n_kept = x.kept_off + b->n_loci;
+        launch_read_seq_records(ReadSeqArgs{x.kept_pair, n_kept, x.seq_qbeg, x.seq_len, x.seq_recs, b->n_pairs}, s);
+        launch_scan_seq_rec_bytes(x.seq_recs, n_kept, x.seq_rec_off, b->n_pairs, x.seq_rec_off + b->n_pairs + 1, s);
         HIP_TRY(c, hipGetLastError());
     }
     if (ev) HIP_TRY(c, hipEventRecord(ev->e2, s));
@@ -455,6 +465,71 @@ static int read_origins_fetch_impl(inq_ctx_t *c, inq_read_origin_t *origins, uin
 }
 int inq_read_origins_fetch(inq_ctx_t *c, inq_read_origin_t *origins, uint64_t n, uint8_t *names, uint64_t name_bytes) {
     return guarded([&] { return read_origins_fetch_impl(c, origins, n, names, name_bytes); });
+}
+
+uint32_t inq_seq_window_tile(void) { return kSeqWindowTile; }
+
+static int read_seqs_fetch_impl(inq_ctx_t *c, inq_read_seq_t *seqs, uint64_t n, uint8_t *packed, uint64_t seq_bytes) {
+    if (!c || n > c->read_seqs_total || seq_bytes > c->read_seq_bytes_total || (n && !seqs) || (seq_bytes && !packed)) return INQ_ERR_ARG;
+    if (!n && !seq_bytes) return INQ_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n) HIP_TRY(c, hipMemcpyAsync(seqs, c->rseqs.p, (size_t)n * sizeof(inq_read_seq_t), hipMemcpyDeviceToHost, c->stream));
+    if (seq_bytes) HIP_TRY(c, hipMemcpyAsync(packed, c->rseqbytes.p, (size_t)seq_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return INQ_OK;
+}
+int inq_read_seqs_fetch(inq_ctx_t *c, inq_read_seq_t *seqs, uint64_t n, uint8_t *packed, uint64_t seq_bytes) {
+    return guarded([&] { return read_seqs_fetch_impl(c, seqs, n, packed, seq_bytes); });
+}
+
+// the window walk alone: the batch goes up as a call's does, two arrays come down
+static int seq_windows_impl(inq_ctx_t *c, const inq_batch_t *b, const uint32_t *l_seq, uint32_t *q_beg, uint32_t *n_bases) {
+    if (!c || !b) return INQ_ERR_ARG;
+    extras_reset(c);
+    if (b->n_loci && (!b->locus_pair_off || !b->locus_start || !b->locus_end)) return INQ_ERR_ARG;
+    if (b->n_pairs && (!b->pair_read || !b->reads || !b->n_reads || !q_beg || !n_bases)) return INQ_ERR_ARG;
+    if ((b->n_cigar_words && !b->cigar) || b->n_cigar_words % 4 != 0 || b->reserved != 0) return INQ_ERR_ARG;
+    if ((!b->n_loci && b->n_pairs) || b->n_loci >= 0xfffffff0ull || b->n_pairs >= (1ull << 40)) return INQ_ERR_ARG;
+    if (b->n_loci && (b->locus_pair_off[0] != 0 || b->locus_pair_off[b->n_loci] != b->n_pairs)) return INQ_ERR_ARG;
+    for (uint64_t j = 0; j < b->n_loci; ++j)
+        if (b->locus_pair_off[j] > b->locus_pair_off[j + 1]) return INQ_ERR_ARG;
+    if (!b->n_pairs) return INQ_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc;
+    struct Up {
+        DevBuf *d;
+        const void *h;
+        size_t bytes;
+    } ups[] = {
+        {&c->cigar, b->cigar, (size_t)b->n_cigar_words * 4},
+        {&c->reads, b->reads, (size_t)b->n_reads * sizeof(inq_read_t)},
+        {&c->pair_read, b->pair_read, (size_t)b->n_pairs * 4},
+        {&c->off, b->locus_pair_off, (size_t)(b->n_loci + 1) * 8},
+        {&c->lstart, b->locus_start, (size_t)b->n_loci * 4},
+        {&c->lend, b->locus_end, (size_t)b->n_loci * 4},
+        {&c->rseqoff, l_seq, l_seq ? (size_t)b->n_reads * 4 : 0},  // (scratch of the flushes' sequences, free between calls)
+    };
+    for (auto &u : ups) {
+        if ((rc = ensure(c, *u.d, u.bytes)) != INQ_OK) return rc;
+        if (u.bytes) HIP_TRY(c, hipMemcpyAsync(u.d->p, u.h, u.bytes, hipMemcpyHostToDevice, s));
+    }
+    if ((rc = ensure(c, c->rseqs, (size_t)b->n_pairs * 8)) != INQ_OK) return rc;  // q_beg[n_pairs], n_bases[n_pairs]
+    uint32_t *const d_qbeg = (uint32_t *)c->rseqs.p, *const d_len = d_qbeg + b->n_pairs;
+    SeqWindowArgs a{(const uint4 *)c->cigar.p, b->n_cigar_words / 4, (const uint4 *)c->reads.p, b->n_reads, (const uint32_t *)c->pair_read.p,
+                    (const uint64_t *)c->off.p, (const uint32_t *)c->lstart.p, (const uint32_t *)c->lend.p, b->n_loci, b->n_pairs, SeqLenSource{},
+                    d_qbeg, d_len};
+    if (l_seq) a.len.l_seq = (const uint32_t *)c->rseqoff.p;
+    launch_seq_window(a, s);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(q_beg, d_qbeg, (size_t)b->n_pairs * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(n_bases, d_len, (size_t)b->n_pairs * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    purge_retired(c);
+    return INQ_OK;
+}
+int inq_seq_windows(inq_ctx_t *c, const inq_batch_t *b, const uint32_t *l_seq, uint32_t *q_beg, uint32_t *n_bases) {
+    return guarded([&] { return seq_windows_impl(c, b, l_seq, q_beg, n_bases); });
 }
 
 int inq_ctx_status(inq_ctx_t *c, uint64_t *n_tie_loci) {
@@ -815,6 +890,15 @@ int inq::extras_prepare(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const Hos
         d->origins = (inq_read_origin_t *)c->rorigins.p;
         d->origin_off = (uint64_t *)c->rnameoff.p;
     }
+    if (h.seq_bytes) {  // (the batch's own slices, LocusExtras::seq_qbeg / seq_len, are the caller's to set, like its names)
+        if (!h.kept_off || !h.name_bytes) return INQ_ERR_ARG;
+        if ((rc = ensure(c, c->rkeptpair, (size_t)n_pairs * 8)) != INQ_OK) return rc;
+        if ((rc = ensure(c, c->rseqs, (size_t)n_pairs * sizeof(inq_read_seq_t))) != INQ_OK) return rc;
+        if ((rc = ensure(c, c->rseqoff, (size_t)(n_pairs + 1 + scan_tmp_words(std::max<uint64_t>(n_pairs, 1))) * 8)) != INQ_OK) return rc;
+        d->kept_pair = (uint64_t *)c->rkeptpair.p;
+        d->seq_recs = (inq_read_seq_t *)c->rseqs.p;
+        d->seq_rec_off = (uint64_t *)c->rseqoff.p;
+    }
     return INQ_OK;
 }
 
@@ -826,17 +910,29 @@ int inq::extras_download(inq_ctx *c, uint64_t n_loci, const HostExtras &h, const
 }
 
 int inq::extras_names(inq_ctx *c, uint64_t n_pairs, const HostExtras &h, const LocusExtras &d, uint64_t n_kept, const uint8_t *batch_names,
-                      uint64_t batch_name_bytes, uint64_t n_reads, uint64_t *total, hipStream_t s) {
-    *total = 0;
+                      uint64_t batch_name_bytes, uint64_t n_reads, const uint8_t *batch_seqs, uint64_t batch_seq_bytes,
+                      const uint64_t *batch_seq_off, hipStream_t s) {
+    if (h.name_bytes) *h.name_bytes = 0;
+    if (h.seq_bytes) *h.seq_bytes = 0;
     if (!h.name_bytes || !n_pairs || !n_kept) return INQ_OK;
-    // (the scan's total sits behind the last element; nothing else is in flight on s: a plain 8-byte copy)
+    // (each scan's total sits behind its last element; nothing else is in flight on s: plain 8-byte copies, one wait for both)
+    uint64_t *const total = h.name_bytes;
     HIP_TRY(c, hipMemcpyAsync(total, d.origin_off + n_pairs, 8, hipMemcpyDeviceToHost, s));
+    if (h.seq_bytes) HIP_TRY(c, hipMemcpyAsync(h.seq_bytes, d.seq_rec_off + n_pairs, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    if (!*total) return INQ_OK;
-    const int rc = ensure(c, c->rnames, (size_t)*total);
-    if (rc != INQ_OK) return rc;
-    launch_name_copy(NameCopyArgs{batch_names, batch_name_bytes, d.name_off, n_reads, 0, d.kept, (uint8_t *)c->rnames.p, *total, d.origin_off,
-                                  std::min(n_kept, n_pairs)}, s);
+    const uint64_t seq_total = h.seq_bytes ? *h.seq_bytes : 0;
+    if (!*total && !seq_total) return INQ_OK;
+    int rc;
+    if (*total) {
+        if ((rc = ensure(c, c->rnames, (size_t)*total)) != INQ_OK) return rc;
+        launch_name_copy(NameCopyArgs{batch_names, batch_name_bytes, d.name_off, n_reads, 0, d.kept, (uint8_t *)c->rnames.p, *total, d.origin_off,
+                                      std::min(n_kept, n_pairs)}, s);
+    }
+    if (seq_total) {  // the kept records' packed slices: segment k out of the batch's at seq_off[kept_pair[k]]
+        if ((rc = ensure(c, c->rseqbytes, (size_t)seq_total)) != INQ_OK) return rc;
+        launch_name_copy(NameCopyArgs{batch_seqs, batch_seq_bytes, batch_seq_off, n_pairs, 0, nullptr, (uint8_t *)c->rseqbytes.p, seq_total,
+                                      d.seq_rec_off, std::min(n_kept, n_pairs), d.kept_pair}, s);
+    }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(s));
     return INQ_OK;
@@ -847,4 +943,5 @@ void inq::extras_finish(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const Hos
     if (!n_loci) h.kept_off[0] = 0;  // (nothing was launched: no list, no record)
     if (err == 0) c->read_calls_total = std::min<uint64_t>(h.kept_off[n_loci], n_pairs);
     if (h.name_bytes && err == 0) c->read_origins_total = c->read_calls_total, c->read_names_total = *h.name_bytes;
+    if (h.seq_bytes && err == 0) c->read_seqs_total = c->read_calls_total, c->read_seq_bytes_total = *h.seq_bytes;
 }

@@ -51,11 +51,17 @@ struct inq_ctx {
     // Allocated by flushes with origins only
     inq::DevBuf rorigins, rnameoff, rnames;
     uint64_t read_origins_total = 0, read_names_total = 0;  // origins and name bytes of the last flush (0: it had no origins)
+    // the bases behind those records (read_seqs.hip; inq_call_flush_seqs): the pair each record came from, one inq_read_seq_t per record,
+    // the scan of their packed lengths with its tile totals, the packed slices back to back.  They stay until the context's next call
+    // (inq_read_seqs_fetch).  Allocated by flushes with sequences only
+    inq::DevBuf rkeptpair, rseqs, rseqoff, rseqbytes;
+    uint64_t read_seqs_total = 0, read_seq_bytes_total = 0;  // records and packed bytes of the last flush (0: it had no sequences)
     inq::DevBuf ovalues, olen, oflags, okeep, otrans;  // inq_outlier_rows
     // every DevBuf above, for inq_ctx_destroy (DevBuf frees nothing itself): a member missing here leaks
     auto bufs() {
         return std::array{&worklist, &sval, &smeta, &deep, &cigar, &reads, &pair_read, &off, &lstart, &lend, &p1, &p2, &pcall, &pbits, &lflags,
-                          &levidence, &evwork, &rctiles, &rcoff, &rckept, &rorigins, &rnameoff, &rnames, &ovalues, &olen, &oflags, &okeep, &otrans};
+                          &levidence, &evwork, &rctiles, &rcoff, &rckept, &rorigins, &rnameoff, &rnames, &rkeptpair, &rseqs, &rseqoff,
+                          &rseqbytes, &ovalues, &olen, &oflags, &okeep, &otrans};
     }
     uint32_t n_cus = 0;        // compute units of the device
     uint32_t grid_tail = 256;  // workgroups of the persistent locus_call_tail: they meet at grid barriers, so never more than n_cus
@@ -167,6 +173,13 @@ struct LocusExtras {
     inq_read_origin_t *origins = nullptr;
     uint64_t *origin_off = nullptr;
     const uint64_t *name_off = nullptr;        // [n_reads + 1]
+    // the bases behind those records (needs kept): kept_pair[n_pairs], the pair each record came from, written by the compaction's
+    // scatter; one seq_recs per record; seq_rec_off laid out like origin_off, the scan of their packed lengths; seq_qbeg / seq_len:
+    // the batch's slices, per pair
+    uint64_t *kept_pair = nullptr;
+    inq_read_seq_t *seq_recs = nullptr;
+    uint64_t *seq_rec_off = nullptr;
+    const uint32_t *seq_qbeg = nullptr, *seq_len = nullptr;  // [n_pairs]
 };
 // ... and as a host-buffer call or a flush takes them: HOST pointers, [n_loci] / [n_loci] / [n_loci + 1] in the call's locus order, each
 // may be null.  The records behind kept_off stay in context scratch (inq_read_calls_fetch).
@@ -175,21 +188,27 @@ struct HostExtras {
     inq_locus_evidence_t *evidence = nullptr;
     uint64_t *kept_off = nullptr;
     uint64_t *name_bytes = nullptr;  // a flush with origins (needs kept_off): receives the bytes of the kept records' names
+    uint64_t *seq_bytes = nullptr;   // a flush with sequences (needs kept_off): receives the bytes of the kept records' packed slices
     // the evidence is counted and the lists are compacted from the per-pair outputs: the call keeps those (pcall / pbits) also when
     // its caller did not ask for them
     bool per_pair() const { return evidence || kept_off; }
 };
 // The three steps of a host-buffer call or a flush around its launch sequence.  First of all extras_reset: the records of the call
 // before are no longer offered, however this one ends.
-inline void extras_reset(inq_ctx *c) { c->read_calls_total = c->read_origins_total = c->read_names_total = 0; }
+inline void extras_reset(inq_ctx *c) {
+    c->read_calls_total = c->read_origins_total = c->read_names_total = c->read_seqs_total = c->read_seq_bytes_total = 0;
+}
 // the context buffers behind what h asks for (and pcall / pbits where h.per_pair()), as device pointers
 int extras_prepare(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const HostExtras &h, LocusExtras *d);
 // enqueues the copies down on s; the flags go to flags_dst (the caller's array, or page-locked staging on their way there)
 int extras_download(inq_ctx *c, uint64_t n_loci, const HostExtras &h, const LocusExtras &d, uint8_t *flags_dst, hipStream_t s);
 // a flush with origins, after its synchronisation (n_kept = kept_off[n_loci] is known then): the bytes of the kept records' names come
-// down (*total), c->rnames is sized from them, the copy launch runs and is waited for.  Without origins, pairs or records: nothing
+// down (*h.name_bytes), c->rnames is sized from them, the copy launch runs and is waited for.  Without origins, pairs or records:
+// nothing.  A flush with sequences: the bytes of the kept records' packed slices come down in the same readback (*h.seq_bytes) and
+// their copy runs beside the names'; batch_seqs / batch_seq_off: the batch's packed slices and seq_off[n_pairs + 1]
 int extras_names(inq_ctx *c, uint64_t n_pairs, const HostExtras &h, const LocusExtras &d, uint64_t n_kept, const uint8_t *batch_names,
-                 uint64_t batch_name_bytes, uint64_t n_reads, uint64_t *total, hipStream_t s);
+                 uint64_t batch_name_bytes, uint64_t n_reads, const uint8_t *batch_seqs, uint64_t batch_seq_bytes, const uint64_t *batch_seq_off,
+                 hipStream_t s);
 // after the call's synchronisation, or at once for a call without loci: how many records inq_read_calls_fetch offers.  err: the
 // kernels' status word - after a domain error the lists are unspecified and none is offered, whatever the offsets say
 void extras_finish(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const HostExtras &h, uint32_t err);

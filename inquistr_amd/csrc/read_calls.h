@@ -15,6 +15,7 @@ struct ReadCallArgs : PairView {
     inq_read_call_t *kept;           // [n_pairs]: records [0, kept_off[n_loci]) are written, 16-byte aligned
     uint32_t *tile_count;            // [n_tiles]      context scratch
     uint64_t *tile_base;             // [n_tiles + 1]  context scratch; the last entry is the total
+    uint64_t *kept_pair = nullptr;   // [n_pairs] or null: the pair each record came from (what the slices of read_seqs.hip are indexed by)
 };
 
 inline uint64_t read_call_tiles(uint64_t n_pairs) { return (n_pairs + kReadCallTile - 1) / kReadCallTile; }
@@ -30,8 +31,8 @@ constexpr uint32_t kReadNameTile = 256 / kReadNameLanes;  // segments per workgr
 constexpr uint32_t kReadNameMax = 254;                    // l_read_name is a byte and counts the terminator
 
 // The segmented byte gather: segment i copies dst_off[i + 1] - dst_off[i] bytes from src + src_off[r] + src_add to dst + dst_off[i],
-// r = index[i].read, or i where index is null.  dst_off is an exclusive prefix sum ([n + 1]).  A segment is cut to [dst, dst + dst_bytes)
-// and to [src, src + src_bytes); r >= n_src copies nothing.
+// r = index[i].read, or index64[i] (a plain index: the kept records' pairs), or i where both are null.  dst_off is an exclusive prefix
+// sum ([n + 1]).  A segment is cut to [dst, dst + dst_bytes) and to [src, src + src_bytes); r >= n_src copies nothing.
 struct NameCopyArgs {
     const uint8_t *src;
     uint64_t src_bytes;
@@ -42,6 +43,7 @@ struct NameCopyArgs {
     uint64_t dst_bytes;
     const uint64_t *dst_off;       // [n + 1]
     uint64_t n;
+    const uint64_t *index64 = nullptr;  // [n] or null; read where index is null
 };
 void launch_name_copy(const NameCopyArgs &a, hipStream_t s);  // n == 0 launches nothing
 

@@ -164,6 +164,7 @@ __global__ __launch_bounds__(256) void read_call_scatter(ReadCallArgs a) {
         // call | read | group, flags, reserved: the 16 bytes of inq_read_call_t in one store
         *(uint4 *)(a.kept + (base + prefix[pos])) =
             make_uint4((uint32_t)(uint64_t)call[k], (uint32_t)((uint64_t)call[k] >> 32), read[k], tail[k]);
+        if (a.kept_pair) a.kept_pair[base + prefix[pos]] = tile_start + pos;  // (a call with sequences only)
     }
 
     // kept_off of the loci that begin in this tile: from the first j with locus_pair_off[j] >= tile_start on, until one begins at or

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void name_copy_kernel(NameCopyArgs a) {
         uint64_t d1 = a.dst_off[i + 1];
         if (d1 > a.dst_bytes) d1 = a.dst_bytes;
         if (d0 >= d1) continue;  // an empty name (or offsets that do not ascend): nothing moves
-        const uint64_t r = a.index ? (uint64_t)a.index[i].read : i;
+        const uint64_t r = a.index ? (uint64_t)a.index[i].read : a.index64 ? a.index64[i] : i;
         if (r >= a.n_src) continue;
         const uint64_t s0 = a.src_off[r] + a.src_add;
         if (s0 >= a.src_bytes) continue;

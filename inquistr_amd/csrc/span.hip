@@ -15,6 +15,7 @@
 #include "deflate_probe.h"
 #include "front_kernels.h"
 #include "read_calls.h"
+#include "read_seqs.h"
 
 namespace inq {
 
@@ -23,10 +24,13 @@ struct SpanState {
     DevBuf comp, blocks, u, block_status, anchors, anchor_cnt, anchor_base, rec_off, reads, info, key, endkey, pmax, cig_off, cigar,
         anchor_stop, ltid, lstart, lend, locus_cnt, locus_off, pair_read, p1, p2, tmp;
     DevBuf name_off;  // [n_records + 1] of a span appended with names: where each record's name begins among the span's (read_names.hip)
+    // of a span appended with sequences: seq_off[n_pairs + 1], where each pair's packed slice begins among the span's, with the scan's
+    // tile totals behind it (read_seqs.hip)
+    DevBuf seq_off;
     auto bufs() {  // every DevBuf above, for span_state_destroy
         return std::array{&tok, &comp, &blocks, &u, &block_status, &anchors, &anchor_cnt, &anchor_base, &rec_off, &reads, &info, &key, &endkey,
                           &pmax, &cig_off, &cigar, &anchor_stop, &ltid, &lstart, &lend, &locus_cnt, &locus_off, &pair_read, &p1, &p2, &tmp,
-                          &name_off};
+                          &name_off, &seq_off};
     }
     FrontStatus *d_st = nullptr;
     struct Host {  // pinned readback area
@@ -34,6 +38,7 @@ struct SpanState {
         DevStatus ks;
         uint64_t count;  // what a stage of call_span_impl reads back to size the next one
         uint64_t name_bytes;  // ... and, for a span appended with names, the bytes of its names
+        uint64_t seq_bytes;   // ... with sequences, the bytes of its packed slices
         unsigned long long init_n_valid;
     } *h = nullptr;
     // pinned staging of the rows: the caller's result arrays are ordinary memory, and the FIRST copy to or from pageable
@@ -75,18 +80,26 @@ struct SpanState {
     bool last_from_acc = false;
     bool last_names = false;  // that batch was appended with names (inq_span_fetch_names) ...
     uint64_t n_name_bytes = 0;  // ... this many bytes of them
+    bool last_seqs = false;     // ... and with sequences (inq_span_fetch_seqs),
+    uint64_t n_seq_bytes = 0;   // this many packed bytes
     // inq_call_span_deferred: the batches of several spans appended to one (CIGAR units, reads, pairs, loci so far), called
     // together by inq_call_flush - a span of SEQ-bearing records holds a few hundred loci, far too few to fill the chip
     struct Acc {
         DevBuf cigar, reads, pair_read, off, lstart, lend;
         // a batch appended with names (inq_call_span_deferred_names): the names of its reads back to back, name_off[n_reads + 1]
         DevBuf names, name_off;
+        // ... with sequences (inq_call_span_deferred_seqs): per pair the slice (seq_qbeg, seq_len) and seq_off[n_pairs + 1], where its
+        // packed bytes begin in seqs
+        DevBuf seqs, seq_off, seq_qbeg, seq_len;
         uint64_t n_units = 0, n_reads = 0, n_pairs = 0, n_loci = 0, n_spans = 0;
         uint32_t minlen = 0, support = 0, unphased = 0, max_reads = 0;
         uint64_t n_name_bytes = 0;
         bool with_names = false;  // every span of the batch, or none
-        auto bufs() { return std::array{&cigar, &reads, &pair_read, &off, &lstart, &lend, &names, &name_off}; }
-        void reset() { *this = Acc{cigar, reads, pair_read, off, lstart, lend, names, name_off}; }  // the batch is gone, its buffers stay
+        uint64_t n_seq_bytes = 0;
+        bool with_seqs = false;  // likewise
+        auto bufs() { return std::array{&cigar, &reads, &pair_read, &off, &lstart, &lend, &names, &name_off, &seqs, &seq_off, &seq_qbeg, &seq_len}; }
+        // the batch is gone, its buffers stay
+        void reset() { *this = Acc{cigar, reads, pair_read, off, lstart, lend, names, name_off, seqs, seq_off, seq_qbeg, seq_len}; }
     } acc;
 };
 
@@ -300,9 +313,10 @@ int bgzf_inflate_impl(inq_ctx *c, const uint8_t *comp, uint64_t comp_bytes, cons
 }
 
 // defer: the span's batch is appended to S->acc instead of being called (r may be null then)
-// names: with the names of the span's placed records (deferred only)
-int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_stats_t *stats, int slot, bool defer = false, bool names = false) {
-    if (!c || !sp || (!r && !defer) || slot >= INQ_SPAN_SLOTS || (names && !defer)) return INQ_ERR_ARG;
+// names: with the names of the span's placed records (deferred only); seqs: and with every pair's slice of SEQ (with names only)
+int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_stats_t *stats, int slot, bool defer = false, bool names = false,
+                   bool seqs = false) {
+    if (!c || !sp || (!r && !defer) || slot >= INQ_SPAN_SLOTS || (names && !defer) || (seqs && !names)) return INQ_ERR_ARG;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (sp->reserved || sp->unphased > 1) return INQ_ERR_ARG;
     if (sp->n_loci && (!sp->locus_tid || !sp->locus_start || !sp->locus_end || (!defer && (!r->phase1 || !r->phase2)))) return INQ_ERR_ARG;
@@ -332,6 +346,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     SpanState::Acc &A = S->acc;
     if (defer && A.n_spans && (A.minlen != sp->minlen || A.support != sp->support || A.unphased != sp->unphased)) return INQ_ERR_ARG;
     if (defer && A.n_spans && A.with_names != names) return INQ_ERR_ARG;  // all spans of a batch with names, or all without
+    if (defer && A.n_spans && A.with_seqs != seqs) return INQ_ERR_ARG;    // ... and with sequences
     const SpanState::Stage *staged = nullptr;
     if (slot >= 0) {  // the span inq_span_stage put there, and nothing else
         const SpanState::Stage &g = S->stage[slot];
@@ -540,9 +555,30 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
         if ((rc = ensure_keep(c, A.off, (A.n_loci + nl + 1) * 8, (A.n_loci + 1) * 8, s)) != INQ_OK) return rc;
         if ((rc = ensure_keep(c, A.lstart, (A.n_loci + nl) * 4, A.n_loci * 4, s)) != INQ_OK) return rc;
         if ((rc = ensure_keep(c, A.lend, (A.n_loci + nl) * 4, A.n_loci * 4, s)) != INQ_OK) return rc;
+        uint64_t *span_seq_off = nullptr;
+        uint32_t *span_qbeg = nullptr, *span_len = nullptr;
+        if (seqs) {
+            // (of the first span of a batch nothing is kept: seq_off[0] is written with the span's offsets)
+            if ((rc = ensure_keep(c, A.seq_qbeg, (A.n_pairs + n_pairs) * 4, A.n_pairs * 4, s)) != INQ_OK) return rc;
+            if ((rc = ensure_keep(c, A.seq_len, (A.n_pairs + n_pairs) * 4, A.n_pairs * 4, s)) != INQ_OK) return rc;
+            if ((rc = ensure_keep(c, A.seq_off, (A.n_pairs + n_pairs + 1) * 8, A.n_spans ? (A.n_pairs + 1) * 8 : 0, s)) != INQ_OK) return rc;
+            if ((rc = ensure(c, S->seq_off, (n_pairs + 1 + scan_tmp_words(std::max<uint64_t>(n_pairs, 1))) * 8)) != INQ_OK) return rc;
+            span_seq_off = (uint64_t *)S->seq_off.p;
+            span_qbeg = (uint32_t *)A.seq_qbeg.p + A.n_pairs, span_len = (uint32_t *)A.seq_len.p + A.n_pairs;
+        }
         a.pair_read = (uint32_t *)A.pair_read.p + A.n_pairs;
         launch_join_fill(a, n_valid, s);
         launch_offset_copy((uint64_t *)A.off.p + A.n_loci, a.locus_pair_off, nl + 1, A.n_pairs, s);
+        if (seqs) {
+            // every pair's slice: the window walk over the batch's CIGARs (this span's are in place: the gather ran), cut to the records'
+            // l_seq; then where each packed slice begins among the span's, and their total: it comes down with the front status
+            SeqLenSource lens;
+            lens.u = a.u, lens.u_bytes = a.u_bytes, lens.rec_off = a.rec_off, lens.n_records = n_valid, lens.read_base = A.n_reads;
+            launch_seq_window(SeqWindowArgs{(const uint4 *)A.cigar.p, A.n_units + n_units, (const uint4 *)A.reads.p, A.n_reads + n_valid, a.pair_read,
+                                            a.locus_pair_off, a.locus_start, a.locus_end, nl, n_pairs, lens, span_qbeg, span_len}, s);
+            launch_scan_seq_bytes(span_len, span_seq_off, n_pairs, span_seq_off + n_pairs + 1, s);
+            HIP_TRY(c, hipMemcpyAsync(&S->h->seq_bytes, span_seq_off + n_pairs, 8, hipMemcpyDeviceToHost, s));
+        }
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync((uint32_t *)A.lstart.p + A.n_loci, a.locus_start, nl * 4, hipMemcpyDeviceToDevice, s));
         HIP_TRY(c, hipMemcpyAsync((uint32_t *)A.lend.p + A.n_loci, a.locus_end, nl * 4, hipMemcpyDeviceToDevice, s));
@@ -551,8 +587,21 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
         HIP_TRY(c, hipStreamSynchronize(s));  // the span's slot and the scan buffers are free again when this returns
         fill_stats();
         if ((rc = front_fail(S->h->st)) != INQ_OK) return rc;
-        if (A.n_spans == 0) A.minlen = sp->minlen, A.support = sp->support, A.unphased = sp->unphased, A.max_reads = 0, A.with_names = names;
+        const uint64_t seq_bytes = seqs ? S->h->seq_bytes : 0;
+        if (seqs) {
+            // the packed slices, out of the inflated bytes into the batch behind those that are there; seq_off[pair base + p] = the
+            // batch's bytes so far + the span's offset.  The slot's bytes are read: one more wait before it is given back
+            if ((rc = ensure_keep(c, A.seqs, A.n_seq_bytes + seq_bytes, A.n_seq_bytes, s)) != INQ_OK) return rc;
+            launch_offset_copy((uint64_t *)A.seq_off.p + A.n_pairs, span_seq_off, n_pairs + 1, A.n_seq_bytes, s);
+            launch_seq_slice(SeqSliceArgs{a.u, a.u_bytes, a.rec_off, n_valid, A.n_reads, a.pair_read, span_qbeg, span_len,
+                                          (uint8_t *)A.seqs.p + A.n_seq_bytes, seq_bytes, span_seq_off, n_pairs}, s);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipStreamSynchronize(s));
+        }
+        if (A.n_spans == 0)
+            A.minlen = sp->minlen, A.support = sp->support, A.unphased = sp->unphased, A.max_reads = 0, A.with_names = names, A.with_seqs = seqs;
         A.n_name_bytes += name_bytes;
+        A.n_seq_bytes += seq_bytes;
         A.max_reads = std::max<uint32_t>(A.max_reads, S->h->st.max_reads);
         A.n_units += n_units, A.n_reads += n_valid, A.n_pairs += n_pairs, A.n_loci += nl, ++A.n_spans;
         clock.at("appended to the deferred batch");
@@ -582,6 +631,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     S->n_loci = nl;
     S->last_from_acc = false;
     S->last_names = false, S->n_name_bytes = 0;
+    S->last_seqs = false, S->n_seq_bytes = 0;
     fill_stats();
     r->n_tie_loci = S->h->ks.ties;
     if ((rc = front_fail(S->h->st)) != INQ_OK) return rc;
@@ -611,6 +661,10 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
         if (!h.kept_off || (A.n_spans && !A.with_names)) return INQ_ERR_ARG;
         *h.name_bytes = 0;
     }
+    if (h.seq_bytes) {  // the bases behind those records, out of a batch that was appended with sequences
+        if (!h.name_bytes || (A.n_spans && !A.with_seqs)) return INQ_ERR_ARG;
+        *h.seq_bytes = 0;
+    }
     if (A.n_loci == 0) {
         A.reset();
         extras_finish(c, 0, 0, h, 0);
@@ -631,6 +685,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     LocusExtras x;
     if ((rc = extras_prepare(c, nl, A.n_pairs, h, &x)) != INQ_OK) return rc;
     if (h.name_bytes) x.name_off = (const uint64_t *)A.name_off.p;
+    if (h.seq_bytes) x.seq_qbeg = (const uint32_t *)A.seq_qbeg.p, x.seq_len = (const uint32_t *)A.seq_len.p;
     const bool per_pair = h.per_pair();
     if ((rc = ensure_row_staging(c, S, nl, 2 * nl + (h.flags ? (nl + 7) / 8 : 0))) != INQ_OK) return rc;  // the rows, then the flags
     DevBatch d = device_batch(A.cigar.p, A.reads.p, A.pair_read.p, A.off.p, A.lstart.p, A.lend.p, A.n_reads, A.n_units * 4, A.n_pairs, nl,
@@ -644,7 +699,8 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
         ~Spent() { a.reset(); }
     } spent{A};
     const uint64_t n_reads_all = A.n_reads, n_units_all = A.n_units, n_pairs_all = A.n_pairs, n_name_bytes_all = A.n_name_bytes;
-    const bool with_names = A.with_names;
+    const bool with_names = A.with_names, with_seqs = A.with_seqs;
+    const uint64_t n_seq_bytes_all = A.n_seq_bytes;
     HIP_TRY(c, hipEventRecord(S->ev[4], s));
     if ((rc = call_batch_device_impl(c, &db, &dr, s, x)) != INQ_OK) return rc;
     HIP_TRY(c, hipEventRecord(S->ev[5], s));
@@ -675,7 +731,8 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     HIP_TRY(c, hipStreamSynchronize(s));
     if (h.flags) std::memcpy(h.flags, S->h_rows + 2 * nl, nl);
     if (h.name_bytes && S->h->ks.err == 0 &&  // the kept records' names, now that their number is known
-        (rc = extras_names(c, n_pairs_all, h, x, h.kept_off[nl], (const uint8_t *)A.names.p, n_name_bytes_all, n_reads_all, h.name_bytes, s)) != INQ_OK)
+        (rc = extras_names(c, n_pairs_all, h, x, h.kept_off[nl], (const uint8_t *)A.names.p, n_name_bytes_all, n_reads_all,
+                           (const uint8_t *)A.seqs.p, n_seq_bytes_all, (const uint64_t *)A.seq_off.p, s)) != INQ_OK)
         return rc;
     if (!dev) {
         std::memcpy(r->phase1, S->h_rows, nl * 8);
@@ -697,6 +754,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     S->n_reads = n_reads_all, S->n_cigar_words = n_units_all * 4, S->n_pairs = n_pairs_all, S->n_loci = nl;
     S->last_from_acc = true;  // inq_span_fetch_batch reads the accumulated buffers (their contents stay until the next append)
     S->last_names = with_names, S->n_name_bytes = n_name_bytes_all;
+    S->last_seqs = with_seqs, S->n_seq_bytes = n_seq_bytes_all;
     r->n_tie_loci = S->h->ks.ties;
     extras_finish(c, nl, n_pairs_all, h, S->h->ks.err);
     return status_to_code(S->h->ks.err);  // (`spent` puts the counters back to zero, the buffers stay)
@@ -823,6 +881,20 @@ int fetch_names_impl(inq_ctx *c, uint64_t *name_off, uint8_t *names, uint64_t ca
     return INQ_OK;
 }
 
+// ... and its pairs' slices
+int fetch_seqs_impl(inq_ctx *c, uint32_t *q_beg, uint32_t *n_bases, uint64_t *seq_off, uint8_t *packed, uint64_t cap_bytes) {
+    if (!c || !c->span) return INQ_ERR_ARG;
+    SpanState *S = c->span;
+    if (!S->last_from_acc || !S->last_seqs || cap_bytes < S->n_seq_bytes) return INQ_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (q_beg && S->n_pairs) HIP_TRY(c, hipMemcpy(q_beg, S->acc.seq_qbeg.p, S->n_pairs * 4, hipMemcpyDeviceToHost));
+    if (n_bases && S->n_pairs) HIP_TRY(c, hipMemcpy(n_bases, S->acc.seq_len.p, S->n_pairs * 4, hipMemcpyDeviceToHost));
+    if (seq_off) HIP_TRY(c, hipMemcpy(seq_off, S->acc.seq_off.p, (S->n_pairs + 1) * 8, hipMemcpyDeviceToHost));
+    if (packed && S->n_seq_bytes) HIP_TRY(c, hipMemcpy(packed, S->acc.seqs.p, S->n_seq_bytes, hipMemcpyDeviceToHost));
+    return INQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -861,6 +933,10 @@ int inq_call_span_deferred_names(inq_ctx_t *c, const inq_span_t *span, int slot,
     return guarded([&] { return call_span_impl(c, span, nullptr, stats, slot < 0 ? -1 : slot, true, true); });
 }
 
+int inq_call_span_deferred_seqs(inq_ctx_t *c, const inq_span_t *span, int slot, inq_span_stats_t *stats) {
+    return guarded([&] { return call_span_impl(c, span, nullptr, stats, slot < 0 ? -1 : slot, true, true, true); });
+}
+
 int inq_call_flush(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call) {
     return inq_call_flush_flags(c, result, n_loci, ms_call, nullptr);
 }
@@ -881,9 +957,14 @@ int inq_call_flush_reads(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, do
 
 int inq_call_flush_origins(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
                            inq_locus_evidence_t *evidence, uint64_t *kept_off, uint64_t *name_bytes) {
+    return inq_call_flush_seqs(c, result, n_loci, ms_call, locus_flags, evidence, kept_off, name_bytes, nullptr);
+}
+
+int inq_call_flush_seqs(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
+                        inq_locus_evidence_t *evidence, uint64_t *kept_off, uint64_t *name_bytes, uint64_t *seq_bytes) {
     return guarded([&] {
         if (!kept_off || !name_bytes) return (int)INQ_ERR_ARG;
-        return call_flush_impl(c, result, n_loci, ms_call, nullptr, HostExtras{locus_flags, evidence, kept_off, name_bytes});
+        return call_flush_impl(c, result, n_loci, ms_call, nullptr, HostExtras{locus_flags, evidence, kept_off, name_bytes, seq_bytes});
     });
 }
 
@@ -950,6 +1031,10 @@ int inq_span_fetch_batch(inq_ctx_t *c, uint32_t *cigar, inq_read_t *reads, uint3
 
 int inq_span_fetch_names(inq_ctx_t *c, uint64_t *name_off, uint8_t *names, uint64_t cap_bytes) {
     return guarded([&] { return fetch_names_impl(c, name_off, names, cap_bytes); });
+}
+
+int inq_span_fetch_seqs(inq_ctx_t *c, uint32_t *q_beg, uint32_t *n_bases, uint64_t *seq_off, uint8_t *packed, uint64_t cap_bytes) {
+    return guarded([&] { return fetch_seqs_impl(c, q_beg, n_bases, seq_off, packed, cap_bytes); });
 }
 
 }  // extern "C"

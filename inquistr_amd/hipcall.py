@@ -87,6 +87,12 @@ ABI_SYMBOLS = (
     "inq_read_origins_fetch",
     "inq_span_fetch_names",
     "inq_read_name_tile",
+    "inq_call_span_deferred_seqs",
+    "inq_call_flush_seqs",
+    "inq_read_seqs_fetch",
+    "inq_span_fetch_seqs",
+    "inq_seq_windows",
+    "inq_seq_window_tile",
 )
 
 
@@ -195,6 +201,23 @@ class ReadOriginC(C.Structure):
 ORIGIN_DTYPE = np.dtype([("pos", "<i4"), ("mapq", "u1"), ("bits", "u1"), ("name_len", "<u2")])
 
 
+class ReadSeqC(C.Structure):
+    """inq_read_seq_t"""
+
+    _fields_ = [("q_beg", C.c_uint32), ("n_bases", C.c_uint32)]
+
+
+SEQ_DTYPE = np.dtype([("q_beg", "<u4"), ("n_bases", "<u4")])
+SEQ_CODES = "=ACMGRSVTWYHKDBN"  # the BAM's 4-bit base codes
+
+
+def unpack_seq(packed, n_bases: int) -> str:
+    """The text of a packed slice (two bases to a byte, the first in the high nibble)."""
+    b = np.asarray(packed, dtype=np.uint8)
+    codes = np.stack((b >> 4, b & 15), axis=1).reshape(-1)[:n_bases]
+    return "".join(SEQ_CODES[c] for c in codes)
+
+
 def scan_bgzf(data) -> np.ndarray:
     """Walks the BGZF headers of `data` (whole blocks): the block table inq_bgzf_inflate / inq_call_span take
     (payload offset and length, ISIZE, dense output offsets)."""
@@ -229,8 +252,8 @@ class InqError(RuntimeError):
 
 
 _lib = None
-# the entries of a family: each takes the side outputs of the one before and its own (`_origins`: the flush family only)
-_SIDE_SUFFIXES = ("", "_flags", "_evidence", "_reads", "_origins")
+# the entries of a family: each takes the side outputs of the one before and its own (`_origins`, `_seqs`: the flush family only)
+_SIDE_SUFFIXES = ("", "_flags", "_evidence", "_reads", "_origins", "_seqs")
 
 
 def load(path: Optional[str] = None):
@@ -270,11 +293,12 @@ def load(path: Optional[str] = None):
     L.inq_ctx_destroy.restype = None
     L.inq_ctx_destroy.argtypes = [vp]
     # The three families of calls with per-locus side outputs: a member takes the family's arguments, then one pointer for each side
-    # output it adds (flags | evidence | kept_off, and kept for the device form | name_bytes), then - the device form - the stream.
+    # output it adds (flags | evidence | kept_off, and kept for the device form | name_bytes | seq_bytes), then - the device form - the
+    # stream.
     for family, head, widths, tail in (
         ("inq_call_batch", [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC)], (0, 1, 2, 3), []),
         ("inq_call_batch_device", [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC)], (0, 1, 2, 4), [vp]),
-        ("inq_call_flush", [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double)], (0, 1, 2, 3, 4), []),
+        ("inq_call_flush", [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double)], (0, 1, 2, 3, 4, 5), []),
     ):
         for suffix, n_side in zip(_SIDE_SUFFIXES, widths):
             fn = getattr(L, family + suffix)
@@ -292,6 +316,16 @@ def load(path: Optional[str] = None):
     L.inq_call_span_deferred_names.argtypes = [vp, C.POINTER(SpanC), C.c_int, C.POINTER(SpanStatsC)]
     L.inq_span_fetch_names.restype = C.c_int
     L.inq_span_fetch_names.argtypes = [vp, vp, vp, C.c_uint64]
+    L.inq_call_span_deferred_seqs.restype = C.c_int
+    L.inq_call_span_deferred_seqs.argtypes = [vp, C.POINTER(SpanC), C.c_int, C.POINTER(SpanStatsC)]
+    L.inq_read_seqs_fetch.restype = C.c_int
+    L.inq_read_seqs_fetch.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64]
+    L.inq_span_fetch_seqs.restype = C.c_int
+    L.inq_span_fetch_seqs.argtypes = [vp, vp, vp, vp, vp, C.c_uint64]
+    L.inq_seq_windows.restype = C.c_int
+    L.inq_seq_windows.argtypes = [vp, C.POINTER(InqBatchC), vp, vp, vp]
+    L.inq_seq_window_tile.restype = C.c_uint32
+    L.inq_seq_window_tile.argtypes = []
     L.inq_ctx_status.restype = C.c_int
     L.inq_ctx_status.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.inq_ctx_timing_enable.restype = C.c_int
@@ -409,21 +443,23 @@ class Context:
         raise InqError(rc, strerror(rc) + (f" [{detail}]" if detail and rc == -8 else ""))
 
     @staticmethod
-    def _side_arrays(n: int, flags: bool, evidence: bool, kept_off: bool, name_bytes: bool = False):
+    def _side_arrays(n: int, flags: bool, evidence: bool, kept_off: bool, name_bytes: bool = False, seq_bytes: bool = False):
         """The arrays of a call of n loci for the side outputs asked for (else None), every byte 0xFF: one the call did not write shows."""
         fl = np.full(max(n, 1), 0xFF, dtype=np.uint8) if flags else None
         ev = np.full(max(n, 1) * EVIDENCE_DTYPE.itemsize, 0xFF, dtype=np.uint8) if evidence else None
         off = np.full(n + 1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if kept_off else None
         nb = np.full(1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if name_bytes else None
-        return fl, ev, off, nb
+        sb = np.full(1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if seq_bytes else None
+        return fl, ev, off, nb, sb
 
     def _side_call(self, entry: str, head, n: int, width: int, check: bool, flags: bool = True, evidence: bool = True):
         """Calls `entry`, the member of its family that takes `width` side outputs, with `head` and the arrays of _side_arrays; raises on
         error if check.  Returns (code, flags, evidence, kept_off, records), each cut to the n loci, None where not taken; the records are
         fetched behind a successful call with the lists.  width 4 (a flush with origins) adds a sixth element: (origins, names,
-        name_bytes) fetched the same way, (None, None, name_bytes) after a failed call."""
-        fl, ev, off, nb = self._side_arrays(n, flags and width >= 1, evidence and width >= 2, width >= 3, width >= 4)
-        side = [None if a is None else a.ctypes.data for a in (fl, ev, off, nb)][:width]
+        name_bytes) fetched the same way, (None, None, name_bytes) after a failed call; width 5 (a flush with sequences) a seventh:
+        (seqs, packed, seq_bytes)."""
+        fl, ev, off, nb, sb = self._side_arrays(n, flags and width >= 1, evidence and width >= 2, width >= 3, width >= 4, width >= 5)
+        side = [None if a is None else a.ctypes.data for a in (fl, ev, off, nb, sb)][:width]
         rc = getattr(self._L, entry)(self._h, *head, *side)
         if rc != INQ_OK and check:
             self._raise(rc)
@@ -432,6 +468,9 @@ class Context:
         if nb is not None:
             who = self.read_origins_fetch(int(off[-1]), int(nb[0])) if rc == INQ_OK else (None, None)
             out += (who + (int(nb[0]),),)
+        if sb is not None:
+            what = self.read_seqs_fetch(int(off[-1]), int(sb[0])) if rc == INQ_OK else (None, None)
+            out += (what + (int(sb[0]),),)
         return out
 
     def _batch_call(self, entry: str, batch: Batch, debug: bool, width: int, check: bool, **which):
@@ -492,6 +531,35 @@ class Context:
     @property
     def read_name_tile(self) -> int:
         return int(self._L.inq_read_name_tile())
+
+    def read_seqs_fetch(self, n: int, seq_bytes: int, check: bool = True):
+        """inq_read_seqs_fetch: the first n records (SEQ_DTYPE) and the first seq_bytes packed bytes (uint8) of the last
+        call_flush_seqs; record k's (n_bases + 1) // 2 bytes begin at the sum of those in front of it (check=False: (code, seqs,
+        packed))."""
+        rec = np.full(max(n, 1) * SEQ_DTYPE.itemsize, 0xFF, dtype=np.uint8)
+        packed = np.full(max(seq_bytes, 1), 0xFF, dtype=np.uint8)
+        rc = self._L.inq_read_seqs_fetch(self._h, rec.ctypes.data, n, packed.ctypes.data, seq_bytes)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        got = (rec.view(SEQ_DTYPE)[:n], packed[:seq_bytes])
+        return got if check else (rc,) + got
+
+    @property
+    def seq_window_tile(self) -> int:
+        return int(self._L.inq_seq_window_tile())
+
+    def seq_windows(self, batch: Batch, l_seq=None, check: bool = True):
+        """inq_seq_windows: (q_beg, n_bases), u32 [n_pairs], of every pair of a host-buffer batch - the window walk alone; l_seq u32
+        [n_reads] cuts both, None = no cut (check=False: (code, q_beg, n_bases))."""
+        q = np.full(max(batch.n_pairs, 1), 0xFFFFFFFF, dtype=np.uint32)
+        nbs = np.full(max(batch.n_pairs, 1), 0xFFFFFFFF, dtype=np.uint32)
+        ls = None if l_seq is None else np.ascontiguousarray(l_seq, dtype=np.uint32)
+        bc = batch.as_c()
+        rc = self._L.inq_seq_windows(self._h, C.byref(bc), None if ls is None else ls.ctypes.data, q.ctypes.data, nbs.ctypes.data)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        got = (q[: batch.n_pairs], nbs[: batch.n_pairs])
+        return got if check else (rc,) + got
 
     def call_batch_reads(self, batch: Batch, debug: bool = False, check: bool = True, flags: bool = True, evidence: bool = True):
         """inq_call_batch_reads: (code, Result, per-locus flags or None, per-locus evidence or None, kept_off [n_loci + 1], the records
@@ -573,11 +641,11 @@ class Context:
 
     def call_span_deferred(self, comp, blocks, anchors, anchor_stop, locus_tid, locus_start, locus_end, minlen: int = 5, support: int = 3,
                            unphased: bool = False, check: bool = True, stage_slot: Optional[int] = None, prestaged: bool = False,
-                           names: bool = False):
+                           names: bool = False, seqs: bool = False):
         """inq_call_span_deferred: appends the span's batch to the deferred one; returns (code, stats).  Rows: call_flush().
         prestaged: the span already sits in stage_slot (span_stage_begin + span_stage_wait): it is not staged again.
         names: inq_call_span_deferred_names - the names of the span's placed records are gathered into the batch too (every span of
-        a batch, or none)."""
+        a batch, or none).  seqs: inq_call_span_deferred_seqs - names, and every pair's slice of SEQ over its locus window."""
         comp = np.frombuffer(comp, dtype=np.uint8)
         blocks = np.ascontiguousarray(blocks, dtype=BGZF_BLOCK_DTYPE)
         anchors = np.ascontiguousarray(anchors, dtype=np.uint64)
@@ -592,7 +660,8 @@ class Context:
         if stage_slot is not None and not prestaged:
             rc = self._L.inq_span_stage(self._h, C.byref(sp), stage_slot)
         if rc == INQ_OK:
-            entry = self._L.inq_call_span_deferred_names if names else self._L.inq_call_span_deferred
+            entry = (self._L.inq_call_span_deferred_seqs if seqs else
+                     self._L.inq_call_span_deferred_names if names else self._L.inq_call_span_deferred)
             rc = entry(self._h, C.byref(sp), -1 if stage_slot is None else stage_slot, C.byref(stats))
         if rc != INQ_OK and check:
             self._raise(rc)
@@ -607,14 +676,14 @@ class Context:
 
     def _flush_call(self, entry: str, width: int, check: bool):
         """(code, phase1, phase2, n_tie_loci, ms_call) of `entry` for every locus deferred since the last flush, then the first `width`
-        of flags, evidence, kept_off + records, origins + names + name_bytes."""
+        of flags, evidence, kept_off + records, origins + names + name_bytes, seqs + packed + seq_bytes."""
         n = self.deferred_loci
         p1 = np.full(n, np.nan)
         p2 = np.full(n, np.nan)
         res = InqResultC(p1.ctypes.data, p2.ctypes.data, None, None, 0)
         ms = C.c_double(0.0)
         rc, fl, ev, off, rec, *who = self._side_call(entry, (C.byref(res), n, C.byref(ms)), n, width, check)
-        return (rc, p1, p2, int(res.n_tie_loci), float(ms.value)) + (fl, ev, off, rec)[: width + (width >= 3)] + (who[0] if who else ())
+        return (rc, p1, p2, int(res.n_tie_loci), float(ms.value)) + (fl, ev, off, rec)[: width + (width >= 3)] + tuple(x for w in who for x in w)
 
     def call_flush(self, check: bool = True):
         """inq_call_flush: (code, phase1, phase2, n_tie_loci, ms_call) for every locus deferred since the last flush."""
@@ -637,6 +706,24 @@ class Context:
         """inq_call_flush_origins: as call_flush_reads, plus the origins of the records (ORIGIN_DTYPE, same order), their names back to
         back (uint8) and the names' total as the tenth to twelfth element (None, None, total after a failed call)."""
         return self._flush_call("inq_call_flush_origins", 4, check)
+
+    def call_flush_seqs(self, check: bool = True):
+        """inq_call_flush_seqs: as call_flush_origins, plus one SEQ_DTYPE record per kept record (same order), their packed slices
+        back to back (uint8) and the slices' total as the thirteenth to fifteenth element (None, None, total after a failed call)."""
+        return self._flush_call("inq_call_flush_seqs", 5, check)
+
+    def span_fetch_seqs(self, n_pairs: int, cap_bytes: int, check: bool = True):
+        """inq_span_fetch_seqs: (q_beg u32, n_bases u32, seq_off u64 [n_pairs + 1], packed uint8) of ALL pairs of the batch the last
+        flush ran on, n_pairs from the appended spans' stats; cap_bytes: room for the packed bytes.  check=False: (code, ...)."""
+        q = np.full(max(n_pairs, 1), 0xFFFFFFFF, dtype=np.uint32)
+        nbs = np.full(max(n_pairs, 1), 0xFFFFFFFF, dtype=np.uint32)
+        off = np.full(n_pairs + 1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+        packed = np.full(max(cap_bytes, 1), 0xFF, dtype=np.uint8)
+        rc = self._L.inq_span_fetch_seqs(self._h, q.ctypes.data, nbs.ctypes.data, off.ctypes.data, packed.ctypes.data, cap_bytes)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        got = (q[:n_pairs], nbs[:n_pairs], off, packed[: int(off[-1])] if rc == INQ_OK else packed[:0])
+        return got if check else (rc,) + got
 
     def span_fetch_names(self, n_reads: int, cap_bytes: Optional[int] = None, check: bool = True):
         """inq_span_fetch_names: (name_off u64 [n_reads + 1], names uint8) of ALL reads of the batch the last flush ran on, n_reads from

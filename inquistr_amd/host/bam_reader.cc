@@ -442,6 +442,8 @@ int BamFile::next(BamRec &rec, std::string *err) {
     rec.n_cigar = n_cigar;
     rec.name = b + 32;
     rec.name_len = l_read_name > 1 ? l_read_name - 1u : 0u;  // (without the terminator; l_read_name == 0: no byte of it is read)
+    rec.seq = b + off_seq;
+    rec.l_seq = l_seq;
     rec.cigar = reinterpret_cast<const uint32_t *>(b + off_cigar);  // block payload starts 4-aligned in buf_
     if ((off_cigar & 3) != 0) {  // read name length not a multiple of 4: take an aligned copy
         cg_.resize(n_cigar);

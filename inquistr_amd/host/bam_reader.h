@@ -127,6 +127,9 @@ struct BamRec {
     // QNAME: bytes [0, max(l_read_name, 1) - 1) of the name field, as they stand, into the reader's record buffer (the read table)
     const uint8_t *name = nullptr;
     uint32_t name_len = 0;
+    // SEQ as stored: l_seq bases, two 4-bit codes to a byte, (l_seq + 1) / 2 bytes into the reader's record buffer (the read-seqs file)
+    const uint8_t *seq = nullptr;
+    uint32_t l_seq = 0;
 };
 
 class BamFile {

@@ -292,6 +292,13 @@ struct ReadIdentities {
     std::vector<uint8_t> names;
 };
 
+// ... and the bases behind them, for the read-seqs file: [k] = the slice of each of target k's records (inq_read_seq_t), in the records'
+// order, and the packed slices back to back
+struct ReadSlices {
+    std::vector<inq_read_seq_t> seqs;
+    std::vector<uint8_t> packed;
+};
+
 // src[j] -> dst[index[j]]: rows and reports of a batch, a flush or a device part into their targets' places
 template <class T>
 inline void scatter(const T *src, const uint32_t *index, size_t n, T *dst) {
@@ -300,14 +307,18 @@ inline void scatter(const T *src, const uint32_t *index, size_t n, T *dst) {
 
 // The per-target reports of a call, beside its rows: the tie report (inq_call_args_t::ties_path), the evidence file (::evidence_path), the
 // read-calls file (inq_genotype_repeats_reads), the read table (inq_genotype_repeats_table; it needs the read-calls lists, which are
-// then collected with it).  One value at every layer; a further report is one more member of each of the three
+// then collected with it), the read-seqs file (inq_genotype_repeats_seqs; its lines name the reads: the table's lists are collected
+// with it).  One value at every layer; a further report is one more member of each of the three
 // structs, a line in begin / scatter_from, a row in write_rows' table and a pointer in BatchRows::call / flush.
 struct ReportSet {  // which of them are collected: what is not adds nothing to the launch sequence
-    bool ties = false, evidence = false, read_calls = false, read_table = false;
+    bool ties = false, evidence = false, read_calls = false, read_table = false, read_seqs = false;
 };
 struct ReportFds {  // where a text call writes them, in the .inq's row order (-1: no file)
-    int ties = -1, evidence = -1, read_calls = -1, read_table = -1;
-    ReportSet wanted() const { return ReportSet{ties >= 0, evidence >= 0, read_calls >= 0 || read_table >= 0, read_table >= 0}; }
+    int ties = -1, evidence = -1, read_calls = -1, read_table = -1, read_seqs = -1;
+    ReportSet wanted() const {
+        const bool who = read_table >= 0 || read_seqs >= 0;
+        return ReportSet{ties >= 0, evidence >= 0, read_calls >= 0 || who, who, read_seqs >= 0};
+    }
 };
 // ... of a set of targets (a call's, a device part's, one device call's loci): [k] belongs to target k of the set.  A target no batch or
 // span holds keeps what begin put there: no flag, zeros, an empty list.
@@ -317,12 +328,14 @@ struct TargetReports {
     std::vector<inq_locus_evidence_t> evidence;
     ReadCallLists read_calls;                    // the records of the target's kept reads in file order
     std::vector<ReadIdentities> read_table;      // ... and who each of them is
+    std::vector<ReadSlices> read_seqs;           // ... and the bases behind each Call
     void begin(size_t n, ReportSet which) {
         has = which;
         ties.assign(which.ties ? n : 0, 0);
         evidence.assign(which.evidence ? n : 0, inq_locus_evidence_t{});
         read_calls.assign(which.read_calls ? n : 0, std::vector<inq_read_call_t>());
         read_table.assign(which.read_table ? n : 0, ReadIdentities());
+        read_seqs.assign(which.read_seqs ? n : 0, ReadSlices());
     }
     // what part collected (nothing this one does not), part's k-th -> target idx[k]; the lists are moved out of part
     void scatter_from(TargetReports &part, const uint32_t *idx, size_t n) {
@@ -332,6 +345,8 @@ struct TargetReports {
             for (size_t k = 0; k < n; ++k) read_calls[idx[k]] = std::move(part.read_calls[k]);
         if (part.has.read_table)
             for (size_t k = 0; k < n; ++k) read_table[idx[k]] = std::move(part.read_table[k]);
+        if (part.has.read_seqs)
+            for (size_t k = 0; k < n; ++k) read_seqs[idx[k]] = std::move(part.read_seqs[k]);
     }
 };
 
@@ -370,21 +385,22 @@ struct ReportFile {
     int open(const char *path, const char *what, std::string &msg);
 };
 constexpr const char *kTiesWhat = "the tie report", *kEvidenceWhat = "the evidence file", *kReadCallsWhat = "the read-calls file",
-                      *kReadTableWhat = "the read table";
+                      *kReadTableWhat = "the read table", *kReadSeqsWhat = "the read-seqs file";
 // the paths of the files that are no field of inq_call_args_t (it does not grow): what the widest entry of the family takes
 struct ReportPaths {
-    const char *read_calls = nullptr, *read_table = nullptr;
+    const char *read_calls = nullptr, *read_table = nullptr, *read_seqs = nullptr;
 };
-// the files of a text call (inq_call_args_t::ties_path, ::evidence_path; `more` of inq_genotype_repeats_table, else nulls)
+// the files of a text call (inq_call_args_t::ties_path, ::evidence_path; `more` of inq_genotype_repeats_seqs, else nulls)
 struct CallReports {
-    ReportFile ties, evidence, read_calls, read_table;
+    ReportFile ties, evidence, read_calls, read_table, read_seqs;
     int open(const inq_call_args_t &a, const ReportPaths &more, std::string &msg) {
         int rc = ties.open(a.ties_path, kTiesWhat, msg);
         if (rc == INQ_EXIT_OK) rc = evidence.open(a.evidence_path, kEvidenceWhat, msg);
         if (rc == INQ_EXIT_OK) rc = read_calls.open(more.read_calls, kReadCallsWhat, msg);
-        return rc != INQ_EXIT_OK ? rc : read_table.open(more.read_table, kReadTableWhat, msg);
+        if (rc == INQ_EXIT_OK) rc = read_table.open(more.read_table, kReadTableWhat, msg);
+        return rc != INQ_EXIT_OK ? rc : read_seqs.open(more.read_seqs, kReadSeqsWhat, msg);
     }
-    ReportFds fds() const { return ReportFds{ties.fd, evidence.fd, read_calls.fd, read_table.fd}; }
+    ReportFds fds() const { return ReportFds{ties.fd, evidence.fd, read_calls.fd, read_table.fd, read_seqs.fd}; }
     void to(SessionHooks &hooks) const { hooks.report_fds = fds(); }
 };
 // an entry that returns rows or keeps its context for many files writes no evidence file and says so (INQ_EXIT_ERROR) instead of
@@ -421,6 +437,8 @@ struct BatchRows {
     std::vector<inq_read_call_t> bc;  // ... and the records, fetched behind the call
     std::vector<inq_read_origin_t> bo;  // the read table: the records' origins ...
     std::vector<uint8_t> bn;            // ... and names, fetched with them (a flush) or looked up in the batch the host owns (a call)
+    std::vector<inq_read_seq_t> bs;     // the read-seqs file: the records' slices ...
+    std::vector<uint8_t> bp;            // ... and their packed bases, fetched (a flush) or cut out of the batch's SEQ (a call)
     void begin(size_t n, ReportSet which) {
         b1.assign(n, NAN), b2.assign(n, NAN);
         std::memset(&res, 0, sizeof res);
@@ -450,6 +468,20 @@ struct BatchRows {
             bn.insert(bn.end(), owner->names.begin() + at, owner->names.begin() + at + len);
         }
         cut_read_table();
+        if (!rep.has.read_seqs) return INQ_OK;
+        // the slices: record k of locus j is read bc[k].read under j's window, cut out of the SEQ the sweep kept (inq_host_seq_window)
+        if (owner->seq_off.size() != owner->reads.size() + 1 || owner->l_seq.size() != owner->reads.size()) return INQ_ERR_ARG;
+        bs.resize(bc.size());
+        bp.clear();
+        for (size_t j = 0; j + 1 < bk.size(); ++j)
+            for (uint64_t k = bk[j]; k < bk[j + 1]; ++k) {
+                const uint32_t r = bc[k].read;
+                const inq_read_t &rd = owner->reads[r];
+                seq_window(owner->cigar.data() + (size_t)rd.cigar_off4 * 4, rd.n_cigar, rd.pos, owner->l_seq[r], batch.locus_start[j],
+                           batch.locus_end[j], &bs[k].q_beg, &bs[k].n_bases);
+                pack_seq_slice(owner->seqs.data() + owner->seq_off[r], bs[k].q_beg, bs[k].n_bases, bp);
+            }
+        cut_read_seqs();
         return INQ_OK;
     }
     int flush(inq_ctx_t *ctx, uint64_t n, double *ms_call) {
@@ -457,14 +489,30 @@ struct BatchRows {
             const int rc = inq_call_flush_reads(ctx, &res, n, ms_call, flags(), evidence(), kept_off());
             return rc != INQ_OK ? rc : fetch_read_calls(ctx);
         }
-        uint64_t name_bytes = 0;
-        int rc = inq_call_flush_origins(ctx, &res, n, ms_call, flags(), evidence(), kept_off(), &name_bytes);
+        uint64_t name_bytes = 0, seq_bytes = 0;
+        int rc = inq_call_flush_seqs(ctx, &res, n, ms_call, flags(), evidence(), kept_off(), &name_bytes, rep.has.read_seqs ? &seq_bytes : nullptr);
         if (rc == INQ_OK) rc = fetch_read_calls(ctx);
         if (rc != INQ_OK) return rc;
         bo.resize(bc.size()), bn.resize(name_bytes);
         if ((rc = inq_read_origins_fetch(ctx, bo.data(), bo.size(), bn.data(), bn.size())) != INQ_OK) return rc;
         cut_read_table();
+        if (!rep.has.read_seqs) return INQ_OK;
+        bs.resize(bc.size()), bp.resize(seq_bytes);
+        if ((rc = inq_read_seqs_fetch(ctx, bs.data(), bs.size(), bp.data(), bp.size())) != INQ_OK) return rc;
+        cut_read_seqs();
         return INQ_OK;
+    }
+    // bs / bp, in the records' order, cut into the loci's shares
+    void cut_read_seqs() {
+        size_t at = 0;
+        for (size_t j = 0; j + 1 < bk.size(); ++j) {
+            ReadSlices &t = rep.read_seqs[j];
+            t.seqs.assign(bs.begin() + bk[j], bs.begin() + bk[j + 1]);
+            size_t bytes = 0;
+            for (const inq_read_seq_t &q : t.seqs) bytes += ((size_t)q.n_bases + 1) / 2;
+            t.packed.assign(bp.begin() + at, bp.begin() + at + bytes);
+            at += bytes;
+        }
     }
     // bo / bn, in the records' order, cut into the loci's shares
     void cut_read_table() {
@@ -519,7 +567,7 @@ int write_report(const std::vector<uint32_t> &order, const std::string &header, 
 // the tie report: `chrom\tbegin\tend\n` for every target order[k] with a flag set (no header)
 int write_ties(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const uint8_t *ties, int fd, char *errbuf,
                size_t errcap);
-// inq_genotype_repeats with the read-calls file and the read table (null: none), for inq_genotype_repeats_table
+// inq_genotype_repeats with the read-calls file, the read table and the read-seqs file (null: none), for inq_genotype_repeats_seqs
 int genotype_single(const inq_call_args_t *args, int out_fd, const ReportPaths &more, char *errbuf, size_t errcap);
 int partition_prepared(Prepared &P, uint64_t world, uint32_t *order, uint64_t *cuts);
 

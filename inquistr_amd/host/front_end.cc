@@ -17,6 +17,9 @@ void HostBatch::clear() {
     locus_index.clear();
     names.clear();
     name_off.clear();
+    seqs.clear();
+    seq_off.clear();
+    l_seq.clear();
 }
 
 void HostBatch::view(inq_batch_t *b, uint32_t minlen, uint32_t support, bool unphased) const {
@@ -62,6 +65,9 @@ bool FrontEnd::begin_group(std::string *err) {
     reads_.clear();
     names_.clear();
     name_off_.assign(keep_names_ ? 1 : 0, 0);
+    seqs_.clear();
+    l_seq_.clear();
+    seq_off_.assign(keep_seqs_ ? 1 : 0, 0);
     lo_ = 0;
     flushed_ = 0;
     group_eof_ = false;
@@ -127,6 +133,11 @@ int FrontEnd::add_read(const BamRec &r, bool has_clip, std::string *err, bool *p
         names_.insert(names_.end(), r.name, r.name + r.name_len);
         name_off_.push_back(names_.size());
     }
+    if (keep_seqs_) {
+        seqs_.insert(seqs_.end(), r.seq, r.seq + ((size_t)r.l_seq + 1) / 2);
+        seq_off_.push_back(seqs_.size());
+        l_seq_.push_back(r.l_seq);
+    }
     return (int)reads_.size() - 1;
 }
 
@@ -159,10 +170,16 @@ void FrontEnd::emit(size_t from, size_t to, HostBatch &out) {
             names_.clear();
             name_off_.assign(1, 0);
         }
+        if (keep_seqs_) {
+            out.seqs.swap(seqs_), out.seq_off.swap(seq_off_), out.l_seq.swap(l_seq_);
+            seqs_.clear(), l_seq_.clear();
+            seq_off_.assign(1, 0);
+        }
         edges_.clear();
     } else {
         remap.assign(reads_.size(), 0xffffffffu);
         if (keep_names_) out.name_off.assign(1, 0);
+        if (keep_seqs_) out.seq_off.assign(1, 0);
         for (const Edge &e : edges_) {
             if (e.locus < from || e.locus >= to) continue;
             if (remap[e.read] == 0xffffffffu) {
@@ -177,6 +194,7 @@ void FrontEnd::emit(size_t from, size_t to, HostBatch &out) {
                     out.names.insert(out.names.end(), names_.begin() + name_off_[e.read], names_.begin() + name_off_[e.read + 1]);
                     out.name_off.push_back(out.names.size());
                 }
+                if (keep_seqs_) copy_seq(e.read, out.seqs, out.seq_off, out.l_seq);
             }
             out.pair_read[bucket_[e.locus - from]++] = remap[e.read];
         }
@@ -195,6 +213,9 @@ void FrontEnd::compact(size_t keep_from) {
     std::vector<inq_read_t> nreads;
     std::vector<uint8_t> nnames;
     std::vector<uint64_t> nname_off(keep_names_ ? 1 : 0, 0);
+    std::vector<uint8_t> nseqs;
+    std::vector<uint64_t> nseq_off(keep_seqs_ ? 1 : 0, 0);
+    std::vector<uint32_t> nl_seq;
     size_t w = 0;
     for (const Edge &e0 : edges_) {
         if (e0.locus < keep_from) continue;
@@ -211,6 +232,7 @@ void FrontEnd::compact(size_t keep_from) {
                 nnames.insert(nnames.end(), names_.begin() + name_off_[e.read], names_.begin() + name_off_[e.read + 1]);
                 nname_off.push_back(nnames.size());
             }
+            if (keep_seqs_) copy_seq(e.read, nseqs, nseq_off, nl_seq);
         }
         e.read = remap[e.read];
         edges_[w++] = e;
@@ -220,6 +242,7 @@ void FrontEnd::compact(size_t keep_from) {
     reads_.swap(nreads);
     names_.swap(nnames);
     name_off_.swap(nname_off);
+    seqs_.swap(nseqs), seq_off_.swap(nseq_off), l_seq_.swap(nl_seq);
 }
 
 int FrontEnd::next(HostBatch &out, std::string *err, bool *panic) {

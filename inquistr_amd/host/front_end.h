@@ -27,6 +27,11 @@ struct HostBatch {
     // the names of the reads back to back, name_off[n_reads + 1]; both empty unless the front end keeps names (the read table)
     std::vector<uint8_t> names;
     std::vector<uint64_t> name_off;
+    // their SEQ as the BAM stores it back to back, seq_off[n_reads + 1] and l_seq[n_reads]; empty unless the front end keeps
+    // sequences (the read-seqs file)
+    std::vector<uint8_t> seqs;
+    std::vector<uint64_t> seq_off;
+    std::vector<uint32_t> l_seq;
     void clear();
     void view(inq_batch_t *b, uint32_t minlen, uint32_t support, bool unphased) const;
 };
@@ -36,6 +41,7 @@ public:
     FrontEnd(BamFile &bam, const std::vector<RepeatInterval> &targets, bool unphased);
     void set_max_batch_words(uint64_t w) { max_words_ = w ? w : max_words_; }
     void set_keep_names(bool on) { keep_names_ = on; }  // before the first next(): every batch then carries its reads' names
+    void set_keep_seqs(bool on) { keep_seqs_ = on; }    // ... and their packed SEQ
     // 1 = batch produced, 0 = done, -1 = error (err = message; panic = reference would panic)
     int next(HostBatch &out, std::string *err, bool *panic);
 
@@ -67,6 +73,16 @@ private:
     bool keep_names_ = false;
     std::vector<uint8_t> names_;      // keep_names_: the names of reads_ back to back ...
     std::vector<uint64_t> name_off_;  // ... and where each begins, [reads_.size() + 1]
+    bool keep_seqs_ = false;
+    std::vector<uint8_t> seqs_;       // keep_seqs_: the packed SEQ of reads_ back to back,
+    std::vector<uint64_t> seq_off_;   // where each begins, [reads_.size() + 1],
+    std::vector<uint32_t> l_seq_;     // and its bases
+    // read `r` of the store's SEQ appended to a batch's (or the compacted store's) three arrays
+    void copy_seq(size_t r, std::vector<uint8_t> &seqs, std::vector<uint64_t> &seq_off, std::vector<uint32_t> &l_seq) const {
+        seqs.insert(seqs.end(), seqs_.begin() + seq_off_[r], seqs_.begin() + seq_off_[r + 1]);
+        seq_off.push_back(seqs.size());
+        l_seq.push_back(l_seq_[r]);
+    }
     // (locus of the group, read of the store) in file order; grouped by locus (stable) when a batch is emitted
     struct Edge {
         uint32_t locus, read;

@@ -8,8 +8,8 @@
 namespace inqhost {
 
 ParallelFrontEnd::ParallelFrontEnd(const std::string &bam_path, BamFile &hdr, const std::vector<RepeatInterval> &targets, bool unphased,
-                 int n_workers, uint64_t max_words, bool keep_names)
-    : path_(bam_path), targets_(targets), unphased_(unphased), max_words_(max_words), keep_names_(keep_names) {
+                 int n_workers, uint64_t max_words, bool keep_names, bool keep_seqs)
+    : path_(bam_path), targets_(targets), unphased_(unphased), max_words_(max_words), keep_names_(keep_names), keep_seqs_(keep_seqs) {
     std::vector<uint32_t> order(targets.size());
     for (uint32_t i = 0; i < order.size(); ++i) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
@@ -40,6 +40,7 @@ void ParallelFrontEnd::work() {
         FrontEnd fe(bam, sub, unphased_);
         if (max_words_) fe.set_max_batch_words(max_words_);
         fe.set_keep_names(keep_names_);
+        fe.set_keep_seqs(keep_seqs_);
         for (;;) {
             Item it;
             {

@@ -24,7 +24,7 @@ public:
         std::vector<uint32_t> index;  // position of each batch locus in the full target list
     };
     ParallelFrontEnd(const std::string &bam_path, BamFile &hdr, const std::vector<RepeatInterval> &targets, bool unphased,
-                     int n_workers, uint64_t max_words = 0, bool keep_names = false);
+                     int n_workers, uint64_t max_words = 0, bool keep_names = false, bool keep_seqs = false);
     ~ParallelFrontEnd() {
         {
             std::lock_guard<std::mutex> g(mu_);
@@ -63,6 +63,7 @@ private:
     bool unphased_;
     uint64_t max_words_ = 0;
     bool keep_names_ = false;  // every batch carries its reads' names (FrontEnd::set_keep_names)
+    bool keep_seqs_ = false;   // ... and their packed SEQ (FrontEnd::set_keep_seqs)
     std::vector<std::vector<uint32_t>> slices_;
     std::atomic<size_t> next_slice_{0};
     std::vector<std::thread> pool_;

@@ -15,7 +15,7 @@
 namespace inq {
 
 struct HostApi {
-    decltype(&::inq_genotype_repeats_table) genotype_repeats_table;  // (inq_genotype_repeats, _devices and _reads are its forms)
+    decltype(&::inq_genotype_repeats_seqs) genotype_repeats_seqs;  // (inq_genotype_repeats, _devices, _reads and _table are its forms)
     decltype(&::inq_host_ctx_option) ctx_option;
     decltype(&::inq_combine) combine;
     decltype(&::inq_outlier) outlier;
@@ -53,7 +53,7 @@ inline const HostApi &host_api() {
             }
             return p;
         };
-        a.genotype_repeats_table = reinterpret_cast<decltype(a.genotype_repeats_table)>(sym("inq_genotype_repeats_table"));
+        a.genotype_repeats_seqs = reinterpret_cast<decltype(a.genotype_repeats_seqs)>(sym("inq_genotype_repeats_seqs"));
         a.ctx_option = reinterpret_cast<decltype(a.ctx_option)>(sym("inq_host_ctx_option"));
         a.combine = reinterpret_cast<decltype(a.combine)>(sym("inq_combine"));
         a.outlier = reinterpret_cast<decltype(a.outlier)>(sym("inq_outlier"));

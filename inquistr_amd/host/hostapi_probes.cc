@@ -46,6 +46,25 @@ size_t inq_host_format_read_table_rows(const char *chrom, uint32_t start, uint32
     }
     return s.size();
 }
+size_t inq_host_format_read_seq_rows(const char *chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
+                                     const inq_read_origin_t *origins, const uint8_t *names, const inq_read_seq_t *seqs, const uint8_t *packed,
+                                     size_t n, int unphased, char *buf, size_t cap) {
+    if (!chrom || (n && (!calls || !origins || !seqs))) return 0;
+    std::string s;
+    append_read_seq_rows(s, chrom, start, end, calls, origins, names, seqs, packed, n, unphased != 0);
+    if (cap) {
+        const size_t m = std::min(s.size(), cap - 1);
+        std::memcpy(buf, s.data(), m);
+        buf[m] = 0;
+    }
+    return s.size();
+}
+int inq_host_seq_window(const uint32_t *cigar, uint32_t n_cigar, int32_t pos, uint32_t l_seq, uint32_t start, uint32_t end, uint32_t *q_beg,
+                        uint32_t *n_bases) {
+    if ((n_cigar && !cigar) || !q_beg || !n_bases) return 1;
+    seq_window(cigar, n_cigar, pos, l_seq, start, end, q_beg, n_bases);
+    return 0;
+}
 size_t inq_host_sample_name(const char *p, char *buf, size_t cap) {
     return (size_t)std::snprintf(buf, cap, "%s", sample_name_from_path(p).c_str());
 }

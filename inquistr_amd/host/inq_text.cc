@@ -195,8 +195,11 @@ void append_read_calls_row(std::string &out, const std::string &chrom, uint32_t 
 
 const char *const kReadTableHeader = "chrom\tbegin\tend\tgroup\tcall\tkind\tread\tpos\tstrand\tmapq";
 
-void append_read_table_rows(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
-                            const inq_read_origin_t *origins, const uint8_t *names, size_t n, bool unphased) {
+// The lines of one target that name its kept reads, in the order of the read-calls lists: columns chrom .. read, then what `tail`
+// appends for record k (it begins with its own tab), then the newline
+template <class Tail>
+static void append_read_lines(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
+                              const inq_read_origin_t *origins, const uint8_t *names, size_t n, bool unphased, Tail tail) {
     if (!n) return;
     std::vector<const inq_read_call_t *> g[3];
     split_read_calls(calls, n, unphased, g);
@@ -214,10 +217,77 @@ void append_read_table_rows(std::string &out, const std::string &chrom, uint32_t
             const size_t len = o.name_len ? ::strnlen(name, o.name_len) : 0;  // cut at the first NUL
             if (len) out.append(name, len);
             else out += '*';
-            out += '\t', out += std::to_string((int64_t)o.pos + 1);  // SAM POS
-            out += (o.bits & INQ_READ_REVERSE) ? "\t-\t" : "\t+\t";
-            out += std::to_string((unsigned)o.mapq), out += '\n';
+            tail(out, k);
+            out += '\n';
         }
+}
+
+void append_read_table_rows(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
+                            const inq_read_origin_t *origins, const uint8_t *names, size_t n, bool unphased) {
+    append_read_lines(out, chrom, start, end, calls, origins, names, n, unphased, [origins](std::string &o_, size_t k) {
+        const inq_read_origin_t &o = origins[k];
+        o_ += '\t', o_ += std::to_string((int64_t)o.pos + 1);  // SAM POS
+        o_ += (o.bits & INQ_READ_REVERSE) ? "\t-\t" : "\t+\t";
+        o_ += std::to_string((unsigned)o.mapq);
+    });
+}
+
+const char *const kReadSeqsHeader = "chrom\tbegin\tend\tgroup\tcall\tkind\tread\tqbeg\tlen\tseq";
+
+void append_read_seq_rows(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
+                          const inq_read_origin_t *origins, const uint8_t *names, const inq_read_seq_t *seqs, const uint8_t *packed, size_t n,
+                          bool unphased) {
+    std::vector<size_t> seq_at(n + 1, 0);  // where record k's packed slice begins
+    for (size_t k = 0; k < n; ++k) seq_at[k + 1] = seq_at[k] + ((size_t)seqs[k].n_bases + 1) / 2;
+    append_read_lines(out, chrom, start, end, calls, origins, names, n, unphased, [&](std::string &o_, size_t k) {
+        static const char kCodes[] = "=ACMGRSVTWYHKDBN";  // the BAM's 4-bit codes
+        const inq_read_seq_t &q = seqs[k];
+        o_ += '\t', o_ += std::to_string(q.q_beg), o_ += '\t', o_ += std::to_string(q.n_bases), o_ += '\t';
+        if (!q.n_bases) o_ += '*';
+        const uint8_t *b = packed + seq_at[k];
+        for (uint32_t i = 0; i < q.n_bases; ++i) o_ += kCodes[(b[i >> 1] >> ((~i & 1u) * 4u)) & 15u];
+    });
+}
+
+void seq_window(const uint32_t *cigar, uint32_t n_cigar, int32_t pos, uint32_t l_seq, uint32_t start, uint32_t end, uint32_t *q_beg,
+                   uint32_t *n_bases) {
+    *q_beg = *n_bases = 0;
+    const uint32_t se = start - 10u, ee = end + 10u;  // u32, as the locus kernels build the window
+    if ((int64_t)ee - 1 <= (int64_t)se) return;       // width 0 (empty or wrapped), and start = 9
+    const int64_t x[2] = {(int64_t)se, (int64_t)ee - 1};
+    uint64_t q[2] = {0, 0}, query = 0;  // query: the cursor in front of the op
+    bool past[2] = {false, false};
+    int64_t r = pos;
+    // one op at a time, as call_from_cigar walks: Q(x) is the query cursor when the reference cursor reaches x, or - x lying inside an
+    // M - that many bases into it; an insertion or clip AT x (r_op == x) lies behind it
+    for (uint32_t i = 0; i < n_cigar; ++i) {
+        const uint32_t op = cigar[i] & 15u;
+        const uint64_t len = cigar[i] >> 4;
+        const bool in_query = op == 0 || op == 1 || op == 4 || op == 7 || op == 8, in_ref = op == 0 || op == 2 || op == 3 || op == 7 || op == 8;
+        for (int w = 0; w < 2; ++w) {
+            if (past[w]) continue;
+            if (r >= x[w]) {  // the cursor has reached x in front of this op: nothing from here on lies in front of x
+                q[w] = query, past[w] = true;
+            } else if (in_ref && in_query && r + (int64_t)len > x[w]) {
+                q[w] = query + (uint64_t)(x[w] - r), past[w] = true;
+            }
+        }
+        if (past[0] && past[1]) break;
+        if (in_query) query += len;
+        if (in_ref) r += (int64_t)len;
+    }
+    for (int w = 0; w < 2; ++w) {
+        if (!past[w]) q[w] = query;  // the read ends in front of x: all of it
+        if (q[w] > l_seq) q[w] = l_seq;
+    }
+    *q_beg = (uint32_t)q[0];
+    *n_bases = (uint32_t)(q[1] - q[0]);
+}
+
+void pack_seq_slice(const uint8_t *seq, uint32_t q_beg, uint32_t n_bases, std::vector<uint8_t> &out) {
+    auto base = [&](uint32_t k) -> uint8_t { return (seq[k >> 1] >> ((~k & 1u) * 4u)) & 15u; };
+    for (uint32_t i = 0; i < n_bases; i += 2)
+        out.push_back((uint8_t)(base(q_beg + i) << 4 | (i + 1 < n_bases ? base(q_beg + i + 1) : 0)));
 }
 
 static void erase_all(std::string &s, const std::string &pat) {

@@ -36,6 +36,18 @@ void append_read_calls_row(std::string &out, const std::string &chrom, uint32_t 
 extern const char *const kReadTableHeader;
 void append_read_table_rows(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
                             const inq_read_origin_t *origins, const uint8_t *names, size_t n, bool unphased);
+// the read-seqs file (inq_genotype_repeats_seqs; not a reference output): its header, and the lines of one target - those of the read
+// table in columns chrom .. read, then qbeg, len and the bases of the read's SEQ over the locus window (inq_read_seq_t of
+// include/inquistr_hip.h: seqs in the records' order, their packed slices back to back, (n_bases + 1) / 2 bytes each); `*` for an empty one
+extern const char *const kReadSeqsHeader;
+void append_read_seq_rows(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
+                          const inq_read_origin_t *origins, const uint8_t *names, const inq_read_seq_t *seqs, const uint8_t *packed, size_t n,
+                          bool unphased);
+// The slice contract of inq_read_seq_t as a plain sequential CIGAR walk: what the host sweep cuts with (inq_host_seq_window)
+void seq_window(const uint32_t *cigar, uint32_t n_cigar, int32_t pos, uint32_t l_seq, uint32_t start, uint32_t end, uint32_t *q_beg,
+                uint32_t *n_bases);
+// bases [q_beg, q_beg + n_bases) of a BAM SEQ field appended to out, packed from the high nibble of a fresh byte on
+void pack_seq_slice(const uint8_t *seq, uint32_t q_beg, uint32_t n_bases, std::vector<uint8_t> &out);
 // src/call.rs:91-100: file_stem, then every ".bam" and ".cram" removed
 std::string sample_name_from_path(const std::string &bam_path);
 // [3P] human_sort::compare as used by Genotype::cmp (src/call.rs:33-38): <0, 0, >0

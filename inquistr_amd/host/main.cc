@@ -33,6 +33,7 @@ static void usage(FILE *f) {
         "      --evidence <FILE>            write the read evidence behind every row there: fetched, kept, h1, h2, clipped, min, max\n"
         "      --read-calls <FILE>          write the per-read Calls behind every row's two medians there: h1, h2, other\n"
         "      --read-table <FILE>          write one line per kept read there: group, call, kind, read name, pos, strand, mapq\n"
+        "      --read-seqs <FILE>           write one line per kept read there: group, call, kind, read name, and the read's bases over the locus\n"
         "  -h, --help                       Print help\n",
         f);
 }
@@ -145,6 +146,10 @@ int main(int argc, char **argv) {
                 std::fputs("error: '--read-table <FILE>' cannot be used with cohort: a session does not write the read table\n", stderr);
                 return 2;
             }
+            else if (k == "--read-seqs") {  // (likewise)
+                std::fputs("error: '--read-seqs <FILE>' cannot be used with cohort: a session does not write the read-seqs file\n", stderr);
+                return 2;
+            }
             else if (k.size() > 1 && k[0] == '-') {
                 std::fprintf(stderr, "error: unexpected argument '%s' found\n", k.c_str());
                 return 2;
@@ -239,6 +244,7 @@ int main(int argc, char **argv) {
     std::string bam;
     const char *read_calls_path = nullptr;  // --read-calls (not a field of inq_call_args_t: inq_genotype_repeats_table takes it)
     const char *read_table_path = nullptr;  // --read-table (likewise)
+    const char *read_seqs_path = nullptr;   // --read-seqs (likewise: inq_genotype_repeats_seqs)
     std::vector<int32_t> devices;  // --devices: one part of the targets per entry (an ordinal may repeat: N parts on one GPU)
     std::vector<std::pair<std::string, long long>> ctx_options;  // --ctx-option key=value
     auto num = [&](const char *s, const char *flag) -> unsigned long long {
@@ -273,6 +279,7 @@ int main(int argc, char **argv) {
         else if (key == "--evidence") a.evidence_path = val();
         else if (key == "--read-calls") read_calls_path = val();
         else if (key == "--read-table") read_table_path = val();
+        else if (key == "--read-seqs") read_seqs_path = val();
         else if (key == "--devices") {
             const std::string list = val();
             for (size_t b = 0; b <= list.size();) {
@@ -318,8 +325,8 @@ int main(int argc, char **argv) {
         char err[1024] = {0};
         ::setenv("INQ_FAST_EXIT", "1", 0);
         std::vector<inq_part_stats_t> st(devices.size());
-        int rc = inq::host_api().genotype_repeats_table(&a, devices.data(), devices.size(), 1 /* stdout */, read_calls_path, read_table_path, st.data(),
-                                                        err, sizeof err);
+        int rc = inq::host_api().genotype_repeats_seqs(&a, devices.data(), devices.size(), 1 /* stdout */, read_calls_path, read_table_path,
+                                                       read_seqs_path, st.data(), err, sizeof err);
         complain(rc, err);
         if (std::getenv("INQ_TIMING"))
             for (size_t r = 0; r < st.size(); ++r)
@@ -343,6 +350,10 @@ int main(int argc, char **argv) {
         }
         if (read_table_path) {  // ... and no read table
             std::fputs("error: '--read-table <FILE>' cannot be used with INQ_SERVER set: a server does not write the read table\n", stderr);
+            return 2;
+        }
+        if (read_seqs_path) {  // ... and no read-seqs file
+            std::fputs("error: '--read-seqs <FILE>' cannot be used with INQ_SERVER set: a server does not write the read-seqs file\n", stderr);
             return 2;
         }
         // INQ_SERVER=auto: this user's server for the device, started (detached; it leaves after INQ_SERVER_IDLE seconds without a
@@ -374,6 +385,7 @@ int main(int argc, char **argv) {
     }
     char err[1024] = {0};
     ::setenv("INQ_FAST_EXIT", "1", 0);  // this process ends with the call: see leave()
-    return leave(inq::host_api().genotype_repeats_table(&a, nullptr, 0, 1 /* stdout */, read_calls_path, read_table_path, nullptr, err, sizeof err),
+    return leave(inq::host_api().genotype_repeats_seqs(&a, nullptr, 0, 1 /* stdout */, read_calls_path, read_table_path, read_seqs_path, nullptr, err,
+                                                       sizeof err),
                  err);
 }

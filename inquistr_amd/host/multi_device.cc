@@ -148,15 +148,20 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
                       RowReports{&reports, files.fds(), args->unphased != 0});
 }
 
-static int genotype_table_impl(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const ReportPaths &more,
+static int genotype_seqs_impl(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const ReportPaths &more,
                                inq_part_stats_t *stats, char *errbuf, size_t errcap) {
     if (n_devices == 0) return genotype_single(args, out_fd, more, errbuf, errcap);
     return genotype_devices_impl(args, device_ids, n_devices, out_fd, stats, errbuf, errcap, more);
 }
+int inq_genotype_repeats_seqs(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,
+                              const char *read_table_path, const char *read_seqs_path, inq_part_stats_t *stats, char *errbuf, size_t errcap) {
+    INQ_GUARD(genotype_seqs_impl(args, device_ids, n_devices, out_fd, ReportPaths{read_calls_path, read_table_path, read_seqs_path}, stats,
+                                 errbuf, errcap),
+              errbuf, errcap)
+}
 int inq_genotype_repeats_table(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,
                                const char *read_table_path, inq_part_stats_t *stats, char *errbuf, size_t errcap) {
-    INQ_GUARD(genotype_table_impl(args, device_ids, n_devices, out_fd, ReportPaths{read_calls_path, read_table_path}, stats, errbuf, errcap), errbuf,
-              errcap)
+    return inq_genotype_repeats_seqs(args, device_ids, n_devices, out_fd, read_calls_path, read_table_path, nullptr, stats, errbuf, errcap);
 }
 int inq_genotype_repeats_reads(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,
                                inq_part_stats_t *stats, char *errbuf, size_t errcap) {

@@ -211,7 +211,7 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
         }
     } pin;
     const int n_workers = (int)std::max<uint64_t>(1, std::min<uint64_t>(args->threads > 1 ? args->threads - 1 : 1, 64));
-    ParallelFrontEnd pfe(args->bam, V.bam, V.targets, V.opt.unphased, n_workers, 0, reports->has.read_table);
+    ParallelFrontEnd pfe(args->bam, V.bam, V.targets, V.opt.unphased, n_workers, 0, reports->has.read_table, reports->has.read_seqs);
     auto t_ctx = Clock::now();
     BatchRows br;
     for (;;) {
@@ -456,6 +456,15 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
                      append_read_table_rows(text, targets[i].chrom, targets[i].start, targets[i].end, l.data(), w.origins.data(), w.names.data(),
                                             l.size(), unphased);
              }},
+            {tr->has.read_seqs, reports.fds.read_seqs, std::string(kReadSeqsHeader) + '\n', kReadSeqsWhat,
+             [&targets, tr, unphased](std::string &text, uint32_t i) {  // the table's lines, with the bases instead of the origin
+                 const std::vector<inq_read_call_t> &l = tr->read_calls[i];
+                 const ReadIdentities &w = tr->read_table[i];
+                 const ReadSlices &q = tr->read_seqs[i];
+                 if (w.origins.size() == l.size() && q.seqs.size() == l.size())
+                     append_read_seq_rows(text, targets[i].chrom, targets[i].start, targets[i].end, l.data(), w.origins.data(), w.names.data(),
+                                          q.seqs.data(), q.packed.data(), l.size(), unphased);
+             }},
         };
         for (const auto &f : files) {
             if (!f.on || f.fd < 0) continue;
@@ -480,7 +489,8 @@ struct inq_frontend {
     std::string bam_path;
     CallOptions opt;
     uint64_t threads = 1, max_words = 0;
-    const HostBatch *current = nullptr;  // the batch the last inq_frontend_next handed out (inq_frontend_read_names)
+    const HostBatch *current = nullptr;  // the batch the last inq_frontend_next handed out (inq_frontend_read_names, _read_seqs)
+    bool keep_seqs = false;              // inq_frontend_set_keep_seqs
 };
 
 // target i of a prepared call, for the two handles that show their list (0, or -1 past its end)
@@ -523,6 +533,12 @@ void inq_frontend_set_batch_words(inq_frontend_t *fe, uint64_t w) {
     if (fe->fe) fe->fe->set_max_batch_words(w);
 }
 
+void inq_frontend_set_keep_seqs(inq_frontend_t *fe, int on) {
+    if (!fe) return;
+    fe->keep_seqs = on != 0;
+    if (fe->fe) fe->fe->set_keep_seqs(on != 0);
+}
+
 static int inq_frontend_next_impl(inq_frontend_t *fe, inq_batch_t *batch, const uint32_t **locus_index, char *errbuf,
                       size_t errcap) {
     if (!fe || !batch) return -INQ_EXIT_ERROR;
@@ -532,7 +548,7 @@ static int inq_frontend_next_impl(inq_frontend_t *fe, inq_batch_t *batch, const 
     if (fe->threads > 1) {  // batches arrive in completion order; locus_index says where each row belongs
         if (!fe->pfe)
             fe->pfe.reset(new ParallelFrontEnd(fe->bam_path, *fe->P.bam, fe->P.targets, fe->opt.unphased,
-                                               (int)std::min<uint64_t>(fe->threads, 64), fe->max_words, true));
+                                               (int)std::min<uint64_t>(fe->threads, 64), fe->max_words, true, fe->keep_seqs));
         fe->pfe->recycle(std::move(fe->item));
         fe->item = ParallelFrontEnd::Item();
         int rc = fe->pfe->next(fe->item, &err, &panic);
@@ -562,6 +578,15 @@ int inq_frontend_read_names(const inq_frontend_t *fe, const uint64_t **name_off,
     if (!fe || !fe->current || fe->current->name_off.size() != fe->current->reads.size() + 1) return INQ_EXIT_ERROR;
     if (name_off) *name_off = fe->current->name_off.data();
     if (names) *names = fe->current->names.data();
+    if (n_reads) *n_reads = fe->current->reads.size();
+    return INQ_EXIT_OK;
+}
+
+int inq_frontend_read_seqs(const inq_frontend_t *fe, const uint32_t **l_seq, const uint64_t **seq_off, const uint8_t **seqs, uint64_t *n_reads) {
+    if (!fe || !fe->current || fe->current->seq_off.size() != fe->current->reads.size() + 1) return INQ_EXIT_ERROR;
+    if (l_seq) *l_seq = fe->current->l_seq.data();
+    if (seq_off) *seq_off = fe->current->seq_off.data();
+    if (seqs) *seqs = fe->current->seqs.data();
     if (n_reads) *n_reads = fe->current->reads.size();
     return INQ_EXIT_OK;
 }

@@ -543,12 +543,13 @@ int run_device_front(const inq_call_args_t *args, const CallView &V, AsyncCtx &a
     SpanLoop loop;
     BatchRows br;
     const bool with_names = hooks.reports->has.read_table && !hooks.dev_p1;
+    const bool with_seqs = hooks.reports->has.read_seqs && !hooks.dev_p1;  // (the read-seqs file: its lines name the reads too)
     auto flush = [&]() -> int {
         if (pending.empty()) return INQ_EXIT_OK;
         const auto f0 = Clock::now();
         // rows that stay on the device take flags only (they belong to a prepared run, which takes no evidence: run.cc inq_run_open_impl)
         ReportSet which = hooks.reports->has;
-        if (hooks.dev_p1) which.evidence = which.read_calls = which.read_table = false;
+        if (hooks.dev_p1) which.evidence = which.read_calls = which.read_table = which.read_seqs = false;
         br.begin(pending.size(), which);
         double ms_call = 0;
         // (rows that travel on from device memory stay there: pending[j] is the row's place in the caller's device arrays)
@@ -597,8 +598,10 @@ int run_device_front(const inq_call_args_t *args, const CallView &V, AsyncCtx &a
         loop.comp_bytes += sp.comp_bytes;
         g_span_bytes_read.fetch_add(sp.comp_bytes, std::memory_order_relaxed);
         // (the read table: the names exist only in the span's inflated bytes - gathered into the batch now, or never)
-        int rc2 = with_names ? inq_call_span_deferred_names(ctx, &sp, it->staged ? it->slot : -1, &stt)
-                             : inq_call_span_deferred(ctx, &sp, it->staged ? it->slot : -1, &stt);
+        // ... and so do the bases: the slices are cut out of them now
+        int rc2 = with_seqs    ? inq_call_span_deferred_seqs(ctx, &sp, it->staged ? it->slot : -1, &stt)
+                  : with_names ? inq_call_span_deferred_names(ctx, &sp, it->staged ? it->slot : -1, &stt)
+                               : inq_call_span_deferred(ctx, &sp, it->staged ? it->slot : -1, &stt);
         *t_dev += secs(tb, Clock::now());
         if (timing == 2)
             std::fprintf(stderr,
