@@ -324,7 +324,10 @@ __global__ __launch_bounds__(256) void cigar_gather_kernel(ScanArgs a, uint64_t 
         if (!bad_op && rd.pos >= -1 && (int64_t)rd.pos + 1 + rlen < ((int64_t)1 << 31)) rd.promise = INQ_READ_CHECKED;
         if ((rd.bits & INQ_READ_UNMAPPED) || rlen == 0) rlen = 1;  // [3P] bam_endpos
         const int64_t endpos = (int64_t)rd.pos + rlen;
-        a.endkey[i] = (a.key[i] & ~0xffffffffll) + (endpos + 1);
+        // a span that carries endpos + 1 past 2^32 (N ops add up to that) must not reach the next contig's keys: the low word saturates,
+        // which still exceeds every kstart of its own contig (locus starts lie below 2^31)
+        const int64_t endlow = endpos + 1 < 0xffffffffll ? endpos + 1 : 0xffffffffll;
+        a.endkey[i] = (a.key[i] & ~0xffffffffll) + endlow;
         rd.cigar_off4 = (uint32_t)unit0 + a.unit_base;
         // is_accidental_2d is only reached from a soft-clip op (src/call.rs:394)
         if (clip && ri.sa_off) {

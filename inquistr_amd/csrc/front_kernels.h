@@ -68,7 +68,7 @@ struct ScanArgs {
     inq_read_t *reads;      // [n_records]
     RecInfo *info;          // [n_records]
     int64_t *key;           // [n_records] (tid << 32) | (pos + 1): ascending in a coordinate-sorted file
-    int64_t *endkey;        // [n_records] (tid << 32) + (endpos + 1)
+    int64_t *endkey;        // [n_records] (tid << 32) + min(endpos + 1, 0xffffffff): an end past 2^32 stays on its contig
     int64_t *pmax;          // [n_records] running maximum of endkey
     uint64_t *cig_off;      // [n_records + 1] exclusive scan of CIGAR sizes in units of 4 words
     uint32_t *cigar;        // gathered CIGAR words

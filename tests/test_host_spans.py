@@ -36,7 +36,7 @@ def emulate_span(sp):
     bb = B.BatchBuilder(minlen=sp["minlen"], support=sp["support"], unphased=sp["unphased"])
     ends = []
     for r in reads:
-        ops = [("MIDNSHP=X"[w & 15], w >> 4) for w in r["cigar"]]
+        ops = [("MIDNSHP=X???????"[w & 15], w >> 4) for w in r["cigar"]]  # (op codes 9-15 consume nothing and clip nothing)
         rec = py.Record(pos=r["pos"], cigar=ops, mapq=r["mapq"], flag=r["flag"], hp=r["hp"], sa=r["sa"])
         ends.append(py.reference_end(rec))
         hp = r["hp"]

@@ -283,6 +283,8 @@ def read_records(u: bytes, off: int):
             v = p + 3
             if typ in _AUX_FIXED:
                 sz = _AUX_FIXED[typ]
+                if v + sz > end:  # the value is cut by the record's end
+                    break
                 val = u[v : v + 1].decode("latin1") if typ == "A" else (struct.unpack_from("<" + _AUX_FMT[typ], u, v)[0] if typ != "d" else None)
             elif typ in "ZH":
                 z = u.index(b"\0", v, end) if b"\0" in u[v:end] else -1
@@ -290,11 +292,17 @@ def read_records(u: bytes, off: int):
                     break
                 sz, val = z - v + 1, u[v:z].decode("latin1")
             elif typ == "B":
+                if v + 5 > end:  # the array's header is cut by the record's end
+                    break
                 sub = chr(u[v])
                 (cnt,) = struct.unpack_from("<I", u, v + 1)
+                # a subtype outside cCsSiIf counts 4 bytes per element, as in the three C readers (bam_scan.hip, host/bam_reader.cc,
+                # oracle/minibam.h); its elements stay opaque
                 es = 1 if sub in "cC" else 2 if sub in "sS" else 4
                 sz = 5 + cnt * es
-                val = (sub, list(struct.unpack_from("<%d%s" % (cnt, _AUX_FMT[sub]), u, v + 5))) if v + sz <= end else None
+                if v + sz > end:
+                    break
+                val = (sub, list(struct.unpack_from("<%d%s" % (cnt, _AUX_FMT[sub]), u, v + 5)) if sub in _AUX_FMT else None)
             else:
                 break
             if v + sz > end:
