@@ -15,8 +15,9 @@
 //     descriptor's range check returns 0 (= `0M`, a no-op) for an offset past num_records.
 //   * whole: the wave is on one read at a time, in 256-op chunks (1 KiB per wave instruction, coalesced), flattened over reads
 //     and the chunks of long reads.  Reference positions: advance4 in the lane + DPP wave scan + scalar carry between chunks.
-//   * rows: the wave is four rows of 16 lanes, each a read stream of its own, in pieces of up to 64 ops: piece 0 of every read
-//     statically, the reads it has not settled from a list in LDS.  Positions: advance4 + DPP row scan + a carry per row.
+//   * rows: every row of the wave is a read stream of its own.  Head: eight rows of 8 lanes walk the first four 128-byte lines of
+//     every read, a line at a time, read k in a fixed row; the reads it does not settle go on from a list in LDS, in four rows
+//     of 16 lanes and pieces of two lines.  Positions: advance4 + DPP row scan + a carry per row.
 //   * both: only the few lanes whose ops can start inside [start_ext, end_ext) matter for the call: they are compacted into an
 //     LDS queue (push_window_lanes) and evaluated 64 at a time (drain_queue, one entry per lane); their signed lengths land in
 //     the owning read's LDS accumulator (ds_add_u64).  The per-op window/minlen/sign logic runs once per ~64 window lanes.
@@ -87,7 +88,7 @@ struct WaveLds {
 
 // four waves x 5 120 B = 20 480 B per workgroup: eight workgroups fill a CU's 160 KB at 8 waves per SIMD
 static_assert(sizeof(WaveLds) == 5120, "a larger WaveLds costs resident workgroups per CU");
-// The continuation list of walk_pairs_rows, up to 64 reads to go on behind piece 0: entry i is the read's next group and its
+// The continuation list of walk_pairs_rows, up to 64 reads to go on behind the head: entry i is the read's next group and its
 // row word (rw_pack) in q[i].pad, the position reached in q[64 + i].pad.x.  It outlives the queue's pushes and drains because
 // push_window_lanes, the one store to the queue, writes .w and .info and never a whole QueueEntry.  (i is unsigned in put and
 // signed in get, as the two callers hold it: a cast at either changes the addresses the compiler forms.)
@@ -299,6 +300,10 @@ __device__ __forceinline__ void walk_pairs_whole(const BatchView &b, const PairM
     uint32_t lane_range = 0, lane_bad = 0;
     uint32_t end_carry = 0;  // lane k: reference_position after the last op of read k
 
+    // (a scalar pair of its own for the CIGAR's base: taken from the kernel's argument block at every load, that whole block has
+    // to stay in scalar registers through the loop, or be restored from spill lanes in every step)
+    const uint4 *cigar4 = b.cigar4;
+    asm volatile("" : "+s"(cigar4));
     // ---- load cursor: runs 4 chunk loads ahead of the compute cursor ----
     int hk = 0;
     uint32_t hc = 0, h_nchunks = 1, h_off4 = 0, h_n4 = 0;
@@ -317,7 +322,7 @@ __device__ __forceinline__ void walk_pairs_whole(const BatchView &b, const PairM
     auto issue = [&]() -> u32x4 {
         // raw buffer load: offsets at or beyond num_records return 0, no exec masking needed
         const __amdgpu_buffer_rsrc_t rsrc =
-            __builtin_amdgcn_make_buffer_rsrc((void *)(b.cigar4 + h_off4), (short)0, (int)(h_n4 * 16u), 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc((void *)(cigar4 + h_off4), (short)0, (int)(h_n4 * 16u), 0x00020000);
         const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((hc * 64u + (uint32_t)lane) * 16u), 0, AUX);
         ++hc;
         if (hc >= h_nchunks) {
@@ -392,14 +397,12 @@ __device__ __forceinline__ void walk_pairs_whole(const BatchView &b, const PairM
 // never decrease), and a lower bound of bam_endpos that is already >= end_ext settles the fetch rule and both
 // filters (rend > start_ext, rend < end_ext) exactly as the true value does.
 //
-// Shape: the wave is 4 rows of kRowLanes = 16 lanes; a row walks one read in pieces of up to 64 ops (one
-// buffer_load_dwordx4 per lane: up to 256 contiguous bytes per row, see kLineMask below for where they lie).  Four load slots per wave, as in the
-// whole walk, but every row of a slot is a read stream of its own: piece 0 of the block's reads is dealt to the
-// rows in order, and from piece 1 on a row that has scanned a piece loads either its read's next piece or - the
-// read done - the next piece 1 waiting, so nothing is loaded past the point where a read stops.  A checked read
-// stops after the piece that takes carry = pos + 1 + consumed past end_ext (carry > end_ext <=> pos + consumed >=
-// end_ext, without the u32 wrap of pos = -1); an unchecked one is walked to its end, with the device's own domain
-// checks.
+// Shape: four load slots per wave, as in the whole walk, but every row of a slot is a read stream of its own (one
+// buffer_load_dwordx4 per lane, see kLineMask below for where the pieces lie).  In the head a slot is 8 rows of kHeadLanes = 8
+// lanes and a piece one line of up to 32 ops; behind it 4 rows of kRowLanes = 16 lanes and a piece two lines.  The stop is
+// tested after every piece, so nothing is loaded past the piece in which a read stops.  A checked read stops after the
+// piece that takes carry = pos + 1 + consumed past end_ext (carry > end_ext <=> pos + consumed >= end_ext, without the
+// u32 wrap of pos = -1); an unchecked one is walked to its end, with the device's own domain checks.
 constexpr uint32_t RP_CHECKED = 1u;  // INQ_READ_CHECKED
 
 constexpr int kRowLanes = 16;  // lanes of one row = one read stream = one DPP row
@@ -416,19 +419,33 @@ __device__ __forceinline__ uint32_t row_inclusive_scan_u32(uint32_t x) {
 // ((l & 0x10) | 0x0f) of its 32-lane half.
 __device__ __forceinline__ uint32_t row_last(uint32_t x) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, 0x10 | (0x0f << 5)); }
 
+// The head phase's rows are half DPP rows: kHeadLanes = 8 lanes, one 128-byte line per load.
+constexpr int kHeadLanes = 8;
+constexpr int kHeadLines = 4;  // lines of a read the head phase walks before the list takes it
+// Inclusive prefix sum and total inside each 8-lane row, exact in wrapping u32: the 16-lane scan, less the lower half's
+// total (lane 7 of the DPP row) in the upper half; the total is then lane 7 of the half.  ds_swizzle in bit-mask mode reads
+// lane ((l & and) | or): and = 0x10 keeps the DPP row, and = 0x18 the half.
+__device__ __forceinline__ void head_row_scan_u32(uint32_t x, bool upper, uint32_t &incl, uint32_t &tot) {
+    const uint32_t s = row_inclusive_scan_u32(x);
+    const uint32_t lower = (uint32_t)__builtin_amdgcn_ds_swizzle((int)s, 0x10 | (0x07 << 5));
+    incl = s - (upper ? lower : 0u);
+    tot = (uint32_t)__builtin_amdgcn_ds_swizzle((int)incl, 0x18 | (0x07 << 5));
+}
+
 // One read stream: the same value in every lane of a row.
 struct RowStream {
-    uint32_t cur4;   // the next 16-byte group of the read this row loads (the piece's first)
+    uint32_t cur4;   // the next 16-byte group of the read this row loads (the piece's first); in the head see head_issue
     uint32_t carry;  // (reference_start + 1) + reference span of the ops walked so far, u32
     uint32_t st;     // groups left << RS_LEFT | RS_LIVE | RS_STOP | is_2d << 6 | read slot; 0 = idle
 };
 constexpr uint32_t RS_STOP = 128u, RS_LIVE = 256u;
 constexpr int RS_LEFT = 9;
 // Where the pieces lie.  A read starts on a 16-byte boundary, off4 & 7 groups into a 128-byte line of the batch's CIGAR.
-// Piece 0 keeps the read's own start (16 groups from off4: laid from the line's start it would hold fewer of the read's
-// ops and send 0.78 of the reads on to a later piece instead of 0.46).  Every later piece ends on the second line boundary
-// behind its start: lane rl of the row loads group (cur4 & ~7) + rl, and the lanes before cur4 and past the read's end
-// get the out-of-range offset.  So piece 1 holds 16 - (off4 & 7) groups and every piece behind it two whole lines.
+// Every piece ends on a line boundary, so no line is asked for by two loads of one read.  The head's pieces are single lines:
+// the first holds the read's groups from off4 to the end of its line, 8 - (off4 & 7) of them, every later one a whole line.
+// Behind the head a piece ends on the second line boundary behind its start: lane rl of the row loads group (cur4 & ~7) + rl,
+// and the lanes before cur4 and past the read's end get the out-of-range offset; the head hands a read over on a line
+// boundary, so these are two whole lines each.
 constexpr uint32_t kLineMask = 7u;  // groups of a 128-byte line - 1
 // st holds at most 2^23 - 1 groups left: a read of kRowMaxGroups groups or more (n_cigar > 2^25 - 4) sends its block to
 // the whole walk
@@ -459,10 +476,11 @@ __device__ __forceinline__ uint32_t row_state(uint32_t groups, uint32_t slot, ui
 // read of the block is not promised, so every piece gets the device's own domain checks; a block whose reads are
 // all promised walks without them.
 //
-// Two phases.  Piece 0 is needed of every read that is not settled by its descriptor alone, so it is walked
-// statically: read 4s + row in turn s, four loads in flight, no queue of idle rows.  The reads that have not
-// stopped after piece 0 are then compacted into a list in LDS (cont_put: the spare words of the lane queue's entries) and
-// walked from piece 1 on by rows that take the next of them whenever they fall idle.
+// Two phases.  The head: a block is walked in passes of 32 reads, read k of the pass in row k % 8 of slot k / 8 for up to
+// kHeadLines lines - no claim, no list, no ballot but the wave-uniform one that skips a slot whose rows are all idle; most
+// promised reads stop inside it.  The reads that have not (long, far from their window, or unpromised) are then compacted into
+// a list in LDS (cont_put: the spare words of the lane queue's entries) and walked on in two-line pieces by 16-lane rows that
+// take the next of them whenever they fall idle.
 template <bool UNPHASED, int AUX>
 __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMeta &m, bool valid, int cnt,
                                                 const Window &W, int lane, bool checks, uint32_t &status, WaveLds &L,
@@ -473,35 +491,44 @@ __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMe
     uint32_t qcount = 0;
     // bit 0: an op code 9..15 was seen, bit 1: a reference position reached 2^31
     uint32_t lane_err = ((m.pos + 1u) >> 31) << 1;
-    const int rl = lane & (kRowLanes - 1);
-    const int row = lane >> 4;
     const uint64_t row_heads = 0x0001000100010001ull;  // lane 0 of each row
     // out-of-range offsets (past num_records) load 0 = `0M`: lanes past a read's end and idle rows
     const __amdgpu_buffer_rsrc_t rsrc =
         __builtin_amdgcn_make_buffer_rsrc((void *)b.cigar4, (short)0, (int)(uint32_t)(b.n_cigar4 * 16u), 0x00020000);
 
-    const uint32_t groups = cigar_groups(m.nc & 0x0fffffffu);
-    const bool promised = ((m.misc >> 24) & RP_CHECKED) != 0u;
-    const uint32_t d_w = rw_pack(groups, m.nc >> 31, promised);  // read k's row word in lane k; an empty read where none is owned
+    // read k's row word in lane k; an empty read where none is owned
+    const uint32_t d_w = rw_pack(cigar_groups(m.nc & 0x0fffffffu), m.nc >> 31, ((m.misc >> 24) & RP_CHECKED) != 0u);
 
-    // piece 0 from the read's own start
-    auto issue0 = [&](const RowStream &S) -> u32x4 {
-        const uint32_t voff = (uint32_t)rl < (S.st >> RS_LEFT) ? (S.cur4 + (uint32_t)rl) * 16u : 0xfffffff0u;
-        return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, AUX);
-    };
-    // a piece on the line grid: the lanes from cur4 to the piece's end that the read still has groups for
+    const int rl = lane & (kRowLanes - 1);
+    // the head phase's row: 8 lanes, one line; the upper half of a DPP row is a row of its own
+    const int hl = lane & (kHeadLanes - 1);
+    const int hrow = lane >> 3;
+    const bool upper = (lane & kHeadLanes) != 0;
+
+    // a piece on the line grid: the lanes from cur4 to the second line boundary behind it that the read still has groups for
     auto issue = [&](const RowStream &S) -> u32x4 {
         const uint32_t g = (S.cur4 & ~kLineMask) + (uint32_t)rl;
         const bool on = g - S.cur4 < (S.st >> RS_LEFT);
         return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(on ? g * 16u : 0xfffffff0u), 0, AUX);
     };
-    // PIECE0: the row's state is not carried on; the position reached goes to the read's owner through L.endc
-    auto step = [&](const u32x4 w, RowStream &S, auto piece0) {
+    // The head's rows count a read's groups from the start of the line it starts in, so every line is 8 groups to them, and
+    // hold in cur4 not a group but the byte offset of the lane's own group of the next line.
+    auto head_issue = [&](const RowStream &S) -> u32x4 {
+        return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((uint32_t)hl < (S.st >> RS_LEFT) ? S.cur4 : 0xfffffff0u), 0, AUX);
+    };
+    // One piece of every row of a slot: LANES = 8 in the head, 16 behind it.  `last` (wave-uniform, head only): the row gives
+    // its read up whether it has stopped or not; the read's owner finds the position reached in L.endc either way.
+    auto step = [&](const u32x4 w, RowStream &S, auto lanes, bool last) {
+        constexpr uint32_t LANES = decltype(lanes)::value;
         const bool live = S.st != 0u;
-        uint32_t e1, e2, e3, tot;
+        uint32_t e1, e2, e3, tot, incl, rtot;
         advance4(w, e1, e2, e3, tot);
-        const uint32_t incl = row_inclusive_scan_u32(tot);
-        const uint32_t rtot = row_last(incl);
+        if (LANES == (uint32_t)kHeadLanes) {
+            head_row_scan_u32(tot, upper, incl, rtot);
+        } else {
+            incl = row_inclusive_scan_u32(tot);
+            rtot = row_last(incl);
+        }
         if (checks) {
             if (live) {
                 lane_err |= bad_ops(w) & 1u;
@@ -512,11 +539,15 @@ __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMe
         const uint32_t x = (S.carry - W.se1) + incl;
         if (push_window_lanes(L, qcount, live && x < W.width + tot, w, x, tot, S.st, 127u)) drain_queue(L, qcount, W, lane);
         S.carry += rtot;
-        if (decltype(piece0)::value) {
-            if (live && rl == 0) L.endc[S.st & 63u] = S.carry;
+        if (LANES == (uint32_t)kHeadLanes) {
+            S.cur4 += 16u * LANES;
+            // (an idle row has no groups left: it is `done` and stays idle)
+            const bool done = last || (S.st >> RS_LEFT) <= LANES || ((S.st & RS_STOP) && S.carry > W.ee);
+            if (live && done && hl == 0) L.endc[S.st & 63u] = S.carry;
+            S.st = done ? 0u : S.st - (LANES << RS_LEFT);
         } else {
             // the piece ran from cur4 to a line boundary: lim groups
-            const uint32_t end4 = (S.cur4 & ~kLineMask) + (uint32_t)kRowLanes;
+            const uint32_t end4 = (S.cur4 & ~kLineMask) + LANES;
             const uint32_t lim = end4 - S.cur4;
             S.cur4 = end4;
             if (live) {
@@ -529,61 +560,74 @@ __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMe
             }
         }
     };
-    using Piece0 = std::true_type;
-    using Later = std::false_type;
+    using Head = std::integral_constant<uint32_t, (uint32_t)kHeadLanes>;
+    using Later = std::integral_constant<uint32_t, (uint32_t)kRowLanes>;
 
-    // ---- piece 0: rows of turn k0 / 4 take reads k0 .. k0 + 3 ----
-    auto assign = [&](RowStream &S, int k0) {
+    // ---- head: read k of the pass is slot k / 8's row k % 8, for up to kHeadLines lines ----
+    // The descriptors wait for their rows in LDS, not in registers: read k's first group and row word in the words the
+    // continuation list takes over behind the head (q[k].pad), its start position in L.endc[k].
+    L.q[lane].pad = make_uint2(m.off4, d_w);
+    __builtin_amdgcn_wave_barrier();
+    // ... and loads the first line: the lanes from the read's start on
+    auto assign = [&](RowStream &S, int k0) -> u32x4 {
         S.st = 0u;
-        if (k0 < cnt) {  // wave-uniform; k0 + row <= 63
-            const int src = (k0 + row) << 2;
-            const uint32_t r_off4 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)m.off4);
-            const uint32_t r_w = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)d_w);
-            const uint32_t r_pos = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)m.pos);
-            S.cur4 = r_off4;
-            S.carry = r_pos + 1u;
+        uint32_t voff = 0xfffffff0u;
+        if (k0 < cnt) {  // wave-uniform; k0 + hrow <= 63
+            const uint2 d = L.q[k0 + hrow].pad;
+            const uint32_t r_w = d.y, skip = d.x & kLineMask;
+            S.cur4 = ((d.x & ~kLineMask) + (uint32_t)hl) * 16u;
+            S.carry = L.endc[k0 + hrow];
             // an empty CIGAR, or a promised read that starts past the window: nothing to load
-            if (rw_groups_slot0(r_w) != 0u && !(rw_promised(r_w) && S.carry > W.ee))
-                S.st = row_state(rw_groups_slot0(r_w), (uint32_t)(k0 + row), rw_2d(r_w), rw_promised(r_w));
+            if (rw_groups_slot0(r_w) != 0u && !(rw_promised(r_w) && S.carry > W.ee)) {
+                // (the head asks of the groups left only whether they end in the line at hand)
+                const uint32_t left = min(rw_groups_slot0(r_w) + skip, (uint32_t)((kHeadLines + 1) * kHeadLanes));
+                S.st = row_state(left, (uint32_t)(k0 + hrow), rw_2d(r_w), rw_promised(r_w));
+                if ((uint32_t)hl - skip < left - skip) voff = S.cur4;
+            }
         }
+        return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, AUX);
     };
     RowStream sa{0u, 0u, 0u}, sb = sa, sc = sa, sd = sa;
-    assign(sa, 0);
-    u32x4 qa = issue0(sa);
-    assign(sb, 4);
-    u32x4 qb = issue0(sb);
-    assign(sc, 8);
-    u32x4 qc = issue0(sc);
-    assign(sd, 12);
-    u32x4 qd = issue0(sd);
+    u32x4 qa, qb, qc, qd;
     // four named buffers, one load per slot and round whether its rows are live or not: each step waits only
     // for its own load (vmcnt(3)); an idle slot's load is out of range everywhere and moves no bytes
-    for (int k0 = 0; k0 < cnt; k0 += 16) {
-        step(qa, sa, Piece0{});
-        assign(sa, k0 + 16);
-        qa = issue0(sa);
-        if (k0 + 4 < cnt) step(qb, sb, Piece0{});
-        assign(sb, k0 + 20);
-        qb = issue0(sb);
-        if (k0 + 8 < cnt) step(qc, sc, Piece0{});
-        assign(sc, k0 + 24);
-        qc = issue0(sc);
-        if (k0 + 12 < cnt) step(qd, sd, Piece0{});
-        assign(sd, k0 + 28);
-        qd = issue0(sd);
+    for (int k0 = 0; k0 < cnt; k0 += 4 * kHeadLanes) {
+        qa = assign(sa, k0);
+        qb = assign(sb, k0 + kHeadLanes);
+        qc = assign(sc, k0 + 2 * kHeadLanes);
+        qd = assign(sd, k0 + 3 * kHeadLanes);
+        if (ballot64((sa.st | sb.st | sc.st | sd.st) != 0u)) {
+            int line = 0;
+            do {
+                const bool last = ++line == kHeadLines;
+                if (ballot64(sa.st != 0u)) step(qa, sa, Head{}, last);
+                qa = head_issue(sa);
+                if (ballot64(sb.st != 0u)) step(qb, sb, Head{}, last);
+                qb = head_issue(sb);
+                if (ballot64(sc.st != 0u)) step(qc, sc, Head{}, last);
+                qc = head_issue(sc);
+                if (ballot64(sd.st != 0u)) step(qd, sd, Head{}, last);
+                qd = head_issue(sd);
+            } while (ballot64((sa.st | sb.st | sc.st | sd.st) != 0u));
+        }
     }
 
-    // ---- later pieces: the reads piece 0 has not settled, as a list of ncont entries in LDS ----
+    // ---- later pieces: the reads the head has not settled, as a list of ncont entries in LDS ----
     __builtin_amdgcn_wave_barrier();
     const uint32_t endc0 = L.endc[lane];
-    const bool cont = groups > (uint32_t)kRowLanes && !(promised && endc0 > W.ee);
+    const uint2 own = L.q[lane].pad;  // this lane's read again: first group, row word (read before any cont_put)
+    const uint32_t groups = rw_groups_slot0(own.y) & (kRowMaxGroups - 1u);
+    const bool promised = rw_promised(own.y);
+    // what the head took of read k: kHeadLines lines from the start of the line the read starts in
+    const uint32_t head_groups = (uint32_t)(kHeadLines * kHeadLanes) - (own.x & kLineMask);
+    const bool cont = groups > head_groups && !(promised && endc0 > W.ee);
     const uint64_t cmask = ballot64(cont);
     if (cmask) {
         const int ncont = (int)__popcll(cmask);
-        // the i-th read to go on: behind piece 0, which took kRowLanes of its groups, for the row that claims it
+        // the i-th read to go on: on the line boundary behind the head's lines, for the row that claims it
         if (cont) {
             const uint32_t i = __builtin_amdgcn_mbcnt_hi((uint32_t)(cmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cmask, 0u));
-            cont_put(L, i, m.off4 + (uint32_t)kRowLanes, (d_w - (uint32_t)kRowLanes) | ((uint32_t)lane << RW_SLOT), endc0);
+            cont_put(L, i, own.x + head_groups, (own.y - head_groups) | ((uint32_t)lane << RW_SLOT), endc0);
         }
         __builtin_amdgcn_wave_barrier();
 
@@ -615,22 +659,22 @@ __device__ __forceinline__ void walk_pairs_rows(const BatchView &b, const PairMe
         qd = issue(sd);
         while (ballot64((sa.st | sb.st | sc.st | sd.st) != 0u)) {
             if (ballot64(sa.st != 0u)) {
-                step(qa, sa, Later{});
+                step(qa, sa, Later{}, false);
                 claim(sa);
             }
             qa = issue(sa);
             if (ballot64(sb.st != 0u)) {
-                step(qb, sb, Later{});
+                step(qb, sb, Later{}, false);
                 claim(sb);
             }
             qb = issue(sb);
             if (ballot64(sc.st != 0u)) {
-                step(qc, sc, Later{});
+                step(qc, sc, Later{}, false);
                 claim(sc);
             }
             qc = issue(sc);
             if (ballot64(sd.st != 0u)) {
-                step(qd, sd, Later{});
+                step(qd, sd, Later{}, false);
                 claim(sd);
             }
             qd = issue(sd);

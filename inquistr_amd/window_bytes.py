@@ -3,7 +3,8 @@
 `checked_mask` restates the domain rules a producer vouches for with INQ_READ_CHECKED (op codes <= 8,
 pos >= -1, pos + 1 + reference span < 2^31); `mark_checked` sets the byte where they hold.
 
-`window_bounded_bytes` counts what the locus kernel's row walk (csrc/cigar_walk.h walk_pairs_rows) reads:
+`window_bounded_bytes` counts what the locus kernel's row walk (csrc/cigar_walk.h walk_pairs_rows) reads, in pieces
+laid from each read's start (the LAYOUTS restate the pieces of earlier walks; `head_layout` is the walk's own now):
 a checked read up to the piece after which pos + consumed >= end_ext, in whole 16-byte groups, nothing when
 pos >= end_ext already; an unchecked read (or a wrapped window, see walk_pairs for the rest) whole.  Next to it the same per-pair and
 per-locus bytes as `Batch.algorithmic_bytes()`, which keeps counting every op.
@@ -178,6 +179,50 @@ def row_steps(batch: Batch, layout: str = "read", factor=(HALF_NUM, HALF_DEN)) -
     cnt = np.bincount(block)
     later = pieces - (pieces > 0)
     return float(((cnt + 3) // 4).sum() + later.sum() / 4.0)
+
+
+HEAD_LANES = 8  # cigar_walk.h kHeadLanes: a row of the head phase, one 128-byte line per load
+HEAD_LINES = 4  # cigar_walk.h kHeadLines
+
+
+def head_layout(batch: Batch, head_lines: int = HEAD_LINES):
+    """What the row walk does since its head phase (cigar_walk.h walk_pairs_rows), per pair: (groups it loads, 128-byte lines
+    it loads, lines of them that the head walks), and the head steps of the whole batch.
+
+    A read that starts skip = g0 & 7 groups into its line is walked one line at a time: 8 - skip groups, then whole lines,
+    the stop rule of `_walked_pieces` after each, up to `head_lines` lines; no line is asked for twice.  What is left then
+    goes on in pieces of two whole lines.  A block of up to 64 pairs is walked in passes of 32: pair k of the pass is row
+    k % 8 of load slot k // 8 throughout, and a slot is stepped while one of its eight reads is live - so a slot costs as
+    many head steps as the most lines any of its reads needs.  (A block without a promised read takes the whole walk, which
+    has no head; its reads are counted here as the row walk would take them.)"""
+    if batch.n_pairs == 0:
+        z = np.zeros(0, dtype=np.int64)
+        return z, z, z, 0
+    csum, before, ee, n, n4, o, carry0, bounded, block = _bounded(batch, 4 * PIECE_GROUPS)
+    g0 = o // 4
+    groups = np.zeros_like(n4)
+    head = np.zeros_like(n4)
+    live = (n4 > 0) & ~(bounded & (carry0 > ee))  # an empty CIGAR, or starts past the window: nothing loaded
+    lim = HEAD_LANES - (g0 & 7)
+    piece = 0
+    while live.any():
+        g_new = np.where(live, np.minimum(groups + lim, n4), groups)
+        at = o + np.minimum(4 * g_new, n) - 1
+        c_new = np.where(g_new > 0, carry0 + csum[np.maximum(at, 0)] - before, carry0)
+        ends = (n4 - groups <= lim) | (bounded & (c_new > ee))
+        piece += 1
+        if piece <= head_lines:
+            head += live
+        groups = g_new
+        live = live & ~ends
+        lim = np.full_like(n4, HEAD_LANES if piece < head_lines else PIECE_GROUPS)
+    lines = np.where(groups > 0, ((g0 + groups) * 16 + 127) // 128 - (g0 * 16) // 128, 0)
+    off = batch.locus_pair_off.astype(np.int64)
+    k = np.arange(batch.n_pairs, dtype=np.int64) - np.repeat(off[:-1], np.diff(off))
+    slot = block * 8 + (k % 64) // HEAD_LANES  # 64-pair block, then its eight slots of eight reads: passes of four slots
+    per_slot = np.zeros(int(slot.max()) + 1, dtype=np.int64)
+    np.maximum.at(per_slot, slot, head)
+    return groups, lines, head, int(per_slot.sum())
 
 
 def window_bounded_bytes(batch: Batch, piece_ops: int = 64) -> int:
