@@ -425,22 +425,16 @@ struct LoadNameLen {
         return len < room ? len : room;
     }
 };
-// name_len of origin k, 0 at and behind min(*n_kept, n)
-struct LoadOriginLen {
-    const inq_read_origin_t *origins;
+// bytes of kept record k's run (run_bytes.h: its name, its packed slice), 0 at and behind min(*n_kept, n)
+template <class Rec> struct LoadRunBytes {
+    const Rec *recs;
     const uint64_t *n_kept;
-    __device__ uint64_t operator()(uint64_t k) const { return k < *n_kept ? origins[k].name_len : 0u; }
+    __device__ uint64_t operator()(uint64_t k) const { return k < *n_kept ? run_bytes(recs[k]) : 0u; }
 };
 // packed bytes of pair p's slice, (n_bases + 1) / 2
 struct LoadSeqBytes {
     const uint32_t *n_bases;
     __device__ uint64_t operator()(uint64_t p) const { return ((uint64_t)n_bases[p] + 1u) / 2u; }
-};
-// ... and of record k's, 0 at and behind min(*n_kept, n)
-struct LoadSeqRecBytes {
-    const inq_read_seq_t *recs;
-    const uint64_t *n_kept;
-    __device__ uint64_t operator()(uint64_t k) const { return k < *n_kept ? ((uint64_t)recs[k].n_bases + 1u) / 2u : 0u; }
 };
 struct LoadI64 {
     const int64_t *in;
@@ -612,14 +606,13 @@ void launch_scan_name_len(const uint8_t *u, uint64_t u_bytes, const uint64_t *re
                           uint64_t n, uint64_t *tmp, hipStream_t s) {
     run_scan<SumOp, LoadNameLen, true>(LoadNameLen{u, u_bytes, rec_off, n_valid}, out, n, tmp, s);
 }
-void launch_scan_origin_len(const inq_read_origin_t *origins, const uint64_t *n_kept, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s) {
-    run_scan<SumOp, LoadOriginLen, true>(LoadOriginLen{origins, n_kept}, out, n, tmp, s);
+template <class Rec> void launch_scan_run_bytes(const Rec *recs, const uint64_t *n_kept, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s) {
+    run_scan<SumOp, LoadRunBytes<Rec>, true>(LoadRunBytes<Rec>{recs, n_kept}, out, n, tmp, s);
 }
+template void launch_scan_run_bytes(const inq_read_origin_t *, const uint64_t *, uint64_t *, uint64_t, uint64_t *, hipStream_t);
+template void launch_scan_run_bytes(const inq_read_seq_t *, const uint64_t *, uint64_t *, uint64_t, uint64_t *, hipStream_t);
 void launch_scan_seq_bytes(const uint32_t *n_bases, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s) {
     run_scan<SumOp, LoadSeqBytes, true>(LoadSeqBytes{n_bases}, out, n, tmp, s);
-}
-void launch_scan_seq_rec_bytes(const inq_read_seq_t *recs, const uint64_t *n_kept, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s) {
-    run_scan<SumOp, LoadSeqRecBytes, true>(LoadSeqRecBytes{recs, n_kept}, out, n, tmp, s);
 }
 void launch_scan_max_i64(const int64_t *in, int64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s) {
     run_scan<MaxOp, LoadI64, false>(LoadI64{in}, out, n, (int64_t *)tmp, s);

@@ -330,8 +330,8 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     if (x.evidence && b->n_pairs && (!r->pair_call || !r->pair_bits)) return INQ_ERR_ARG;  // the counting reads both
     if (!x.kept_off != !x.kept || ((uintptr_t)x.kept & 15u) || ((uintptr_t)x.kept_off & 7u)) return INQ_ERR_ARG;
     if (x.kept && b->n_pairs && (!r->pair_call || !r->pair_bits)) return INQ_ERR_ARG;  // ... and so does the compaction
-    if (x.origins && (!x.kept || !x.origin_off || !x.name_off || ((uintptr_t)x.origins & 7u))) return INQ_ERR_ARG;  // who the records are
-    if (x.seq_recs && (!x.kept || !x.kept_pair || !x.seq_rec_off || !x.seq_qbeg || !x.seq_len || ((uintptr_t)x.seq_recs & 7u))) return INQ_ERR_ARG;
+    if (x.names.recs && (!x.kept || !x.names.off || !x.name_off || ((uintptr_t)x.names.recs & 7u))) return INQ_ERR_ARG;  // who the records are
+    if (x.seqs.recs && (!x.kept || !x.kept_pair || !x.seqs.off || !x.seq_qbeg || !x.seq_len || ((uintptr_t)x.seqs.recs & 7u))) return INQ_ERR_ARG;
     if (((uintptr_t)b->cigar & 15u) || ((uintptr_t)b->reads & 15u)) return INQ_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
@@ -402,20 +402,21 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
                           b->unphased != 0, s);
         HIP_TRY(c, hipGetLastError());
     }
-    if (x.origins && !b->n_pairs) HIP_TRY(c, hipMemsetAsync(x.origin_off, 0, 8, s));  // no record, no name byte
-    if (x.origins && b->n_pairs) {  // behind the scatter: an origin per record it wrote, then where each record's name will go
-        const uint64_t *const n_kept = x.kept_off + b->n_loci;
-        launch_read_origins(ReadOriginArgs{x.kept, n_kept, view.read_words, b->n_reads, x.name_off, x.origins, b->n_pairs}, s);
-        launch_scan_origin_len(x.origins, n_kept, x.origin_off, b->n_pairs, x.origin_off + b->n_pairs + 1, s);
-        HIP_TRY(c, hipGetLastError());
-    }
-    if (x.seq_recs && !b->n_pairs) HIP_TRY(c, hipMemsetAsync(x.seq_rec_off, 0, 8, s));  // no record, no base
-    if (x.seq_recs && b->n_pairs) {  // behind the scatter: the slice of the pair each record came from, then where its packed bytes will go
-        const uint64_t *const n_kept = x.kept_off + b->n_loci;
-        launch_read_seq_records(ReadSeqArgs{x.kept_pair, n_kept, x.seq_qbeg, x.seq_len, x.seq_recs, b->n_pairs}, s);
-        launch_scan_seq_rec_bytes(x.seq_recs, n_kept, x.seq_rec_off, b->n_pairs, x.seq_rec_off + b->n_pairs + 1, s);
-        HIP_TRY(c, hipGetLastError());
-    }
+    // The byte runs of a kind, behind the scatter: a record per record it wrote (`records`: the kind's own kernel), then where each
+    // record's bytes will go.  No pair: no record, no byte
+    const uint64_t *const n_kept = x.kept_off ? x.kept_off + b->n_loci : nullptr;
+    auto place_runs = [&](const auto &runs, auto &&records) {
+        if (!runs.recs) return hipSuccess;
+        if (!b->n_pairs) return hipMemsetAsync(runs.off, 0, 8, s);
+        records();
+        launch_scan_run_bytes(runs.recs, n_kept, runs.off, b->n_pairs, runs.off + b->n_pairs + 1, s);
+        return hipGetLastError();
+    };
+    // an origin per record (its read's descriptor and name length); the slice of the pair each record came from
+    const auto origins = [&] { launch_read_origins(ReadOriginArgs{x.kept, n_kept, view.read_words, b->n_reads, x.name_off, x.names.recs, b->n_pairs}, s); };
+    const auto slices = [&] { launch_read_seq_records(ReadSeqArgs{x.kept_pair, n_kept, x.seq_qbeg, x.seq_len, x.seqs.recs, b->n_pairs}, s); };
+    HIP_TRY(c, place_runs(x.names, origins));
+    HIP_TRY(c, place_runs(x.seqs, slices));
     if (ev) HIP_TRY(c, hipEventRecord(ev->e2, s));
     return INQ_OK;
 }
@@ -454,32 +455,26 @@ int inq_read_calls_fetch(inq_ctx_t *c, inq_read_call_t *out, uint64_t n) {
 
 uint32_t inq_read_name_tile(void) { return kReadNameTile; }
 
-static int read_origins_fetch_impl(inq_ctx_t *c, inq_read_origin_t *origins, uint64_t n, uint8_t *names, uint64_t name_bytes) {
-    if (!c || n > c->read_origins_total || name_bytes > c->read_names_total || (n && !origins) || (name_bytes && !names)) return INQ_ERR_ARG;
-    if (!n && !name_bytes) return INQ_OK;
+// the first n records (rec_size bytes each) and the first n_bytes bytes of the runs of one kind that the last flush left in c
+static int kept_runs_fetch(inq_ctx_t *c, KeptRuns inq_ctx::*kind, void *recs, uint64_t n, size_t rec_size, uint8_t *bytes, uint64_t n_bytes) {
+    if (!c) return INQ_ERR_ARG;
+    const KeptRuns *const k = &(c->*kind);
+    if (n > k->n_recs || n_bytes > k->n_bytes || (n && !recs) || (n_bytes && !bytes)) return INQ_ERR_ARG;
+    if (!n && !n_bytes) return INQ_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (n) HIP_TRY(c, hipMemcpyAsync(origins, c->rorigins.p, (size_t)n * sizeof(inq_read_origin_t), hipMemcpyDeviceToHost, c->stream));
-    if (name_bytes) HIP_TRY(c, hipMemcpyAsync(names, c->rnames.p, (size_t)name_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (n) HIP_TRY(c, hipMemcpyAsync(recs, k->recs.p, (size_t)n * rec_size, hipMemcpyDeviceToHost, c->stream));
+    if (n_bytes) HIP_TRY(c, hipMemcpyAsync(bytes, k->bytes.p, (size_t)n_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return INQ_OK;
 }
 int inq_read_origins_fetch(inq_ctx_t *c, inq_read_origin_t *origins, uint64_t n, uint8_t *names, uint64_t name_bytes) {
-    return guarded([&] { return read_origins_fetch_impl(c, origins, n, names, name_bytes); });
+    return guarded([&] { return kept_runs_fetch(c, &inq_ctx::rnames, origins, n, sizeof *origins, names, name_bytes); });
 }
 
 uint32_t inq_seq_window_tile(void) { return kSeqWindowTile; }
 
-static int read_seqs_fetch_impl(inq_ctx_t *c, inq_read_seq_t *seqs, uint64_t n, uint8_t *packed, uint64_t seq_bytes) {
-    if (!c || n > c->read_seqs_total || seq_bytes > c->read_seq_bytes_total || (n && !seqs) || (seq_bytes && !packed)) return INQ_ERR_ARG;
-    if (!n && !seq_bytes) return INQ_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (n) HIP_TRY(c, hipMemcpyAsync(seqs, c->rseqs.p, (size_t)n * sizeof(inq_read_seq_t), hipMemcpyDeviceToHost, c->stream));
-    if (seq_bytes) HIP_TRY(c, hipMemcpyAsync(packed, c->rseqbytes.p, (size_t)seq_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return INQ_OK;
-}
 int inq_read_seqs_fetch(inq_ctx_t *c, inq_read_seq_t *seqs, uint64_t n, uint8_t *packed, uint64_t seq_bytes) {
-    return guarded([&] { return read_seqs_fetch_impl(c, seqs, n, packed, seq_bytes); });
+    return guarded([&] { return kept_runs_fetch(c, &inq_ctx::rseqs, seqs, n, sizeof *seqs, packed, seq_bytes); });
 }
 
 // the window walk alone: the batch goes up as a call's does, two arrays come down
@@ -508,18 +503,18 @@ static int seq_windows_impl(inq_ctx_t *c, const inq_batch_t *b, const uint32_t *
         {&c->off, b->locus_pair_off, (size_t)(b->n_loci + 1) * 8},
         {&c->lstart, b->locus_start, (size_t)b->n_loci * 4},
         {&c->lend, b->locus_end, (size_t)b->n_loci * 4},
-        {&c->rseqoff, l_seq, l_seq ? (size_t)b->n_reads * 4 : 0},  // (scratch of the flushes' sequences, free between calls)
+        {&c->rseqs.off, l_seq, l_seq ? (size_t)b->n_reads * 4 : 0},  // (scratch of the flushes' sequences, free between calls)
     };
     for (auto &u : ups) {
         if ((rc = ensure(c, *u.d, u.bytes)) != INQ_OK) return rc;
         if (u.bytes) HIP_TRY(c, hipMemcpyAsync(u.d->p, u.h, u.bytes, hipMemcpyHostToDevice, s));
     }
-    if ((rc = ensure(c, c->rseqs, (size_t)b->n_pairs * 8)) != INQ_OK) return rc;  // q_beg[n_pairs], n_bases[n_pairs]
-    uint32_t *const d_qbeg = (uint32_t *)c->rseqs.p, *const d_len = d_qbeg + b->n_pairs;
+    if ((rc = ensure(c, c->rseqs.recs, (size_t)b->n_pairs * 8)) != INQ_OK) return rc;  // q_beg[n_pairs], n_bases[n_pairs]
+    uint32_t *const d_qbeg = (uint32_t *)c->rseqs.recs.p, *const d_len = d_qbeg + b->n_pairs;
     SeqWindowArgs a{(const uint4 *)c->cigar.p, b->n_cigar_words / 4, (const uint4 *)c->reads.p, b->n_reads, (const uint32_t *)c->pair_read.p,
                     (const uint64_t *)c->off.p, (const uint32_t *)c->lstart.p, (const uint32_t *)c->lend.p, b->n_loci, b->n_pairs, SeqLenSource{},
                     d_qbeg, d_len};
-    if (l_seq) a.len.l_seq = (const uint32_t *)c->rseqoff.p;
+    if (l_seq) a.len.l_seq = (const uint32_t *)c->rseqs.off.p;
     launch_seq_window(a, s);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(q_beg, d_qbeg, (size_t)b->n_pairs * 4, hipMemcpyDeviceToHost, s));
@@ -883,21 +878,24 @@ int inq::extras_prepare(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const Hos
     d->evidence = h.evidence ? (inq_locus_evidence_t *)c->levidence.p : nullptr;
     d->kept_off = h.kept_off ? (uint64_t *)c->rcoff.p : nullptr;
     d->kept = h.kept_off ? (inq_read_call_t *)c->rckept.p : nullptr;
-    if (h.name_bytes) {  // (the batch's own names, LocusExtras::name_off, are the caller's to set: only a deferred batch has them)
+    // a kind's records and the scan of their byte lengths (the batch's own names and slices, LocusExtras::name_off, seq_qbeg / seq_len,
+    // are the caller's to set: only a deferred batch has them)
+    auto runs = [&](KeptRuns &k, auto &out) -> int {
+        if ((rc = ensure(c, k.recs, (size_t)n_pairs * sizeof *out.recs)) != INQ_OK) return rc;
+        if ((rc = ensure(c, k.off, (size_t)(n_pairs + 1 + scan_tmp_words(std::max<uint64_t>(n_pairs, 1))) * 8)) != INQ_OK) return rc;
+        out.recs = (decltype(out.recs))k.recs.p;
+        out.off = (uint64_t *)k.off.p;
+        return INQ_OK;
+    };
+    if (h.name_bytes) {
         if (!h.kept_off) return INQ_ERR_ARG;
-        if ((rc = ensure(c, c->rorigins, (size_t)n_pairs * sizeof(inq_read_origin_t))) != INQ_OK) return rc;
-        if ((rc = ensure(c, c->rnameoff, (size_t)(n_pairs + 1 + scan_tmp_words(std::max<uint64_t>(n_pairs, 1))) * 8)) != INQ_OK) return rc;
-        d->origins = (inq_read_origin_t *)c->rorigins.p;
-        d->origin_off = (uint64_t *)c->rnameoff.p;
+        if ((rc = runs(c->rnames, d->names)) != INQ_OK) return rc;
     }
-    if (h.seq_bytes) {  // (the batch's own slices, LocusExtras::seq_qbeg / seq_len, are the caller's to set, like its names)
+    if (h.seq_bytes) {
         if (!h.kept_off || !h.name_bytes) return INQ_ERR_ARG;
         if ((rc = ensure(c, c->rkeptpair, (size_t)n_pairs * 8)) != INQ_OK) return rc;
-        if ((rc = ensure(c, c->rseqs, (size_t)n_pairs * sizeof(inq_read_seq_t))) != INQ_OK) return rc;
-        if ((rc = ensure(c, c->rseqoff, (size_t)(n_pairs + 1 + scan_tmp_words(std::max<uint64_t>(n_pairs, 1))) * 8)) != INQ_OK) return rc;
+        if ((rc = runs(c->rseqs, d->seqs)) != INQ_OK) return rc;
         d->kept_pair = (uint64_t *)c->rkeptpair.p;
-        d->seq_recs = (inq_read_seq_t *)c->rseqs.p;
-        d->seq_rec_off = (uint64_t *)c->rseqoff.p;
     }
     return INQ_OK;
 }
@@ -909,30 +907,32 @@ int inq::extras_download(inq_ctx *c, uint64_t n_loci, const HostExtras &h, const
     return INQ_OK;
 }
 
-int inq::extras_names(inq_ctx *c, uint64_t n_pairs, const HostExtras &h, const LocusExtras &d, uint64_t n_kept, const uint8_t *batch_names,
-                      uint64_t batch_name_bytes, uint64_t n_reads, const uint8_t *batch_seqs, uint64_t batch_seq_bytes,
-                      const uint64_t *batch_seq_off, hipStream_t s) {
-    if (h.name_bytes) *h.name_bytes = 0;
-    if (h.seq_bytes) *h.seq_bytes = 0;
+int inq::extras_names(inq_ctx *c, uint64_t n_pairs, uint64_t n_kept, const HostExtras &h, const LocusExtras &d, const RunSource &names,
+                      const RunSource &seqs, hipStream_t s) {
+    // per kind: where its byte total goes (null: not asked for), the scan it sits behind, where the runs come from and where they go
+    const struct {
+        uint64_t *total;
+        const uint64_t *off;
+        const RunSource &src;
+        DevBuf &dst;
+    } kinds[] = {{h.name_bytes, d.names.off, names, c->rnames.bytes}, {h.seq_bytes, d.seqs.off, seqs, c->rseqs.bytes}};
+    for (auto &k : kinds)
+        if (k.total) *k.total = 0;
     if (!h.name_bytes || !n_pairs || !n_kept) return INQ_OK;
-    // (each scan's total sits behind its last element; nothing else is in flight on s: plain 8-byte copies, one wait for both)
-    uint64_t *const total = h.name_bytes;
-    HIP_TRY(c, hipMemcpyAsync(total, d.origin_off + n_pairs, 8, hipMemcpyDeviceToHost, s));
-    if (h.seq_bytes) HIP_TRY(c, hipMemcpyAsync(h.seq_bytes, d.seq_rec_off + n_pairs, 8, hipMemcpyDeviceToHost, s));
+    // (each scan's total sits behind its last element; nothing else is in flight on s: plain 8-byte copies, one wait for all)
+    for (auto &k : kinds)
+        if (k.total) HIP_TRY(c, hipMemcpyAsync(k.total, k.off + n_pairs, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    const uint64_t seq_total = h.seq_bytes ? *h.seq_bytes : 0;
-    if (!*total && !seq_total) return INQ_OK;
-    int rc;
-    if (*total) {
-        if ((rc = ensure(c, c->rnames, (size_t)*total)) != INQ_OK) return rc;
-        launch_name_copy(NameCopyArgs{batch_names, batch_name_bytes, d.name_off, n_reads, 0, d.kept, (uint8_t *)c->rnames.p, *total, d.origin_off,
-                                      std::min(n_kept, n_pairs)}, s);
+    bool any = false;
+    for (auto &k : kinds) {
+        if (!k.total || !*k.total) continue;
+        const int rc = ensure(c, k.dst, (size_t)*k.total);
+        if (rc != INQ_OK) return rc;
+        launch_name_copy(NameCopyArgs{k.src.bytes, k.src.n_bytes, k.src.off, k.src.n, 0, k.src.by_pair ? nullptr : d.kept, (uint8_t *)k.dst.p,
+                                      *k.total, k.off, std::min(n_kept, n_pairs), k.src.by_pair ? d.kept_pair : nullptr}, s);
+        any = true;
     }
-    if (seq_total) {  // the kept records' packed slices: segment k out of the batch's at seq_off[kept_pair[k]]
-        if ((rc = ensure(c, c->rseqbytes, (size_t)seq_total)) != INQ_OK) return rc;
-        launch_name_copy(NameCopyArgs{batch_seqs, batch_seq_bytes, batch_seq_off, n_pairs, 0, nullptr, (uint8_t *)c->rseqbytes.p, seq_total,
-                                      d.seq_rec_off, std::min(n_kept, n_pairs), d.kept_pair}, s);
-    }
+    if (!any) return INQ_OK;
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(s));
     return INQ_OK;
@@ -942,6 +942,6 @@ void inq::extras_finish(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const Hos
     if (!h.kept_off) return;
     if (!n_loci) h.kept_off[0] = 0;  // (nothing was launched: no list, no record)
     if (err == 0) c->read_calls_total = std::min<uint64_t>(h.kept_off[n_loci], n_pairs);
-    if (h.name_bytes && err == 0) c->read_origins_total = c->read_calls_total, c->read_names_total = *h.name_bytes;
-    if (h.seq_bytes && err == 0) c->read_seqs_total = c->read_calls_total, c->read_seq_bytes_total = *h.seq_bytes;
+    if (h.name_bytes && err == 0) c->rnames.n_recs = c->read_calls_total, c->rnames.n_bytes = *h.name_bytes;
+    if (h.seq_bytes && err == 0) c->rseqs.n_recs = c->read_calls_total, c->rseqs.n_bytes = *h.seq_bytes;
 }

@@ -26,6 +26,16 @@ struct EvTriple {
     hipEvent_t e0, e1, e2;
 };
 
+// The byte runs behind the kept records of a flush, one kind each (the names: read_names.hip; the packed bases: read_seqs.hip): one
+// 8-byte record per kept record, the exclusive scan of the records' byte lengths with its tile totals behind it, the runs back to back
+// in the records' order.  They stay until the context's next call (inq_read_origins_fetch, inq_read_seqs_fetch).  Allocated by flushes
+// that ask for the kind only
+struct KeptRuns {
+    DevBuf recs, off, bytes;
+    uint64_t n_recs = 0, n_bytes = 0;  // records and bytes the last flush offers (0: it had none of this kind)
+    auto bufs() { return std::array{&recs, &off, &bytes}; }
+};
+
 struct SpanState;  // device front end (span.hip)
 
 }  // namespace inq
@@ -46,22 +56,18 @@ struct inq_ctx {
     // which stay until the context's next call (inq_read_calls_fetch).  Allocated by calls with the lists only
     inq::DevBuf rctiles, rcoff, rckept;
     uint64_t read_calls_total = 0;  // records of the last host-buffer call or flush (0: it had no lists)
-    // the names and origins of those records (read_names.hip; inq_call_flush_origins): one origin per record, the scan of their name
-    // lengths with its tile totals, the names back to back.  They stay until the context's next call (inq_read_origins_fetch).
-    // Allocated by flushes with origins only
-    inq::DevBuf rorigins, rnameoff, rnames;
-    uint64_t read_origins_total = 0, read_names_total = 0;  // origins and name bytes of the last flush (0: it had no origins)
-    // the bases behind those records (read_seqs.hip; inq_call_flush_seqs): the pair each record came from, one inq_read_seq_t per record,
-    // the scan of their packed lengths with its tile totals, the packed slices back to back.  They stay until the context's next call
-    // (inq_read_seqs_fetch).  Allocated by flushes with sequences only
-    inq::DevBuf rkeptpair, rseqs, rseqoff, rseqbytes;
-    uint64_t read_seqs_total = 0, read_seq_bytes_total = 0;  // records and packed bytes of the last flush (0: it had no sequences)
+    // who those records are and the bases behind them (inq_call_flush_origins, inq_call_flush_seqs): the records of rnames are
+    // inq_read_origin_t, those of rseqs inq_read_seq_t; rkeptpair: the pair each record came from, which only the bases are indexed by
+    inq::KeptRuns rnames, rseqs;
+    inq::DevBuf rkeptpair;
     inq::DevBuf ovalues, olen, oflags, okeep, otrans;  // inq_outlier_rows
     // every DevBuf above, for inq_ctx_destroy (DevBuf frees nothing itself): a member missing here leaks
     auto bufs() {
-        return std::array{&worklist, &sval, &smeta, &deep, &cigar, &reads, &pair_read, &off, &lstart, &lend, &p1, &p2, &pcall, &pbits, &lflags,
-                          &levidence, &evwork, &rctiles, &rcoff, &rckept, &rorigins, &rnameoff, &rnames, &rkeptpair, &rseqs, &rseqoff,
-                          &rseqbytes, &ovalues, &olen, &oflags, &okeep, &otrans};
+        std::vector<inq::DevBuf *> all{&worklist, &sval, &smeta, &deep, &cigar, &reads, &pair_read, &off, &lstart, &lend, &p1, &p2, &pcall, &pbits,
+                                       &lflags, &levidence, &evwork, &rctiles, &rcoff, &rckept, &rkeptpair, &ovalues, &olen, &oflags, &okeep, &otrans};
+        for (inq::KeptRuns *k : {&rnames, &rseqs})
+            for (inq::DevBuf *b : k->bufs()) all.push_back(b);
+        return all;
     }
     uint32_t n_cus = 0;        // compute units of the device
     uint32_t grid_tail = 256;  // workgroups of the persistent locus_call_tail: they meet at grid barriers, so never more than n_cus
@@ -168,18 +174,28 @@ struct LocusExtras {
     inq_locus_evidence_t *evidence = nullptr;  // [n_loci]
     uint64_t *kept_off = nullptr;              // [n_loci + 1] the per-read Calls: offsets ...
     inq_read_call_t *kept = nullptr;           // [n_pairs] ... and records; both or neither
-    // the origins of those records (needs kept): one per record, and origin_off[n_pairs + 1 + scan_tmp_words(n_pairs)], the exclusive
-    // scan of their name lengths (origin_off[n_pairs] = the total) with the scan's tile totals behind it; name_off: the batch's names
-    inq_read_origin_t *origins = nullptr;
-    uint64_t *origin_off = nullptr;
-    const uint64_t *name_off = nullptr;        // [n_reads + 1]
-    // the bases behind those records (needs kept): kept_pair[n_pairs], the pair each record came from, written by the compaction's
-    // scatter; one seq_recs per record; seq_rec_off laid out like origin_off, the scan of their packed lengths; seq_qbeg / seq_len:
+    // the byte runs behind those records (need kept), per kind: one record per kept record, and off[n_pairs + 1 + scan_tmp_words(n_pairs)],
+    // the exclusive scan of the records' run_bytes() (off[n_pairs] = the total) with the scan's tile totals behind it
+    template <class Rec> struct Runs {
+        Rec *recs = nullptr;
+        uint64_t *off = nullptr;
+    };
+    Runs<inq_read_origin_t> names;       // who the records are; name_off: the batch's names
+    const uint64_t *name_off = nullptr;  // [n_reads + 1]
+    // the bases behind them; kept_pair[n_pairs]: the pair each record came from, written by the compaction's scatter; seq_qbeg / seq_len:
     // the batch's slices, per pair
+    Runs<inq_read_seq_t> seqs;
     uint64_t *kept_pair = nullptr;
-    inq_read_seq_t *seq_recs = nullptr;
-    uint64_t *seq_rec_off = nullptr;
     const uint32_t *seq_qbeg = nullptr, *seq_len = nullptr;  // [n_pairs]
+};
+// Where a flush takes the runs of one kind from, the deferred batch's (SpanState::Acc hands them over): n runs back to back in `bytes`,
+// run i at off[i].  by_pair: a kept record's run is that of the pair it came from (the bases), else that of its read (the names)
+struct RunSource {
+    const uint8_t *bytes;
+    uint64_t n_bytes;
+    const uint64_t *off;  // [n + 1]
+    uint64_t n;
+    bool by_pair;
 };
 // ... and as a host-buffer call or a flush takes them: HOST pointers, [n_loci] / [n_loci] / [n_loci + 1] in the call's locus order, each
 // may be null.  The records behind kept_off stay in context scratch (inq_read_calls_fetch).
@@ -196,19 +212,18 @@ struct HostExtras {
 // The three steps of a host-buffer call or a flush around its launch sequence.  First of all extras_reset: the records of the call
 // before are no longer offered, however this one ends.
 inline void extras_reset(inq_ctx *c) {
-    c->read_calls_total = c->read_origins_total = c->read_names_total = c->read_seqs_total = c->read_seq_bytes_total = 0;
+    c->read_calls_total = 0;
+    for (KeptRuns *k : {&c->rnames, &c->rseqs}) k->n_recs = k->n_bytes = 0;
 }
 // the context buffers behind what h asks for (and pcall / pbits where h.per_pair()), as device pointers
 int extras_prepare(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const HostExtras &h, LocusExtras *d);
 // enqueues the copies down on s; the flags go to flags_dst (the caller's array, or page-locked staging on their way there)
 int extras_download(inq_ctx *c, uint64_t n_loci, const HostExtras &h, const LocusExtras &d, uint8_t *flags_dst, hipStream_t s);
-// a flush with origins, after its synchronisation (n_kept = kept_off[n_loci] is known then): the bytes of the kept records' names come
-// down (*h.name_bytes), c->rnames is sized from them, the copy launch runs and is waited for.  Without origins, pairs or records:
-// nothing.  A flush with sequences: the bytes of the kept records' packed slices come down in the same readback (*h.seq_bytes) and
-// their copy runs beside the names'; batch_seqs / batch_seq_off: the batch's packed slices and seq_off[n_pairs + 1]
-int extras_names(inq_ctx *c, uint64_t n_pairs, const HostExtras &h, const LocusExtras &d, uint64_t n_kept, const uint8_t *batch_names,
-                 uint64_t batch_name_bytes, uint64_t n_reads, const uint8_t *batch_seqs, uint64_t batch_seq_bytes, const uint64_t *batch_seq_off,
-                 hipStream_t s);
+// a flush with origins, after its synchronisation (n_kept = kept_off[n_loci] is known then): the byte totals of the kinds asked for
+// come down with one wait (*h.name_bytes, *h.seq_bytes), the context's byte buffers are sized from them, one copy launch per kind runs
+// out of the batch's runs (names, seqs) and they are waited for once.  Without origins, pairs or records: nothing
+int extras_names(inq_ctx *c, uint64_t n_pairs, uint64_t n_kept, const HostExtras &h, const LocusExtras &d, const RunSource &names,
+                 const RunSource &seqs, hipStream_t s);
 // after the call's synchronisation, or at once for a call without loci: how many records inq_read_calls_fetch offers.  err: the
 // kernels' status word - after a domain error the lists are unspecified and none is offered, whatever the offsets say
 void extras_finish(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const HostExtras &h, uint32_t err);

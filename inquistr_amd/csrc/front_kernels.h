@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/inquistr_hip.h"
+#include "run_bytes.h"
 
 namespace inq {
 
@@ -108,12 +109,10 @@ void launch_scan_cigar_units(const inq_read_t *reads, const unsigned long long *
 // to the inflated bytes, for i < *n_valid, else 0 ...
 void launch_scan_name_len(const uint8_t *u, uint64_t u_bytes, const uint64_t *rec_off, const unsigned long long *n_valid, uint64_t *out,
                           uint64_t n, uint64_t *tmp, hipStream_t s);
-// ... and name_len of origin k for k < *n_kept (DEVICE), else 0
-void launch_scan_origin_len(const inq_read_origin_t *origins, const uint64_t *n_kept, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s);
 // read sequences (read_seqs.hip packs what these place): (n_bases[p] + 1) / 2 of every pair ...
 void launch_scan_seq_bytes(const uint32_t *n_bases, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s);
-// ... and of record k for k < *n_kept (DEVICE), else 0
-void launch_scan_seq_rec_bytes(const inq_read_seq_t *recs, const uint64_t *n_kept, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s);
+// the kept records' runs (run_bytes.h): run_bytes(recs[k]) for k < *n_kept (DEVICE), else 0; Rec: inq_read_origin_t, inq_read_seq_t
+template <class Rec> void launch_scan_run_bytes(const Rec *recs, const uint64_t *n_kept, uint64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s);
 void launch_scan_max_i64(const int64_t *in, int64_t *out, uint64_t n, uint64_t *tmp, hipStream_t s);
 inline uint64_t scan_tmp_words(uint64_t n) { return (n + 4095) / 4096 + 2; }
 

@@ -5,21 +5,20 @@
 //   flush time  for the kept records only, out of the batch's names into context scratch, behind read_call_scatter: what crosses
 //               PCIe is proportional to the table, not to the BAM
 // Both are ONE kernel, name_copy_kernel, over (source offset, destination offset, length) triples.  The destination offsets are an
-// exclusive prefix sum of the lengths (bam_scan.hip's scan templates through LoadNameLen / LoadOriginLen), so segment i's length is
+// exclusive prefix sum of the lengths (bam_scan.hip's scan templates through LoadNameLen / LoadRunBytes), so segment i's length is
 // dst_off[i + 1] - dst_off[i] and the segments tile the destination without gap or overlap.
 //
 // Layout: kReadNameLanes = 8 lanes per segment, 32 segments per 256-thread workgroup (kReadNameTile).  A name is 0 - 254 bytes,
 // typically 10 - 60: a wave per segment would leave 50 of 64 lanes idle, a lane per segment would serialise 60 dependent byte
-// moves.  Eight lanes move 32 bytes a step as aligned words of the DESTINATION (the source is read with unaligned word loads); the
-// up to three bytes in front of the first whole word and behind the last go one by one, since the word they lie in is shared with
-// the neighbouring segment, whose lanes write it at the same time.  No atomics, no LDS, no workgroup waits for another; every output
-// byte is a plain function of the inputs.
+// moves.  Eight lanes move 32 bytes a step as aligned words of the DESTINATION (store_segment of segment_store.h; the source is read
+// with unaligned word loads).  No atomics, no LDS, no workgroup waits for another; every output byte is a plain function of the inputs.
 //
 // Bounds hold whatever the offsets and lengths are: a segment is cut to what the destination and the source hold before a byte of
 // it moves, and an index outside the source's offsets copies nothing.
 #include <hip/hip_runtime.h>
 
 #include "read_calls.h"
+#include "segment_store.h"
 
 namespace inq {
 namespace {
@@ -43,18 +42,13 @@ __global__ __launch_bounds__(256) void name_copy_kernel(NameCopyArgs a) {
         uint64_t len = d1 - d0;
         if (len > a.src_bytes - s0) len = a.src_bytes - s0;
         const uint8_t *src = a.src + s0;
-        uint8_t *dst = a.dst + d0;
-        // [0, head): up to the destination's first word boundary; then n_words whole words; then what is left (< 4 bytes)
-        uint64_t head = (4u - (uint32_t)((uintptr_t)dst & 3u)) & 3u;
-        if (head > len) head = len;
-        const uint64_t n_words = (len - head) / 4u, tail = head + n_words * 4u;
-        if (sub < head) dst[sub] = src[sub];
-        for (uint64_t w = sub; w < n_words; w += kReadNameLanes) {
-            uint32_t v;
-            __builtin_memcpy(&v, src + head + w * 4u, 4);  // the source lies wherever the record does
-            *reinterpret_cast<uint32_t *>(dst + head + w * 4u) = v;
-        }
-        if (tail + sub < len) dst[tail + sub] = src[tail + sub];
+        store_segment<kReadNameLanes>(
+            a.dst + d0, len, sub, [&](uint64_t d) { return src[d]; },
+            [&](uint64_t d) {
+                uint32_t v;
+                __builtin_memcpy(&v, src + d, 4);  // the source lies wherever the record does
+                return v;
+            });
     }
 }
 
@@ -73,19 +67,18 @@ __global__ __launch_bounds__(256) void read_origin_kernel(ReadOriginArgs a) {
     }
 }
 
-// one workgroup per tile up to 2^20 of them, the rest by stride
-uint32_t capped_grid(uint64_t tiles) { return (uint32_t)(tiles < (1u << 20) ? tiles : (1u << 20)); }
+constexpr uint32_t kGridCap = 1u << 20;  // workgroups of a launch (capped_grid)
 
 }  // namespace
 
 void launch_name_copy(const NameCopyArgs &a, hipStream_t s) {
     if (!a.n) return;
-    hipLaunchKernelGGL(name_copy_kernel, dim3(capped_grid((a.n + kReadNameTile - 1) / kReadNameTile)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(name_copy_kernel, dim3(capped_grid((a.n + kReadNameTile - 1) / kReadNameTile, kGridCap)), dim3(kThreads), 0, s, a);
 }
 
 void launch_read_origins(const ReadOriginArgs &a, hipStream_t s) {
     if (!a.n_pairs) return;
-    hipLaunchKernelGGL(read_origin_kernel, dim3(capped_grid((a.n_pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(read_origin_kernel, dim3(capped_grid((a.n_pairs + kThreads - 1) / kThreads, kGridCap)), dim3(kThreads), 0, s, a);
 }
 
 }  // namespace inq

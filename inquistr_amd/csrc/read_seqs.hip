@@ -22,6 +22,7 @@
 
 #include "cigar_walk.h"
 #include "read_seqs.h"
+#include "segment_store.h"
 
 namespace inq {
 namespace {
@@ -197,31 +198,17 @@ __global__ __launch_bounds__(256) void seq_slice_kernel(SeqSliceArgs a) {
         const uint64_t end = q + n < src.n_bases ? q + n : src.n_bases;
         auto base_at = [&](uint64_t k) -> uint32_t { return k < end ? (src.seq[k >> 1] >> ((~k & 1u) * 4u)) & 15u : 0u; };
         auto byte_at = [&](uint64_t d) -> uint8_t { return (uint8_t)(base_at(q + 2u * d) << 4 | base_at(q + 2u * d + 1u)); };
-        uint8_t *dst = a.dst + d0;
-        // [0, head): up to the destination's first word boundary; then n_words whole words; then what is left (< 4 bytes).  The bytes
-        // in front of the first whole word and behind the last go one by one: the word they lie in is shared with the neighbouring
-        // segment, whose lanes write it at the same time
-        uint64_t head = (4u - (uint32_t)((uintptr_t)dst & 3u)) & 3u;
-        if (head > len) head = len;
-        const uint64_t n_words = (len - head) / 4u, tail = head + n_words * 4u;
-        if (sub < head) dst[sub] = byte_at(sub);
-        for (uint64_t w = sub; w < n_words; w += kSeqSliceLanes) {  // (a soft clip in the window is tens of kilobases: the lanes stride)
-            const uint64_t d = head + w * 4u, k = q + 2u * d;
-            uint32_t v;
-            if (k + 9u <= end) {  // all eight bases and the one behind them are the record's: five source bytes at most
-                const uint8_t *s = src.seq + (k >> 1);
-                if (k & 1u) {
-                    const uint64_t x = (uint64_t)load_le32(s) | (uint64_t)s[4] << 32;
-                    v = ((uint32_t)x & 0x0f0f0f0fu) << 4 | ((uint32_t)(x >> 12) & 0x0f0f0f0fu);
-                } else {
-                    v = load_le32(s);
-                }
-            } else {
-                v = (uint32_t)byte_at(d) | (uint32_t)byte_at(d + 1u) << 8 | (uint32_t)byte_at(d + 2u) << 16 | (uint32_t)byte_at(d + 3u) << 24;
-            }
-            *reinterpret_cast<uint32_t *>(dst + d) = v;
-        }
-        if (tail + sub < len) dst[tail + sub] = byte_at(tail + sub);
+        // (a soft clip in the window is tens of kilobases: the lanes stride over the words)
+        store_segment<kSeqSliceLanes>(a.dst + d0, len, sub, byte_at, [&](uint64_t d) -> uint32_t {
+            const uint64_t k = q + 2u * d;
+            if (k + 9u > end)
+                return (uint32_t)byte_at(d) | (uint32_t)byte_at(d + 1u) << 8 | (uint32_t)byte_at(d + 2u) << 16 | (uint32_t)byte_at(d + 3u) << 24;
+            // all eight bases and the one behind them are the record's: five source bytes at most
+            const uint8_t *s = src.seq + (k >> 1);
+            if (!(k & 1u)) return load_le32(s);
+            const uint64_t x = (uint64_t)load_le32(s) | (uint64_t)s[4] << 32;
+            return ((uint32_t)x & 0x0f0f0f0fu) << 4 | ((uint32_t)(x >> 12) & 0x0f0f0f0fu);
+        });
     }
 }
 
@@ -235,24 +222,23 @@ __global__ __launch_bounds__(256) void read_seq_record_kernel(ReadSeqArgs a) {
     }
 }
 
-// one workgroup per tile up to 2^16 of them, the rest by stride
-uint32_t capped_grid(uint64_t tiles) { return (uint32_t)(tiles < (1u << 16) ? tiles : (1u << 16)); }
+constexpr uint32_t kGridCap = 1u << 16;  // workgroups of a launch (capped_grid)
 
 }  // namespace
 
 void launch_seq_window(const SeqWindowArgs &a, hipStream_t s) {
     if (!a.n_pairs) return;
-    hipLaunchKernelGGL(seq_window_kernel, dim3(capped_grid((a.n_pairs + kSeqWindowTile - 1) / kSeqWindowTile)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(seq_window_kernel, dim3(capped_grid((a.n_pairs + kSeqWindowTile - 1) / kSeqWindowTile, kGridCap)), dim3(kThreads), 0, s, a);
 }
 
 void launch_seq_slice(const SeqSliceArgs &a, hipStream_t s) {
     if (!a.n_pairs) return;
-    hipLaunchKernelGGL(seq_slice_kernel, dim3(capped_grid((a.n_pairs + kSeqSliceTile - 1) / kSeqSliceTile)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(seq_slice_kernel, dim3(capped_grid((a.n_pairs + kSeqSliceTile - 1) / kSeqSliceTile, kGridCap)), dim3(kThreads), 0, s, a);
 }
 
 void launch_read_seq_records(const ReadSeqArgs &a, hipStream_t s) {
     if (!a.n_pairs) return;
-    hipLaunchKernelGGL(read_seq_record_kernel, dim3(capped_grid((a.n_pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(read_seq_record_kernel, dim3(capped_grid((a.n_pairs + kThreads - 1) / kThreads, kGridCap)), dim3(kThreads), 0, s, a);
 }
 
 }  // namespace inq

@@ -78,28 +78,40 @@ struct SpanState {
     // the batch the last inq_call_span built
     uint64_t n_reads = 0, n_cigar_words = 0, n_pairs = 0, n_loci = 0;
     bool last_from_acc = false;
-    bool last_names = false;  // that batch was appended with names (inq_span_fetch_names) ...
-    uint64_t n_name_bytes = 0;  // ... this many bytes of them
-    bool last_seqs = false;     // ... and with sequences (inq_span_fetch_seqs),
-    uint64_t n_seq_bytes = 0;   // this many packed bytes
+    // what a span is called for: at once, or appended to the deferred batch - bare, with its reads' names, or with the names and every
+    // pair's bases (each level needs the one before)
+    enum class Use { kCall, kDefer, kDeferNames, kDeferSeqs };
+    // a batch's byte runs of one kind: whether its spans were appended with them (every span of a batch, or none), and how many bytes
+    struct RunsState {
+        bool on = false;
+        uint64_t n_bytes = 0;
+    };
+    RunsState last_names, last_seqs;  // of that batch, where a flush built it (inq_span_fetch_names, inq_span_fetch_seqs)
     // inq_call_span_deferred: the batches of several spans appended to one (CIGAR units, reads, pairs, loci so far), called
     // together by inq_call_flush - a span of SEQ-bearing records holds a few hundred loci, far too few to fill the chip
     struct Acc {
         DevBuf cigar, reads, pair_read, off, lstart, lend;
-        // a batch appended with names (inq_call_span_deferred_names): the names of its reads back to back, name_off[n_reads + 1]
-        DevBuf names, name_off;
-        // ... with sequences (inq_call_span_deferred_seqs): per pair the slice (seq_qbeg, seq_len) and seq_off[n_pairs + 1], where its
-        // packed bytes begin in seqs
-        DevBuf seqs, seq_off, seq_qbeg, seq_len;
+        struct Runs : RunsState {
+            DevBuf bytes, off;  // the runs back to back; off[n + 1], where each begins
+            RunSource source(uint64_t n, bool by_pair) const { return RunSource{(const uint8_t *)bytes.p, n_bytes, (const uint64_t *)off.p, n, by_pair}; }
+        };
+        // a batch appended with names (inq_call_span_deferred_names): one run per read; with sequences (inq_call_span_deferred_seqs):
+        // one run per pair, the packed bases of its slice (seq_qbeg, seq_len)
+        Runs names, seqs;
+        DevBuf seq_qbeg, seq_len;
         uint64_t n_units = 0, n_reads = 0, n_pairs = 0, n_loci = 0, n_spans = 0;
         uint32_t minlen = 0, support = 0, unphased = 0, max_reads = 0;
-        uint64_t n_name_bytes = 0;
-        bool with_names = false;  // every span of the batch, or none
-        uint64_t n_seq_bytes = 0;
-        bool with_seqs = false;  // likewise
-        auto bufs() { return std::array{&cigar, &reads, &pair_read, &off, &lstart, &lend, &names, &name_off, &seqs, &seq_off, &seq_qbeg, &seq_len}; }
+        Use use = Use::kDefer;  // of every span of the batch
+        auto bufs() {
+            return std::array{&cigar, &reads, &pair_read, &off, &lstart, &lend, &names.bytes, &names.off, &seqs.bytes, &seqs.off, &seq_qbeg, &seq_len};
+        }
         // the batch is gone, its buffers stay
-        void reset() { *this = Acc{cigar, reads, pair_read, off, lstart, lend, names, name_off, seqs, seq_off, seq_qbeg, seq_len}; }
+        void reset() {
+            Acc fresh;
+            const auto mine = bufs(), theirs = fresh.bufs();
+            for (size_t i = 0; i < mine.size(); ++i) *theirs[i] = *mine[i];
+            *this = fresh;
+        }
     } acc;
 };
 
@@ -312,11 +324,25 @@ int bgzf_inflate_impl(inq_ctx *c, const uint8_t *comp, uint64_t comp_bytes, cons
     return S->h->st.inflate ? INQ_ERR_INFLATE : INQ_OK;
 }
 
-// defer: the span's batch is appended to S->acc instead of being called (r may be null then)
-// names: with the names of the span's placed records (deferred only); seqs: and with every pair's slice of SEQ (with names only)
-int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_stats_t *stats, int slot, bool defer = false, bool names = false,
-                   bool seqs = false) {
-    if (!c || !sp || (!r && !defer) || slot >= INQ_SPAN_SLOTS || (names && !defer) || (seqs && !names)) return INQ_ERR_ARG;
+// One span's runs of a kind appended to the batch's: room for its bytes behind those that are there, room for its n + 1 offsets behind
+// the batch's n_before (of the first span of a batch nothing is kept: off[0] is written with the span's offsets), then
+// off[n_before + i] = the batch's bytes so far + span_off[i], so that off[n_before + n] is where the next span's begin.  The gather of
+// the bytes themselves, to bytes + n_bytes, is the caller's next launch; n_bytes grows once the span is in
+int append_runs(inq_ctx *c, SpanState::Acc::Runs &R, bool first_span, uint64_t n_before, uint64_t n, uint64_t span_bytes, const uint64_t *span_off,
+                hipStream_t s) {
+    int rc;
+    if ((rc = ensure_keep(c, R.bytes, R.n_bytes + span_bytes, R.n_bytes, s)) != INQ_OK) return rc;
+    if ((rc = ensure_keep(c, R.off, (n_before + n + 1) * 8, first_span ? 0 : (n_before + 1) * 8, s)) != INQ_OK) return rc;
+    launch_offset_copy((uint64_t *)R.off.p + n_before, span_off, n + 1, R.n_bytes, s);
+    return INQ_OK;
+}
+
+// use: the span's batch is called at once, or appended to S->acc instead (r may be null then) - bare, with the names of the span's
+// placed records, or with those and every pair's slice of SEQ
+int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_stats_t *stats, int slot, SpanState::Use use = SpanState::Use::kCall) {
+    using Use = SpanState::Use;
+    const bool defer = use >= Use::kDefer, names = use >= Use::kDeferNames, seqs = use >= Use::kDeferSeqs;
+    if (!c || !sp || (!r && !defer) || slot >= INQ_SPAN_SLOTS) return INQ_ERR_ARG;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (sp->reserved || sp->unphased > 1) return INQ_ERR_ARG;
     if (sp->n_loci && (!sp->locus_tid || !sp->locus_start || !sp->locus_end || (!defer && (!r->phase1 || !r->phase2)))) return INQ_ERR_ARG;
@@ -345,8 +371,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     const uint64_t nl = sp->n_loci, na = sp->n_anchors;
     SpanState::Acc &A = S->acc;
     if (defer && A.n_spans && (A.minlen != sp->minlen || A.support != sp->support || A.unphased != sp->unphased)) return INQ_ERR_ARG;
-    if (defer && A.n_spans && A.with_names != names) return INQ_ERR_ARG;  // all spans of a batch with names, or all without
-    if (defer && A.n_spans && A.with_seqs != seqs) return INQ_ERR_ARG;    // ... and with sequences
+    if (defer && A.n_spans && A.use != use) return INQ_ERR_ARG;  // all spans of a batch with names, or all without; likewise the sequences
     const SpanState::Stage *staged = nullptr;
     if (slot >= 0) {  // the span inq_span_stage put there, and nothing else
         const SpanState::Stage &g = S->stage[slot];
@@ -489,11 +514,6 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
         clock.at("  batch CIGAR buffer ready");
         if ((rc = ensure_keep(c, A.reads, (A.n_reads + n_valid) * sizeof(inq_read_t), A.n_reads * sizeof(inq_read_t), s, res_reads)) != INQ_OK) return rc;
         clock.at("  batch read buffer ready");
-        if (names) {
-            // (of the first span of a batch nothing is kept: name_off[0] is written with the span's offsets)
-            if ((rc = ensure_keep(c, A.names, A.n_name_bytes + name_bytes, A.n_name_bytes, s)) != INQ_OK) return rc;
-            if ((rc = ensure_keep(c, A.name_off, (A.n_reads + n_valid + 1) * 8, A.n_spans ? (A.n_reads + 1) * 8 : 0, s)) != INQ_OK) return rc;
-        }
         a.cigar = (uint32_t *)A.cigar.p + A.n_units * 4;
         a.unit_base = (uint32_t)A.n_units;
         a.read_base = (uint32_t)A.n_reads;
@@ -505,10 +525,9 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     a.gather_nt = c->gather_nt ? 1u : 0u;
     launch_cigar_gather(a, n_valid, s);
     if (names) {
-        // the names of the placed records, out of the inflated bytes (rec_off[i] + 36) into the batch behind the names that are there;
-        // name_off[read_base + i] = the batch's bytes so far + the span's offset, [read_base + n_valid] = where the next span's begin
-        launch_offset_copy((uint64_t *)A.name_off.p + A.n_reads, span_name_off, n_valid + 1, A.n_name_bytes, s);
-        launch_name_copy(NameCopyArgs{a.u, a.u_bytes, a.rec_off, n_valid, 36, nullptr, (uint8_t *)A.names.p + A.n_name_bytes, name_bytes,
+        // the names of the placed records, one run per read, out of the inflated bytes (rec_off[i] + 36)
+        if ((rc = append_runs(c, A.names, A.n_spans == 0, A.n_reads, n_valid, name_bytes, span_name_off, s)) != INQ_OK) return rc;
+        launch_name_copy(NameCopyArgs{a.u, a.u_bytes, a.rec_off, n_valid, 36, nullptr, (uint8_t *)A.names.bytes.p + A.names.n_bytes, name_bytes,
                                       span_name_off, n_valid}, s);
     }
     if (defer && n_valid)  // the descriptors, CIGAR offsets already counted from the start of the accumulated buffer
@@ -558,10 +577,8 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
         uint64_t *span_seq_off = nullptr;
         uint32_t *span_qbeg = nullptr, *span_len = nullptr;
         if (seqs) {
-            // (of the first span of a batch nothing is kept: seq_off[0] is written with the span's offsets)
             if ((rc = ensure_keep(c, A.seq_qbeg, (A.n_pairs + n_pairs) * 4, A.n_pairs * 4, s)) != INQ_OK) return rc;
             if ((rc = ensure_keep(c, A.seq_len, (A.n_pairs + n_pairs) * 4, A.n_pairs * 4, s)) != INQ_OK) return rc;
-            if ((rc = ensure_keep(c, A.seq_off, (A.n_pairs + n_pairs + 1) * 8, A.n_spans ? (A.n_pairs + 1) * 8 : 0, s)) != INQ_OK) return rc;
             if ((rc = ensure(c, S->seq_off, (n_pairs + 1 + scan_tmp_words(std::max<uint64_t>(n_pairs, 1))) * 8)) != INQ_OK) return rc;
             span_seq_off = (uint64_t *)S->seq_off.p;
             span_qbeg = (uint32_t *)A.seq_qbeg.p + A.n_pairs, span_len = (uint32_t *)A.seq_len.p + A.n_pairs;
@@ -589,19 +606,18 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
         if ((rc = front_fail(S->h->st)) != INQ_OK) return rc;
         const uint64_t seq_bytes = seqs ? S->h->seq_bytes : 0;
         if (seqs) {
-            // the packed slices, out of the inflated bytes into the batch behind those that are there; seq_off[pair base + p] = the
-            // batch's bytes so far + the span's offset.  The slot's bytes are read: one more wait before it is given back
-            if ((rc = ensure_keep(c, A.seqs, A.n_seq_bytes + seq_bytes, A.n_seq_bytes, s)) != INQ_OK) return rc;
-            launch_offset_copy((uint64_t *)A.seq_off.p + A.n_pairs, span_seq_off, n_pairs + 1, A.n_seq_bytes, s);
+            // the packed slices, one run per pair, out of the inflated bytes.  The slot's bytes are read: one more wait before it is
+            // given back
+            if ((rc = append_runs(c, A.seqs, A.n_spans == 0, A.n_pairs, n_pairs, seq_bytes, span_seq_off, s)) != INQ_OK) return rc;
             launch_seq_slice(SeqSliceArgs{a.u, a.u_bytes, a.rec_off, n_valid, A.n_reads, a.pair_read, span_qbeg, span_len,
-                                          (uint8_t *)A.seqs.p + A.n_seq_bytes, seq_bytes, span_seq_off, n_pairs}, s);
+                                          (uint8_t *)A.seqs.bytes.p + A.seqs.n_bytes, seq_bytes, span_seq_off, n_pairs}, s);
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, hipStreamSynchronize(s));
         }
         if (A.n_spans == 0)
-            A.minlen = sp->minlen, A.support = sp->support, A.unphased = sp->unphased, A.max_reads = 0, A.with_names = names, A.with_seqs = seqs;
-        A.n_name_bytes += name_bytes;
-        A.n_seq_bytes += seq_bytes;
+            A.minlen = sp->minlen, A.support = sp->support, A.unphased = sp->unphased, A.max_reads = 0, A.use = use, A.names.on = names, A.seqs.on = seqs;
+        A.names.n_bytes += name_bytes;
+        A.seqs.n_bytes += seq_bytes;
         A.max_reads = std::max<uint32_t>(A.max_reads, S->h->st.max_reads);
         A.n_units += n_units, A.n_reads += n_valid, A.n_pairs += n_pairs, A.n_loci += nl, ++A.n_spans;
         clock.at("appended to the deferred batch");
@@ -630,8 +646,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
     S->n_pairs = n_pairs;
     S->n_loci = nl;
     S->last_from_acc = false;
-    S->last_names = false, S->n_name_bytes = 0;
-    S->last_seqs = false, S->n_seq_bytes = 0;
+    S->last_names = S->last_seqs = SpanState::RunsState();
     fill_stats();
     r->n_tie_loci = S->h->ks.ties;
     if ((rc = front_fail(S->h->st)) != INQ_OK) return rc;
@@ -658,11 +673,11 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     if (ms_call) *ms_call = 0.0;
     if (n_loci != A.n_loci) return INQ_ERR_ARG;
     if (h.name_bytes) {  // origins: of the records behind kept_off, out of a batch that was appended with names (an empty one has none to lack)
-        if (!h.kept_off || (A.n_spans && !A.with_names)) return INQ_ERR_ARG;
+        if (!h.kept_off || (A.n_spans && !A.names.on)) return INQ_ERR_ARG;
         *h.name_bytes = 0;
     }
     if (h.seq_bytes) {  // the bases behind those records, out of a batch that was appended with sequences
-        if (!h.name_bytes || (A.n_spans && !A.with_seqs)) return INQ_ERR_ARG;
+        if (!h.name_bytes || (A.n_spans && !A.seqs.on)) return INQ_ERR_ARG;
         *h.seq_bytes = 0;
     }
     if (A.n_loci == 0) {
@@ -684,7 +699,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     // (the evidence and the per-read Calls need the per-pair outputs, which a flush otherwise does not produce)
     LocusExtras x;
     if ((rc = extras_prepare(c, nl, A.n_pairs, h, &x)) != INQ_OK) return rc;
-    if (h.name_bytes) x.name_off = (const uint64_t *)A.name_off.p;
+    if (h.name_bytes) x.name_off = (const uint64_t *)A.names.off.p;
     if (h.seq_bytes) x.seq_qbeg = (const uint32_t *)A.seq_qbeg.p, x.seq_len = (const uint32_t *)A.seq_len.p;
     const bool per_pair = h.per_pair();
     if ((rc = ensure_row_staging(c, S, nl, 2 * nl + (h.flags ? (nl + 7) / 8 : 0))) != INQ_OK) return rc;  // the rows, then the flags
@@ -698,9 +713,9 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
         SpanState::Acc &a;
         ~Spent() { a.reset(); }
     } spent{A};
-    const uint64_t n_reads_all = A.n_reads, n_units_all = A.n_units, n_pairs_all = A.n_pairs, n_name_bytes_all = A.n_name_bytes;
-    const bool with_names = A.with_names, with_seqs = A.with_seqs;
-    const uint64_t n_seq_bytes_all = A.n_seq_bytes;
+    const uint64_t n_reads_all = A.n_reads, n_units_all = A.n_units, n_pairs_all = A.n_pairs;
+    const SpanState::RunsState names_all = A.names, seqs_all = A.seqs;
+    const RunSource names_src = A.names.source(A.n_reads, false), seqs_src = A.seqs.source(A.n_pairs, true);
     HIP_TRY(c, hipEventRecord(S->ev[4], s));
     if ((rc = call_batch_device_impl(c, &db, &dr, s, x)) != INQ_OK) return rc;
     HIP_TRY(c, hipEventRecord(S->ev[5], s));
@@ -731,8 +746,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     HIP_TRY(c, hipStreamSynchronize(s));
     if (h.flags) std::memcpy(h.flags, S->h_rows + 2 * nl, nl);
     if (h.name_bytes && S->h->ks.err == 0 &&  // the kept records' names, now that their number is known
-        (rc = extras_names(c, n_pairs_all, h, x, h.kept_off[nl], (const uint8_t *)A.names.p, n_name_bytes_all, n_reads_all,
-                           (const uint8_t *)A.seqs.p, n_seq_bytes_all, (const uint64_t *)A.seq_off.p, s)) != INQ_OK)
+        (rc = extras_names(c, n_pairs_all, h.kept_off[nl], h, x, names_src, seqs_src, s)) != INQ_OK)
         return rc;
     if (!dev) {
         std::memcpy(r->phase1, S->h_rows, nl * 8);
@@ -753,8 +767,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     }
     S->n_reads = n_reads_all, S->n_cigar_words = n_units_all * 4, S->n_pairs = n_pairs_all, S->n_loci = nl;
     S->last_from_acc = true;  // inq_span_fetch_batch reads the accumulated buffers (their contents stay until the next append)
-    S->last_names = with_names, S->n_name_bytes = n_name_bytes_all;
-    S->last_seqs = with_seqs, S->n_seq_bytes = n_seq_bytes_all;
+    S->last_names = names_all, S->last_seqs = seqs_all;
     r->n_tie_loci = S->h->ks.ties;
     extras_finish(c, nl, n_pairs_all, h, S->h->ks.err);
     return status_to_code(S->h->ks.err);  // (`spent` puts the counters back to zero, the buffers stay)
@@ -869,29 +882,33 @@ int fetch_batch_impl(inq_ctx *c, uint32_t *cigar, inq_read_t *reads, uint32_t *p
     return INQ_OK;
 }
 
-// the names of the batch the last flush ran on (their contents stay until the next append, like the batch's other arrays)
+// The runs of one kind of the batch the last flush ran on, n of them (their contents stay until the next append, like the batch's
+// other arrays): the offsets and the bytes, each where asked for.  Comes back behind the stream's work
+int fetch_runs(inq_ctx *c, const SpanState::Acc::Runs &R, const SpanState::RunsState &last, uint64_t n, uint64_t *off, uint8_t *bytes,
+               uint64_t cap_bytes) {
+    if (!c->span->last_from_acc || !last.on || cap_bytes < last.n_bytes) return INQ_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (off) HIP_TRY(c, hipMemcpy(off, R.off.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+    if (bytes && last.n_bytes) HIP_TRY(c, hipMemcpy(bytes, R.bytes.p, last.n_bytes, hipMemcpyDeviceToHost));
+    return INQ_OK;
+}
+
+// the names of its reads
 int fetch_names_impl(inq_ctx *c, uint64_t *name_off, uint8_t *names, uint64_t cap_bytes) {
     if (!c || !c->span) return INQ_ERR_ARG;
     SpanState *S = c->span;
-    if (!S->last_from_acc || !S->last_names || cap_bytes < S->n_name_bytes) return INQ_ERR_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (name_off) HIP_TRY(c, hipMemcpy(name_off, S->acc.name_off.p, (S->n_reads + 1) * 8, hipMemcpyDeviceToHost));
-    if (names && S->n_name_bytes) HIP_TRY(c, hipMemcpy(names, S->acc.names.p, S->n_name_bytes, hipMemcpyDeviceToHost));
-    return INQ_OK;
+    return fetch_runs(c, S->acc.names, S->last_names, S->n_reads, name_off, names, cap_bytes);
 }
 
 // ... and its pairs' slices
 int fetch_seqs_impl(inq_ctx *c, uint32_t *q_beg, uint32_t *n_bases, uint64_t *seq_off, uint8_t *packed, uint64_t cap_bytes) {
     if (!c || !c->span) return INQ_ERR_ARG;
     SpanState *S = c->span;
-    if (!S->last_from_acc || !S->last_seqs || cap_bytes < S->n_seq_bytes) return INQ_ERR_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const int rc = fetch_runs(c, S->acc.seqs, S->last_seqs, S->n_pairs, seq_off, packed, cap_bytes);
+    if (rc != INQ_OK) return rc;
     if (q_beg && S->n_pairs) HIP_TRY(c, hipMemcpy(q_beg, S->acc.seq_qbeg.p, S->n_pairs * 4, hipMemcpyDeviceToHost));
     if (n_bases && S->n_pairs) HIP_TRY(c, hipMemcpy(n_bases, S->acc.seq_len.p, S->n_pairs * 4, hipMemcpyDeviceToHost));
-    if (seq_off) HIP_TRY(c, hipMemcpy(seq_off, S->acc.seq_off.p, (S->n_pairs + 1) * 8, hipMemcpyDeviceToHost));
-    if (packed && S->n_seq_bytes) HIP_TRY(c, hipMemcpy(packed, S->acc.seqs.p, S->n_seq_bytes, hipMemcpyDeviceToHost));
     return INQ_OK;
 }
 
@@ -926,15 +943,15 @@ int inq_call_span(inq_ctx_t *c, const inq_span_t *span, inq_result_t *result, in
 }
 
 int inq_call_span_deferred(inq_ctx_t *c, const inq_span_t *span, int slot, inq_span_stats_t *stats) {
-    return guarded([&] { return call_span_impl(c, span, nullptr, stats, slot < 0 ? -1 : slot, true); });
+    return guarded([&] { return call_span_impl(c, span, nullptr, stats, slot < 0 ? -1 : slot, SpanState::Use::kDefer); });
 }
 
 int inq_call_span_deferred_names(inq_ctx_t *c, const inq_span_t *span, int slot, inq_span_stats_t *stats) {
-    return guarded([&] { return call_span_impl(c, span, nullptr, stats, slot < 0 ? -1 : slot, true, true); });
+    return guarded([&] { return call_span_impl(c, span, nullptr, stats, slot < 0 ? -1 : slot, SpanState::Use::kDeferNames); });
 }
 
 int inq_call_span_deferred_seqs(inq_ctx_t *c, const inq_span_t *span, int slot, inq_span_stats_t *stats) {
-    return guarded([&] { return call_span_impl(c, span, nullptr, stats, slot < 0 ? -1 : slot, true, true, true); });
+    return guarded([&] { return call_span_impl(c, span, nullptr, stats, slot < 0 ? -1 : slot, SpanState::Use::kDeferSeqs); });
 }
 
 int inq_call_flush(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call) {

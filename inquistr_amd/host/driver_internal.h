@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/inquistr_host.h"
+#include "../csrc/run_bytes.h"
 #include "front_end.h"
 #include "front_pool.h"
 #include "inq_text.h"
@@ -286,18 +287,27 @@ struct CallView {
 // the per-read Calls of a call's targets: [k] = the records of target k's kept reads in file order (empty: no batch or span held it)
 using ReadCallLists = std::vector<std::vector<inq_read_call_t>>;
 
-// who those reads are, for the read table: [k] = the origins of target k's records, in the records' order, and their names back to back
-struct ReadIdentities {
-    std::vector<inq_read_origin_t> origins;
-    std::vector<uint8_t> names;
+// A byte run behind each of those records: one Rec per record, in the records' order, and the runs back to back, inq::run_bytes(rec)
+// bytes each (csrc/run_bytes.h).  Who the reads are, for the read table: their origins and names; the bases behind them, for the read-seqs
+// file: their slices (inq_read_seq_t) and packed bases.  Of one target ([k] of TargetReports), or of a whole device call (BatchRows)
+template <class Rec> struct RecordRuns {
+    std::vector<Rec> recs;
+    std::vector<uint8_t> bytes;
+    // this call's runs cut into the shares of its loci: locus j holds the records [kept_off[j], kept_off[j + 1])
+    void cut(const std::vector<uint64_t> &kept_off, std::vector<RecordRuns> &loci) const {
+        size_t at = 0;
+        for (size_t j = 0; j + 1 < kept_off.size(); ++j) {
+            RecordRuns &t = loci[j];
+            t.recs.assign(recs.begin() + kept_off[j], recs.begin() + kept_off[j + 1]);
+            size_t n = 0;
+            for (const Rec &r : t.recs) n += inq::run_bytes(r);
+            t.bytes.assign(bytes.begin() + at, bytes.begin() + at + n);
+            at += n;
+        }
+    }
 };
-
-// ... and the bases behind them, for the read-seqs file: [k] = the slice of each of target k's records (inq_read_seq_t), in the records'
-// order, and the packed slices back to back
-struct ReadSlices {
-    std::vector<inq_read_seq_t> seqs;
-    std::vector<uint8_t> packed;
-};
+using ReadIdentities = RecordRuns<inq_read_origin_t>;
+using ReadSlices = RecordRuns<inq_read_seq_t>;
 
 // src[j] -> dst[index[j]]: rows and reports of a batch, a flush or a device part into their targets' places
 template <class T>
@@ -309,7 +319,9 @@ inline void scatter(const T *src, const uint32_t *index, size_t n, T *dst) {
 // read-calls file (inq_genotype_repeats_reads), the read table (inq_genotype_repeats_table; it needs the read-calls lists, which are
 // then collected with it), the read-seqs file (inq_genotype_repeats_seqs; its lines name the reads: the table's lists are collected
 // with it).  One value at every layer; a further report is one more member of each of the three
-// structs, a line in begin / scatter_from, a row in write_rows' table and a pointer in BatchRows::call / flush.
+// structs, a line in begin / scatter_from, a row in write_rows' table and a pointer in BatchRows::call / flush.  A further per-read
+// payload (a byte run behind each record, as the names and the bases are) is a record type with its inq::run_bytes(), one more
+// RecordRuns in TargetReports and in BatchRows, and a ByteRuns in ReadStore (front_end.h) where the host sweep is to keep it.
 struct ReportSet {  // which of them are collected: what is not adds nothing to the launch sequence
     bool ties = false, evidence = false, read_calls = false, read_table = false, read_seqs = false;
 };
@@ -435,10 +447,10 @@ struct BatchRows {
     TargetReports rep;                // of the call's loci, in the call's order
     std::vector<uint64_t> bk;         // kept_off of the per-read Calls
     std::vector<inq_read_call_t> bc;  // ... and the records, fetched behind the call
-    std::vector<inq_read_origin_t> bo;  // the read table: the records' origins ...
-    std::vector<uint8_t> bn;            // ... and names, fetched with them (a flush) or looked up in the batch the host owns (a call)
-    std::vector<inq_read_seq_t> bs;     // the read-seqs file: the records' slices ...
-    std::vector<uint8_t> bp;            // ... and their packed bases, fetched (a flush) or cut out of the batch's SEQ (a call)
+    // the read table: the records' origins and names, fetched with them (a flush) or looked up in the batch the host owns (a call); the
+    // read-seqs file: their slices and packed bases, fetched (a flush) or cut out of the batch's SEQ (a call)
+    ReadIdentities who;
+    ReadSlices bases;
     void begin(size_t n, ReportSet which) {
         b1.assign(n, NAN), b2.assign(n, NAN);
         std::memset(&res, 0, sizeof res);
@@ -457,31 +469,32 @@ struct BatchRows {
         int rc = inq_call_batch_reads(ctx, &batch, &res, flags(), evidence(), kept_off());
         if (rc == INQ_OK) rc = fetch_read_calls(ctx);
         if (rc != INQ_OK || !rep.has.read_table) return rc;
-        if (!owner || owner->name_off.size() != owner->reads.size() + 1) return INQ_ERR_ARG;
-        bo.resize(bc.size());
-        bn.clear();
+        if (!owner || owner->names.off.size() != owner->reads.size() + 1) return INQ_ERR_ARG;
+        who.recs.resize(bc.size());
+        who.bytes.clear();
         for (size_t k = 0; k < bc.size(); ++k) {
             const uint32_t r = bc[k].read;  // (the call succeeded: every index lies inside the batch)
             const inq_read_t &rd = owner->reads[r];
-            const uint64_t at = owner->name_off[r], len = owner->name_off[r + 1] - at;
-            bo[k] = inq_read_origin_t{rd.pos, rd.mapq, rd.bits, (uint16_t)len};
-            bn.insert(bn.end(), owner->names.begin() + at, owner->names.begin() + at + len);
+            const uint64_t at = owner->names.off[r], len = owner->names.off[r + 1] - at;
+            who.recs[k] = inq_read_origin_t{rd.pos, rd.mapq, rd.bits, (uint16_t)len};
+            who.bytes.insert(who.bytes.end(), owner->names.bytes.begin() + at, owner->names.bytes.begin() + at + len);
         }
-        cut_read_table();
+        who.cut(bk, rep.read_table);
         if (!rep.has.read_seqs) return INQ_OK;
         // the slices: record k of locus j is read bc[k].read under j's window, cut out of the SEQ the sweep kept (inq_host_seq_window)
-        if (owner->seq_off.size() != owner->reads.size() + 1 || owner->l_seq.size() != owner->reads.size()) return INQ_ERR_ARG;
-        bs.resize(bc.size());
-        bp.clear();
+        if (owner->seqs.off.size() != owner->reads.size() + 1 || owner->l_seq.size() != owner->reads.size()) return INQ_ERR_ARG;
+        bases.recs.resize(bc.size());
+        bases.bytes.clear();
         for (size_t j = 0; j + 1 < bk.size(); ++j)
             for (uint64_t k = bk[j]; k < bk[j + 1]; ++k) {
                 const uint32_t r = bc[k].read;
                 const inq_read_t &rd = owner->reads[r];
+                inq_read_seq_t &q = bases.recs[k];
                 seq_window(owner->cigar.data() + (size_t)rd.cigar_off4 * 4, rd.n_cigar, rd.pos, owner->l_seq[r], batch.locus_start[j],
-                           batch.locus_end[j], &bs[k].q_beg, &bs[k].n_bases);
-                pack_seq_slice(owner->seqs.data() + owner->seq_off[r], bs[k].q_beg, bs[k].n_bases, bp);
+                           batch.locus_end[j], &q.q_beg, &q.n_bases);
+                pack_seq_slice(owner->seqs.bytes.data() + owner->seqs.off[r], q.q_beg, q.n_bases, bases.bytes);
             }
-        cut_read_seqs();
+        bases.cut(bk, rep.read_seqs);
         return INQ_OK;
     }
     int flush(inq_ctx_t *ctx, uint64_t n, double *ms_call) {
@@ -493,38 +506,14 @@ struct BatchRows {
         int rc = inq_call_flush_seqs(ctx, &res, n, ms_call, flags(), evidence(), kept_off(), &name_bytes, rep.has.read_seqs ? &seq_bytes : nullptr);
         if (rc == INQ_OK) rc = fetch_read_calls(ctx);
         if (rc != INQ_OK) return rc;
-        bo.resize(bc.size()), bn.resize(name_bytes);
-        if ((rc = inq_read_origins_fetch(ctx, bo.data(), bo.size(), bn.data(), bn.size())) != INQ_OK) return rc;
-        cut_read_table();
+        who.recs.resize(bc.size()), who.bytes.resize(name_bytes);
+        if ((rc = inq_read_origins_fetch(ctx, who.recs.data(), who.recs.size(), who.bytes.data(), who.bytes.size())) != INQ_OK) return rc;
+        who.cut(bk, rep.read_table);
         if (!rep.has.read_seqs) return INQ_OK;
-        bs.resize(bc.size()), bp.resize(seq_bytes);
-        if ((rc = inq_read_seqs_fetch(ctx, bs.data(), bs.size(), bp.data(), bp.size())) != INQ_OK) return rc;
-        cut_read_seqs();
+        bases.recs.resize(bc.size()), bases.bytes.resize(seq_bytes);
+        if ((rc = inq_read_seqs_fetch(ctx, bases.recs.data(), bases.recs.size(), bases.bytes.data(), bases.bytes.size())) != INQ_OK) return rc;
+        bases.cut(bk, rep.read_seqs);
         return INQ_OK;
-    }
-    // bs / bp, in the records' order, cut into the loci's shares
-    void cut_read_seqs() {
-        size_t at = 0;
-        for (size_t j = 0; j + 1 < bk.size(); ++j) {
-            ReadSlices &t = rep.read_seqs[j];
-            t.seqs.assign(bs.begin() + bk[j], bs.begin() + bk[j + 1]);
-            size_t bytes = 0;
-            for (const inq_read_seq_t &q : t.seqs) bytes += ((size_t)q.n_bases + 1) / 2;
-            t.packed.assign(bp.begin() + at, bp.begin() + at + bytes);
-            at += bytes;
-        }
-    }
-    // bo / bn, in the records' order, cut into the loci's shares
-    void cut_read_table() {
-        size_t at = 0;
-        for (size_t j = 0; j + 1 < bk.size(); ++j) {
-            ReadIdentities &t = rep.read_table[j];
-            t.origins.assign(bo.begin() + bk[j], bo.begin() + bk[j + 1]);
-            size_t bytes = 0;
-            for (const inq_read_origin_t &o : t.origins) bytes += o.name_len;
-            t.names.assign(bn.begin() + at, bn.begin() + at + bytes);
-            at += bytes;
-        }
     }
     // the records behind a call that filled kept_off, out of the context's scratch, cut into the loci's lists
     int fetch_read_calls(inq_ctx_t *ctx) {

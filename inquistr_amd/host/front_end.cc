@@ -8,18 +8,12 @@
 namespace inqhost {
 
 void HostBatch::clear() {
-    cigar.clear();
-    reads.clear();
+    reset(false, false);
     pair_read.clear();
     locus_pair_off.clear();
     locus_start.clear();
     locus_end.clear();
     locus_index.clear();
-    names.clear();
-    name_off.clear();
-    seqs.clear();
-    seq_off.clear();
-    l_seq.clear();
 }
 
 void HostBatch::view(inq_batch_t *b, uint32_t minlen, uint32_t support, bool unphased) const {
@@ -61,13 +55,7 @@ FrontEnd::FrontEnd(BamFile &bam, const std::vector<RepeatInterval> &targets, boo
 bool FrontEnd::begin_group(std::string *err) {
     Group &G = groups_[g_];
     edges_.clear();
-    cig_.clear();
-    reads_.clear();
-    names_.clear();
-    name_off_.assign(keep_names_ ? 1 : 0, 0);
-    seqs_.clear();
-    l_seq_.clear();
-    seq_off_.assign(keep_seqs_ ? 1 : 0, 0);
+    store_.reset(keep_names_, keep_seqs_);
     lo_ = 0;
     flushed_ = 0;
     group_eof_ = false;
@@ -111,7 +99,8 @@ int FrontEnd::add_read(const BamRec &r, bool has_clip, std::string *err, bool *p
     }
     inq_read_t rd;
     std::memset(&rd, 0, sizeof rd);
-    rd.cigar_off4 = (uint32_t)(cig_.size() / 4);
+    std::vector<uint32_t> &cig = store_.cigar;
+    rd.cigar_off4 = (uint32_t)(cig.size() / 4);
     rd.n_cigar = r.n_cigar;
     rd.pos = r.pos;
     rd.mapq = r.mapq;
@@ -126,19 +115,12 @@ int FrontEnd::add_read(const BamRec &r, bool has_clip, std::string *err, bool *p
         if ((0x18Du >> op) & 1u) span += r.cigar[k] >> 4;  // M D N = X consume the reference
     }
     if (!bad_op && r.pos >= -1 && (int64_t)r.pos + 1 + span < ((int64_t)1 << 31)) rd.promise = INQ_READ_CHECKED;
-    cig_.insert(cig_.end(), r.cigar, r.cigar + r.n_cigar);
-    while (cig_.size() & 3) cig_.push_back(0u);  // 0M padding to the next 16-byte boundary
-    reads_.push_back(rd);
-    if (keep_names_) {
-        names_.insert(names_.end(), r.name, r.name + r.name_len);
-        name_off_.push_back(names_.size());
-    }
-    if (keep_seqs_) {
-        seqs_.insert(seqs_.end(), r.seq, r.seq + ((size_t)r.l_seq + 1) / 2);
-        seq_off_.push_back(seqs_.size());
-        l_seq_.push_back(r.l_seq);
-    }
-    return (int)reads_.size() - 1;
+    cig.insert(cig.end(), r.cigar, r.cigar + r.n_cigar);
+    while (cig.size() & 3) cig.push_back(0u);  // 0M padding to the next 16-byte boundary
+    store_.reads.push_back(rd);
+    if (keep_names_) store_.names.append(r.name, r.name_len);
+    if (keep_seqs_) store_.seqs.append(r.seq, ((size_t)r.l_seq + 1) / 2), store_.l_seq.push_back(r.l_seq);
+    return (int)store_.reads.size() - 1;
 }
 
 void FrontEnd::emit(size_t from, size_t to, HostBatch &out) {
@@ -157,45 +139,18 @@ void FrontEnd::emit(size_t from, size_t to, HostBatch &out) {
     out.locus_pair_off.assign(bucket_.begin(), bucket_.end());
     out.pair_read.resize(n_out);
     const bool whole = n_out == edges_.size();  // nothing stays behind: the store becomes the batch as it is
-    std::vector<uint32_t> remap;
+    ReadStore &batch = out;
     if (whole) {
         for (const Edge &e : edges_) out.pair_read[bucket_[e.locus - from]++] = e.read;
-        out.cigar.swap(cig_);
-        out.reads.swap(reads_);
-        cig_.clear();
-        reads_.clear();
-        if (keep_names_) {
-            out.names.swap(names_);
-            out.name_off.swap(name_off_);
-            names_.clear();
-            name_off_.assign(1, 0);
-        }
-        if (keep_seqs_) {
-            out.seqs.swap(seqs_), out.seq_off.swap(seq_off_), out.l_seq.swap(l_seq_);
-            seqs_.clear(), l_seq_.clear();
-            seq_off_.assign(1, 0);
-        }
+        std::swap(batch, store_);
+        store_.reset(keep_names_, keep_seqs_);
         edges_.clear();
     } else {
-        remap.assign(reads_.size(), 0xffffffffu);
-        if (keep_names_) out.name_off.assign(1, 0);
-        if (keep_seqs_) out.seq_off.assign(1, 0);
+        std::vector<uint32_t> remap(store_.reads.size(), 0xffffffffu);
+        batch.reset(keep_names_, keep_seqs_);
         for (const Edge &e : edges_) {
             if (e.locus < from || e.locus >= to) continue;
-            if (remap[e.read] == 0xffffffffu) {
-                remap[e.read] = (uint32_t)out.reads.size();
-                inq_read_t rd = reads_[e.read];
-                const uint32_t *src = cig_.data() + (size_t)rd.cigar_off4 * 4;
-                rd.cigar_off4 = (uint32_t)(out.cigar.size() / 4);
-                const size_t n4 = ((size_t)rd.n_cigar + 3) / 4 * 4;
-                out.cigar.insert(out.cigar.end(), src, src + n4);
-                out.reads.push_back(rd);
-                if (keep_names_) {
-                    out.names.insert(out.names.end(), names_.begin() + name_off_[e.read], names_.begin() + name_off_[e.read + 1]);
-                    out.name_off.push_back(out.names.size());
-                }
-                if (keep_seqs_) copy_seq(e.read, out.seqs, out.seq_off, out.l_seq);
-            }
+            if (remap[e.read] == 0xffffffffu) remap[e.read] = batch.take(store_, e.read);
             out.pair_read[bucket_[e.locus - from]++] = remap[e.read];
         }
     }
@@ -208,41 +163,19 @@ void FrontEnd::emit(size_t from, size_t to, HostBatch &out) {
 
 void FrontEnd::compact(size_t keep_from) {
     // drop the edges of emitted loci and the reads no open locus references
-    std::vector<uint32_t> remap(reads_.size(), 0xffffffffu);
-    std::vector<uint32_t> ncig;
-    std::vector<inq_read_t> nreads;
-    std::vector<uint8_t> nnames;
-    std::vector<uint64_t> nname_off(keep_names_ ? 1 : 0, 0);
-    std::vector<uint8_t> nseqs;
-    std::vector<uint64_t> nseq_off(keep_seqs_ ? 1 : 0, 0);
-    std::vector<uint32_t> nl_seq;
+    std::vector<uint32_t> remap(store_.reads.size(), 0xffffffffu);
+    ReadStore kept;
+    kept.reset(keep_names_, keep_seqs_);
     size_t w = 0;
     for (const Edge &e0 : edges_) {
         if (e0.locus < keep_from) continue;
         Edge e = e0;
-        if (remap[e.read] == 0xffffffffu) {
-            remap[e.read] = (uint32_t)nreads.size();
-            inq_read_t rd = reads_[e.read];
-            const uint32_t *src = cig_.data() + (size_t)rd.cigar_off4 * 4;
-            rd.cigar_off4 = (uint32_t)(ncig.size() / 4);
-            const size_t n4 = ((size_t)rd.n_cigar + 3) / 4 * 4;
-            ncig.insert(ncig.end(), src, src + n4);
-            nreads.push_back(rd);
-            if (keep_names_) {
-                nnames.insert(nnames.end(), names_.begin() + name_off_[e.read], names_.begin() + name_off_[e.read + 1]);
-                nname_off.push_back(nnames.size());
-            }
-            if (keep_seqs_) copy_seq(e.read, nseqs, nseq_off, nl_seq);
-        }
+        if (remap[e.read] == 0xffffffffu) remap[e.read] = kept.take(store_, e.read);
         e.read = remap[e.read];
         edges_[w++] = e;
     }
     edges_.resize(w);
-    cig_.swap(ncig);
-    reads_.swap(nreads);
-    names_.swap(nnames);
-    name_off_.swap(nname_off);
-    seqs_.swap(nseqs), seq_off_.swap(nseq_off), l_seq_.swap(nl_seq);
+    std::swap(store_, kept);
 }
 
 int FrontEnd::next(HostBatch &out, std::string *err, bool *panic) {
@@ -309,7 +242,7 @@ int FrontEnd::next(HostBatch &out, std::string *err, bool *panic) {
                     edges_.push_back({(uint32_t)j, (uint32_t)ridx});
                 }
             }
-            if (cig_.size() > max_words_ && lo_ > flushed_) {
+            if (store_.cigar.size() > max_words_ && lo_ > flushed_) {
                 emit(flushed_, lo_, out);
                 compact(lo_);
                 flushed_ = lo_;

@@ -17,21 +17,53 @@
 
 namespace inqhost {
 
-struct HostBatch {
+// a byte run per read, back to back: run i is bytes[off[i], off[i + 1]).  Not kept (off): both vectors empty
+struct ByteRuns {
+    std::vector<uint8_t> bytes;
+    std::vector<uint64_t> off;  // [n + 1]
+    void reset(bool on) {
+        bytes.clear();
+        off.assign(on ? 1 : 0, 0);
+    }
+    void append(const uint8_t *p, size_t len) {
+        bytes.insert(bytes.end(), p, p + len);
+        off.push_back(bytes.size());
+    }
+    void append_from(const ByteRuns &o, size_t i) { append(o.bytes.data() + o.off[i], o.off[i + 1] - o.off[i]); }
+};
+
+// reads stored once: CIGARs padded to 16-byte groups, descriptors, and what the front end was told to keep beside them - the names
+// (the read table) and the SEQ as the BAM stores it with l_seq[n_reads] (the read-seqs file)
+struct ReadStore {
     std::vector<uint32_t> cigar;
     std::vector<inq_read_t> reads;
+    ByteRuns names, seqs;
+    std::vector<uint32_t> l_seq;
+    void reset(bool keep_names, bool keep_seqs) {
+        cigar.clear();
+        reads.clear();
+        names.reset(keep_names);
+        seqs.reset(keep_seqs);
+        l_seq.clear();
+    }
+    // read r of `from` copied here with everything both stores keep, its cigar_off4 counted from this store's start; its index here
+    uint32_t take(const ReadStore &from, uint32_t r) {
+        inq_read_t rd = from.reads[r];
+        const uint32_t *src = from.cigar.data() + (size_t)rd.cigar_off4 * 4;
+        rd.cigar_off4 = (uint32_t)(cigar.size() / 4);
+        cigar.insert(cigar.end(), src, src + ((size_t)rd.n_cigar + 3) / 4 * 4);
+        reads.push_back(rd);
+        if (!names.off.empty()) names.append_from(from.names, r);
+        if (!seqs.off.empty()) seqs.append_from(from.seqs, r), l_seq.push_back(from.l_seq[r]);
+        return (uint32_t)reads.size() - 1;
+    }
+};
+
+struct HostBatch : ReadStore {
     std::vector<uint32_t> pair_read;
     std::vector<uint64_t> locus_pair_off;
     std::vector<uint32_t> locus_start, locus_end;
     std::vector<uint32_t> locus_index;  // index into the target list
-    // the names of the reads back to back, name_off[n_reads + 1]; both empty unless the front end keeps names (the read table)
-    std::vector<uint8_t> names;
-    std::vector<uint64_t> name_off;
-    // their SEQ as the BAM stores it back to back, seq_off[n_reads + 1] and l_seq[n_reads]; empty unless the front end keeps
-    // sequences (the read-seqs file)
-    std::vector<uint8_t> seqs;
-    std::vector<uint64_t> seq_off;
-    std::vector<uint32_t> l_seq;
     void clear();
     void view(inq_batch_t *b, uint32_t minlen, uint32_t support, bool unphased) const;
 };
@@ -67,22 +99,8 @@ private:
     size_t lo_ = 0;      // first locus of the group not yet closed
     size_t flushed_ = 0; // loci [0, flushed_) already emitted
     int64_t last_pos_ = -1;  // position of the previous record of the sweep (sortedness check)
-    // contig-local store
-    std::vector<uint32_t> cig_;
-    std::vector<inq_read_t> reads_;
-    bool keep_names_ = false;
-    std::vector<uint8_t> names_;      // keep_names_: the names of reads_ back to back ...
-    std::vector<uint64_t> name_off_;  // ... and where each begins, [reads_.size() + 1]
-    bool keep_seqs_ = false;
-    std::vector<uint8_t> seqs_;       // keep_seqs_: the packed SEQ of reads_ back to back,
-    std::vector<uint64_t> seq_off_;   // where each begins, [reads_.size() + 1],
-    std::vector<uint32_t> l_seq_;     // and its bases
-    // read `r` of the store's SEQ appended to a batch's (or the compacted store's) three arrays
-    void copy_seq(size_t r, std::vector<uint8_t> &seqs, std::vector<uint64_t> &seq_off, std::vector<uint32_t> &l_seq) const {
-        seqs.insert(seqs.end(), seqs_.begin() + seq_off_[r], seqs_.begin() + seq_off_[r + 1]);
-        seq_off.push_back(seqs.size());
-        l_seq.push_back(l_seq_[r]);
-    }
+    bool keep_names_ = false, keep_seqs_ = false;
+    ReadStore store_;  // contig-local
     // (locus of the group, read of the store) in file order; grouped by locus (stable) when a batch is emitted
     struct Edge {
         uint32_t locus, read;

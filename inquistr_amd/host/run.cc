@@ -452,8 +452,8 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
              [&targets, tr, unphased](std::string &text, uint32_t i) {  // one line per kept read: none for a target without one
                  const std::vector<inq_read_call_t> &l = tr->read_calls[i];
                  const ReadIdentities &w = tr->read_table[i];
-                 if (w.origins.size() == l.size())
-                     append_read_table_rows(text, targets[i].chrom, targets[i].start, targets[i].end, l.data(), w.origins.data(), w.names.data(),
+                 if (w.recs.size() == l.size())
+                     append_read_table_rows(text, targets[i].chrom, targets[i].start, targets[i].end, l.data(), w.recs.data(), w.bytes.data(),
                                             l.size(), unphased);
              }},
             {tr->has.read_seqs, reports.fds.read_seqs, std::string(kReadSeqsHeader) + '\n', kReadSeqsWhat,
@@ -461,9 +461,9 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
                  const std::vector<inq_read_call_t> &l = tr->read_calls[i];
                  const ReadIdentities &w = tr->read_table[i];
                  const ReadSlices &q = tr->read_seqs[i];
-                 if (w.origins.size() == l.size() && q.seqs.size() == l.size())
-                     append_read_seq_rows(text, targets[i].chrom, targets[i].start, targets[i].end, l.data(), w.origins.data(), w.names.data(),
-                                          q.seqs.data(), q.packed.data(), l.size(), unphased);
+                 if (w.recs.size() == l.size() && q.recs.size() == l.size())
+                     append_read_seq_rows(text, targets[i].chrom, targets[i].start, targets[i].end, l.data(), w.recs.data(), w.bytes.data(),
+                                          q.recs.data(), q.bytes.data(), l.size(), unphased);
              }},
         };
         for (const auto &f : files) {
@@ -575,18 +575,18 @@ static int inq_frontend_next_impl(inq_frontend_t *fe, inq_batch_t *batch, const 
 }
 
 int inq_frontend_read_names(const inq_frontend_t *fe, const uint64_t **name_off, const uint8_t **names, uint64_t *n_reads) {
-    if (!fe || !fe->current || fe->current->name_off.size() != fe->current->reads.size() + 1) return INQ_EXIT_ERROR;
-    if (name_off) *name_off = fe->current->name_off.data();
-    if (names) *names = fe->current->names.data();
+    if (!fe || !fe->current || fe->current->names.off.size() != fe->current->reads.size() + 1) return INQ_EXIT_ERROR;
+    if (name_off) *name_off = fe->current->names.off.data();
+    if (names) *names = fe->current->names.bytes.data();
     if (n_reads) *n_reads = fe->current->reads.size();
     return INQ_EXIT_OK;
 }
 
 int inq_frontend_read_seqs(const inq_frontend_t *fe, const uint32_t **l_seq, const uint64_t **seq_off, const uint8_t **seqs, uint64_t *n_reads) {
-    if (!fe || !fe->current || fe->current->seq_off.size() != fe->current->reads.size() + 1) return INQ_EXIT_ERROR;
+    if (!fe || !fe->current || fe->current->seqs.off.size() != fe->current->reads.size() + 1) return INQ_EXIT_ERROR;
     if (l_seq) *l_seq = fe->current->l_seq.data();
-    if (seq_off) *seq_off = fe->current->seq_off.data();
-    if (seqs) *seqs = fe->current->seqs.data();
+    if (seq_off) *seq_off = fe->current->seqs.off.data();
+    if (seqs) *seqs = fe->current->seqs.bytes.data();
     if (n_reads) *n_reads = fe->current->reads.size();
     return INQ_EXIT_OK;
 }
