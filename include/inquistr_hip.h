@@ -210,6 +210,31 @@ typedef struct inq_read_seq {  /* 8 bytes, every byte written; one per record of
     uint32_t n_bases;
 } inq_read_seq_t;
 
+/* How much of those bases is the locus's motif: the pure runs of the motif in a kept record's slice.
+ * Motif word, one uint64_t per locus: nibble 15 is k, the motif length, 1 .. 15; nibbles 0 .. k - 1 are the motif's bases m[0 .. k) as
+ * BAM codes (A = 1, C = 2, G = 4, T = 8); the nibbles between are not read.  A word is "no motif" when k = 0 or when any of nibbles
+ * 0 .. k - 1 is not one of those four codes.  The device checks this itself: no word makes it read or write out of bounds.
+ * Let s[0 .. n) be the slice of a kept record: the n_bases 4-bit codes inq_read_seq_t describes, indexed from the slice's first base.
+ * For a rotation r in [0, k), position i HITS when s[i] == m[(i + r) mod k]; equality is exact, so `=`, N and every ambiguity code
+ * hit nothing.  A RUN is a maximal interval [a, b) of consecutive hits at one rotation, and R is the set of all runs of all k
+ * rotations.  Then
+ *     run_beg, run_len   the longest run in R (a, b - a); on a tie the one with the smallest a; (0, 0) when R is empty.  A run
+ *                        shorter than k counts here
+ *     motif_bases        the number of positions that lie in at least one run of R with b - a >= k
+ *     n_runs             the number of runs in R with b - a >= k
+ * No motif, or n = 0, gives four zeros.  The word is taken literally: a non-primitive one (CAGCAG) has identical runs at equivalent
+ * rotations and each counts in n_runs.  The host encoder, inq_host_motif_encode of include/inquistr_host.h, reduces a motif to its
+ * primitive root; for a
+ * primitive motif no run of length >= k at one rotation is a run at another or contains one, so n_runs is the number of distinct
+ * maximal pure stretches and n_runs - 1 the number of interruptions and phase shifts.  Runs of different rotations may overlap by up
+ * to k - 1 bases (a one-base deletion inside the repeat); motif_bases is the union. */
+typedef struct inq_read_motif {  /* 16 bytes, every byte written; one per record of inq_read_calls_fetch, same order */
+    uint32_t run_beg;      /* 0-based offset into the slice */
+    uint32_t run_len;
+    uint32_t motif_bases;
+    uint32_t n_runs;
+} inq_read_motif_t;
+
 typedef struct inq_ctx inq_ctx_t;
 
 /* Opens HIP device `device_id` (must be gfx950), creates the library's stream and
@@ -504,6 +529,24 @@ int inq_seq_windows(inq_ctx_t *ctx, const inq_batch_t *batch, const uint32_t *l_
                     uint32_t *n_bases /* [n_pairs] */);
 /* pairs per workgroup and turn of the window walk (a constant of the build) */
 uint32_t inq_seq_window_tile(void);
+/* The motif runs of those bases (inq_read_motif_t above), computed on the device at flush time out of the batch's own slices.
+ * inq_call_flush_motifs is inq_call_flush_seqs plus `motif`, a HOST array of one motif word per locus in append order, and one
+ * inq_read_motif_t per kept record.  motif NULL = exactly inq_call_flush_seqs; with it, seq_bytes NULL or a batch appended without
+ * sequences is INQ_ERR_ARG (the batch stays).  The records stay in context scratch until the context's next call:
+ * inq_read_motifs_fetch copies the first n; n above the last flush's total is INQ_ERR_ARG, and a flush without motifs has a total of 0.
+ * inq_motif_runs: the kernel alone over host buffers in exactly the format inq_read_seqs_fetch returns - n records, their packed
+ * slices back to back in seq_bytes bytes -, with kept_off[n_loci + 1] telling which records belong to which locus (ascending,
+ * kept_off[n_loci] <= n, else INQ_ERR_ARG; a record at or past kept_off[n_loci] has no locus and gets four zeros) and one motif word
+ * per locus; out[n].  A record whose slice does not fit into seq_bytes gets four zeros. */
+int inq_call_flush_motifs(inq_ctx_t *ctx, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
+                          inq_locus_evidence_t *evidence, uint64_t *kept_off, uint64_t *name_bytes, uint64_t *seq_bytes,
+                          const uint64_t *motif /* [n_loci], host */);
+int inq_read_motifs_fetch(inq_ctx_t *ctx, inq_read_motif_t *recs, uint64_t n);
+int inq_motif_runs(inq_ctx_t *ctx, const inq_read_seq_t *recs, uint64_t n, const uint8_t *packed, uint64_t seq_bytes,
+                   const uint64_t *kept_off /* [n_loci + 1] */, const uint64_t *motif /* [n_loci] */, uint64_t n_loci,
+                   inq_read_motif_t *out);
+/* records per workgroup and turn of the motif kernel (a constant of the build) */
+uint32_t inq_read_motif_tile(void);
 /* Row arrays in device memory for a host that does not link the HIP runtime itself: n f64, filled with quiet NaN (a locus no span
  * holds prints NaN NaN); plain synchronous copies in and out. */
 int inq_dev_alloc_rows(inq_ctx_t *ctx, uint64_t n, double **out);

@@ -144,6 +144,19 @@ int inq_genotype_repeats_table(const inq_call_args_t *args, const int32_t *devic
  * inq_run_*, inq_session_* - have no way to be handed the path: they write no such file. */
 int inq_genotype_repeats_seqs(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,
                               const char *read_table_path, const char *read_seqs_path, inq_part_stats_t *stats, char *errbuf, size_t errcap);
+/* ... and with the read-motifs file (`inquistr call --read-motifs`), the widest entry of the family: read_motifs_path NULL = exactly
+ * inq_genotype_repeats_seqs.  The file tells how much of each read's bases over the locus window is the locus's motif: a header line
+ * `chrom\tbegin\tend\tgroup\tcall\tkind\tread\tqbeg\tlen\tmotif\trun_beg\trun_len\tunits\tmotif_bases\truns`, then one line per KEPT read,
+ * line for line beside the read-seqs file, columns 1 - 9 the same.  motif is the target's motif reduced to its primitive root
+ * (inq_host_motif_encode): `motif` for every target when given, else column 4 of the BED; run_beg, run_len, motif_bases and runs are
+ * inq_read_motif_t of include/inquistr_hip.h, units = run_len / k in integers.  A target whose motif does not encode prints `.` in the
+ * motif field and the five behind it, and the number of such targets goes to stderr once.  Neither `motif` nor a fourth BED column
+ * (a region string has none): status 1, its message names column 4, nothing is written to out_fd.  Both front ends produce it: the host
+ * sweep walks its slices with inq_host_motif_runs, the device front end computes the records on the GPU at flush time
+ * (inq_call_flush_motifs). */
+int inq_genotype_repeats_motifs(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,
+                                const char *read_table_path, const char *read_seqs_path, const char *read_motifs_path, const char *motif,
+                                inq_part_stats_t *stats, char *errbuf, size_t errcap);
 /* How many processes (or device parts) share this host's cores with this one, and which of them it is (0 .. sharers - 1): sizes the
  * reader pool of every later call (granted cores / sharers, bound to L3 domains from a different start per sharer).  Default:
  * LOCAL_WORLD_SIZE / LOCAL_RANK of the environment (torch.distributed.run exports them), else 1 / 0.  sharers <= 0 = that default. */
@@ -230,6 +243,9 @@ typedef struct inq_frontend inq_frontend_t;
 int inq_frontend_open(const inq_call_args_t *args, inq_frontend_t **out, char *errbuf, size_t errcap);
 uint64_t inq_frontend_n_targets(const inq_frontend_t *fe);
 int inq_frontend_target(const inq_frontend_t *fe, uint64_t i, const char **chrom, uint32_t *start, uint32_t *end);
+/* column 4 of target i's BED line as it stands (an STR catalogue keeps the motif there: what the read-motifs file takes when no
+ * `motif` is given), NULL for a BED of three columns, for a region string and for i past the list.  Valid until inq_frontend_close. */
+const char *inq_frontend_target_name(const inq_frontend_t *fe, uint64_t i);
 const char *inq_frontend_sample(const inq_frontend_t *fe);
 /* Next batch: 1 = *batch filled (host pointers, valid until the next call), 0 = no more, <0 = exit
  * status negated.  locus_index[j] = position of batch locus j in the target list. */
@@ -305,6 +321,19 @@ size_t inq_host_format_read_table_rows(const char *chrom, uint32_t start, uint32
 size_t inq_host_format_read_seq_rows(const char *chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
                                      const inq_read_origin_t *origins, const uint8_t *names, const inq_read_seq_t *seqs, const uint8_t *packed,
                                      size_t n, int unphased, char *buf, size_t cap);
+/* ... and of the read-motifs file (inq_genotype_repeats_motifs): the same lines in columns chrom .. len, then the target's motif as text
+ * (motif_word: inq_read_motif_t's motif word in include/inquistr_hip.h) and run_beg, run_len, units = run_len / k, motif_bases and runs
+ * of each record's inq_read_motif_t, same order; a word that is no motif prints `.` in all six */
+size_t inq_host_format_read_motif_rows(const char *chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
+                                       const inq_read_origin_t *origins, const uint8_t *names, const inq_read_seq_t *seqs,
+                                       const inq_read_motif_t *motifs, uint64_t motif_word, size_t n, int unphased, char *buf, size_t cap);
+/* A motif's text as the motif word of inq_read_motif_t: upper-cased, A C G T only, reduced to its primitive root (CAGCAG -> CAG), which
+ * must have 1 .. 15 bases.  0 and *word; else *word = 0 and 1 (NULL or empty text), 2 (a character that is none of ACGT: `.`, `CAG,CCG`,
+ * `GCN`) or 3 (a primitive root of 16 bases or more). */
+int inq_host_motif_encode(const char *text, uint64_t *word);
+/* The run contract of inq_read_motif_t restated as a plain sequential walk, one rotation at a time, over n_bases packed bases (first
+ * base in the high nibble of the first byte): what the host sweep computes with.  0, or 1 for a null pointer. */
+int inq_host_motif_runs(const uint8_t *packed, uint32_t n_bases, uint64_t motif_word, inq_read_motif_t *out);
 /* The slice contract of inq_read_seq_t, as include/inquistr_hip.h states it, restated as a plain sequential walk of n_cigar packed ops (len << 4 | op) from
  * pos: what the host sweep cuts its slices with.  0, or 1 for a null pointer. */
 int inq_host_seq_window(const uint32_t *cigar, uint32_t n_cigar, int32_t pos, uint32_t l_seq, uint32_t start, uint32_t end, uint32_t *q_beg,

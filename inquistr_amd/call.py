@@ -27,6 +27,7 @@ HOST_ABI_SYMBOLS = (
     "inq_genotype_repeats_reads",
     "inq_genotype_repeats_table",
     "inq_genotype_repeats_seqs",
+    "inq_genotype_repeats_motifs",
     "inq_host_set_local_share",
     "inq_host_granted_cpus",
     "inq_host_ctx_option",
@@ -58,6 +59,7 @@ HOST_ABI_SYMBOLS = (
     "inq_frontend_open",
     "inq_frontend_n_targets",
     "inq_frontend_target",
+    "inq_frontend_target_name",
     "inq_frontend_sample",
     "inq_frontend_next",
     "inq_frontend_read_names",
@@ -72,6 +74,9 @@ HOST_ABI_SYMBOLS = (
     "inq_host_format_read_calls_row",
     "inq_host_format_read_table_rows",
     "inq_host_format_read_seq_rows",
+    "inq_host_format_read_motif_rows",
+    "inq_host_motif_encode",
+    "inq_host_motif_runs",
     "inq_host_seq_window",
     "inq_host_sample_name",
     "inq_host_human_compare",
@@ -171,6 +176,16 @@ def load():
         L.inq_genotype_repeats_seqs.restype = C.c_int
         L.inq_genotype_repeats_seqs.argtypes = [C.POINTER(CallArgsC), C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p,
                                                 C.POINTER(PartStatsC), C.c_char_p, C.c_size_t]
+        L.inq_genotype_repeats_motifs.restype = C.c_int
+        L.inq_genotype_repeats_motifs.argtypes = [C.POINTER(CallArgsC), C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p,
+                                                  C.c_char_p, C.c_char_p, C.POINTER(PartStatsC), C.c_char_p, C.c_size_t]
+        L.inq_host_format_read_motif_rows.restype = C.c_size_t
+        L.inq_host_format_read_motif_rows.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_uint64, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t]
+        L.inq_host_motif_encode.restype = C.c_int
+        L.inq_host_motif_encode.argtypes = [C.c_char_p, C.POINTER(C.c_uint64)]
+        L.inq_host_motif_runs.restype = C.c_int
+        L.inq_host_motif_runs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
         L.inq_genotype_repeats_devices.restype = C.c_int
         L.inq_genotype_repeats_devices.argtypes = [C.POINTER(CallArgsC), C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.POINTER(PartStatsC), C.c_char_p, C.c_size_t]
         L.inq_host_set_local_share.restype = None
@@ -229,6 +244,8 @@ def load():
         L.inq_frontend_n_targets.argtypes = [vp]
         L.inq_frontend_target.restype = C.c_int
         L.inq_frontend_target.argtypes = [vp, C.c_uint64, C.POINTER(C.c_char_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.inq_frontend_target_name.restype = C.c_char_p
+        L.inq_frontend_target_name.argtypes = [vp, C.c_uint64]
         L.inq_frontend_sample.restype = C.c_char_p
         L.inq_frontend_sample.argtypes = [vp]
         L.inq_frontend_next.restype = C.c_int
@@ -369,7 +386,8 @@ def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str
                      threads: int = 1, unphased: bool = False, sample_name: Optional[str] = None,
                      reference: Optional[str] = None, out=None, device: int = 0, frontend: Optional[str] = None,
                      ties: Optional[str] = None, evidence: Optional[str] = None, read_calls: Optional[str] = None, devices=None,
-                     read_table: Optional[str] = None, read_seqs: Optional[str] = None) -> None:
+                     read_table: Optional[str] = None, read_seqs: Optional[str] = None, read_motifs: Optional[str] = None,
+                     motif: Optional[str] = None) -> None:
     """src/call.rs:76-86: same parameters, same output; raises CallError instead of exiting.
     frontend: "host" (BGZF inflate + record decode on CPU threads), "device" (inq_call_span: both on the GPU)
     or None (env INQ_FRONTEND, else the library default).
@@ -378,12 +396,14 @@ def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str
     read_calls: path of the read-calls file (inquistr call --read-calls): one line per row with the Calls behind its two medians.
     read_table: path of the read table (inquistr call --read-table): one line per kept read with its Call, group, name, pos, strand, mapq.
     read_seqs: path of the read-seqs file (inquistr call --read-seqs): the table's lines with the read's bases over the locus window.
-    devices: with read_calls, read_table or read_seqs, the HIP devices of inq_genotype_repeats_seqs (None: the one device `device`)."""
+    read_motifs: path of the read-motifs file (inquistr call --read-motifs): the same lines with the pure runs of the locus's motif in
+    those bases; motif: one motif for every target (default: column 4 of the BED; needed with a region string).
+    devices: with any of the four read files, the HIP devices of inq_genotype_repeats_motifs (None: the one device `device`)."""
     L = load()
     a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, reference, device, frontend, ties, evidence)
     out = sys.stdout if out is None else out
     out.flush()
-    if read_calls is None and read_table is None and read_seqs is None and devices is None:
+    if read_calls is None and read_table is None and read_seqs is None and read_motifs is None and devices is None:
         _checked(L.inq_genotype_repeats, C.byref(a), out.fileno())
         return
     devices = [] if devices is None else [int(d) for d in devices]
@@ -392,7 +412,9 @@ def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str
     path = os.fspath(read_calls).encode() if read_calls is not None else None
     table = os.fspath(read_table).encode() if read_table is not None else None
     seqs = os.fspath(read_seqs).encode() if read_seqs is not None else None
-    _checked(L.inq_genotype_repeats_seqs, C.byref(a), ids, len(devices), out.fileno(), path, table, seqs, st)
+    motifs = os.fspath(read_motifs).encode() if read_motifs is not None else None
+    _checked(L.inq_genotype_repeats_motifs, C.byref(a), ids, len(devices), out.fileno(), path, table, seqs, motifs,
+             motif.encode() if motif is not None else None, st)
 
 
 def genotype_repeats_devices(bamp: str, region: Optional[str], region_file: Optional[str], devices, minlen: int = 5, support: int = 3,
@@ -654,6 +676,11 @@ class FrontEnd(_Handle):
             self._L.inq_frontend_target(self._h, i, C.byref(c), C.byref(s), C.byref(e))
             out.append((c.value.decode(), s.value, e.value))
         return out
+
+    def target_names(self):
+        """inq_frontend_target_name of every target: column 4 of its BED line (str), None where the BED has none"""
+        got = [self._L.inq_frontend_target_name(self._h, i) for i in range(self._L.inq_frontend_n_targets(self._h))]
+        return [None if g is None else g.decode() for g in got]
 
     def read_names(self):
         """inq_frontend_read_names: the names of the reads of the batch batches() handed out last, as a list of bytes (read i's QNAME

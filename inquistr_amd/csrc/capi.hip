@@ -18,7 +18,9 @@
 #include "front_kernels.h"
 #include "kernels.h"
 #include "read_calls.h"
+#include "read_motifs.h"
 #include "read_seqs.h"
+#include "run_bytes.h"
 
 using namespace inq;
 
@@ -417,6 +419,12 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     const auto slices = [&] { launch_read_seq_records(ReadSeqArgs{x.kept_pair, n_kept, x.seq_qbeg, x.seq_len, x.seqs.recs, b->n_pairs}, s); };
     HIP_TRY(c, place_runs(x.names, origins));
     HIP_TRY(c, place_runs(x.seqs, slices));
+    // the motif runs of each record's bases, out of the batch's own slices: behind the slices' records, in front of nothing
+    if (x.motifs && b->n_pairs) {
+        launch_read_motifs(ReadMotifArgs{x.kept_pair, n_kept, x.kept_off, x.motif_word, b->n_loci, x.seq_bytes, x.seq_n_bytes, x.seq_off, x.seq_len,
+                                         b->n_pairs, x.motifs, b->n_pairs}, s);
+        HIP_TRY(c, hipGetLastError());
+    }
     if (ev) HIP_TRY(c, hipEventRecord(ev->e2, s));
     return INQ_OK;
 }
@@ -475,6 +483,73 @@ uint32_t inq_seq_window_tile(void) { return kSeqWindowTile; }
 
 int inq_read_seqs_fetch(inq_ctx_t *c, inq_read_seq_t *seqs, uint64_t n, uint8_t *packed, uint64_t seq_bytes) {
     return guarded([&] { return kept_runs_fetch(c, &inq_ctx::rseqs, seqs, n, sizeof *seqs, packed, seq_bytes); });
+}
+
+uint32_t inq_read_motif_tile(void) { return kReadMotifTile; }
+
+static int read_motifs_fetch_impl(inq_ctx_t *c, inq_read_motif_t *out, uint64_t n) {
+    if (!c || n > c->read_motifs_total || (n && !out)) return INQ_ERR_ARG;
+    if (!n) return INQ_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(out, c->rmotifs.p, (size_t)n * sizeof(inq_read_motif_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return INQ_OK;
+}
+int inq_read_motifs_fetch(inq_ctx_t *c, inq_read_motif_t *recs, uint64_t n) {
+    return guarded([&] { return read_motifs_fetch_impl(c, recs, n); });
+}
+
+// the motif kernel alone: records and packed slices as inq_read_seqs_fetch returns them go up, a record each comes down
+static int motif_runs_impl(inq_ctx_t *c, const inq_read_seq_t *recs, uint64_t n, const uint8_t *packed, uint64_t seq_bytes,
+                           const uint64_t *kept_off, const uint64_t *motif, uint64_t n_loci, inq_read_motif_t *out) {
+    if (!c) return INQ_ERR_ARG;
+    extras_reset(c);
+    if ((n && (!recs || !out)) || (seq_bytes && !packed) || !kept_off || (n_loci && !motif)) return INQ_ERR_ARG;
+    if (n >= (1ull << 40) || n_loci >= 0xfffffff0ull) return INQ_ERR_ARG;
+    for (uint64_t j = 0; j < n_loci; ++j)
+        if (kept_off[j] > kept_off[j + 1]) return INQ_ERR_ARG;
+    if (kept_off[n_loci] > n) return INQ_ERR_ARG;
+    if (!n) return INQ_OK;
+    if (!n_loci) {  // no record has a locus
+        std::memset(out, 0, (size_t)n * sizeof *out);
+        return INQ_OK;
+    }
+    // where each record's slice begins, and its length: the kernel's per-segment arrays
+    std::vector<uint64_t> seg_off(n);
+    std::vector<uint32_t> seg_len(n);
+    uint64_t at = 0;
+    for (uint64_t k = 0; k < n; ++k) seg_off[k] = at, seg_len[k] = recs[k].n_bases, at += run_bytes(recs[k]);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc;
+    struct Up {
+        DevBuf *d;
+        const void *h;
+        size_t bytes;
+    } ups[] = {
+        {&c->rseqs.bytes, packed, (size_t)seq_bytes},  // (scratch of the flushes' sequences and motifs, free between calls)
+        {&c->rseqs.off, seg_off.data(), (size_t)n * 8},
+        {&c->rseqs.recs, seg_len.data(), (size_t)n * 4},
+        {&c->rcoff, kept_off, (size_t)(n_loci + 1) * 8},
+        {&c->rmotifword, motif, (size_t)n_loci * 8},
+    };
+    for (auto &u : ups) {
+        if ((rc = ensure(c, *u.d, u.bytes)) != INQ_OK) return rc;
+        if (u.bytes) HIP_TRY(c, hipMemcpyAsync(u.d->p, u.h, u.bytes, hipMemcpyHostToDevice, s));
+    }
+    if ((rc = ensure(c, c->rmotifs, (size_t)n * sizeof(inq_read_motif_t))) != INQ_OK) return rc;
+    launch_read_motifs(ReadMotifArgs{nullptr, nullptr, (const uint64_t *)c->rcoff.p, (const uint64_t *)c->rmotifword.p, n_loci,
+                                     (const uint8_t *)c->rseqs.bytes.p, seq_bytes, (const uint64_t *)c->rseqs.off.p,
+                                     (const uint32_t *)c->rseqs.recs.p, n, (inq_read_motif_t *)c->rmotifs.p, n}, s);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, c->rmotifs.p, (size_t)n * sizeof(inq_read_motif_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));  // (the uploads' sources above live until here)
+    purge_retired(c);
+    return INQ_OK;
+}
+int inq_motif_runs(inq_ctx_t *c, const inq_read_seq_t *recs, uint64_t n, const uint8_t *packed, uint64_t seq_bytes, const uint64_t *kept_off,
+                   const uint64_t *motif, uint64_t n_loci, inq_read_motif_t *out) {
+    return guarded([&] { return motif_runs_impl(c, recs, n, packed, seq_bytes, kept_off, motif, n_loci, out); });
 }
 
 // the window walk alone: the batch goes up as a call's does, two arrays come down
@@ -897,6 +972,13 @@ int inq::extras_prepare(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const Hos
         if ((rc = runs(c->rseqs, d->seqs)) != INQ_OK) return rc;
         d->kept_pair = (uint64_t *)c->rkeptpair.p;
     }
+    if (h.motif) {
+        if (!h.seq_bytes) return INQ_ERR_ARG;
+        if ((rc = ensure(c, c->rmotifs, (size_t)n_pairs * sizeof(inq_read_motif_t))) != INQ_OK) return rc;
+        if ((rc = ensure(c, c->rmotifword, (size_t)n_loci * 8)) != INQ_OK) return rc;
+        d->motifs = (inq_read_motif_t *)c->rmotifs.p;
+        d->motif_word = (const uint64_t *)c->rmotifword.p;
+    }
     return INQ_OK;
 }
 
@@ -944,4 +1026,5 @@ void inq::extras_finish(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const Hos
     if (err == 0) c->read_calls_total = std::min<uint64_t>(h.kept_off[n_loci], n_pairs);
     if (h.name_bytes && err == 0) c->rnames.n_recs = c->read_calls_total, c->rnames.n_bytes = *h.name_bytes;
     if (h.seq_bytes && err == 0) c->rseqs.n_recs = c->read_calls_total, c->rseqs.n_bytes = *h.seq_bytes;
+    if (h.motif && err == 0) c->read_motifs_total = c->read_calls_total;
 }

@@ -60,11 +60,15 @@ struct inq_ctx {
     // inq_read_origin_t, those of rseqs inq_read_seq_t; rkeptpair: the pair each record came from, which only the bases are indexed by
     inq::KeptRuns rnames, rseqs;
     inq::DevBuf rkeptpair;
+    // the motif runs of those bases (inq_call_flush_motifs, read_motifs.hip): one inq_read_motif_t per kept record, which stay until the
+    // context's next call (inq_read_motifs_fetch), and the loci's motif words.  Allocated by flushes with motifs only
+    inq::DevBuf rmotifs, rmotifword;
+    uint64_t read_motifs_total = 0;  // records of the last flush with motifs (0: it had none)
     inq::DevBuf ovalues, olen, oflags, okeep, otrans;  // inq_outlier_rows
     // every DevBuf above, for inq_ctx_destroy (DevBuf frees nothing itself): a member missing here leaks
     auto bufs() {
         std::vector<inq::DevBuf *> all{&worklist, &sval, &smeta, &deep, &cigar, &reads, &pair_read, &off, &lstart, &lend, &p1, &p2, &pcall, &pbits,
-                                       &lflags, &levidence, &evwork, &rctiles, &rcoff, &rckept, &rkeptpair, &ovalues, &olen, &oflags, &okeep, &otrans};
+                                       &lflags, &levidence, &evwork, &rctiles, &rcoff, &rckept, &rkeptpair, &rmotifs, &rmotifword, &ovalues, &olen, &oflags, &okeep, &otrans};
         for (inq::KeptRuns *k : {&rnames, &rseqs})
             for (inq::DevBuf *b : k->bufs()) all.push_back(b);
         return all;
@@ -187,6 +191,13 @@ struct LocusExtras {
     Runs<inq_read_seq_t> seqs;
     uint64_t *kept_pair = nullptr;
     const uint32_t *seq_qbeg = nullptr, *seq_len = nullptr;  // [n_pairs]
+    // the motif runs of those bases (needs seqs): a record per kept record out of motif_word[n_loci] and the batch's own per-pair
+    // slices, seq_len[p] bases packed from byte seq_off[p] of seq_bytes on
+    inq_read_motif_t *motifs = nullptr;
+    const uint64_t *motif_word = nullptr;
+    const uint8_t *seq_bytes = nullptr;
+    uint64_t seq_n_bytes = 0;
+    const uint64_t *seq_off = nullptr;  // [n_pairs]
 };
 // Where a flush takes the runs of one kind from, the deferred batch's (SpanState::Acc hands them over): n runs back to back in `bytes`,
 // run i at off[i].  by_pair: a kept record's run is that of the pair it came from (the bases), else that of its read (the names)
@@ -205,6 +216,7 @@ struct HostExtras {
     uint64_t *kept_off = nullptr;
     uint64_t *name_bytes = nullptr;  // a flush with origins (needs kept_off): receives the bytes of the kept records' names
     uint64_t *seq_bytes = nullptr;   // a flush with sequences (needs kept_off): receives the bytes of the kept records' packed slices
+    const uint64_t *motif = nullptr;  // a flush with motifs (needs seq_bytes): the loci's motif words, read, not written
     // the evidence is counted and the lists are compacted from the per-pair outputs: the call keeps those (pcall / pbits) also when
     // its caller did not ask for them
     bool per_pair() const { return evidence || kept_off; }
@@ -212,7 +224,7 @@ struct HostExtras {
 // The three steps of a host-buffer call or a flush around its launch sequence.  First of all extras_reset: the records of the call
 // before are no longer offered, however this one ends.
 inline void extras_reset(inq_ctx *c) {
-    c->read_calls_total = 0;
+    c->read_calls_total = c->read_motifs_total = 0;
     for (KeptRuns *k : {&c->rnames, &c->rseqs}) k->n_recs = k->n_bytes = 0;
 }
 // the context buffers behind what h asks for (and pcall / pbits where h.per_pair()), as device pointers

@@ -1,0 +1,217 @@
+// read_motifs.hip — the motif runs of the bases behind each Call (inq_read_motif_t): where the longest pure run of the locus's motif
+// lies in a kept record's slice, how many bases pure runs of at least one motif copy cover, and how many such runs there are.
+//
+// Layout: one 16-lane row per kept record, four records per wave, sixteen per workgroup (kReadMotifTile); LANE r OF A ROW OWNS
+// ROTATION r, lanes >= k idle.  All lanes of a row read the same 8 bytes of the slice per step, 16 bases, and each compares them with
+// its own view of the motif: the word repeated to 32 nibbles, shifted by (16 * step + r) mod k.  XOR and a zero-nibble test give a
+// 16-bit hit mask; the lane walks the mask's runs with count-trailing-zero steps and carries its open run's length (u32) to the next
+// word, so a 40 000-base soft clip is the same loop as a 30-base window.  Whether a base lies in a run of >= k is known once the run
+// has ended or has reached k: at a word's end at most k - 1 <= 14 trailing bases are undecided, all of them in that word, and the
+// next word decides them.  So the coverage mask of word w - 1 is final while word w is handled; it is ORed across the row (four DPP
+// steps) and pop-counted.  At the end a row maximum of (run_len, -run_beg), a row sum of the run counts and one 16-byte store.
+// No LDS, no atomics, no workgroup waits for another: every output is a plain function of the inputs.
+//
+// Bounds: a record whose segment index, locus, offset or length lies outside what the launch holds gets four zeros and reads nothing
+// of the bases; every byte read lies in [seg_off[p], seg_off[p] + (n + 1) / 2) and inside `bytes`; the odd last nibble is masked out
+// of the hits, so neither it nor the next segment's first base can extend a run.
+#include <hip/hip_runtime.h>
+
+#include "cigar_walk.h"
+#include "read_motifs.h"
+#include "segment_store.h"
+
+namespace inq {
+namespace {
+
+constexpr uint32_t kThreads = 256;
+static_assert(kReadMotifTile * kMotifRowLanes == kThreads, "a workgroup's lanes are dealt among its rows");
+static_assert(kMotifRowLanes == (uint32_t)kRowLanes, "a row is one DPP row");
+static_assert(sizeof(inq_read_motif_t) == 16, "a record is one 16-byte store");
+
+constexpr uint64_t kNibbleOnes = 0x1111111111111111ull;
+
+// the motif repeated to 32 nibbles (nibble j = m[j mod k]); k = 0: no motif
+struct Motif {
+    unsigned __int128 rep;
+    uint32_t k;
+};
+__device__ __forceinline__ Motif decode_motif(uint64_t word) {
+    Motif M{0, (uint32_t)(word >> 60)};
+    if (!M.k) return M;
+    const uint64_t mask = ~0ull >> (64u - 4u * M.k), m = word & mask;
+    // every nibble one of 1, 2, 4, 8: exactly one bit set
+    if ((m & kNibbleOnes) + (m >> 1 & kNibbleOnes) + (m >> 2 & kNibbleOnes) + (m >> 3 & kNibbleOnes) != (kNibbleOnes & mask)) {
+        M.k = 0;
+        return M;
+    }
+    M.rep = m;
+    for (uint32_t len = M.k; len < 32u; len *= 2u) M.rep |= M.rep << (4u * len);
+    return M;
+}
+
+// Bytes [8 w, 8 w + 8) of a segment of nb bytes as a little-endian word, cut to the segment: a byte at or past nb is 0 and is not read.
+// The segment starts wherever its slice does, so the loads are unaligned ones
+__device__ __forceinline__ uint64_t load_segment_word(const uint8_t *seg, uint64_t nb, uint64_t w) {
+    const uint64_t o = w * 8u;
+    uint64_t v = 0;
+    if (o >= nb) return v;
+    if (nb - o >= 8u) {
+        __builtin_memcpy(&v, seg + o, 8);
+        return v;
+    }
+    for (uint32_t i = 0; i < (uint32_t)(nb - o); ++i) v |= (uint64_t)seg[o + i] << (8u * i);
+    return v;
+}
+
+// bit t of the result: nibble t of x is zero
+__device__ __forceinline__ uint32_t zero_nibbles(uint64_t x) {
+    uint64_t t = ~x;
+    t &= t >> 1;
+    t &= t >> 2;
+    t &= kNibbleOnes;  // bit 4 t: nibble t was all ones
+    t = (t | t >> 3) & 0x0303030303030303ull;
+    t = (t | t >> 6) & 0x000f000f000f000full;
+    t = (t | t >> 12) & 0x000000ff000000ffull;
+    return (uint32_t)(t | t >> 24) & 0xffffu;
+}
+
+__device__ __forceinline__ uint32_t row_or(uint32_t x) {  // lane 15 of the row holds the OR of its lanes
+    x |= dpp_shr_zero<DPP_ROW_SHR1>(x);
+    x |= dpp_shr_zero<DPP_ROW_SHR2>(x);
+    x |= dpp_shr_zero<DPP_ROW_SHR4>(x);
+    x |= dpp_shr_zero<DPP_ROW_SHR8>(x);
+    return x;
+}
+__device__ __forceinline__ uint64_t row_max_u64(uint64_t x) {  // ... the maximum
+#define INQ_STEP(CTRL)                                                                                                              \
+    {                                                                                                                               \
+        const uint64_t o = (uint64_t)dpp_shr_zero<CTRL>((uint32_t)x) | (uint64_t)dpp_shr_zero<CTRL>((uint32_t)(x >> 32)) << 32;    \
+        x = o > x ? o : x;                                                                                                          \
+    }
+    INQ_STEP(DPP_ROW_SHR1)
+    INQ_STEP(DPP_ROW_SHR2)
+    INQ_STEP(DPP_ROW_SHR4)
+    INQ_STEP(DPP_ROW_SHR8)
+#undef INQ_STEP
+    return x;
+}
+
+__global__ __launch_bounds__(256) void read_motif_kernel(ReadMotifArgs a) {
+    const int lane = lane_id();
+    const uint32_t rl = (uint32_t)lane & (kMotifRowLanes - 1u);
+    const int row_shift = lane & ~(int)(kMotifRowLanes - 1u);  // where this row's bits lie in a ballot
+    uint64_t total = a.n_kept ? *a.n_kept : a.n_recs;  // the records the compaction wrote
+    if (total > a.n_recs) total = a.n_recs;
+    // (the grid is capped, launch_read_motifs: a workgroup takes every gridDim.x-th tile)
+    for (uint64_t base = (uint64_t)blockIdx.x * kReadMotifTile; base < total; base += (uint64_t)gridDim.x * kReadMotifTile) {
+        const uint64_t rec = base + threadIdx.x / kMotifRowLanes;
+        const bool has = rec < total;
+
+        // the record's locus: the j with kept_off[j] <= rec < kept_off[j + 1], sixteen probes a step (as seq_window_kernel finds a
+        // pair's).  Offsets that do not ascend end the search all the same, and what it found is checked below.
+        uint64_t lo = 0, hi = has ? a.n_loci : 0;
+        while (ballot64(hi - lo > 1u)) {
+            const uint64_t size = hi - lo, step = (size + kMotifRowLanes - 1u) / kMotifRowLanes, idx = lo + rl * step;
+            const bool below = size > 1u && idx < hi && a.kept_off[idx + 1] <= rec;
+            const uint32_t c = (uint32_t)__popc((uint32_t)(ballot64(below) >> row_shift) & 0xffffu);
+            if (size > 1u) {
+                if (c == 0u) {
+                    hi = lo + 1u;
+                } else {
+                    const uint64_t last = lo + (uint64_t)(c - 1u) * step;  // the last probe at or below rec; it lies in front of hi
+                    lo = last + 1u;
+                    hi = last + step + 1u < hi ? last + step + 1u : hi;
+                }
+            }
+        }
+        bool live = has && lo < a.n_loci && a.kept_off[lo] <= rec && rec < a.kept_off[lo + 1];
+        Motif M{0, 0u};
+        if (live) M = decode_motif(a.motif[lo]);
+        live = live && M.k != 0u;
+        const uint8_t *seg = a.bytes;
+        uint64_t n = 0;  // bases of the slice
+        if (live) {
+            const uint64_t p = a.kept_pair ? a.kept_pair[rec] : rec;
+            live = p < a.n_segs;
+            if (live) {
+                const uint64_t o = a.seg_off[p], nb = ((uint64_t)a.seg_len[p] + 1u) / 2u;
+                live = o <= a.n_bytes && nb <= a.n_bytes - o;
+                if (live) seg += o, n = a.seg_len[p];
+            }
+        }
+        const uint64_t n_words = (n + 15u) / 16u, nb = (n + 1u) / 2u;
+        const uint32_t k = M.k;
+        const bool mine = live && rl < k;         // this lane has a rotation
+        const uint32_t step16 = k ? 16u % k : 0u;  // what 16 bases add to the phase
+        uint32_t ph = mine ? rl : 0u;             // (16 w + r) mod k
+
+        // the lane's runs: the open one's length at the last word's end, the longest and its start, the runs of >= k; the coverage of
+        // the word before (cov_prev) and what of it waits for the open run to reach k (pend)
+        uint32_t open = 0, best_len = 0, best_beg = 0, n_runs = 0, cov_prev = 0, pend = 0, covered = 0;
+        auto finish = [&](uint32_t len, uint32_t beg) -> bool {
+            if (len > best_len) best_len = len, best_beg = beg;  // (runs come in ascending order of their start: a tie keeps the first)
+            if (len < k) return false;
+            ++n_runs;
+            return true;
+        };
+        for (uint64_t w = 0; ballot64(w < n_words); ++w) {
+            const bool on = w < n_words;
+            uint32_t h = 0, cov_cur = 0;
+            if (on) {
+                uint64_t s = load_segment_word(seg, nb, w);
+                s = (s & 0x0f0f0f0f0f0f0f0full) << 4 | (s >> 4 & 0x0f0f0f0f0f0f0f0full);  // base t of the word in nibble t
+                const uint64_t left = n - w * 16u;
+                h = zero_nibbles(s ^ (uint64_t)(M.rep >> (4u * ph))) & (left >= 16u ? 0xffffu : (1u << (uint32_t)left) - 1u);
+                if (!mine) h = 0u;
+                ph += step16;
+                if (ph >= k) ph -= k;
+                const uint32_t pos0 = (uint32_t)(w * 16u);
+                const uint32_t lead = (uint32_t)__builtin_ctz(~h | 0x10000u);  // hits that carry the open run on
+                if (lead == 16u) {  // the whole word: the run is longer than any motif
+                    open += 16u;
+                    cov_prev |= pend;
+                    pend = 0u;
+                    cov_cur = 0xffffu;
+                } else {
+                    if (open + lead != 0u && finish(open + lead, pos0 - open)) cov_prev |= pend, cov_cur = (1u << lead) - 1u;
+                    pend = 0u, open = 0u;
+                    uint32_t hh = h & ~((1u << lead) - 1u);
+                    while (hh) {
+                        const uint32_t b = (uint32_t)__builtin_ctz(hh), len = (uint32_t)__builtin_ctz(~(hh >> b)), bits = ((1u << len) - 1u) << b;
+                        if (b + len == 16u) {  // open at the word's end
+                            open = len;
+                            if (len >= k)
+                                cov_cur |= bits;
+                            else
+                                pend = bits;
+                        } else if (finish(len, pos0 + b)) {
+                            cov_cur |= bits;
+                        }
+                        hh &= ~bits;
+                    }
+                }
+            }
+            // word w - 1 is decided now
+            covered += (uint32_t)__popc(row_or(on ? cov_prev : 0u));
+            if (on) cov_prev = cov_cur;
+        }
+        if (open != 0u && finish(open, (uint32_t)n - open)) cov_prev |= pend;
+        covered += (uint32_t)__popc(row_or(cov_prev));
+        // the longest run of the row, the smallest start among equals
+        const uint64_t best = row_max_u64((uint64_t)best_len << 32 | (uint64_t)(0xffffffffu - best_beg));
+        const uint32_t runs = row_inclusive_scan_u32(n_runs);
+        if (has && rl == kMotifRowLanes - 1u)
+            *reinterpret_cast<uint4 *>(a.recs + rec) = make_uint4(0xffffffffu - (uint32_t)best, (uint32_t)(best >> 32), covered, runs);
+    }
+}
+
+constexpr uint32_t kGridCap = 1u << 16;  // workgroups of a launch (capped_grid)
+
+}  // namespace
+
+void launch_read_motifs(const ReadMotifArgs &a, hipStream_t s) {
+    if (!a.n_recs || !a.motif) return;
+    hipLaunchKernelGGL(read_motif_kernel, dim3(capped_grid((a.n_recs + kReadMotifTile - 1) / kReadMotifTile, kGridCap)), dim3(kThreads), 0, s, a);
+}
+
+}  // namespace inq

@@ -15,6 +15,7 @@
 #include "deflate_probe.h"
 #include "front_kernels.h"
 #include "read_calls.h"
+#include "read_motifs.h"
 #include "read_seqs.h"
 
 namespace inq {
@@ -680,6 +681,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
         if (!h.name_bytes || (A.n_spans && !A.seqs.on)) return INQ_ERR_ARG;
         *h.seq_bytes = 0;
     }
+    if (h.motif && !h.seq_bytes) return INQ_ERR_ARG;  // the motif runs are those of the bases
     if (A.n_loci == 0) {
         A.reset();
         extras_finish(c, 0, 0, h, 0);
@@ -701,6 +703,10 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     if ((rc = extras_prepare(c, nl, A.n_pairs, h, &x)) != INQ_OK) return rc;
     if (h.name_bytes) x.name_off = (const uint64_t *)A.names.off.p;
     if (h.seq_bytes) x.seq_qbeg = (const uint32_t *)A.seq_qbeg.p, x.seq_len = (const uint32_t *)A.seq_len.p;
+    if (h.motif) {  // the loci's motif words go up; the bases are the batch's own per-pair slices
+        x.seq_bytes = (const uint8_t *)A.seqs.bytes.p, x.seq_n_bytes = A.seqs.n_bytes, x.seq_off = (const uint64_t *)A.seqs.off.p;
+        HIP_TRY(c, hipMemcpyAsync(c->rmotifword.p, h.motif, nl * 8, hipMemcpyHostToDevice, s));
+    }
     const bool per_pair = h.per_pair();
     if ((rc = ensure_row_staging(c, S, nl, 2 * nl + (h.flags ? (nl + 7) / 8 : 0))) != INQ_OK) return rc;  // the rows, then the flags
     DevBatch d = device_batch(A.cigar.p, A.reads.p, A.pair_read.p, A.off.p, A.lstart.p, A.lend.p, A.n_reads, A.n_units * 4, A.n_pairs, nl,
@@ -979,9 +985,14 @@ int inq_call_flush_origins(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, 
 
 int inq_call_flush_seqs(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
                         inq_locus_evidence_t *evidence, uint64_t *kept_off, uint64_t *name_bytes, uint64_t *seq_bytes) {
+    return inq_call_flush_motifs(c, result, n_loci, ms_call, locus_flags, evidence, kept_off, name_bytes, seq_bytes, nullptr);
+}
+
+int inq_call_flush_motifs(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
+                          inq_locus_evidence_t *evidence, uint64_t *kept_off, uint64_t *name_bytes, uint64_t *seq_bytes, const uint64_t *motif) {
     return guarded([&] {
         if (!kept_off || !name_bytes) return (int)INQ_ERR_ARG;
-        return call_flush_impl(c, result, n_loci, ms_call, nullptr, HostExtras{locus_flags, evidence, kept_off, name_bytes, seq_bytes});
+        return call_flush_impl(c, result, n_loci, ms_call, nullptr, HostExtras{locus_flags, evidence, kept_off, name_bytes, seq_bytes, motif});
     });
 }
 

@@ -93,6 +93,10 @@ ABI_SYMBOLS = (
     "inq_span_fetch_seqs",
     "inq_seq_windows",
     "inq_seq_window_tile",
+    "inq_call_flush_motifs",
+    "inq_read_motifs_fetch",
+    "inq_motif_runs",
+    "inq_read_motif_tile",
 )
 
 
@@ -211,6 +215,27 @@ SEQ_DTYPE = np.dtype([("q_beg", "<u4"), ("n_bases", "<u4")])
 SEQ_CODES = "=ACMGRSVTWYHKDBN"  # the BAM's 4-bit base codes
 
 
+class ReadMotifC(C.Structure):
+    """inq_read_motif_t"""
+
+    _fields_ = [("run_beg", C.c_uint32), ("run_len", C.c_uint32), ("motif_bases", C.c_uint32), ("n_runs", C.c_uint32)]
+
+
+MOTIF_DTYPE = np.dtype([("run_beg", "<u4"), ("run_len", "<u4"), ("motif_bases", "<u4"), ("n_runs", "<u4")])
+
+
+def encode_motif(text: str) -> int:
+    """The motif word of inq_read_motif_t for a motif's text (nibble 15: k, nibbles 0 .. k - 1: A = 1, C = 2, G = 4, T = 8): upper-cased,
+    ACGT only, reduced to its primitive root, 1 to 15 bases; 0 ("no motif") for anything else.  The rule of inq_host_motif_encode."""
+    t = text.upper()
+    if not t or any(ch not in "ACGT" for ch in t):
+        return 0
+    k = next(k for k in range(1, len(t) + 1) if len(t) % k == 0 and t[:k] * (len(t) // k) == t)
+    if k > 15:
+        return 0
+    return k << 60 | sum({"A": 1, "C": 2, "G": 4, "T": 8}[ch] << (4 * i) for i, ch in enumerate(t[:k]))
+
+
 def unpack_seq(packed, n_bases: int) -> str:
     """The text of a packed slice (two bases to a byte, the first in the high nibble)."""
     b = np.asarray(packed, dtype=np.uint8)
@@ -252,8 +277,8 @@ class InqError(RuntimeError):
 
 
 _lib = None
-# the entries of a family: each takes the side outputs of the one before and its own (`_origins`, `_seqs`: the flush family only)
-_SIDE_SUFFIXES = ("", "_flags", "_evidence", "_reads", "_origins", "_seqs")
+# the entries of a family: each takes the side outputs of the one before and its own (`_origins`, `_seqs`, `_motifs`: the flush family only)
+_SIDE_SUFFIXES = ("", "_flags", "_evidence", "_reads", "_origins", "_seqs", "_motifs")
 
 
 def load(path: Optional[str] = None):
@@ -293,12 +318,12 @@ def load(path: Optional[str] = None):
     L.inq_ctx_destroy.restype = None
     L.inq_ctx_destroy.argtypes = [vp]
     # The three families of calls with per-locus side outputs: a member takes the family's arguments, then one pointer for each side
-    # output it adds (flags | evidence | kept_off, and kept for the device form | name_bytes | seq_bytes), then - the device form - the
+    # output it adds (flags | evidence | kept_off, and kept for the device form | name_bytes | seq_bytes | motif), then - the device form - the
     # stream.
     for family, head, widths, tail in (
         ("inq_call_batch", [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC)], (0, 1, 2, 3), []),
         ("inq_call_batch_device", [vp, C.POINTER(InqBatchC), C.POINTER(InqResultC)], (0, 1, 2, 4), [vp]),
-        ("inq_call_flush", [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double)], (0, 1, 2, 3, 4, 5), []),
+        ("inq_call_flush", [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double)], (0, 1, 2, 3, 4, 5, 6), []),
     ):
         for suffix, n_side in zip(_SIDE_SUFFIXES, widths):
             fn = getattr(L, family + suffix)
@@ -326,6 +351,12 @@ def load(path: Optional[str] = None):
     L.inq_seq_windows.argtypes = [vp, C.POINTER(InqBatchC), vp, vp, vp]
     L.inq_seq_window_tile.restype = C.c_uint32
     L.inq_seq_window_tile.argtypes = []
+    L.inq_read_motifs_fetch.restype = C.c_int
+    L.inq_read_motifs_fetch.argtypes = [vp, vp, C.c_uint64]
+    L.inq_motif_runs.restype = C.c_int
+    L.inq_motif_runs.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp]
+    L.inq_read_motif_tile.restype = C.c_uint32
+    L.inq_read_motif_tile.argtypes = []
     L.inq_ctx_status.restype = C.c_int
     L.inq_ctx_status.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.inq_ctx_timing_enable.restype = C.c_int
@@ -452,14 +483,17 @@ class Context:
         sb = np.full(1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if seq_bytes else None
         return fl, ev, off, nb, sb
 
-    def _side_call(self, entry: str, head, n: int, width: int, check: bool, flags: bool = True, evidence: bool = True):
+    def _side_call(self, entry: str, head, n: int, width: int, check: bool, flags: bool = True, evidence: bool = True, motif=None):
         """Calls `entry`, the member of its family that takes `width` side outputs, with `head` and the arrays of _side_arrays; raises on
         error if check.  Returns (code, flags, evidence, kept_off, records), each cut to the n loci, None where not taken; the records are
         fetched behind a successful call with the lists.  width 4 (a flush with origins) adds a sixth element: (origins, names,
         name_bytes) fetched the same way, (None, None, name_bytes) after a failed call; width 5 (a flush with sequences) a seventh:
-        (seqs, packed, seq_bytes)."""
+        (seqs, packed, seq_bytes); width 6 (a flush with motifs; motif: the loci's words, u64 [n], or None for a null pointer) an
+        eighth: the MOTIF_DTYPE records, fetched the same way (None after a failed call)."""
         fl, ev, off, nb, sb = self._side_arrays(n, flags and width >= 1, evidence and width >= 2, width >= 3, width >= 4, width >= 5)
-        side = [None if a is None else a.ctypes.data for a in (fl, ev, off, nb, sb)][:width]
+        mw = None if motif is None else np.ascontiguousarray(motif, dtype=np.uint64)
+        assert mw is None or (width >= 6 and len(mw) >= n)
+        side = [None if a is None else a.ctypes.data for a in (fl, ev, off, nb, sb, mw)][:width]
         rc = getattr(self._L, entry)(self._h, *head, *side)
         if rc != INQ_OK and check:
             self._raise(rc)
@@ -471,6 +505,8 @@ class Context:
         if sb is not None:
             what = self.read_seqs_fetch(int(off[-1]), int(sb[0])) if rc == INQ_OK else (None, None)
             out += (what + (int(sb[0]),),)
+        if width >= 6:
+            out += ((self.read_motifs_fetch(int(off[-1]) if mw is not None else 0) if rc == INQ_OK else None,),)
         return out
 
     def _batch_call(self, entry: str, batch: Batch, debug: bool, width: int, check: bool, **which):
@@ -674,7 +710,7 @@ class Context:
     def deferred_loci(self) -> int:
         return int(self._L.inq_call_deferred_loci(self._h))
 
-    def _flush_call(self, entry: str, width: int, check: bool):
+    def _flush_call(self, entry: str, width: int, check: bool, motif=None):
         """(code, phase1, phase2, n_tie_loci, ms_call) of `entry` for every locus deferred since the last flush, then the first `width`
         of flags, evidence, kept_off + records, origins + names + name_bytes, seqs + packed + seq_bytes."""
         n = self.deferred_loci
@@ -682,7 +718,7 @@ class Context:
         p2 = np.full(n, np.nan)
         res = InqResultC(p1.ctypes.data, p2.ctypes.data, None, None, 0)
         ms = C.c_double(0.0)
-        rc, fl, ev, off, rec, *who = self._side_call(entry, (C.byref(res), n, C.byref(ms)), n, width, check)
+        rc, fl, ev, off, rec, *who = self._side_call(entry, (C.byref(res), n, C.byref(ms)), n, width, check, motif=motif)
         return (rc, p1, p2, int(res.n_tie_loci), float(ms.value)) + (fl, ev, off, rec)[: width + (width >= 3)] + tuple(x for w in who for x in w)
 
     def call_flush(self, check: bool = True):
@@ -711,6 +747,43 @@ class Context:
         """inq_call_flush_seqs: as call_flush_origins, plus one SEQ_DTYPE record per kept record (same order), their packed slices
         back to back (uint8) and the slices' total as the thirteenth to fifteenth element (None, None, total after a failed call)."""
         return self._flush_call("inq_call_flush_seqs", 5, check)
+
+    def call_flush_motifs(self, motif, check: bool = True):
+        """inq_call_flush_motifs: as call_flush_seqs, plus one MOTIF_DTYPE record per kept record (same order) as the sixteenth element
+        (None after a failed call).  motif: the motif words of the deferred loci in append order (u64), or None for a null pointer,
+        which is exactly call_flush_seqs (the records then number 0)."""
+        return self._flush_call("inq_call_flush_motifs", 6, check, motif=motif)
+
+    def read_motifs_fetch(self, n: int, check: bool = True):
+        """inq_read_motifs_fetch: the first n records (MOTIF_DTYPE) of the last call_flush_motifs (check=False: (code, records))."""
+        rec = np.full(max(n, 1) * MOTIF_DTYPE.itemsize, 0xFF, dtype=np.uint8)
+        rc = self._L.inq_read_motifs_fetch(self._h, rec.ctypes.data, n)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        got = rec.view(MOTIF_DTYPE)[:n]
+        return got if check else (rc, got)
+
+    @property
+    def read_motif_tile(self) -> int:
+        return int(self._L.inq_read_motif_tile())
+
+    def motif_runs(self, seqs, packed, kept_off, motif, check: bool = True):
+        """inq_motif_runs: the motif kernel alone over what read_seqs_fetch returns - seqs (SEQ_DTYPE [n]) and their packed slices back
+        to back (uint8) -, kept_off u64 [n_loci + 1] and the loci's motif words u64 [n_loci]; MOTIF_DTYPE [n] (check=False: (code,
+        records))."""
+        seqs = np.ascontiguousarray(seqs, dtype=SEQ_DTYPE)
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        kept_off = np.ascontiguousarray(kept_off, dtype=np.uint64)
+        motif = np.ascontiguousarray(motif, dtype=np.uint64)
+        n, n_loci = len(seqs), len(kept_off) - 1
+        assert len(motif) >= n_loci >= 0
+        out = np.full(max(n, 1) * MOTIF_DTYPE.itemsize, 0xFF, dtype=np.uint8)
+        rc = self._L.inq_motif_runs(self._h, seqs.ctypes.data if n else None, n, packed.ctypes.data if packed.size else None, packed.size,
+                                    kept_off.ctypes.data, motif.ctypes.data if n_loci else None, n_loci, out.ctypes.data)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        got = out.view(MOTIF_DTYPE)[:n]
+        return got if check else (rc, got)
 
     def span_fetch_seqs(self, n_pairs: int, cap_bytes: int, check: bool = True):
         """inq_span_fetch_seqs: (q_beg u32, n_bases u32, seq_off u64 [n_pairs + 1], packed uint8) of ALL pairs of the batch the last

@@ -83,6 +83,7 @@ inline bool write_all(int fd, const std::string &s) { return write_all(fd, s.dat
 struct Prepared {
     std::unique_ptr<BamFile> bam;
     std::vector<RepeatInterval> targets;
+    std::vector<std::string> target_name;  // column 4 of the BED, [k] of targets[k]; empty where there is none (TargetsResult::name)
     std::string sample;
 };
 
@@ -107,6 +108,10 @@ struct BedCache {
 };
 
 int prepare(const inq_call_args_t *a, Prepared &P, std::string &msg, BedCache *bed_cache = nullptr);
+// The motif words of P's targets for the read-motifs file: `motif` for every target, or (null) column 4 of the BED, each through
+// motif_encode; a target whose text does not encode gets word 0 and their number goes to stderr once.  INQ_EXIT_ERROR and a message
+// when `motif` does not encode, or when there is neither it nor a fourth column
+int target_motif_words(const Prepared &P, const char *motif, std::vector<uint64_t> &words, std::string &msg);
 // ... for an entry of the C ABI: the message goes to the caller's buffer
 inline int prepare(const inq_call_args_t *a, Prepared &P, char *errbuf, size_t errcap, BedCache *bed_cache = nullptr) {
     std::string msg;
@@ -318,18 +323,18 @@ inline void scatter(const T *src, const uint32_t *index, size_t n, T *dst) {
 // The per-target reports of a call, beside its rows: the tie report (inq_call_args_t::ties_path), the evidence file (::evidence_path), the
 // read-calls file (inq_genotype_repeats_reads), the read table (inq_genotype_repeats_table; it needs the read-calls lists, which are
 // then collected with it), the read-seqs file (inq_genotype_repeats_seqs; its lines name the reads: the table's lists are collected
-// with it).  One value at every layer; a further report is one more member of each of the three
+// with it), the read-motifs file (inq_genotype_repeats_motifs; the runs are those of the bases: the slices are collected with it).  One value at every layer; a further report is one more member of each of the three
 // structs, a line in begin / scatter_from, a row in write_rows' table and a pointer in BatchRows::call / flush.  A further per-read
 // payload (a byte run behind each record, as the names and the bases are) is a record type with its inq::run_bytes(), one more
 // RecordRuns in TargetReports and in BatchRows, and a ByteRuns in ReadStore (front_end.h) where the host sweep is to keep it.
 struct ReportSet {  // which of them are collected: what is not adds nothing to the launch sequence
-    bool ties = false, evidence = false, read_calls = false, read_table = false, read_seqs = false;
+    bool ties = false, evidence = false, read_calls = false, read_table = false, read_seqs = false, read_motifs = false;
 };
 struct ReportFds {  // where a text call writes them, in the .inq's row order (-1: no file)
-    int ties = -1, evidence = -1, read_calls = -1, read_table = -1, read_seqs = -1;
-    ReportSet wanted() const {
-        const bool who = read_table >= 0 || read_seqs >= 0;
-        return ReportSet{ties >= 0, evidence >= 0, read_calls >= 0 || who, who, read_seqs >= 0};
+    int ties = -1, evidence = -1, read_calls = -1, read_table = -1, read_seqs = -1, read_motifs = -1;
+    ReportSet wanted() const {  // (the motif runs are those of the bases: the slices are collected with them)
+        const bool bases = read_seqs >= 0 || read_motifs >= 0, who = read_table >= 0 || bases;
+        return ReportSet{ties >= 0, evidence >= 0, read_calls >= 0 || who, who, bases, read_motifs >= 0};
     }
 };
 // ... of a set of targets (a call's, a device part's, one device call's loci): [k] belongs to target k of the set.  A target no batch or
@@ -341,6 +346,9 @@ struct TargetReports {
     ReadCallLists read_calls;                    // the records of the target's kept reads in file order
     std::vector<ReadIdentities> read_table;      // ... and who each of them is
     std::vector<ReadSlices> read_seqs;           // ... and the bases behind each Call
+    std::vector<std::vector<inq_read_motif_t>> read_motifs;  // ... and the motif runs of those bases
+    // what the runs are measured with, an INPUT: the targets' motif words (inq_read_motif_t), set by whoever begins the reports
+    std::vector<uint64_t> motif_word;
     void begin(size_t n, ReportSet which) {
         has = which;
         ties.assign(which.ties ? n : 0, 0);
@@ -348,6 +356,8 @@ struct TargetReports {
         read_calls.assign(which.read_calls ? n : 0, std::vector<inq_read_call_t>());
         read_table.assign(which.read_table ? n : 0, ReadIdentities());
         read_seqs.assign(which.read_seqs ? n : 0, ReadSlices());
+        read_motifs.assign(which.read_motifs ? n : 0, std::vector<inq_read_motif_t>());
+        motif_word.assign(which.read_motifs ? n : 0, 0);
     }
     // what part collected (nothing this one does not), part's k-th -> target idx[k]; the lists are moved out of part
     void scatter_from(TargetReports &part, const uint32_t *idx, size_t n) {
@@ -359,6 +369,8 @@ struct TargetReports {
             for (size_t k = 0; k < n; ++k) read_table[idx[k]] = std::move(part.read_table[k]);
         if (part.has.read_seqs)
             for (size_t k = 0; k < n; ++k) read_seqs[idx[k]] = std::move(part.read_seqs[k]);
+        if (part.has.read_motifs)
+            for (size_t k = 0; k < n; ++k) read_motifs[idx[k]] = std::move(part.read_motifs[k]);
     }
 };
 
@@ -378,6 +390,8 @@ struct SessionHooks {
     // what report_fds asks for into one of its own); a text call writes each file whose fd is set
     TargetReports *reports = nullptr;
     ReportFds report_fds;
+    // the motif words of the call's whole target list (the read-motifs file), [i] of target i of Prepared::targets; null: none has one
+    const std::vector<uint64_t> *motif_words = nullptr;
     // the caller owns the context AND the process ends with this call (fast_exit()): a pipeline the call made itself is left to the
     // operating system after a clean run (unmapping a GB of touched pages takes ~0.1 s), as the caller then leaves its context
     bool process_is_leaving = false;
@@ -397,22 +411,24 @@ struct ReportFile {
     int open(const char *path, const char *what, std::string &msg);
 };
 constexpr const char *kTiesWhat = "the tie report", *kEvidenceWhat = "the evidence file", *kReadCallsWhat = "the read-calls file",
-                      *kReadTableWhat = "the read table", *kReadSeqsWhat = "the read-seqs file";
+                      *kReadTableWhat = "the read table", *kReadSeqsWhat = "the read-seqs file", *kReadMotifsWhat = "the read-motifs file";
 // the paths of the files that are no field of inq_call_args_t (it does not grow): what the widest entry of the family takes
 struct ReportPaths {
-    const char *read_calls = nullptr, *read_table = nullptr, *read_seqs = nullptr;
+    const char *read_calls = nullptr, *read_table = nullptr, *read_seqs = nullptr, *read_motifs = nullptr;
+    const char *motif = nullptr;  // one motif for every target of the read-motifs file (null: column 4 of the BED)
 };
-// the files of a text call (inq_call_args_t::ties_path, ::evidence_path; `more` of inq_genotype_repeats_seqs, else nulls)
+// the files of a text call (inq_call_args_t::ties_path, ::evidence_path; `more` of inq_genotype_repeats_motifs, else nulls)
 struct CallReports {
-    ReportFile ties, evidence, read_calls, read_table, read_seqs;
+    ReportFile ties, evidence, read_calls, read_table, read_seqs, read_motifs;
     int open(const inq_call_args_t &a, const ReportPaths &more, std::string &msg) {
         int rc = ties.open(a.ties_path, kTiesWhat, msg);
         if (rc == INQ_EXIT_OK) rc = evidence.open(a.evidence_path, kEvidenceWhat, msg);
         if (rc == INQ_EXIT_OK) rc = read_calls.open(more.read_calls, kReadCallsWhat, msg);
         if (rc == INQ_EXIT_OK) rc = read_table.open(more.read_table, kReadTableWhat, msg);
-        return rc != INQ_EXIT_OK ? rc : read_seqs.open(more.read_seqs, kReadSeqsWhat, msg);
+        if (rc == INQ_EXIT_OK) rc = read_seqs.open(more.read_seqs, kReadSeqsWhat, msg);
+        return rc != INQ_EXIT_OK ? rc : read_motifs.open(more.read_motifs, kReadMotifsWhat, msg);
     }
-    ReportFds fds() const { return ReportFds{ties.fd, evidence.fd, read_calls.fd, read_table.fd, read_seqs.fd}; }
+    ReportFds fds() const { return ReportFds{ties.fd, evidence.fd, read_calls.fd, read_table.fd, read_seqs.fd, read_motifs.fd}; }
     void to(SessionHooks &hooks) const { hooks.report_fds = fds(); }
 };
 // an entry that returns rows or keeps its context for many files writes no evidence file and says so (INQ_EXIT_ERROR) instead of
@@ -451,12 +467,25 @@ struct BatchRows {
     // read-seqs file: their slices and packed bases, fetched (a flush) or cut out of the batch's SEQ (a call)
     ReadIdentities who;
     ReadSlices bases;
+    // the read-motifs file: the loci's motif words (motifs_of) and a record per record, fetched (a flush) or walked here (a call)
+    std::vector<uint64_t> words;
+    std::vector<inq_read_motif_t> runs;
     void begin(size_t n, ReportSet which) {
         b1.assign(n, NAN), b2.assign(n, NAN);
         std::memset(&res, 0, sizeof res);
         res.phase1 = b1.data(), res.phase2 = b2.data();
         rep.begin(n, which);
         if (which.read_calls) bk.assign(n + 1, 0);
+    }
+    // the motif words of the call's loci, locus j being target index[j] of `all`; behind begin
+    void motifs_of(const uint32_t *index, const TargetReports &all) {
+        if (!rep.has.read_motifs) return;
+        words.resize(b1.size());
+        for (size_t j = 0; j < words.size(); ++j) words[j] = index[j] < all.motif_word.size() ? all.motif_word[index[j]] : 0;
+    }
+    // the records' runs cut into the loci's lists
+    void cut_runs() {
+        for (size_t j = 0; j + 1 < bk.size(); ++j) rep.read_motifs[j].assign(runs.begin() + bk[j], runs.begin() + bk[j + 1]);
     }
     // what the device call takes (null: not collected)
     uint8_t *flags() { return rep.has.ties ? rep.ties.data() : nullptr; }
@@ -495,6 +524,17 @@ struct BatchRows {
                 pack_seq_slice(owner->seqs.bytes.data() + owner->seqs.off[r], q.q_beg, q.n_bases, bases.bytes);
             }
         bases.cut(bk, rep.read_seqs);
+        if (!rep.has.read_motifs) return INQ_OK;
+        // the runs: a sequential walk of each slice under its locus's word (inq_host_motif_runs)
+        if (words.size() + 1 != bk.size()) return INQ_ERR_ARG;
+        runs.resize(bc.size());
+        size_t at = 0;
+        for (size_t j = 0; j + 1 < bk.size(); ++j)
+            for (uint64_t k = bk[j]; k < bk[j + 1]; ++k) {
+                motif_runs(bases.bytes.data() + at, bases.recs[k].n_bases, words[j], &runs[k]);
+                at += inq::run_bytes(bases.recs[k]);
+            }
+        cut_runs();
         return INQ_OK;
     }
     int flush(inq_ctx_t *ctx, uint64_t n, double *ms_call) {
@@ -503,7 +543,9 @@ struct BatchRows {
             return rc != INQ_OK ? rc : fetch_read_calls(ctx);
         }
         uint64_t name_bytes = 0, seq_bytes = 0;
-        int rc = inq_call_flush_seqs(ctx, &res, n, ms_call, flags(), evidence(), kept_off(), &name_bytes, rep.has.read_seqs ? &seq_bytes : nullptr);
+        if (rep.has.read_motifs && words.size() != n) return INQ_ERR_ARG;
+        int rc = inq_call_flush_motifs(ctx, &res, n, ms_call, flags(), evidence(), kept_off(), &name_bytes, rep.has.read_seqs ? &seq_bytes : nullptr,
+                                       rep.has.read_motifs ? words.data() : nullptr);
         if (rc == INQ_OK) rc = fetch_read_calls(ctx);
         if (rc != INQ_OK) return rc;
         who.recs.resize(bc.size()), who.bytes.resize(name_bytes);
@@ -513,6 +555,10 @@ struct BatchRows {
         bases.recs.resize(bc.size()), bases.bytes.resize(seq_bytes);
         if ((rc = inq_read_seqs_fetch(ctx, bases.recs.data(), bases.recs.size(), bases.bytes.data(), bases.bytes.size())) != INQ_OK) return rc;
         bases.cut(bk, rep.read_seqs);
+        if (!rep.has.read_motifs) return INQ_OK;
+        runs.resize(bc.size());
+        if ((rc = inq_read_motifs_fetch(ctx, runs.data(), runs.size())) != INQ_OK) return rc;
+        cut_runs();
         return INQ_OK;
     }
     // the records behind a call that filled kept_off, out of the context's scratch, cut into the loci's lists
@@ -556,7 +602,7 @@ int write_report(const std::vector<uint32_t> &order, const std::string &header, 
 // the tie report: `chrom\tbegin\tend\n` for every target order[k] with a flag set (no header)
 int write_ties(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const uint8_t *ties, int fd, char *errbuf,
                size_t errcap);
-// inq_genotype_repeats with the read-calls file, the read table and the read-seqs file (null: none), for inq_genotype_repeats_seqs
+// inq_genotype_repeats with the read-calls file, the read table, the read-seqs and the read-motifs file (null: none), for inq_genotype_repeats_motifs
 int genotype_single(const inq_call_args_t *args, int out_fd, const ReportPaths &more, char *errbuf, size_t errcap);
 int partition_prepared(Prepared &P, uint64_t world, uint32_t *order, uint64_t *cuts);
 

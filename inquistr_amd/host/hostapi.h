@@ -15,7 +15,7 @@
 namespace inq {
 
 struct HostApi {
-    decltype(&::inq_genotype_repeats_seqs) genotype_repeats_seqs;  // (inq_genotype_repeats, _devices, _reads and _table are its forms)
+    decltype(&::inq_genotype_repeats_motifs) genotype_repeats_motifs;  // (inq_genotype_repeats, _devices, _reads, _table and _seqs are its forms)
     decltype(&::inq_host_ctx_option) ctx_option;
     decltype(&::inq_combine) combine;
     decltype(&::inq_outlier) outlier;
@@ -53,7 +53,7 @@ inline const HostApi &host_api() {
             }
             return p;
         };
-        a.genotype_repeats_seqs = reinterpret_cast<decltype(a.genotype_repeats_seqs)>(sym("inq_genotype_repeats_seqs"));
+        a.genotype_repeats_motifs = reinterpret_cast<decltype(a.genotype_repeats_motifs)>(sym("inq_genotype_repeats_motifs"));
         a.ctx_option = reinterpret_cast<decltype(a.ctx_option)>(sym("inq_host_ctx_option"));
         a.combine = reinterpret_cast<decltype(a.combine)>(sym("inq_combine"));
         a.outlier = reinterpret_cast<decltype(a.outlier)>(sym("inq_outlier"));

@@ -59,6 +59,34 @@ size_t inq_host_format_read_seq_rows(const char *chrom, uint32_t start, uint32_t
     }
     return s.size();
 }
+size_t inq_host_format_read_motif_rows(const char *chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
+                                       const inq_read_origin_t *origins, const uint8_t *names, const inq_read_seq_t *seqs,
+                                       const inq_read_motif_t *motifs, uint64_t motif_word, size_t n, int unphased, char *buf, size_t cap) {
+    if (!chrom || (n && (!calls || !origins || !seqs || !motifs))) return 0;
+    std::string s;
+    append_read_motif_rows(s, chrom, start, end, calls, origins, names, seqs, motifs, motif_word, n, unphased != 0);
+    if (cap) {
+        const size_t m = std::min(s.size(), cap - 1);
+        std::memcpy(buf, s.data(), m);
+        buf[m] = 0;
+    }
+    return s.size();
+}
+int inq_host_motif_encode(const char *text, uint64_t *word) {
+    uint64_t w = 0;
+    const int rc = motif_encode(text, &w);
+    if (word) *word = w;
+    return rc;
+}
+int inq_host_motif_runs(const uint8_t *packed, uint32_t n_bases, uint64_t word, inq_read_motif_t *out) {
+    if ((n_bases && !packed) || !out) return 1;
+    try {
+        motif_runs(packed, n_bases, word, out);
+    } catch (...) {
+        return 1;
+    }
+    return 0;
+}
 int inq_host_seq_window(const uint32_t *cigar, uint32_t n_cigar, int32_t pos, uint32_t l_seq, uint32_t start, uint32_t end, uint32_t *q_beg,
                         uint32_t *n_bases) {
     if ((n_cigar && !cigar) || !q_beg || !n_bases) return 1;

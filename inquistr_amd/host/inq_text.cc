@@ -290,6 +290,87 @@ void pack_seq_slice(const uint8_t *seq, uint32_t q_beg, uint32_t n_bases, std::v
         out.push_back((uint8_t)(base(q_beg + i) << 4 | (i + 1 < n_bases ? base(q_beg + i + 1) : 0)));
 }
 
+// k and the k codes of a motif word; k = 0: no motif
+static uint32_t motif_codes(uint64_t word, uint8_t (&m)[15]) {
+    const uint32_t k = (uint32_t)(word >> 60);
+    for (uint32_t i = 0; i < k; ++i) {
+        m[i] = (uint8_t)(word >> (4u * i) & 15u);
+        if (m[i] != 1 && m[i] != 2 && m[i] != 4 && m[i] != 8) return 0;
+    }
+    return k;
+}
+
+int motif_encode(const char *text, uint64_t *word) {
+    *word = 0;
+    if (!text || !*text) return kMotifEmpty;
+    std::string t(text);
+    for (char &ch : t) {
+        if (ch >= 'a' && ch <= 'z') ch = (char)(ch - 'a' + 'A');
+        if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T') return kMotifLetter;
+    }
+    // the primitive root: the shortest prefix the text is a whole number of copies of
+    size_t k = 1;
+    for (; k < t.size(); ++k)
+        if (t.size() % k == 0 && t.compare(k, t.size() - k, t, 0, t.size() - k) == 0) break;
+    if (k > 15) return kMotifLong;
+    uint64_t w = (uint64_t)k << 60;
+    for (size_t i = 0; i < k; ++i) w |= (uint64_t)(t[i] == 'A' ? 1 : t[i] == 'C' ? 2 : t[i] == 'G' ? 4 : 8) << (4 * i);
+    *word = w;
+    return kMotifOk;
+}
+
+std::string motif_text(uint64_t word) {
+    uint8_t m[15];
+    const uint32_t k = motif_codes(word, m);
+    if (!k) return ".";
+    std::string t;
+    for (uint32_t i = 0; i < k; ++i) t += m[i] == 1 ? 'A' : m[i] == 2 ? 'C' : m[i] == 4 ? 'G' : 'T';
+    return t;
+}
+
+void motif_runs(const uint8_t *packed, uint32_t n_bases, uint64_t word, inq_read_motif_t *out) {
+    *out = inq_read_motif_t{0, 0, 0, 0};
+    uint8_t m[15];
+    const uint32_t k = motif_codes(word, m), n = n_bases;
+    if (!k || !n) return;
+    auto base = [&](uint32_t i) -> uint8_t { return (packed[i >> 1] >> ((~i & 1u) * 4u)) & 15u; };
+    std::vector<uint8_t> in_run(n, 0);  // position i lies in a run of >= k
+    for (uint32_t r = 0; r < k; ++r) {
+        uint32_t a = 0;  // where the open run began
+        for (uint32_t i = 0; i <= n; ++i) {
+            if (i < n && base(i) == m[((uint64_t)i + r) % k]) continue;
+            // [a, i) is a run (empty where the base before missed too)
+            const uint32_t len = i - a;
+            if (len > out->run_len || (len == out->run_len && len && a < out->run_beg)) out->run_len = len, out->run_beg = a;
+            if (len >= k) {
+                ++out->n_runs;
+                for (uint32_t j = a; j < i; ++j) in_run[j] = 1;
+            }
+            a = i + 1;
+        }
+    }
+    for (uint32_t i = 0; i < n; ++i) out->motif_bases += in_run[i];
+}
+
+const char *const kReadMotifsHeader =
+    "chrom\tbegin\tend\tgroup\tcall\tkind\tread\tqbeg\tlen\tmotif\trun_beg\trun_len\tunits\tmotif_bases\truns";
+
+void append_read_motif_rows(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
+                            const inq_read_origin_t *origins, const uint8_t *names, const inq_read_seq_t *seqs, const inq_read_motif_t *motifs,
+                            uint64_t word, size_t n, bool unphased) {
+    const std::string motif = motif_text(word);
+    const uint32_t k = motif == "." ? 0u : (uint32_t)motif.size();
+    append_read_lines(out, chrom, start, end, calls, origins, names, n, unphased, [&](std::string &o_, size_t i) {
+        o_ += '\t', o_ += std::to_string(seqs[i].q_beg), o_ += '\t', o_ += std::to_string(seqs[i].n_bases), o_ += '\t', o_ += motif;
+        if (!k) {
+            o_ += "\t.\t.\t.\t.\t.";
+            return;
+        }
+        const inq_read_motif_t &t = motifs[i];
+        for (const uint32_t v : {t.run_beg, t.run_len, t.run_len / k, t.motif_bases, t.n_runs}) o_ += '\t', o_ += std::to_string(v);
+    });
+}
+
 static void erase_all(std::string &s, const std::string &pat) {
     size_t p = 0;
     while ((p = s.find(pat, p)) != std::string::npos) s.erase(p, pat.size());

@@ -48,6 +48,22 @@ void seq_window(const uint32_t *cigar, uint32_t n_cigar, int32_t pos, uint32_t l
                 uint32_t *n_bases);
 // bases [q_beg, q_beg + n_bases) of a BAM SEQ field appended to out, packed from the high nibble of a fresh byte on
 void pack_seq_slice(const uint8_t *seq, uint32_t q_beg, uint32_t n_bases, std::vector<uint8_t> &out);
+// The motif word of inq_read_motif_t (include/inquistr_hip.h) from a motif's text: upper-cased, A C G T only, reduced to its primitive
+// root, 1 .. 15 bases.  0 and the word, else *word = 0 and kMotifEmpty / kMotifLetter / kMotifLong
+enum { kMotifOk = 0, kMotifEmpty = 1, kMotifLetter = 2, kMotifLong = 3 };
+int motif_encode(const char *text, uint64_t *word);
+// the word's motif as text, `.` for a word that is no motif
+std::string motif_text(uint64_t word);
+// The run contract of inq_read_motif_t as a plain sequential walk, a rotation at a time, over n_bases packed bases (first base in the
+// high nibble of the first byte): what the host sweep computes with (inq_host_motif_runs)
+void motif_runs(const uint8_t *packed, uint32_t n_bases, uint64_t word, inq_read_motif_t *out);
+// the read-motifs file (inq_genotype_repeats_motifs; not a reference output): its header, and the lines of one target - those of the
+// read-seqs file in columns chrom .. len, then the target's motif, run_beg, run_len, units = run_len / k, motif_bases and runs of each
+// record's inq_read_motif_t; a target whose word is no motif prints `.` in all six
+extern const char *const kReadMotifsHeader;
+void append_read_motif_rows(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
+                            const inq_read_origin_t *origins, const uint8_t *names, const inq_read_seq_t *seqs, const inq_read_motif_t *motifs,
+                            uint64_t word, size_t n, bool unphased);
 // src/call.rs:91-100: file_stem, then every ".bam" and ".cram" removed
 std::string sample_name_from_path(const std::string &bam_path);
 // [3P] human_sort::compare as used by Genotype::cmp (src/call.rs:33-38): <0, 0, >0

@@ -80,9 +80,33 @@ int prepare(const inq_call_args_t *a, Prepared &P, std::string &msg, BedCache *b
         }
     }
     P.targets.swap(tr.data);
+    P.target_name.swap(tr.name);
     if (timing_level() == 2)
         std::fprintf(stderr, "[inq prepare] header + index %.2f ms, targets (%zu) %.2f ms\n", ms(t_open, t_targets), P.targets.size(),
                      ms(t_targets, Clock::now()));
+    return INQ_EXIT_OK;
+}
+
+int target_motif_words(const Prepared &P, const char *motif, std::vector<uint64_t> &words, std::string &msg) {
+    const size_t n = P.targets.size();
+    words.assign(n, 0);
+    if (motif) {  // one motif for every target; it overrides column 4
+        uint64_t w = 0;
+        if (motif_encode(motif, &w) != kMotifOk) {
+            msg = std::string("--motif ") + motif + ": not a motif of 1 to 15 bases of ACGT";
+            return INQ_EXIT_ERROR;
+        }
+        words.assign(n, w);
+        return INQ_EXIT_OK;
+    }
+    if (P.target_name.size() != n) {  // a BED of three columns, or a region string
+        msg = "the read-motifs file needs a motif for every target: column 4 of the BED, or --motif <STR> (needed with -r)";
+        return INQ_EXIT_ERROR;
+    }
+    size_t bad = 0;
+    for (size_t i = 0; i < n; ++i) bad += motif_encode(P.target_name[i].c_str(), &words[i]) != kMotifOk;
+    if (bad)
+        std::fprintf(stderr, "%zu of %zu targets have no motif of 1 to 15 bases of ACGT in column 4: `.` in the read-motifs file\n", bad, n);
     return INQ_EXIT_OK;
 }
 
@@ -134,6 +158,11 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
     TargetReports own_reports;
     if (!hooks.reports) own_reports.begin(n, hooks.report_fds.wanted());
     TargetReports *const reports = hooks.reports ? hooks.reports : &own_reports;
+    if (reports->has.read_motifs && hooks.motif_words)  // the words of this call's targets, as p1 / p2 are indexed
+        for (size_t k = 0; k < n; ++k) {
+            const size_t i = rows.active ? rows.idx[k] : k;
+            reports->motif_word[k] = i < hooks.motif_words->size() ? (*hooks.motif_words)[i] : 0;
+        }
     const bool rows_on_device = rows.active && rows.d1 && rows.d2;
     if (rows_on_device && rows.dcap < n) {
         set_err(errbuf, errcap, "device row arrays smaller than the target list");
@@ -254,6 +283,7 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
             batch.locus_end = (const uint32_t *)put(batch.locus_end, batch.n_loci * 4, off, s4);
         }
         br.begin(batch.n_loci, reports->has);
+        br.motifs_of(item.index.data(), *reports);
         auto tc = Clock::now();
         const int rc2 = br.call(ctx, batch, &item.batch);
         t_dev += secs(tb, Clock::now());
@@ -465,6 +495,16 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
                      append_read_seq_rows(text, targets[i].chrom, targets[i].start, targets[i].end, l.data(), w.recs.data(), w.bytes.data(),
                                           q.recs.data(), q.bytes.data(), l.size(), unphased);
              }},
+            {tr->has.read_motifs, reports.fds.read_motifs, std::string(kReadMotifsHeader) + '\n', kReadMotifsWhat,
+             [&targets, tr, unphased](std::string &text, uint32_t i) {  // the same lines again, with the motif runs instead of the bases
+                 const std::vector<inq_read_call_t> &l = tr->read_calls[i];
+                 const ReadIdentities &w = tr->read_table[i];
+                 const ReadSlices &q = tr->read_seqs[i];
+                 const std::vector<inq_read_motif_t> &m = tr->read_motifs[i];
+                 if (w.recs.size() == l.size() && q.recs.size() == l.size() && m.size() == l.size())
+                     append_read_motif_rows(text, targets[i].chrom, targets[i].start, targets[i].end, l.data(), w.recs.data(), w.bytes.data(),
+                                            q.recs.data(), m.data(), tr->motif_word[i], l.size(), unphased);
+             }},
         };
         for (const auto &f : files) {
             if (!f.on || f.fd < 0) continue;
@@ -523,6 +563,10 @@ uint64_t inq_frontend_n_targets(const inq_frontend_t *fe) { return fe ? fe->P.ta
 
 int inq_frontend_target(const inq_frontend_t *fe, uint64_t i, const char **chrom, uint32_t *start, uint32_t *end) {
     return fe ? target_at(fe->P, i, chrom, start, end) : -1;
+}
+
+const char *inq_frontend_target_name(const inq_frontend_t *fe, uint64_t i) {
+    return fe && i < fe->P.target_name.size() ? fe->P.target_name[i].c_str() : nullptr;
 }
 
 const char *inq_frontend_sample(const inq_frontend_t *fe) { return fe ? fe->P.sample.c_str() : ""; }
@@ -610,6 +654,14 @@ static int inq_genotype_repeats_impl(const inq_call_args_t *args, int out_fd, ch
     if (rc != INQ_EXIT_OK) return rc;
     SessionHooks hooks;
     files.to(hooks);
+    std::vector<uint64_t> words;
+    if (more.read_motifs && !rows.active) {
+        if (target_motif_words(P, more.motif, words, msg) != INQ_EXIT_OK) {
+            set_err(errbuf, errcap, msg);
+            return INQ_EXIT_ERROR;
+        }
+        hooks.motif_words = &words;
+    }
     hooks.process_is_leaving = fast_exit();  // the context is this call's own, and so is the process's end (the CLI's `call`)
     rc = genotype_prepared(args, actx, P, out_fd, errbuf, errcap, rows, t_start, hooks);
     actx.leak = rc == INQ_EXIT_OK && hooks.process_is_leaving;  // only after a clean run: error paths tear down normally

@@ -549,8 +549,9 @@ int run_device_front(const inq_call_args_t *args, const CallView &V, AsyncCtx &a
         const auto f0 = Clock::now();
         // rows that stay on the device take flags only (they belong to a prepared run, which takes no evidence: run.cc inq_run_open_impl)
         ReportSet which = hooks.reports->has;
-        if (hooks.dev_p1) which.evidence = which.read_calls = which.read_table = which.read_seqs = false;
+        if (hooks.dev_p1) which.evidence = which.read_calls = which.read_table = which.read_seqs = which.read_motifs = false;
         br.begin(pending.size(), which);
+        br.motifs_of(pending.data(), *hooks.reports);  // (the flush takes the loci's motif words in append order)
         double ms_call = 0;
         // (rows that travel on from device memory stay there: pending[j] is the row's place in the caller's device arrays)
         const int rc2 = hooks.dev_p1 ? inq_call_flush_device_flags(ctx, hooks.dev_p1, hooks.dev_p2, hooks.dev_cap, pending.data(), pending.size(),

@@ -132,6 +132,7 @@ TargetsResult targets_from_bed(const std::string &path, const std::map<std::stri
         r.panicked = true;
         r.message = m;
         r.data.clear();
+        r.name.clear();
         return r;
     };
     std::ifstream in(path);
@@ -153,6 +154,7 @@ TargetsResult targets_from_bed(const std::string &path, const std::map<std::stri
         std::string m = check_interval(f[0], (uint32_t)s64, (uint32_t)e64, chrom_lengths);
         if (!m.empty()) return fail(m);
         r.data.push_back({f[0], (uint32_t)s64, (uint32_t)e64});
+        if (f.size() >= 4) r.name.push_back(f[3]);
     }
     return r;
 }

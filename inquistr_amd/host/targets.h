@@ -15,6 +15,9 @@ struct RepeatInterval {  // src/repeats.rs:75-79
 // Outcome classes of the reference: ok, or a panic (exit code 101) with its message.
 struct TargetsResult {
     std::vector<RepeatInterval> data;  // RepeatIntervalIterator.data (whole BED materialised, :31-44)
+    // column 4 of a BED that has one, as it stands (an STR catalogue keeps the motif there): [k] belongs to data[k]; empty for a BED of
+    // three columns and for a region string.  Not a part of the reference's interval: only the read-motifs file reads it
+    std::vector<std::string> name;
     bool panicked = false;
     std::string message;
 };
