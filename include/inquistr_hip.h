@@ -235,6 +235,32 @@ typedef struct inq_read_motif {  /* 16 bytes, every byte written; one per record
     uint32_t n_runs;
 } inq_read_motif_t;
 
+/* Which short motif a locus's kept reads repeat, for a caller who has no catalogue motif or wants the catalogue's checked against the
+ * reads.  Take locus j with kept records kept_off[j] .. kept_off[j + 1], all groups (h1 / h2 / other); each record's slice is s[0 .. n),
+ * the codes inq_read_seq_t describes; a code is a BASE when it is one of 1, 2, 4, 8.  All of it is integer arithmetic and independent
+ * of the records' order:
+ *     lag counts   for k = 1 .. 6, T_k = the sum over the records of the number of i with k <= i < n, s[i] == s[i - k], s[i] a base
+ *     period       p = the smallest k with T_k == max_j T_j when that maximum is above 0; else p = 0 and the record is all zeros
+ *                  except `bases`
+ *     copies       for each record and each i with i + 2 p <= n: if s[i .. i + p) are all bases and s[i + t] == s[i + p + t] for every
+ *                  t < p, the p-mer s[i .. i + p) gets one count
+ *     class        a p-mer's class is its lexicographically smallest rotation under A < C < G < T, a class's count the sum over its
+ *                  members; the class with the largest count wins, among equal counts the lexicographically smallest.  No count at
+ *                  all: word = 0, copies = 0, period = p still
+ *     word         the winner reduced to its primitive root (ACAC at p = 4 becomes AC; the root of a smallest rotation is itself a
+ *                  smallest rotation), as the motif word of inq_read_motif_t: k in nibble 15, BAM codes in nibbles 0 .. k - 1.  So
+ *                  CAG repeats give AGC, and the word is never a non-primitive one.
+ * Motifs longer than 6 bases are not looked for: they stay the catalogue's business.  Known limit: a locus with little repeat in its
+ * reads is often given a shorter period than its motif's - two or three copies of a 5- or 6-mer between random flanks have fewer lag-p
+ * hits than the chance hits at lags 1 .. 3 of the flanks (measured: DESIGN.md, "Locus motifs"). */
+typedef struct inq_locus_motif {   /* 40 bytes, every byte written; one per locus */
+    uint64_t word;     /* motif word, 0 = none found */
+    uint64_t period;   /* p, 0 .. 6 */
+    uint64_t bases;    /* sum of n over the locus's kept records, every code counted */
+    uint64_t tandem;   /* T_p */
+    uint64_t copies;   /* the winning class's count */
+} inq_locus_motif_t;
+
 typedef struct inq_ctx inq_ctx_t;
 
 /* Opens HIP device `device_id` (must be gfx950), creates the library's stream and
@@ -547,6 +573,22 @@ int inq_motif_runs(inq_ctx_t *ctx, const inq_read_seq_t *recs, uint64_t n, const
                    inq_read_motif_t *out);
 /* records per workgroup and turn of the motif kernel (a constant of the build) */
 uint32_t inq_read_motif_tile(void);
+/* The motif each locus's kept reads repeat (inq_locus_motif_t above), found on the device at flush time out of the batch's own slices and
+ * handed to the motif kernel of the same flush without a host round trip.  inq_call_flush_locus_motifs is inq_call_flush_motifs plus
+ * `found`, a HOST array of n_loci records in append order.  found NULL = exactly inq_call_flush_motifs.  With it, seq_bytes NULL is
+ * INQ_ERR_ARG; `motif` may be NULL (no locus has a given word); the read-motif records are produced for EVERY kept record, locus j
+ * measured with motif[j] where that names a motif and with found[j].word where not, and inq_read_motifs_fetch works as after a flush
+ * with motifs.
+ * inq_locus_motifs_find: the kernel alone over host buffers in the format inq_read_seqs_fetch returns, as inq_motif_runs takes them
+ * (same argument checks; kept_off must not be NULL, found not when n_loci != 0).  given: one word per locus or NULL; use: NULL, or
+ * [n_loci] receiving what the motif kernel would be handed (given[j] where it names a motif, else found[j].word).  A record whose
+ * slice does not fit into seq_bytes contributes nothing. */
+int inq_call_flush_locus_motifs(inq_ctx_t *ctx, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
+                                inq_locus_evidence_t *evidence, uint64_t *kept_off, uint64_t *name_bytes, uint64_t *seq_bytes,
+                                const uint64_t *motif /* [n_loci], host, may be NULL */, inq_locus_motif_t *found /* [n_loci], host */);
+int inq_locus_motifs_find(inq_ctx_t *ctx, const inq_read_seq_t *recs, uint64_t n, const uint8_t *packed, uint64_t seq_bytes,
+                          const uint64_t *kept_off /* [n_loci + 1] */, uint64_t n_loci, const uint64_t *given /* [n_loci] or NULL */,
+                          inq_locus_motif_t *found /* [n_loci] */, uint64_t *use /* [n_loci] or NULL */);
 /* Row arrays in device memory for a host that does not link the HIP runtime itself: n f64, filled with quiet NaN (a locus no span
  * holds prints NaN NaN); plain synchronous copies in and out. */
 int inq_dev_alloc_rows(inq_ctx_t *ctx, uint64_t n, double **out);

@@ -157,6 +157,23 @@ int inq_genotype_repeats_seqs(const inq_call_args_t *args, const int32_t *device
 int inq_genotype_repeats_motifs(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,
                                 const char *read_table_path, const char *read_seqs_path, const char *read_motifs_path, const char *motif,
                                 inq_part_stats_t *stats, char *errbuf, size_t errcap);
+/* ... and with the locus-motifs file (`inquistr call --locus-motifs`) and `motif` = "auto", the widest entry of the family:
+ * locus_motifs_path NULL and a `motif` that is not "auto" = exactly inq_genotype_repeats_motifs.
+ * The motif each target's kept reads repeat is looked for in the bases behind its Calls (inq_locus_motif_t of include/inquistr_hip.h:
+ * periods 1 .. 6, integer counts, no motif typed in by anyone).  `motif` = "auto": every target's motif for the read-motifs file is the
+ * found one, column 4 is not read for it, the `motif` column prints the found motif in its smallest rotation (CAG repeats print AGC), a
+ * target with none found prints `.` in the six fields; a region string and a BED of three columns are fine.
+ * The locus-motifs file, with or without the read-motifs file: a header line
+ * `chrom\tbegin\tend\treads\tbases\tmotif\tperiod\ttandem\tcopies\tcatalogue\tagrees`, then one line per target in the .inq's row order.
+ * reads = the kept records, bases .. copies = the fields of inq_locus_motif_t with the motif as text and `.` for none, catalogue = `motif` when given and not
+ * "auto", else column 4, as its encoded word's text or `.`; agrees = 1 when the catalogue's motif is a rotation of the found one, 0 when it
+ * is not or none was found, `.` without an encodable catalogue motif.  The number of 0 lines goes to stderr once.  Both front ends
+ * produce it: the host sweep with inq_host_locus_motif_find, the device front end on the GPU at flush time
+ * (inq_call_flush_locus_motifs). */
+int inq_genotype_repeats_locus_motifs(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd,
+                                      const char *read_calls_path, const char *read_table_path, const char *read_seqs_path,
+                                      const char *read_motifs_path, const char *motif, const char *locus_motifs_path, inq_part_stats_t *stats,
+                                      char *errbuf, size_t errcap);
 /* How many processes (or device parts) share this host's cores with this one, and which of them it is (0 .. sharers - 1): sizes the
  * reader pool of every later call (granted cores / sharers, bound to L3 domains from a different start per sharer).  Default:
  * LOCAL_WORLD_SIZE / LOCAL_RANK of the environment (torch.distributed.run exports them), else 1 / 0.  sharers <= 0 = that default. */
@@ -327,6 +344,14 @@ size_t inq_host_format_read_seq_rows(const char *chrom, uint32_t start, uint32_t
 size_t inq_host_format_read_motif_rows(const char *chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
                                        const inq_read_origin_t *origins, const uint8_t *names, const inq_read_seq_t *seqs,
                                        const inq_read_motif_t *motifs, uint64_t motif_word, size_t n, int unphased, char *buf, size_t cap);
+/* One line of the locus-motifs file (inq_genotype_repeats_locus_motifs) for a target with `reads` kept records, *found and the
+ * catalogue's motif word (0: none) */
+size_t inq_host_format_locus_motif_row(const char *chrom, uint32_t start, uint32_t end, uint64_t reads, const inq_locus_motif_t *found,
+                                       uint64_t catalogue_word, char *buf, size_t cap);
+/* The contract of inq_locus_motif_t restated as a plain sequential walk, base by base, over one locus's n_records slices packed back to
+ * back (each from a fresh byte on, first base in the high nibble; n_bases[r] bases): what the host sweep computes with.  0, or 1 for a
+ * null pointer. */
+int inq_host_locus_motif_find(const uint8_t *packed, const uint32_t *n_bases, size_t n_records, inq_locus_motif_t *out);
 /* A motif's text as the motif word of inq_read_motif_t: upper-cased, A C G T only, reduced to its primitive root (CAGCAG -> CAG), which
  * must have 1 .. 15 bases.  0 and *word; else *word = 0 and 1 (NULL or empty text), 2 (a character that is none of ACGT: `.`, `CAG,CCG`,
  * `GCN`) or 3 (a primitive root of 16 bases or more). */

@@ -28,6 +28,7 @@ HOST_ABI_SYMBOLS = (
     "inq_genotype_repeats_table",
     "inq_genotype_repeats_seqs",
     "inq_genotype_repeats_motifs",
+    "inq_genotype_repeats_locus_motifs",
     "inq_host_set_local_share",
     "inq_host_granted_cpus",
     "inq_host_ctx_option",
@@ -77,6 +78,8 @@ HOST_ABI_SYMBOLS = (
     "inq_host_format_read_motif_rows",
     "inq_host_motif_encode",
     "inq_host_motif_runs",
+    "inq_host_format_locus_motif_row",
+    "inq_host_locus_motif_find",
     "inq_host_seq_window",
     "inq_host_sample_name",
     "inq_host_human_compare",
@@ -186,6 +189,13 @@ def load():
         L.inq_host_motif_encode.argtypes = [C.c_char_p, C.POINTER(C.c_uint64)]
         L.inq_host_motif_runs.restype = C.c_int
         L.inq_host_motif_runs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
+        L.inq_genotype_repeats_locus_motifs.restype = C.c_int
+        L.inq_genotype_repeats_locus_motifs.argtypes = [C.POINTER(CallArgsC), C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.c_char_p, C.c_char_p,
+                                                        C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PartStatsC), C.c_char_p, C.c_size_t]
+        L.inq_host_format_locus_motif_row.restype = C.c_size_t
+        L.inq_host_format_locus_motif_row.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+        L.inq_host_locus_motif_find.restype = C.c_int
+        L.inq_host_locus_motif_find.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.inq_genotype_repeats_devices.restype = C.c_int
         L.inq_genotype_repeats_devices.argtypes = [C.POINTER(CallArgsC), C.POINTER(C.c_int32), C.c_size_t, C.c_int, C.POINTER(PartStatsC), C.c_char_p, C.c_size_t]
         L.inq_host_set_local_share.restype = None
@@ -387,7 +397,7 @@ def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str
                      reference: Optional[str] = None, out=None, device: int = 0, frontend: Optional[str] = None,
                      ties: Optional[str] = None, evidence: Optional[str] = None, read_calls: Optional[str] = None, devices=None,
                      read_table: Optional[str] = None, read_seqs: Optional[str] = None, read_motifs: Optional[str] = None,
-                     motif: Optional[str] = None) -> None:
+                     motif: Optional[str] = None, locus_motifs: Optional[str] = None) -> None:
     """src/call.rs:76-86: same parameters, same output; raises CallError instead of exiting.
     frontend: "host" (BGZF inflate + record decode on CPU threads), "device" (inq_call_span: both on the GPU)
     or None (env INQ_FRONTEND, else the library default).
@@ -397,13 +407,16 @@ def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str
     read_table: path of the read table (inquistr call --read-table): one line per kept read with its Call, group, name, pos, strand, mapq.
     read_seqs: path of the read-seqs file (inquistr call --read-seqs): the table's lines with the read's bases over the locus window.
     read_motifs: path of the read-motifs file (inquistr call --read-motifs): the same lines with the pure runs of the locus's motif in
-    those bases; motif: one motif for every target (default: column 4 of the BED; needed with a region string).
-    devices: with any of the four read files, the HIP devices of inq_genotype_repeats_motifs (None: the one device `device`)."""
+    those bases; motif: one motif for every target (default: column 4 of the BED; needed with a region string), or "auto": the motif
+    found in each target's own kept reads.
+    locus_motifs: path of the locus-motifs file (inquistr call --locus-motifs): one line per target with the motif its kept reads repeat
+    and whether the catalogue's motif (motif, else column 4) agrees.
+    devices: with any of those files, the HIP devices of inq_genotype_repeats_locus_motifs (None: the one device `device`)."""
     L = load()
     a = _args(bamp, region, region_file, minlen, support, threads, unphased, sample_name, reference, device, frontend, ties, evidence)
     out = sys.stdout if out is None else out
     out.flush()
-    if read_calls is None and read_table is None and read_seqs is None and read_motifs is None and devices is None:
+    if read_calls is None and read_table is None and read_seqs is None and read_motifs is None and locus_motifs is None and devices is None:
         _checked(L.inq_genotype_repeats, C.byref(a), out.fileno())
         return
     devices = [] if devices is None else [int(d) for d in devices]
@@ -413,8 +426,9 @@ def genotype_repeats(bamp: str, region: Optional[str], region_file: Optional[str
     table = os.fspath(read_table).encode() if read_table is not None else None
     seqs = os.fspath(read_seqs).encode() if read_seqs is not None else None
     motifs = os.fspath(read_motifs).encode() if read_motifs is not None else None
-    _checked(L.inq_genotype_repeats_motifs, C.byref(a), ids, len(devices), out.fileno(), path, table, seqs, motifs,
-             motif.encode() if motif is not None else None, st)
+    found = os.fspath(locus_motifs).encode() if locus_motifs is not None else None
+    _checked(L.inq_genotype_repeats_locus_motifs, C.byref(a), ids, len(devices), out.fileno(), path, table, seqs, motifs,
+             motif.encode() if motif is not None else None, found, st)
 
 
 def genotype_repeats_devices(bamp: str, region: Optional[str], region_file: Optional[str], devices, minlen: int = 5, support: int = 3,

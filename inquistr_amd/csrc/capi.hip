@@ -17,6 +17,7 @@
 #include "evidence.h"
 #include "front_kernels.h"
 #include "kernels.h"
+#include "locus_motifs.h"
 #include "read_calls.h"
 #include "read_motifs.h"
 #include "read_seqs.h"
@@ -419,7 +420,15 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     const auto slices = [&] { launch_read_seq_records(ReadSeqArgs{x.kept_pair, n_kept, x.seq_qbeg, x.seq_len, x.seqs.recs, b->n_pairs}, s); };
     HIP_TRY(c, place_runs(x.names, origins));
     HIP_TRY(c, place_runs(x.seqs, slices));
-    // the motif runs of each record's bases, out of the batch's own slices: behind the slices' records, in front of nothing
+    // the motif each locus's reads repeat, out of the batch's own slices: behind the slices' records (kept_pair, kept_off), in front of
+    // the motif kernel, which reads the words this writes.  No pair: no record, every locus's answer is zeros
+    if (x.locus_found && !b->n_pairs) HIP_TRY(c, hipMemsetAsync(x.locus_found, 0, (size_t)b->n_loci * sizeof(inq_locus_motif_t), s));
+    if (x.locus_found && b->n_pairs) {
+        launch_locus_motifs(LocusMotifArgs{x.kept_pair, n_kept, x.kept_off, b->n_loci, x.seq_bytes, x.seq_n_bytes, x.seq_off, x.seq_len, b->n_pairs,
+                                           b->n_pairs, x.motif_given, x.locus_found, x.motif_use}, s);
+        HIP_TRY(c, hipGetLastError());
+    }
+    // the motif runs of each record's bases, out of the same slices: in front of nothing
     if (x.motifs && b->n_pairs) {
         launch_read_motifs(ReadMotifArgs{x.kept_pair, n_kept, x.kept_off, x.motif_word, b->n_loci, x.seq_bytes, x.seq_n_bytes, x.seq_off, x.seq_len,
                                          b->n_pairs, x.motifs, b->n_pairs}, s);
@@ -550,6 +559,57 @@ static int motif_runs_impl(inq_ctx_t *c, const inq_read_seq_t *recs, uint64_t n,
 int inq_motif_runs(inq_ctx_t *c, const inq_read_seq_t *recs, uint64_t n, const uint8_t *packed, uint64_t seq_bytes, const uint64_t *kept_off,
                    const uint64_t *motif, uint64_t n_loci, inq_read_motif_t *out) {
     return guarded([&] { return motif_runs_impl(c, recs, n, packed, seq_bytes, kept_off, motif, n_loci, out); });
+}
+
+// the locus motif kernel alone: records and packed slices go up as motif_runs_impl sends them, a record per locus and the words come down
+static int locus_motifs_find_impl(inq_ctx_t *c, const inq_read_seq_t *recs, uint64_t n, const uint8_t *packed, uint64_t seq_bytes,
+                                  const uint64_t *kept_off, uint64_t n_loci, const uint64_t *given, inq_locus_motif_t *found, uint64_t *use) {
+    if (!c) return INQ_ERR_ARG;
+    extras_reset(c);
+    if ((n && !recs) || (seq_bytes && !packed) || !kept_off || (n_loci && !found)) return INQ_ERR_ARG;
+    if (n >= (1ull << 40) || n_loci >= 0xfffffff0ull) return INQ_ERR_ARG;
+    for (uint64_t j = 0; j < n_loci; ++j)
+        if (kept_off[j] > kept_off[j + 1]) return INQ_ERR_ARG;
+    if (kept_off[n_loci] > n) return INQ_ERR_ARG;
+    if (!n_loci) return INQ_OK;
+    std::vector<uint64_t> seg_off(n);
+    std::vector<uint32_t> seg_len(n);
+    uint64_t at = 0;
+    for (uint64_t k = 0; k < n; ++k) seg_off[k] = at, seg_len[k] = recs[k].n_bases, at += run_bytes(recs[k]);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc;
+    struct Up {
+        DevBuf *d;
+        const void *h;
+        size_t bytes;
+    } ups[] = {
+        {&c->rseqs.bytes, packed, (size_t)seq_bytes},  // (scratch of the flushes' sequences and motifs, free between calls)
+        {&c->rseqs.off, seg_off.data(), (size_t)n * 8},
+        {&c->rseqs.recs, seg_len.data(), (size_t)n * 4},
+        {&c->rcoff, kept_off, (size_t)(n_loci + 1) * 8},
+        {&c->rmotifword, given, given ? (size_t)n_loci * 8 : 0},
+    };
+    for (auto &u : ups) {
+        if ((rc = ensure(c, *u.d, u.bytes)) != INQ_OK) return rc;
+        if (u.bytes) HIP_TRY(c, hipMemcpyAsync(u.d->p, u.h, u.bytes, hipMemcpyHostToDevice, s));
+    }
+    if ((rc = ensure(c, c->rlocusmotif, (size_t)n_loci * sizeof(inq_locus_motif_t))) != INQ_OK) return rc;
+    if (use && (rc = ensure(c, c->rmotifuse, (size_t)n_loci * 8)) != INQ_OK) return rc;
+    launch_locus_motifs(LocusMotifArgs{nullptr, nullptr, (const uint64_t *)c->rcoff.p, n_loci, (const uint8_t *)c->rseqs.bytes.p, seq_bytes,
+                                       (const uint64_t *)c->rseqs.off.p, (const uint32_t *)c->rseqs.recs.p, n, n,
+                                       given ? (const uint64_t *)c->rmotifword.p : nullptr, (inq_locus_motif_t *)c->rlocusmotif.p,
+                                       use ? (uint64_t *)c->rmotifuse.p : nullptr}, s);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(found, c->rlocusmotif.p, (size_t)n_loci * sizeof(inq_locus_motif_t), hipMemcpyDeviceToHost, s));
+    if (use) HIP_TRY(c, hipMemcpyAsync(use, c->rmotifuse.p, (size_t)n_loci * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));  // (the uploads' sources above live until here)
+    purge_retired(c);
+    return INQ_OK;
+}
+int inq_locus_motifs_find(inq_ctx_t *c, const inq_read_seq_t *recs, uint64_t n, const uint8_t *packed, uint64_t seq_bytes, const uint64_t *kept_off,
+                          uint64_t n_loci, const uint64_t *given, inq_locus_motif_t *found, uint64_t *use) {
+    return guarded([&] { return locus_motifs_find_impl(c, recs, n, packed, seq_bytes, kept_off, n_loci, given, found, use); });
 }
 
 // the window walk alone: the batch goes up as a call's does, two arrays come down
@@ -972,12 +1032,20 @@ int inq::extras_prepare(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const Hos
         if ((rc = runs(c->rseqs, d->seqs)) != INQ_OK) return rc;
         d->kept_pair = (uint64_t *)c->rkeptpair.p;
     }
-    if (h.motif) {
+    if (h.motif_runs()) {
         if (!h.seq_bytes) return INQ_ERR_ARG;
         if ((rc = ensure(c, c->rmotifs, (size_t)n_pairs * sizeof(inq_read_motif_t))) != INQ_OK) return rc;
         if ((rc = ensure(c, c->rmotifword, (size_t)n_loci * 8)) != INQ_OK) return rc;
         d->motifs = (inq_read_motif_t *)c->rmotifs.p;
         d->motif_word = (const uint64_t *)c->rmotifword.p;
+    }
+    if (h.found) {  // the motif kernel reads the words the search wrote, the given ones among them
+        if ((rc = ensure(c, c->rlocusmotif, (size_t)n_loci * sizeof(inq_locus_motif_t))) != INQ_OK) return rc;
+        if ((rc = ensure(c, c->rmotifuse, (size_t)n_loci * 8)) != INQ_OK) return rc;
+        d->locus_found = (inq_locus_motif_t *)c->rlocusmotif.p;
+        d->motif_given = h.motif ? (const uint64_t *)c->rmotifword.p : nullptr;
+        d->motif_use = (uint64_t *)c->rmotifuse.p;
+        d->motif_word = d->motif_use;
     }
     return INQ_OK;
 }
@@ -986,6 +1054,7 @@ int inq::extras_download(inq_ctx *c, uint64_t n_loci, const HostExtras &h, const
     if (h.flags) HIP_TRY(c, hipMemcpyAsync(flags_dst, d.flags, (size_t)n_loci, hipMemcpyDeviceToHost, s));
     if (h.evidence) HIP_TRY(c, hipMemcpyAsync(h.evidence, d.evidence, (size_t)n_loci * sizeof(inq_locus_evidence_t), hipMemcpyDeviceToHost, s));
     if (h.kept_off) HIP_TRY(c, hipMemcpyAsync(h.kept_off, d.kept_off, (size_t)(n_loci + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (h.found) HIP_TRY(c, hipMemcpyAsync(h.found, d.locus_found, (size_t)n_loci * sizeof(inq_locus_motif_t), hipMemcpyDeviceToHost, s));
     return INQ_OK;
 }
 
@@ -1026,5 +1095,5 @@ void inq::extras_finish(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const Hos
     if (err == 0) c->read_calls_total = std::min<uint64_t>(h.kept_off[n_loci], n_pairs);
     if (h.name_bytes && err == 0) c->rnames.n_recs = c->read_calls_total, c->rnames.n_bytes = *h.name_bytes;
     if (h.seq_bytes && err == 0) c->rseqs.n_recs = c->read_calls_total, c->rseqs.n_bytes = *h.seq_bytes;
-    if (h.motif && err == 0) c->read_motifs_total = c->read_calls_total;
+    if (h.motif_runs() && err == 0) c->read_motifs_total = c->read_calls_total;
 }

@@ -64,11 +64,14 @@ struct inq_ctx {
     // context's next call (inq_read_motifs_fetch), and the loci's motif words.  Allocated by flushes with motifs only
     inq::DevBuf rmotifs, rmotifword;
     uint64_t read_motifs_total = 0;  // records of the last flush with motifs (0: it had none)
+    // the motif each locus's reads repeat (inq_call_flush_locus_motifs, locus_motifs.hip): one inq_locus_motif_t per locus, and the word
+    // the motif kernel measures each locus with (the given one, else the found one).  Allocated by flushes that look for motifs only
+    inq::DevBuf rlocusmotif, rmotifuse;
     inq::DevBuf ovalues, olen, oflags, okeep, otrans;  // inq_outlier_rows
     // every DevBuf above, for inq_ctx_destroy (DevBuf frees nothing itself): a member missing here leaks
     auto bufs() {
         std::vector<inq::DevBuf *> all{&worklist, &sval, &smeta, &deep, &cigar, &reads, &pair_read, &off, &lstart, &lend, &p1, &p2, &pcall, &pbits,
-                                       &lflags, &levidence, &evwork, &rctiles, &rcoff, &rckept, &rkeptpair, &rmotifs, &rmotifword, &ovalues, &olen, &oflags, &okeep, &otrans};
+                                       &lflags, &levidence, &evwork, &rctiles, &rcoff, &rckept, &rkeptpair, &rmotifs, &rmotifword, &rlocusmotif, &rmotifuse, &ovalues, &olen, &oflags, &okeep, &otrans};
         for (inq::KeptRuns *k : {&rnames, &rseqs})
             for (inq::DevBuf *b : k->bufs()) all.push_back(b);
         return all;
@@ -198,6 +201,11 @@ struct LocusExtras {
     const uint8_t *seq_bytes = nullptr;
     uint64_t seq_n_bytes = 0;
     const uint64_t *seq_off = nullptr;  // [n_pairs]
+    // the motif each locus's reads repeat (needs motifs): a record per locus out of the same slices, in front of the motif kernel, which
+    // then reads motif_word = what this wrote: motif_given[j] where that names a motif (null: none does), else the found word
+    inq_locus_motif_t *locus_found = nullptr;
+    const uint64_t *motif_given = nullptr;
+    uint64_t *motif_use = nullptr;
 };
 // Where a flush takes the runs of one kind from, the deferred batch's (SpanState::Acc hands them over): n runs back to back in `bytes`,
 // run i at off[i].  by_pair: a kept record's run is that of the pair it came from (the bases), else that of its read (the names)
@@ -217,6 +225,8 @@ struct HostExtras {
     uint64_t *name_bytes = nullptr;  // a flush with origins (needs kept_off): receives the bytes of the kept records' names
     uint64_t *seq_bytes = nullptr;   // a flush with sequences (needs kept_off): receives the bytes of the kept records' packed slices
     const uint64_t *motif = nullptr;  // a flush with motifs (needs seq_bytes): the loci's motif words, read, not written
+    inq_locus_motif_t *found = nullptr;  // a flush that looks for the loci's motifs (needs seq_bytes; motif may be null): a record per locus
+    bool motif_runs() const { return motif || found; }  // the flush produces a read-motif record per kept record
     // the evidence is counted and the lists are compacted from the per-pair outputs: the call keeps those (pcall / pbits) also when
     // its caller did not ask for them
     bool per_pair() const { return evidence || kept_off; }

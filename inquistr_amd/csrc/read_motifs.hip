@@ -19,6 +19,7 @@
 #include "cigar_walk.h"
 #include "read_motifs.h"
 #include "segment_store.h"
+#include "slice_words.h"
 
 namespace inq {
 namespace {
@@ -28,8 +29,6 @@ static_assert(kReadMotifTile * kMotifRowLanes == kThreads, "a workgroup's lanes 
 static_assert(kMotifRowLanes == (uint32_t)kRowLanes, "a row is one DPP row");
 static_assert(sizeof(inq_read_motif_t) == 16, "a record is one 16-byte store");
 
-constexpr uint64_t kNibbleOnes = 0x1111111111111111ull;
-
 // the motif repeated to 32 nibbles (nibble j = m[j mod k]); k = 0: no motif
 struct Motif {
     unsigned __int128 rep;
@@ -38,41 +37,13 @@ struct Motif {
 __device__ __forceinline__ Motif decode_motif(uint64_t word) {
     Motif M{0, (uint32_t)(word >> 60)};
     if (!M.k) return M;
-    const uint64_t mask = ~0ull >> (64u - 4u * M.k), m = word & mask;
-    // every nibble one of 1, 2, 4, 8: exactly one bit set
-    if ((m & kNibbleOnes) + (m >> 1 & kNibbleOnes) + (m >> 2 & kNibbleOnes) + (m >> 3 & kNibbleOnes) != (kNibbleOnes & mask)) {
+    if (!motif_word_ok(word)) {  // every nibble one of 1, 2, 4, 8
         M.k = 0;
         return M;
     }
-    M.rep = m;
+    M.rep = word & ~0ull >> (64u - 4u * M.k);
     for (uint32_t len = M.k; len < 32u; len *= 2u) M.rep |= M.rep << (4u * len);
     return M;
-}
-
-// Bytes [8 w, 8 w + 8) of a segment of nb bytes as a little-endian word, cut to the segment: a byte at or past nb is 0 and is not read.
-// The segment starts wherever its slice does, so the loads are unaligned ones
-__device__ __forceinline__ uint64_t load_segment_word(const uint8_t *seg, uint64_t nb, uint64_t w) {
-    const uint64_t o = w * 8u;
-    uint64_t v = 0;
-    if (o >= nb) return v;
-    if (nb - o >= 8u) {
-        __builtin_memcpy(&v, seg + o, 8);
-        return v;
-    }
-    for (uint32_t i = 0; i < (uint32_t)(nb - o); ++i) v |= (uint64_t)seg[o + i] << (8u * i);
-    return v;
-}
-
-// bit t of the result: nibble t of x is zero
-__device__ __forceinline__ uint32_t zero_nibbles(uint64_t x) {
-    uint64_t t = ~x;
-    t &= t >> 1;
-    t &= t >> 2;
-    t &= kNibbleOnes;  // bit 4 t: nibble t was all ones
-    t = (t | t >> 3) & 0x0303030303030303ull;
-    t = (t | t >> 6) & 0x000f000f000f000full;
-    t = (t | t >> 12) & 0x000000ff000000ffull;
-    return (uint32_t)(t | t >> 24) & 0xffffu;
 }
 
 __device__ __forceinline__ uint32_t row_or(uint32_t x) {  // lane 15 of the row holds the OR of its lanes
@@ -158,8 +129,7 @@ __global__ __launch_bounds__(256) void read_motif_kernel(ReadMotifArgs a) {
             const bool on = w < n_words;
             uint32_t h = 0, cov_cur = 0;
             if (on) {
-                uint64_t s = load_segment_word(seg, nb, w);
-                s = (s & 0x0f0f0f0f0f0f0f0full) << 4 | (s >> 4 & 0x0f0f0f0f0f0f0f0full);  // base t of the word in nibble t
+                const uint64_t s = bases_in_order(load_segment_word(seg, nb, w));
                 const uint64_t left = n - w * 16u;
                 h = zero_nibbles(s ^ (uint64_t)(M.rep >> (4u * ph))) & (left >= 16u ? 0xffffu : (1u << (uint32_t)left) - 1u);
                 if (!mine) h = 0u;

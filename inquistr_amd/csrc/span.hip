@@ -681,7 +681,7 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
         if (!h.name_bytes || (A.n_spans && !A.seqs.on)) return INQ_ERR_ARG;
         *h.seq_bytes = 0;
     }
-    if (h.motif && !h.seq_bytes) return INQ_ERR_ARG;  // the motif runs are those of the bases
+    if (h.motif_runs() && !h.seq_bytes) return INQ_ERR_ARG;  // the motif runs, and the motif the reads repeat, are those of the bases
     if (A.n_loci == 0) {
         A.reset();
         extras_finish(c, 0, 0, h, 0);
@@ -703,9 +703,9 @@ int call_flush_impl(inq_ctx *c, inq_result_t *r, uint64_t n_loci, double *ms_cal
     if ((rc = extras_prepare(c, nl, A.n_pairs, h, &x)) != INQ_OK) return rc;
     if (h.name_bytes) x.name_off = (const uint64_t *)A.names.off.p;
     if (h.seq_bytes) x.seq_qbeg = (const uint32_t *)A.seq_qbeg.p, x.seq_len = (const uint32_t *)A.seq_len.p;
-    if (h.motif) {  // the loci's motif words go up; the bases are the batch's own per-pair slices
+    if (h.motif_runs()) {  // the loci's motif words go up (where there are any); the bases are the batch's own per-pair slices
         x.seq_bytes = (const uint8_t *)A.seqs.bytes.p, x.seq_n_bytes = A.seqs.n_bytes, x.seq_off = (const uint64_t *)A.seqs.off.p;
-        HIP_TRY(c, hipMemcpyAsync(c->rmotifword.p, h.motif, nl * 8, hipMemcpyHostToDevice, s));
+        if (h.motif) HIP_TRY(c, hipMemcpyAsync(c->rmotifword.p, h.motif, nl * 8, hipMemcpyHostToDevice, s));
     }
     const bool per_pair = h.per_pair();
     if ((rc = ensure_row_staging(c, S, nl, 2 * nl + (h.flags ? (nl + 7) / 8 : 0))) != INQ_OK) return rc;  // the rows, then the flags
@@ -990,9 +990,15 @@ int inq_call_flush_seqs(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, dou
 
 int inq_call_flush_motifs(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
                           inq_locus_evidence_t *evidence, uint64_t *kept_off, uint64_t *name_bytes, uint64_t *seq_bytes, const uint64_t *motif) {
+    return inq_call_flush_locus_motifs(c, result, n_loci, ms_call, locus_flags, evidence, kept_off, name_bytes, seq_bytes, motif, nullptr);
+}
+
+int inq_call_flush_locus_motifs(inq_ctx_t *c, inq_result_t *result, uint64_t n_loci, double *ms_call, uint8_t *locus_flags,
+                                inq_locus_evidence_t *evidence, uint64_t *kept_off, uint64_t *name_bytes, uint64_t *seq_bytes, const uint64_t *motif,
+                                inq_locus_motif_t *found) {
     return guarded([&] {
         if (!kept_off || !name_bytes) return (int)INQ_ERR_ARG;
-        return call_flush_impl(c, result, n_loci, ms_call, nullptr, HostExtras{locus_flags, evidence, kept_off, name_bytes, seq_bytes, motif});
+        return call_flush_impl(c, result, n_loci, ms_call, nullptr, HostExtras{locus_flags, evidence, kept_off, name_bytes, seq_bytes, motif, found});
     });
 }
 

@@ -97,6 +97,8 @@ ABI_SYMBOLS = (
     "inq_read_motifs_fetch",
     "inq_motif_runs",
     "inq_read_motif_tile",
+    "inq_call_flush_locus_motifs",
+    "inq_locus_motifs_find",
 )
 
 
@@ -222,6 +224,9 @@ class ReadMotifC(C.Structure):
 
 
 MOTIF_DTYPE = np.dtype([("run_beg", "<u4"), ("run_len", "<u4"), ("motif_bases", "<u4"), ("n_runs", "<u4")])
+
+
+LOCUS_MOTIF_DTYPE = np.dtype([("word", "<u8"), ("period", "<u8"), ("bases", "<u8"), ("tandem", "<u8"), ("copies", "<u8")])  # inq_locus_motif_t
 
 
 def encode_motif(text: str) -> int:
@@ -357,6 +362,11 @@ def load(path: Optional[str] = None):
     L.inq_motif_runs.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp]
     L.inq_read_motif_tile.restype = C.c_uint32
     L.inq_read_motif_tile.argtypes = []
+    # (the flush family's widest member, one more side output behind `motif`: found)
+    L.inq_call_flush_locus_motifs.restype = C.c_int
+    L.inq_call_flush_locus_motifs.argtypes = [vp, C.POINTER(InqResultC), C.c_uint64, C.POINTER(C.c_double)] + [vp] * 7
+    L.inq_locus_motifs_find.restype = C.c_int
+    L.inq_locus_motifs_find.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp]
     L.inq_ctx_status.restype = C.c_int
     L.inq_ctx_status.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.inq_ctx_timing_enable.restype = C.c_int
@@ -483,17 +493,20 @@ class Context:
         sb = np.full(1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if seq_bytes else None
         return fl, ev, off, nb, sb
 
-    def _side_call(self, entry: str, head, n: int, width: int, check: bool, flags: bool = True, evidence: bool = True, motif=None):
+    def _side_call(self, entry: str, head, n: int, width: int, check: bool, flags: bool = True, evidence: bool = True, motif=None,
+                   found: bool = True):
         """Calls `entry`, the member of its family that takes `width` side outputs, with `head` and the arrays of _side_arrays; raises on
         error if check.  Returns (code, flags, evidence, kept_off, records), each cut to the n loci, None where not taken; the records are
         fetched behind a successful call with the lists.  width 4 (a flush with origins) adds a sixth element: (origins, names,
         name_bytes) fetched the same way, (None, None, name_bytes) after a failed call; width 5 (a flush with sequences) a seventh:
         (seqs, packed, seq_bytes); width 6 (a flush with motifs; motif: the loci's words, u64 [n], or None for a null pointer) an
-        eighth: the MOTIF_DTYPE records, fetched the same way (None after a failed call)."""
+        eighth: the MOTIF_DTYPE records, fetched the same way (None after a failed call); width 7 (a flush that looks for the loci's
+        motifs; found False: a null pointer) a ninth: the LOCUS_MOTIF_DTYPE records [n] (None for the null pointer)."""
         fl, ev, off, nb, sb = self._side_arrays(n, flags and width >= 1, evidence and width >= 2, width >= 3, width >= 4, width >= 5)
         mw = None if motif is None else np.ascontiguousarray(motif, dtype=np.uint64)
         assert mw is None or (width >= 6 and len(mw) >= n)
-        side = [None if a is None else a.ctypes.data for a in (fl, ev, off, nb, sb, mw)][:width]
+        fd = np.full(max(n, 1) * LOCUS_MOTIF_DTYPE.itemsize, 0xFF, dtype=np.uint8) if width >= 7 and found else None
+        side = [None if a is None else a.ctypes.data for a in (fl, ev, off, nb, sb, mw, fd)][:width]
         rc = getattr(self._L, entry)(self._h, *head, *side)
         if rc != INQ_OK and check:
             self._raise(rc)
@@ -506,7 +519,9 @@ class Context:
             what = self.read_seqs_fetch(int(off[-1]), int(sb[0])) if rc == INQ_OK else (None, None)
             out += (what + (int(sb[0]),),)
         if width >= 6:
-            out += ((self.read_motifs_fetch(int(off[-1]) if mw is not None else 0) if rc == INQ_OK else None,),)
+            out += ((self.read_motifs_fetch(int(off[-1]) if mw is not None or fd is not None else 0) if rc == INQ_OK else None,),)
+        if width >= 7:
+            out += ((None if fd is None else fd.view(LOCUS_MOTIF_DTYPE)[:n],),)
         return out
 
     def _batch_call(self, entry: str, batch: Batch, debug: bool, width: int, check: bool, **which):
@@ -710,7 +725,7 @@ class Context:
     def deferred_loci(self) -> int:
         return int(self._L.inq_call_deferred_loci(self._h))
 
-    def _flush_call(self, entry: str, width: int, check: bool, motif=None):
+    def _flush_call(self, entry: str, width: int, check: bool, motif=None, found: bool = True):
         """(code, phase1, phase2, n_tie_loci, ms_call) of `entry` for every locus deferred since the last flush, then the first `width`
         of flags, evidence, kept_off + records, origins + names + name_bytes, seqs + packed + seq_bytes."""
         n = self.deferred_loci
@@ -718,7 +733,7 @@ class Context:
         p2 = np.full(n, np.nan)
         res = InqResultC(p1.ctypes.data, p2.ctypes.data, None, None, 0)
         ms = C.c_double(0.0)
-        rc, fl, ev, off, rec, *who = self._side_call(entry, (C.byref(res), n, C.byref(ms)), n, width, check, motif=motif)
+        rc, fl, ev, off, rec, *who = self._side_call(entry, (C.byref(res), n, C.byref(ms)), n, width, check, motif=motif, found=found)
         return (rc, p1, p2, int(res.n_tie_loci), float(ms.value)) + (fl, ev, off, rec)[: width + (width >= 3)] + tuple(x for w in who for x in w)
 
     def call_flush(self, check: bool = True):
@@ -753,6 +768,33 @@ class Context:
         (None after a failed call).  motif: the motif words of the deferred loci in append order (u64), or None for a null pointer,
         which is exactly call_flush_seqs (the records then number 0)."""
         return self._flush_call("inq_call_flush_motifs", 6, check, motif=motif)
+
+    def call_flush_locus_motifs(self, motif=None, found: bool = True, check: bool = True):
+        """inq_call_flush_locus_motifs: as call_flush_motifs, plus one LOCUS_MOTIF_DTYPE record per deferred locus as the seventeenth
+        element: the motif its kept reads repeat.  The read-motif records are then those of every kept record, locus j measured with
+        motif[j] where that names a motif (motif None: no locus has one), else with the found word.  found False: a null pointer, which
+        is exactly call_flush_motifs (seventeenth element None)."""
+        return self._flush_call("inq_call_flush_locus_motifs", 7, check, motif=motif, found=found)
+
+    def locus_motifs_find(self, seqs, packed, kept_off, given=None, use: bool = True, check: bool = True):
+        """inq_locus_motifs_find: the locus motif kernel alone over what read_seqs_fetch returns - seqs (SEQ_DTYPE [n]) and their packed
+        slices back to back (uint8) - and kept_off u64 [n_loci + 1]; given: the loci's given motif words u64 [n_loci], or None.  Returns
+        (found LOCUS_MOTIF_DTYPE [n_loci], use u64 [n_loci] or None where use is False); check=False: (code, found, use)."""
+        seqs = np.ascontiguousarray(seqs, dtype=SEQ_DTYPE)
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        kept_off = np.ascontiguousarray(kept_off, dtype=np.uint64)
+        n, n_loci = len(seqs), len(kept_off) - 1
+        gw = None if given is None else np.ascontiguousarray(given, dtype=np.uint64)
+        assert n_loci >= 0 and (gw is None or len(gw) >= n_loci)
+        out = np.full(max(n_loci, 1) * LOCUS_MOTIF_DTYPE.itemsize, 0xFF, dtype=np.uint8)
+        uw = np.full(max(n_loci, 1), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if use else None
+        rc = self._L.inq_locus_motifs_find(self._h, seqs.ctypes.data if n else None, n, packed.ctypes.data if packed.size else None, packed.size,
+                                           kept_off.ctypes.data, n_loci, None if gw is None else gw.ctypes.data, out.ctypes.data,
+                                           None if uw is None else uw.ctypes.data)
+        if rc != INQ_OK and check:
+            self._raise(rc)
+        got = (out.view(LOCUS_MOTIF_DTYPE)[:n_loci], None if uw is None else uw[:n_loci])
+        return got if check else (rc,) + got
 
     def read_motifs_fetch(self, n: int, check: bool = True):
         """inq_read_motifs_fetch: the first n records (MOTIF_DTYPE) of the last call_flush_motifs (check=False: (code, records))."""

@@ -111,7 +111,10 @@ int prepare(const inq_call_args_t *a, Prepared &P, std::string &msg, BedCache *b
 // The motif words of P's targets for the read-motifs file: `motif` for every target, or (null) column 4 of the BED, each through
 // motif_encode; a target whose text does not encode gets word 0 and their number goes to stderr once.  INQ_EXIT_ERROR and a message
 // when `motif` does not encode, or when there is neither it nor a fourth column
-int target_motif_words(const Prepared &P, const char *motif, std::vector<uint64_t> &words, std::string &msg);
+// (need_given false - `--motif auto`, or the locus-motifs file alone: the words are the catalogue's to compare with, a target without
+// one gets 0, a list without a fourth column is no error and nothing goes to stderr; `auto` itself stands for no `motif`)
+int target_motif_words(const Prepared &P, const char *motif, bool need_given, std::vector<uint64_t> &words, std::string &msg);
+inline bool motif_is_auto(const char *motif) { return motif && std::strcmp(motif, "auto") == 0; }
 // ... for an entry of the C ABI: the message goes to the caller's buffer
 inline int prepare(const inq_call_args_t *a, Prepared &P, char *errbuf, size_t errcap, BedCache *bed_cache = nullptr) {
     std::string msg;
@@ -323,18 +326,23 @@ inline void scatter(const T *src, const uint32_t *index, size_t n, T *dst) {
 // The per-target reports of a call, beside its rows: the tie report (inq_call_args_t::ties_path), the evidence file (::evidence_path), the
 // read-calls file (inq_genotype_repeats_reads), the read table (inq_genotype_repeats_table; it needs the read-calls lists, which are
 // then collected with it), the read-seqs file (inq_genotype_repeats_seqs; its lines name the reads: the table's lists are collected
-// with it), the read-motifs file (inq_genotype_repeats_motifs; the runs are those of the bases: the slices are collected with it).  One value at every layer; a further report is one more member of each of the three
+// with it), the read-motifs file (inq_genotype_repeats_motifs; the runs are those of the bases: the slices are collected with it),
+// the locus-motifs file (inq_genotype_repeats_locus_motifs; the motif each target's reads repeat, found in those same slices).  One value at every layer; a further report is one more member of each of the three
 // structs, a line in begin / scatter_from, a row in write_rows' table and a pointer in BatchRows::call / flush.  A further per-read
 // payload (a byte run behind each record, as the names and the bases are) is a record type with its inq::run_bytes(), one more
 // RecordRuns in TargetReports and in BatchRows, and a ByteRuns in ReadStore (front_end.h) where the host sweep is to keep it.
 struct ReportSet {  // which of them are collected: what is not adds nothing to the launch sequence
     bool ties = false, evidence = false, read_calls = false, read_table = false, read_seqs = false, read_motifs = false;
+    bool locus_motifs = false;  // the motif each target's reads repeat is looked for
+    bool motif_auto = false;    // ... and is what the read-motifs file measures with (`--motif auto`): no target has a given word
 };
 struct ReportFds {  // where a text call writes them, in the .inq's row order (-1: no file)
-    int ties = -1, evidence = -1, read_calls = -1, read_table = -1, read_seqs = -1, read_motifs = -1;
-    ReportSet wanted() const {  // (the motif runs are those of the bases: the slices are collected with them)
-        const bool bases = read_seqs >= 0 || read_motifs >= 0, who = read_table >= 0 || bases;
-        return ReportSet{ties >= 0, evidence >= 0, read_calls >= 0 || who, who, bases, read_motifs >= 0};
+    int ties = -1, evidence = -1, read_calls = -1, read_table = -1, read_seqs = -1, read_motifs = -1, locus_motifs = -1;
+    bool motif_auto = false;  // the read-motifs file measures with the motifs found in the reads (`--motif auto`)
+    ReportSet wanted() const {  // (the motif runs are those of the bases, and so is the motif the reads repeat: the slices are collected with them)
+        const bool found = locus_motifs >= 0 || (read_motifs >= 0 && motif_auto);
+        const bool bases = read_seqs >= 0 || read_motifs >= 0 || found, who = read_table >= 0 || bases;
+        return ReportSet{ties >= 0, evidence >= 0, read_calls >= 0 || who, who, bases, read_motifs >= 0, found, read_motifs >= 0 && motif_auto};
     }
 };
 // ... of a set of targets (a call's, a device part's, one device call's loci): [k] belongs to target k of the set.  A target no batch or
@@ -347,8 +355,12 @@ struct TargetReports {
     std::vector<ReadIdentities> read_table;      // ... and who each of them is
     std::vector<ReadSlices> read_seqs;           // ... and the bases behind each Call
     std::vector<std::vector<inq_read_motif_t>> read_motifs;  // ... and the motif runs of those bases
-    // what the runs are measured with, an INPUT: the targets' motif words (inq_read_motif_t), set by whoever begins the reports
+    std::vector<inq_locus_motif_t> locus_motifs;             // the motif the target's kept reads repeat
+    // what the runs are measured with and the found motifs are compared with, an INPUT: the targets' given motif words (inq_read_motif_t;
+    // 0: none), set by whoever begins the reports
     std::vector<uint64_t> motif_word;
+    // the word target k's read-motifs lines are printed under
+    uint64_t printed_word(size_t k) const { return has.motif_auto ? locus_motifs[k].word : motif_word[k]; }
     void begin(size_t n, ReportSet which) {
         has = which;
         ties.assign(which.ties ? n : 0, 0);
@@ -357,7 +369,8 @@ struct TargetReports {
         read_table.assign(which.read_table ? n : 0, ReadIdentities());
         read_seqs.assign(which.read_seqs ? n : 0, ReadSlices());
         read_motifs.assign(which.read_motifs ? n : 0, std::vector<inq_read_motif_t>());
-        motif_word.assign(which.read_motifs ? n : 0, 0);
+        locus_motifs.assign(which.locus_motifs ? n : 0, inq_locus_motif_t{});
+        motif_word.assign(which.read_motifs || which.locus_motifs ? n : 0, 0);
     }
     // what part collected (nothing this one does not), part's k-th -> target idx[k]; the lists are moved out of part
     void scatter_from(TargetReports &part, const uint32_t *idx, size_t n) {
@@ -371,6 +384,7 @@ struct TargetReports {
             for (size_t k = 0; k < n; ++k) read_seqs[idx[k]] = std::move(part.read_seqs[k]);
         if (part.has.read_motifs)
             for (size_t k = 0; k < n; ++k) read_motifs[idx[k]] = std::move(part.read_motifs[k]);
+        if (part.has.locus_motifs) scatter(part.locus_motifs.data(), idx, n, locus_motifs.data());
     }
 };
 
@@ -411,24 +425,31 @@ struct ReportFile {
     int open(const char *path, const char *what, std::string &msg);
 };
 constexpr const char *kTiesWhat = "the tie report", *kEvidenceWhat = "the evidence file", *kReadCallsWhat = "the read-calls file",
-                      *kReadTableWhat = "the read table", *kReadSeqsWhat = "the read-seqs file", *kReadMotifsWhat = "the read-motifs file";
+                      *kReadTableWhat = "the read table", *kReadSeqsWhat = "the read-seqs file", *kReadMotifsWhat = "the read-motifs file",
+                      *kLocusMotifsWhat = "the locus-motifs file";
 // the paths of the files that are no field of inq_call_args_t (it does not grow): what the widest entry of the family takes
 struct ReportPaths {
     const char *read_calls = nullptr, *read_table = nullptr, *read_seqs = nullptr, *read_motifs = nullptr;
-    const char *motif = nullptr;  // one motif for every target of the read-motifs file (null: column 4 of the BED)
+    const char *motif = nullptr;  // one motif for every target of the read-motifs file (null: column 4 of the BED; `auto`: the found one)
+    const char *locus_motifs = nullptr;
 };
 // the files of a text call (inq_call_args_t::ties_path, ::evidence_path; `more` of inq_genotype_repeats_motifs, else nulls)
 struct CallReports {
-    ReportFile ties, evidence, read_calls, read_table, read_seqs, read_motifs;
+    ReportFile ties, evidence, read_calls, read_table, read_seqs, read_motifs, locus_motifs;
+    bool motif_auto = false;
     int open(const inq_call_args_t &a, const ReportPaths &more, std::string &msg) {
         int rc = ties.open(a.ties_path, kTiesWhat, msg);
         if (rc == INQ_EXIT_OK) rc = evidence.open(a.evidence_path, kEvidenceWhat, msg);
         if (rc == INQ_EXIT_OK) rc = read_calls.open(more.read_calls, kReadCallsWhat, msg);
         if (rc == INQ_EXIT_OK) rc = read_table.open(more.read_table, kReadTableWhat, msg);
         if (rc == INQ_EXIT_OK) rc = read_seqs.open(more.read_seqs, kReadSeqsWhat, msg);
-        return rc != INQ_EXIT_OK ? rc : read_motifs.open(more.read_motifs, kReadMotifsWhat, msg);
+        if (rc == INQ_EXIT_OK) rc = read_motifs.open(more.read_motifs, kReadMotifsWhat, msg);
+        motif_auto = motif_is_auto(more.motif);
+        return rc != INQ_EXIT_OK ? rc : locus_motifs.open(more.locus_motifs, kLocusMotifsWhat, msg);
     }
-    ReportFds fds() const { return ReportFds{ties.fd, evidence.fd, read_calls.fd, read_table.fd, read_seqs.fd, read_motifs.fd}; }
+    ReportFds fds() const {
+        return ReportFds{ties.fd, evidence.fd, read_calls.fd, read_table.fd, read_seqs.fd, read_motifs.fd, locus_motifs.fd, motif_auto};
+    }
     void to(SessionHooks &hooks) const { hooks.report_fds = fds(); }
 };
 // an entry that returns rows or keeps its context for many files writes no evidence file and says so (INQ_EXIT_ERROR) instead of
@@ -467,7 +488,8 @@ struct BatchRows {
     // read-seqs file: their slices and packed bases, fetched (a flush) or cut out of the batch's SEQ (a call)
     ReadIdentities who;
     ReadSlices bases;
-    // the read-motifs file: the loci's motif words (motifs_of) and a record per record, fetched (a flush) or walked here (a call)
+    // the read-motifs file: the loci's given motif words (motifs_of; none where the found ones are measured with) and a record per
+    // record, fetched (a flush) or walked here (a call); the locus-motifs file: a record per locus in rep, likewise
     std::vector<uint64_t> words;
     std::vector<inq_read_motif_t> runs;
     void begin(size_t n, ReportSet which) {
@@ -479,7 +501,8 @@ struct BatchRows {
     }
     // the motif words of the call's loci, locus j being target index[j] of `all`; behind begin
     void motifs_of(const uint32_t *index, const TargetReports &all) {
-        if (!rep.has.read_motifs) return;
+        words.clear();
+        if (!rep.has.read_motifs || rep.has.motif_auto) return;
         words.resize(b1.size());
         for (size_t j = 0; j < words.size(); ++j) words[j] = index[j] < all.motif_word.size() ? all.motif_word[index[j]] : 0;
     }
@@ -491,6 +514,8 @@ struct BatchRows {
     uint8_t *flags() { return rep.has.ties ? rep.ties.data() : nullptr; }
     inq_locus_evidence_t *evidence() { return rep.has.evidence ? rep.evidence.data() : nullptr; }
     uint64_t *kept_off() { return rep.has.read_calls ? bk.data() : nullptr; }
+    const uint64_t *given() const { return words.empty() ? nullptr : words.data(); }
+    inq_locus_motif_t *found() { return rep.has.locus_motifs ? rep.locus_motifs.data() : nullptr; }
     // the host-buffer call / the flush of the n deferred loci with what begin asked for, the lists fetched behind it.  The read table:
     // `read` indexes a batch the host owns (owner: the sweep's batch with its names), or one that exists on the device only, whose
     // flush gathers origins and names there (the spans were appended with names)
@@ -524,17 +549,27 @@ struct BatchRows {
                 pack_seq_slice(owner->seqs.bytes.data() + owner->seqs.off[r], q.q_beg, q.n_bases, bases.bytes);
             }
         bases.cut(bk, rep.read_seqs);
-        if (!rep.has.read_motifs) return INQ_OK;
-        // the runs: a sequential walk of each slice under its locus's word (inq_host_motif_runs)
-        if (words.size() + 1 != bk.size()) return INQ_ERR_ARG;
-        runs.resize(bc.size());
+        if (!rep.has.read_motifs && !rep.has.locus_motifs) return INQ_OK;
+        // the motif each locus's slices repeat (inq_host_locus_motif_find), then the runs: a sequential walk of each slice under its
+        // locus's word (inq_host_motif_runs), the given one or, where there is none, the found one
+        if (!words.empty() && words.size() + 1 != bk.size()) return INQ_ERR_ARG;
+        if (rep.has.read_motifs) runs.resize(bc.size());
+        std::vector<uint32_t> lens;
         size_t at = 0;
-        for (size_t j = 0; j + 1 < bk.size(); ++j)
+        for (size_t j = 0; j + 1 < bk.size(); ++j) {
+            uint64_t word = words.empty() ? 0 : words[j];
+            if (rep.has.locus_motifs) {
+                lens.clear();
+                for (uint64_t k = bk[j]; k < bk[j + 1]; ++k) lens.push_back(bases.recs[k].n_bases);
+                locus_motif_find(bases.bytes.data() + at, lens.data(), lens.size(), &rep.locus_motifs[j]);
+                word = motif_word_in_use(word, rep.locus_motifs[j].word);
+            }
             for (uint64_t k = bk[j]; k < bk[j + 1]; ++k) {
-                motif_runs(bases.bytes.data() + at, bases.recs[k].n_bases, words[j], &runs[k]);
+                if (rep.has.read_motifs) motif_runs(bases.bytes.data() + at, bases.recs[k].n_bases, word, &runs[k]);
                 at += inq::run_bytes(bases.recs[k]);
             }
-        cut_runs();
+        }
+        if (rep.has.read_motifs) cut_runs();
         return INQ_OK;
     }
     int flush(inq_ctx_t *ctx, uint64_t n, double *ms_call) {
@@ -543,9 +578,9 @@ struct BatchRows {
             return rc != INQ_OK ? rc : fetch_read_calls(ctx);
         }
         uint64_t name_bytes = 0, seq_bytes = 0;
-        if (rep.has.read_motifs && words.size() != n) return INQ_ERR_ARG;
-        int rc = inq_call_flush_motifs(ctx, &res, n, ms_call, flags(), evidence(), kept_off(), &name_bytes, rep.has.read_seqs ? &seq_bytes : nullptr,
-                                       rep.has.read_motifs ? words.data() : nullptr);
+        if (!words.empty() && words.size() != n) return INQ_ERR_ARG;
+        int rc = inq_call_flush_locus_motifs(ctx, &res, n, ms_call, flags(), evidence(), kept_off(), &name_bytes,
+                                             rep.has.read_seqs ? &seq_bytes : nullptr, given(), found());
         if (rc == INQ_OK) rc = fetch_read_calls(ctx);
         if (rc != INQ_OK) return rc;
         who.recs.resize(bc.size()), who.bytes.resize(name_bytes);
@@ -602,7 +637,8 @@ int write_report(const std::vector<uint32_t> &order, const std::string &header, 
 // the tie report: `chrom\tbegin\tend\n` for every target order[k] with a flag set (no header)
 int write_ties(const std::vector<uint32_t> &order, const std::vector<RepeatInterval> &targets, const uint8_t *ties, int fd, char *errbuf,
                size_t errcap);
-// inq_genotype_repeats with the read-calls file, the read table, the read-seqs and the read-motifs file (null: none), for inq_genotype_repeats_motifs
+// inq_genotype_repeats with the read-calls file, the read table, the read-seqs, the read-motifs and the locus-motifs file (null: none), for
+// inq_genotype_repeats_locus_motifs
 int genotype_single(const inq_call_args_t *args, int out_fd, const ReportPaths &more, char *errbuf, size_t errcap);
 int partition_prepared(Prepared &P, uint64_t world, uint32_t *order, uint64_t *cuts);
 

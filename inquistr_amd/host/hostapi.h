@@ -15,7 +15,7 @@
 namespace inq {
 
 struct HostApi {
-    decltype(&::inq_genotype_repeats_motifs) genotype_repeats_motifs;  // (inq_genotype_repeats, _devices, _reads, _table and _seqs are its forms)
+    decltype(&::inq_genotype_repeats_locus_motifs) genotype_repeats_locus_motifs;  // (inq_genotype_repeats, _devices, _reads, _table, _seqs and _motifs are its forms)
     decltype(&::inq_host_ctx_option) ctx_option;
     decltype(&::inq_combine) combine;
     decltype(&::inq_outlier) outlier;
@@ -53,7 +53,7 @@ inline const HostApi &host_api() {
             }
             return p;
         };
-        a.genotype_repeats_motifs = reinterpret_cast<decltype(a.genotype_repeats_motifs)>(sym("inq_genotype_repeats_motifs"));
+        a.genotype_repeats_locus_motifs = reinterpret_cast<decltype(a.genotype_repeats_locus_motifs)>(sym("inq_genotype_repeats_locus_motifs"));
         a.ctx_option = reinterpret_cast<decltype(a.ctx_option)>(sym("inq_host_ctx_option"));
         a.combine = reinterpret_cast<decltype(a.combine)>(sym("inq_combine"));
         a.outlier = reinterpret_cast<decltype(a.outlier)>(sym("inq_outlier"));

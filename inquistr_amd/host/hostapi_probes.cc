@@ -72,6 +72,30 @@ size_t inq_host_format_read_motif_rows(const char *chrom, uint32_t start, uint32
     }
     return s.size();
 }
+size_t inq_host_format_locus_motif_row(const char *chrom, uint32_t start, uint32_t end, uint64_t reads, const inq_locus_motif_t *found,
+                                       uint64_t catalogue_word, char *buf, size_t cap) {
+    if (!chrom || !found) return 0;
+    std::string s;
+    append_locus_motif_row(s, chrom, start, end, reads, *found, catalogue_word);
+    if (cap) {
+        const size_t m = std::min(s.size(), cap - 1);
+        std::memcpy(buf, s.data(), m);
+        buf[m] = 0;
+    }
+    return s.size();
+}
+int inq_host_locus_motif_find(const uint8_t *packed, const uint32_t *n_bases, size_t n_records, inq_locus_motif_t *out) {
+    if (!out || (n_records && !n_bases)) return 1;
+    try {
+        uint64_t bytes = 0;
+        for (size_t r = 0; r < n_records; ++r) bytes += ((uint64_t)n_bases[r] + 1) / 2;
+        if (bytes && !packed) return 1;
+        locus_motif_find(packed, n_bases, n_records, out);
+    } catch (...) {
+        return 1;
+    }
+    return 0;
+}
 int inq_host_motif_encode(const char *text, uint64_t *word) {
     uint64_t w = 0;
     const int rc = motif_encode(text, &w);

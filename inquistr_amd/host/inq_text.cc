@@ -371,6 +371,86 @@ void append_read_motif_rows(std::string &out, const std::string &chrom, uint32_t
     });
 }
 
+void locus_motif_find(const uint8_t *packed, const uint32_t *n_bases, size_t n_records, inq_locus_motif_t *out) {
+    *out = inq_locus_motif_t{0, 0, 0, 0, 0};
+    constexpr uint32_t kMaxPeriod = 6;
+    auto code_of = [](uint8_t c) -> int { return c == 1 ? 0 : c == 2 ? 1 : c == 4 ? 2 : c == 8 ? 3 : -1; };  // A C G T, -1: no base
+    // every record's bases in turn: each(n, base) with base(i) the slice's i-th code
+    auto each_record = [&](auto &&each) {
+        const uint8_t *at = packed;
+        for (size_t r = 0; r < n_records; ++r) {
+            const uint32_t n = n_bases[r];
+            each(n, [at](uint32_t i) -> uint8_t { return (at[i >> 1] >> ((~i & 1u) * 4u)) & 15u; });
+            at += ((size_t)n + 1) / 2;
+        }
+    };
+    uint64_t lag[kMaxPeriod + 1] = {0};
+    each_record([&](uint32_t n, auto base) {
+        out->bases += n;
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint8_t c = base(i);
+            if (code_of(c) < 0) continue;
+            for (uint32_t k = 1; k <= kMaxPeriod && k <= i; ++k) lag[k] += base(i - k) == c;
+        }
+    });
+    uint32_t p = 0;
+    for (uint32_t k = 1; k <= kMaxPeriod; ++k)
+        if (lag[k] > lag[p]) p = k;  // (lag[0] is 0: the smallest k with the largest count, none when all are 0)
+    if (!p) return;
+    out->period = p, out->tandem = lag[p];
+    // the tandem copies by the smallest rotation of their p-mer, two bits a base with the first base on top: numeric order is A < C < G < T
+    const uint32_t mask = (1u << (2 * p)) - 1;
+    auto turn = [&](uint32_t v) { return ((v << 2) | v >> (2 * (p - 1))) & mask; };
+    std::vector<uint64_t> count((size_t)mask + 1, 0);
+    each_record([&](uint32_t n, auto base) {
+        for (uint32_t i = 0; (uint64_t)i + 2 * p <= n; ++i) {
+            uint32_t v = 0;
+            bool copy = true;
+            for (uint32_t t = 0; t < p && copy; ++t) {
+                const int c = code_of(base(i + t));
+                copy = c >= 0 && base(i + t) == base(i + p + t);
+                v = v << 2 | (uint32_t)(c & 3);
+            }
+            if (!copy) continue;
+            uint32_t least = v;
+            for (uint32_t t = 1; t < p; ++t) v = turn(v), least = std::min(least, v);
+            ++count[least];
+        }
+    });
+    uint32_t win = 0;
+    for (uint32_t v = 1; v <= mask; ++v)
+        if (count[v] > count[win]) win = v;  // (ascending: among equal counts the smallest class)
+    if (!count[win]) return;
+    out->copies = count[win];
+    uint32_t d = 1, turned = turn(win);  // the primitive root: the shortest d dividing p that turns the winner into itself
+    for (; d < p; ++d, turned = turn(turned))
+        if (p % d == 0 && turned == win) break;
+    out->word = (uint64_t)d << 60;
+    for (uint32_t t = 0; t < d; ++t) out->word |= (uint64_t)(1u << (win >> (2 * (p - 1 - t)) & 3u)) << (4 * t);
+}
+
+uint64_t motif_word_in_use(uint64_t given, uint64_t found) {
+    uint8_t m[15];
+    return motif_codes(given, m) ? given : found;
+}
+
+const char *const kLocusMotifsHeader = "chrom\tbegin\tend\treads\tbases\tmotif\tperiod\ttandem\tcopies\tcatalogue\tagrees";
+
+int append_locus_motif_row(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, uint64_t reads, const inq_locus_motif_t &found,
+                           uint64_t catalogue_word) {
+    const std::string motif = motif_text(found.word), catalogue = motif_text(catalogue_word);
+    int agrees = -1;
+    if (catalogue != ".") {  // a rotation of the found motif: the same length, and found somewhere in the found motif written twice
+        agrees = motif != "." && motif.size() == catalogue.size() && (motif + motif).find(catalogue) != std::string::npos;
+    }
+    out += chrom;
+    for (const uint64_t v : {(uint64_t)start, (uint64_t)end, reads, found.bases}) out += '\t', out += std::to_string(v);
+    out += '\t', out += motif;
+    for (const uint64_t v : {found.period, found.tandem, found.copies}) out += '\t', out += std::to_string(v);
+    out += '\t', out += catalogue, out += '\t', out += agrees < 0 ? "." : agrees ? "1" : "0", out += '\n';
+    return agrees;
+}
+
 static void erase_all(std::string &s, const std::string &pat) {
     size_t p = 0;
     while ((p = s.find(pat, p)) != std::string::npos) s.erase(p, pat.size());

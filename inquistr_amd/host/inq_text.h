@@ -64,6 +64,20 @@ extern const char *const kReadMotifsHeader;
 void append_read_motif_rows(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, const inq_read_call_t *calls,
                             const inq_read_origin_t *origins, const uint8_t *names, const inq_read_seq_t *seqs, const inq_read_motif_t *motifs,
                             uint64_t word, size_t n, bool unphased);
+// The motif a locus's kept reads repeat, inq_locus_motif_t of include/inquistr_hip.h, restated as a plain sequential walk, base by base,
+// over the locus's n_records slices packed back to back (each from a fresh byte on, n_bases[r] bases): what the host sweep computes
+// with (inq_host_locus_motif_find)
+void locus_motif_find(const uint8_t *packed, const uint32_t *n_bases, size_t n_records, inq_locus_motif_t *out);
+// the word a locus's runs are measured with when the motifs are looked for: the given one where it names a motif, else the found one
+// (what locus_motif_kernel writes to `use`)
+uint64_t motif_word_in_use(uint64_t given, uint64_t found);
+// the locus-motifs file (inq_genotype_repeats_locus_motifs; not a reference output): its header, and one target's line -
+// `chrom begin end reads bases motif period tandem copies catalogue agrees`, motif and catalogue as motif_text of the found and of the
+// catalogue's word, agrees 1 / 0 where the catalogue's word names a motif and is / is not a rotation of the found one (none found: 0),
+// `.` where it names none.  Returns what it printed there: 1, 0, or -1 for `.`
+extern const char *const kLocusMotifsHeader;
+int append_locus_motif_row(std::string &out, const std::string &chrom, uint32_t start, uint32_t end, uint64_t reads, const inq_locus_motif_t &found,
+                           uint64_t catalogue_word);
 // src/call.rs:91-100: file_stem, then every ".bam" and ".cram" removed
 std::string sample_name_from_path(const std::string &bam_path);
 // [3P] human_sort::compare as used by Genotype::cmp (src/call.rs:33-38): <0, 0, >0

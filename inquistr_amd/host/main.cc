@@ -36,7 +36,10 @@ static void usage(FILE *f) {
         "      --read-seqs <FILE>           write one line per kept read there: group, call, kind, read name, and the read's bases over the locus\n"
         "      --read-motifs <FILE>         write one line per kept read there: group, call, kind, read name, and the pure runs of the locus's motif\n"
         "                                   in the read's bases over the locus (longest run, motif units, bases in runs, number of runs)\n"
-        "      --motif <STR>                the motif of every target for --read-motifs (default: column 4 of the BED; needed with -r)\n"
+        "      --motif <STR>                the motif of every target for --read-motifs (default: column 4 of the BED; needed with -r);\n"
+        "                                   `auto`: the motif found in each target's own kept reads (works with -r and three-column BEDs)\n"
+        "      --locus-motifs <FILE>        write one line per target there: the motif of 1 to 6 bases its kept reads repeat (period, lag\n"
+        "                                   count, tandem copies), the catalogue's motif (--motif, else column 4) and whether they agree\n"
         "  -h, --help                       Print help\n",
         f);
 }
@@ -250,6 +253,7 @@ int main(int argc, char **argv) {
     const char *read_seqs_path = nullptr;   // --read-seqs (likewise: inq_genotype_repeats_seqs)
     const char *read_motifs_path = nullptr; // --read-motifs (likewise: inq_genotype_repeats_motifs)
     const char *motif = nullptr;            // --motif: one motif for every target of the read-motifs file
+    const char *locus_motifs_path = nullptr; // --locus-motifs (likewise: inq_genotype_repeats_locus_motifs)
     std::vector<int32_t> devices;  // --devices: one part of the targets per entry (an ordinal may repeat: N parts on one GPU)
     std::vector<std::pair<std::string, long long>> ctx_options;  // --ctx-option key=value
     auto num = [&](const char *s, const char *flag) -> unsigned long long {
@@ -287,6 +291,7 @@ int main(int argc, char **argv) {
         else if (key == "--read-seqs") read_seqs_path = val();
         else if (key == "--read-motifs") read_motifs_path = val();
         else if (key == "--motif") motif = val();
+        else if (key == "--locus-motifs") locus_motifs_path = val();
         else if (key == "--devices") {
             const std::string list = val();
             for (size_t b = 0; b <= list.size();) {
@@ -332,8 +337,8 @@ int main(int argc, char **argv) {
         char err[1024] = {0};
         ::setenv("INQ_FAST_EXIT", "1", 0);
         std::vector<inq_part_stats_t> st(devices.size());
-        int rc = inq::host_api().genotype_repeats_motifs(&a, devices.data(), devices.size(), 1 /* stdout */, read_calls_path, read_table_path,
-                                                         read_seqs_path, read_motifs_path, motif, st.data(), err, sizeof err);
+        int rc = inq::host_api().genotype_repeats_locus_motifs(&a, devices.data(), devices.size(), 1 /* stdout */, read_calls_path, read_table_path,
+                                                               read_seqs_path, read_motifs_path, motif, locus_motifs_path, st.data(), err, sizeof err);
         complain(rc, err);
         if (std::getenv("INQ_TIMING"))
             for (size_t r = 0; r < st.size(); ++r)
@@ -367,6 +372,10 @@ int main(int argc, char **argv) {
             std::fputs("error: '--read-motifs <FILE>' cannot be used with INQ_SERVER set: a server does not write the read-motifs file\n", stderr);
             return 2;
         }
+        if (locus_motifs_path) {  // ... and no locus-motifs file
+            std::fputs("error: '--locus-motifs <FILE>' cannot be used with INQ_SERVER set: a server does not write the locus-motifs file\n", stderr);
+            return 2;
+        }
         // INQ_SERVER=auto: this user's server for the device, started (detached; it leaves after INQ_SERVER_IDLE seconds without a
         // call, 120 by default) when none is running - the first call of a batch pays the start-up, the others find the context there
         std::string server_path = server_env;
@@ -396,7 +405,7 @@ int main(int argc, char **argv) {
     }
     char err[1024] = {0};
     ::setenv("INQ_FAST_EXIT", "1", 0);  // this process ends with the call: see leave()
-    return leave(inq::host_api().genotype_repeats_motifs(&a, nullptr, 0, 1 /* stdout */, read_calls_path, read_table_path, read_seqs_path,
-                                                         read_motifs_path, motif, nullptr, err, sizeof err),
+    return leave(inq::host_api().genotype_repeats_locus_motifs(&a, nullptr, 0, 1 /* stdout */, read_calls_path, read_table_path, read_seqs_path,
+                                                               read_motifs_path, motif, locus_motifs_path, nullptr, err, sizeof err),
                  err);
 }

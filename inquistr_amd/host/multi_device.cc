@@ -106,7 +106,8 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
     int rc = prepare(args, P, errbuf, errcap);
     if (rc != INQ_EXIT_OK) return rc;
     std::vector<uint64_t> words;  // the read-motifs file: the targets' motif words
-    if (more.read_motifs && target_motif_words(P, more.motif, words, msg) != INQ_EXIT_OK) {
+    if ((more.read_motifs || more.locus_motifs) &&
+        target_motif_words(P, more.motif, more.read_motifs && !motif_is_auto(more.motif), words, msg) != INQ_EXIT_OK) {
         set_err(errbuf, errcap, msg);
         return INQ_EXIT_ERROR;
     }
@@ -114,7 +115,7 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
     // the reports: each part's are scattered like its rows (the parts' target sets are disjoint)
     TargetReports reports;
     reports.begin(P.targets.size(), files.fds().wanted());
-    if (reports.has.read_motifs) reports.motif_word = words;
+    if (reports.has.read_motifs || reports.has.locus_motifs) reports.motif_word = words;
     std::vector<double> p1, p2, part_s;
     std::vector<uint32_t> order;
     std::vector<uint64_t> cuts;
@@ -155,7 +156,7 @@ static int genotype_devices_impl(const inq_call_args_t *args, const int32_t *dev
                       RowReports{&reports, files.fds(), args->unphased != 0});
 }
 
-static int genotype_motifs_impl(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const ReportPaths &more,
+static int genotype_locus_motifs_impl(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const ReportPaths &more,
                                inq_part_stats_t *stats, char *errbuf, size_t errcap) {
     if (n_devices == 0) return genotype_single(args, out_fd, more, errbuf, errcap);
     return genotype_devices_impl(args, device_ids, n_devices, out_fd, stats, errbuf, errcap, more);
@@ -168,8 +169,16 @@ int inq_genotype_repeats_seqs(const inq_call_args_t *args, const int32_t *device
 int inq_genotype_repeats_motifs(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,
                                 const char *read_table_path, const char *read_seqs_path, const char *read_motifs_path, const char *motif,
                                 inq_part_stats_t *stats, char *errbuf, size_t errcap) {
-    INQ_GUARD(genotype_motifs_impl(args, device_ids, n_devices, out_fd,
-                                   ReportPaths{read_calls_path, read_table_path, read_seqs_path, read_motifs_path, motif}, stats, errbuf, errcap),
+    return inq_genotype_repeats_locus_motifs(args, device_ids, n_devices, out_fd, read_calls_path, read_table_path, read_seqs_path, read_motifs_path,
+                                             motif, nullptr, stats, errbuf, errcap);
+}
+int inq_genotype_repeats_locus_motifs(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd,
+                                      const char *read_calls_path, const char *read_table_path, const char *read_seqs_path,
+                                      const char *read_motifs_path, const char *motif, const char *locus_motifs_path, inq_part_stats_t *stats,
+                                      char *errbuf, size_t errcap) {
+    INQ_GUARD(genotype_locus_motifs_impl(args, device_ids, n_devices, out_fd,
+                                         ReportPaths{read_calls_path, read_table_path, read_seqs_path, read_motifs_path, motif, locus_motifs_path},
+                                         stats, errbuf, errcap),
               errbuf, errcap)
 }
 int inq_genotype_repeats_table(const inq_call_args_t *args, const int32_t *device_ids, size_t n_devices, int out_fd, const char *read_calls_path,

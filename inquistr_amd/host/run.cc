@@ -87,9 +87,10 @@ int prepare(const inq_call_args_t *a, Prepared &P, std::string &msg, BedCache *b
     return INQ_EXIT_OK;
 }
 
-int target_motif_words(const Prepared &P, const char *motif, std::vector<uint64_t> &words, std::string &msg) {
+int target_motif_words(const Prepared &P, const char *motif, bool need_given, std::vector<uint64_t> &words, std::string &msg) {
     const size_t n = P.targets.size();
     words.assign(n, 0);
+    if (motif_is_auto(motif)) motif = nullptr;  // (the found motifs are measured with: what is left to tell is what the catalogue says)
     if (motif) {  // one motif for every target; it overrides column 4
         uint64_t w = 0;
         if (motif_encode(motif, &w) != kMotifOk) {
@@ -100,12 +101,13 @@ int target_motif_words(const Prepared &P, const char *motif, std::vector<uint64_
         return INQ_EXIT_OK;
     }
     if (P.target_name.size() != n) {  // a BED of three columns, or a region string
+        if (!need_given) return INQ_EXIT_OK;
         msg = "the read-motifs file needs a motif for every target: column 4 of the BED, or --motif <STR> (needed with -r)";
         return INQ_EXIT_ERROR;
     }
     size_t bad = 0;
     for (size_t i = 0; i < n; ++i) bad += motif_encode(P.target_name[i].c_str(), &words[i]) != kMotifOk;
-    if (bad)
+    if (bad && need_given)
         std::fprintf(stderr, "%zu of %zu targets have no motif of 1 to 15 bases of ACGT in column 4: `.` in the read-motifs file\n", bad, n);
     return INQ_EXIT_OK;
 }
@@ -158,7 +160,7 @@ int genotype_prepared(const inq_call_args_t *args, AsyncCtx &actx, Prepared &P, 
     TargetReports own_reports;
     if (!hooks.reports) own_reports.begin(n, hooks.report_fds.wanted());
     TargetReports *const reports = hooks.reports ? hooks.reports : &own_reports;
-    if (reports->has.read_motifs && hooks.motif_words)  // the words of this call's targets, as p1 / p2 are indexed
+    if ((reports->has.read_motifs || reports->has.locus_motifs) && hooks.motif_words)  // the words of this call's targets, as p1 / p2 are indexed
         for (size_t k = 0; k < n; ++k) {
             const size_t i = rows.active ? rows.idx[k] : k;
             reports->motif_word[k] = i < hooks.motif_words->size() ? (*hooks.motif_words)[i] : 0;
@@ -459,6 +461,7 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
     }
     if (const TargetReports *const tr = reports.reports) {  // each file that was collected and has somewhere to go, in the rows' order
         const bool unphased = reports.unphased;
+        size_t disagree = 0;  // the locus-motifs file: the targets whose catalogue motif is no rotation of the found one
         const struct {
             bool on;
             int fd;
@@ -503,7 +506,12 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
                  const std::vector<inq_read_motif_t> &m = tr->read_motifs[i];
                  if (w.recs.size() == l.size() && q.recs.size() == l.size() && m.size() == l.size())
                      append_read_motif_rows(text, targets[i].chrom, targets[i].start, targets[i].end, l.data(), w.recs.data(), w.bytes.data(),
-                                            q.recs.data(), m.data(), tr->motif_word[i], l.size(), unphased);
+                                            q.recs.data(), m.data(), tr->printed_word(i), l.size(), unphased);
+             }},
+            {tr->has.locus_motifs, reports.fds.locus_motifs, std::string(kLocusMotifsHeader) + '\n', kLocusMotifsWhat,
+             [&targets, tr, &disagree](std::string &text, uint32_t i) {  // one line per target: the motif its kept reads repeat
+                 disagree += append_locus_motif_row(text, targets[i].chrom, targets[i].start, targets[i].end, tr->read_calls[i].size(),
+                                                    tr->locus_motifs[i], tr->motif_word[i]) == 0;
              }},
         };
         for (const auto &f : files) {
@@ -511,6 +519,8 @@ int write_rows(uint64_t threads, const std::vector<RepeatInterval> &targets, con
             const int frc = write_report(order, f.header, f.row, f.what, f.fd, errbuf, errcap);
             if (frc != INQ_EXIT_OK) return frc;
         }
+        if (tr->has.locus_motifs && reports.fds.locus_motifs >= 0 && disagree)
+            std::fprintf(stderr, "%zu of %zu targets have a catalogue motif that their reads do not repeat: `0` in the locus-motifs file\n", disagree, n);
     }
     if (timing_level())
         std::fprintf(stderr, "[inq output] %zu rows: order %.2f ms, bounds %.2f ms, text %.2f ms (%zu threads), write %.2f ms\n", n, ms(t_w0, t_w1), ms(t_w1, t_w1b), ms(t_w1b, t_w2),
@@ -655,8 +665,8 @@ static int inq_genotype_repeats_impl(const inq_call_args_t *args, int out_fd, ch
     SessionHooks hooks;
     files.to(hooks);
     std::vector<uint64_t> words;
-    if (more.read_motifs && !rows.active) {
-        if (target_motif_words(P, more.motif, words, msg) != INQ_EXIT_OK) {
+    if ((more.read_motifs || more.locus_motifs) && !rows.active) {
+        if (target_motif_words(P, more.motif, more.read_motifs && !motif_is_auto(more.motif), words, msg) != INQ_EXIT_OK) {
             set_err(errbuf, errcap, msg);
             return INQ_EXIT_ERROR;
         }

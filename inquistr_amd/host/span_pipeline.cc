@@ -549,7 +549,7 @@ int run_device_front(const inq_call_args_t *args, const CallView &V, AsyncCtx &a
         const auto f0 = Clock::now();
         // rows that stay on the device take flags only (they belong to a prepared run, which takes no evidence: run.cc inq_run_open_impl)
         ReportSet which = hooks.reports->has;
-        if (hooks.dev_p1) which.evidence = which.read_calls = which.read_table = which.read_seqs = which.read_motifs = false;
+        if (hooks.dev_p1) which.evidence = which.read_calls = which.read_table = which.read_seqs = which.read_motifs = which.locus_motifs = which.motif_auto = false;
         br.begin(pending.size(), which);
         br.motifs_of(pending.data(), *hooks.reports);  // (the flush takes the loci's motif words in append order)
         double ms_call = 0;
