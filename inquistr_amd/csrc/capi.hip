@@ -1,4 +1,5 @@
-// capi.hip — implementation of the C ABI in include/inquistr_hip.h on top of kernels.hip.
+// capi.hip — implementation of the C ABI in include/inquistr_hip.h on top of kernels.hip: the context's life cycle and options, the
+// launch sequence of a call and the host-buffer call.  The side outputs' buffers, fetches and stand-alone entries: side_outputs.hip.
 // HIP only: there is no CPU fallback; without a gfx950 device every entry fails loudly.
 #include <hip/hip_runtime.h>
 
@@ -21,7 +22,6 @@
 #include "read_calls.h"
 #include "read_motifs.h"
 #include "read_seqs.h"
-#include "run_bytes.h"
 
 using namespace inq;
 
@@ -101,6 +101,15 @@ int ensure(inq_ctx *c, DevBuf &b, size_t bytes) {
     const int rc = device_alloc(c, &b.p, want, floor_bytes, &got);
     if (rc != INQ_OK) return rc;
     b.cap = got;
+    return INQ_OK;
+}
+
+int upload(inq_ctx *c, hipStream_t s, std::initializer_list<Upload> ups) {
+    for (const Upload &u : ups) {
+        const int rc = ensure(c, *u.d, u.bytes);
+        if (rc != INQ_OK) return rc;
+        if (u.bytes) HIP_TRY(c, hipMemcpyAsync(u.d->p, u.h, u.bytes, hipMemcpyHostToDevice, s));
+    }
     return INQ_OK;
 }
 
@@ -420,18 +429,18 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     const auto slices = [&] { launch_read_seq_records(ReadSeqArgs{x.kept_pair, n_kept, x.seq_qbeg, x.seq_len, x.seqs.recs, b->n_pairs}, s); };
     HIP_TRY(c, place_runs(x.names, origins));
     HIP_TRY(c, place_runs(x.seqs, slices));
-    // the motif each locus's reads repeat, out of the batch's own slices: behind the slices' records (kept_pair, kept_off), in front of
-    // the motif kernel, which reads the words this writes.  No pair: no record, every locus's answer is zeros
+    // what both motif kernels read: the records the scatter wrote, locus by locus, and the batch's own slices, a segment per pair
+    const KeptSlices kept{x.kept_pair, n_kept, x.kept_off, b->n_loci, x.seq_bytes, x.seq_n_bytes, x.seq_off, x.seq_len, b->n_pairs, b->n_pairs};
+    // the motif each locus's reads repeat: behind the slices' records (kept_pair, kept_off), in front of the motif kernel, which reads
+    // the words this writes.  No pair: no record, every locus's answer is zeros
     if (x.locus_found && !b->n_pairs) HIP_TRY(c, hipMemsetAsync(x.locus_found, 0, (size_t)b->n_loci * sizeof(inq_locus_motif_t), s));
     if (x.locus_found && b->n_pairs) {
-        launch_locus_motifs(LocusMotifArgs{x.kept_pair, n_kept, x.kept_off, b->n_loci, x.seq_bytes, x.seq_n_bytes, x.seq_off, x.seq_len, b->n_pairs,
-                                           b->n_pairs, x.motif_given, x.locus_found, x.motif_use}, s);
+        launch_locus_motifs(LocusMotifArgs{kept, x.motif_given, x.locus_found, x.motif_use}, s);
         HIP_TRY(c, hipGetLastError());
     }
-    // the motif runs of each record's bases, out of the same slices: in front of nothing
+    // the motif runs of each record's bases: in front of nothing
     if (x.motifs && b->n_pairs) {
-        launch_read_motifs(ReadMotifArgs{x.kept_pair, n_kept, x.kept_off, x.motif_word, b->n_loci, x.seq_bytes, x.seq_n_bytes, x.seq_off, x.seq_len,
-                                         b->n_pairs, x.motifs, b->n_pairs}, s);
+        launch_read_motifs(ReadMotifArgs{kept, x.motif_word, x.motifs}, s);
         HIP_TRY(c, hipGetLastError());
     }
     if (ev) HIP_TRY(c, hipEventRecord(ev->e2, s));
@@ -456,212 +465,6 @@ int inq_call_batch_device_reads(inq_ctx_t *c, const inq_batch_t *b, inq_result_t
     return guarded([&] { return enqueue_batch(c, b, r, hip_stream, LocusExtras{d_locus_flags, d_evidence, d_kept_off, d_kept}); });
 }
 
-uint32_t inq_read_call_tile(void) { return kReadCallTile; }
-
-static int read_calls_fetch_impl(inq_ctx_t *c, inq_read_call_t *out, uint64_t n) {
-    if (!c || n > c->read_calls_total || (n && !out)) return INQ_ERR_ARG;
-    if (!n) return INQ_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(out, c->rckept.p, (size_t)n * sizeof(inq_read_call_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return INQ_OK;
-}
-int inq_read_calls_fetch(inq_ctx_t *c, inq_read_call_t *out, uint64_t n) {
-    return guarded([&] { return read_calls_fetch_impl(c, out, n); });
-}
-
-uint32_t inq_read_name_tile(void) { return kReadNameTile; }
-
-// the first n records (rec_size bytes each) and the first n_bytes bytes of the runs of one kind that the last flush left in c
-static int kept_runs_fetch(inq_ctx_t *c, KeptRuns inq_ctx::*kind, void *recs, uint64_t n, size_t rec_size, uint8_t *bytes, uint64_t n_bytes) {
-    if (!c) return INQ_ERR_ARG;
-    const KeptRuns *const k = &(c->*kind);
-    if (n > k->n_recs || n_bytes > k->n_bytes || (n && !recs) || (n_bytes && !bytes)) return INQ_ERR_ARG;
-    if (!n && !n_bytes) return INQ_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (n) HIP_TRY(c, hipMemcpyAsync(recs, k->recs.p, (size_t)n * rec_size, hipMemcpyDeviceToHost, c->stream));
-    if (n_bytes) HIP_TRY(c, hipMemcpyAsync(bytes, k->bytes.p, (size_t)n_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return INQ_OK;
-}
-int inq_read_origins_fetch(inq_ctx_t *c, inq_read_origin_t *origins, uint64_t n, uint8_t *names, uint64_t name_bytes) {
-    return guarded([&] { return kept_runs_fetch(c, &inq_ctx::rnames, origins, n, sizeof *origins, names, name_bytes); });
-}
-
-uint32_t inq_seq_window_tile(void) { return kSeqWindowTile; }
-
-int inq_read_seqs_fetch(inq_ctx_t *c, inq_read_seq_t *seqs, uint64_t n, uint8_t *packed, uint64_t seq_bytes) {
-    return guarded([&] { return kept_runs_fetch(c, &inq_ctx::rseqs, seqs, n, sizeof *seqs, packed, seq_bytes); });
-}
-
-uint32_t inq_read_motif_tile(void) { return kReadMotifTile; }
-
-static int read_motifs_fetch_impl(inq_ctx_t *c, inq_read_motif_t *out, uint64_t n) {
-    if (!c || n > c->read_motifs_total || (n && !out)) return INQ_ERR_ARG;
-    if (!n) return INQ_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(out, c->rmotifs.p, (size_t)n * sizeof(inq_read_motif_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return INQ_OK;
-}
-int inq_read_motifs_fetch(inq_ctx_t *c, inq_read_motif_t *recs, uint64_t n) {
-    return guarded([&] { return read_motifs_fetch_impl(c, recs, n); });
-}
-
-// the motif kernel alone: records and packed slices as inq_read_seqs_fetch returns them go up, a record each comes down
-static int motif_runs_impl(inq_ctx_t *c, const inq_read_seq_t *recs, uint64_t n, const uint8_t *packed, uint64_t seq_bytes,
-                           const uint64_t *kept_off, const uint64_t *motif, uint64_t n_loci, inq_read_motif_t *out) {
-    if (!c) return INQ_ERR_ARG;
-    extras_reset(c);
-    if ((n && (!recs || !out)) || (seq_bytes && !packed) || !kept_off || (n_loci && !motif)) return INQ_ERR_ARG;
-    if (n >= (1ull << 40) || n_loci >= 0xfffffff0ull) return INQ_ERR_ARG;
-    for (uint64_t j = 0; j < n_loci; ++j)
-        if (kept_off[j] > kept_off[j + 1]) return INQ_ERR_ARG;
-    if (kept_off[n_loci] > n) return INQ_ERR_ARG;
-    if (!n) return INQ_OK;
-    if (!n_loci) {  // no record has a locus
-        std::memset(out, 0, (size_t)n * sizeof *out);
-        return INQ_OK;
-    }
-    // where each record's slice begins, and its length: the kernel's per-segment arrays
-    std::vector<uint64_t> seg_off(n);
-    std::vector<uint32_t> seg_len(n);
-    uint64_t at = 0;
-    for (uint64_t k = 0; k < n; ++k) seg_off[k] = at, seg_len[k] = recs[k].n_bases, at += run_bytes(recs[k]);
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    int rc;
-    struct Up {
-        DevBuf *d;
-        const void *h;
-        size_t bytes;
-    } ups[] = {
-        {&c->rseqs.bytes, packed, (size_t)seq_bytes},  // (scratch of the flushes' sequences and motifs, free between calls)
-        {&c->rseqs.off, seg_off.data(), (size_t)n * 8},
-        {&c->rseqs.recs, seg_len.data(), (size_t)n * 4},
-        {&c->rcoff, kept_off, (size_t)(n_loci + 1) * 8},
-        {&c->rmotifword, motif, (size_t)n_loci * 8},
-    };
-    for (auto &u : ups) {
-        if ((rc = ensure(c, *u.d, u.bytes)) != INQ_OK) return rc;
-        if (u.bytes) HIP_TRY(c, hipMemcpyAsync(u.d->p, u.h, u.bytes, hipMemcpyHostToDevice, s));
-    }
-    if ((rc = ensure(c, c->rmotifs, (size_t)n * sizeof(inq_read_motif_t))) != INQ_OK) return rc;
-    launch_read_motifs(ReadMotifArgs{nullptr, nullptr, (const uint64_t *)c->rcoff.p, (const uint64_t *)c->rmotifword.p, n_loci,
-                                     (const uint8_t *)c->rseqs.bytes.p, seq_bytes, (const uint64_t *)c->rseqs.off.p,
-                                     (const uint32_t *)c->rseqs.recs.p, n, (inq_read_motif_t *)c->rmotifs.p, n}, s);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(out, c->rmotifs.p, (size_t)n * sizeof(inq_read_motif_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));  // (the uploads' sources above live until here)
-    purge_retired(c);
-    return INQ_OK;
-}
-int inq_motif_runs(inq_ctx_t *c, const inq_read_seq_t *recs, uint64_t n, const uint8_t *packed, uint64_t seq_bytes, const uint64_t *kept_off,
-                   const uint64_t *motif, uint64_t n_loci, inq_read_motif_t *out) {
-    return guarded([&] { return motif_runs_impl(c, recs, n, packed, seq_bytes, kept_off, motif, n_loci, out); });
-}
-
-// the locus motif kernel alone: records and packed slices go up as motif_runs_impl sends them, a record per locus and the words come down
-static int locus_motifs_find_impl(inq_ctx_t *c, const inq_read_seq_t *recs, uint64_t n, const uint8_t *packed, uint64_t seq_bytes,
-                                  const uint64_t *kept_off, uint64_t n_loci, const uint64_t *given, inq_locus_motif_t *found, uint64_t *use) {
-    if (!c) return INQ_ERR_ARG;
-    extras_reset(c);
-    if ((n && !recs) || (seq_bytes && !packed) || !kept_off || (n_loci && !found)) return INQ_ERR_ARG;
-    if (n >= (1ull << 40) || n_loci >= 0xfffffff0ull) return INQ_ERR_ARG;
-    for (uint64_t j = 0; j < n_loci; ++j)
-        if (kept_off[j] > kept_off[j + 1]) return INQ_ERR_ARG;
-    if (kept_off[n_loci] > n) return INQ_ERR_ARG;
-    if (!n_loci) return INQ_OK;
-    std::vector<uint64_t> seg_off(n);
-    std::vector<uint32_t> seg_len(n);
-    uint64_t at = 0;
-    for (uint64_t k = 0; k < n; ++k) seg_off[k] = at, seg_len[k] = recs[k].n_bases, at += run_bytes(recs[k]);
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    int rc;
-    struct Up {
-        DevBuf *d;
-        const void *h;
-        size_t bytes;
-    } ups[] = {
-        {&c->rseqs.bytes, packed, (size_t)seq_bytes},  // (scratch of the flushes' sequences and motifs, free between calls)
-        {&c->rseqs.off, seg_off.data(), (size_t)n * 8},
-        {&c->rseqs.recs, seg_len.data(), (size_t)n * 4},
-        {&c->rcoff, kept_off, (size_t)(n_loci + 1) * 8},
-        {&c->rmotifword, given, given ? (size_t)n_loci * 8 : 0},
-    };
-    for (auto &u : ups) {
-        if ((rc = ensure(c, *u.d, u.bytes)) != INQ_OK) return rc;
-        if (u.bytes) HIP_TRY(c, hipMemcpyAsync(u.d->p, u.h, u.bytes, hipMemcpyHostToDevice, s));
-    }
-    if ((rc = ensure(c, c->rlocusmotif, (size_t)n_loci * sizeof(inq_locus_motif_t))) != INQ_OK) return rc;
-    if (use && (rc = ensure(c, c->rmotifuse, (size_t)n_loci * 8)) != INQ_OK) return rc;
-    launch_locus_motifs(LocusMotifArgs{nullptr, nullptr, (const uint64_t *)c->rcoff.p, n_loci, (const uint8_t *)c->rseqs.bytes.p, seq_bytes,
-                                       (const uint64_t *)c->rseqs.off.p, (const uint32_t *)c->rseqs.recs.p, n, n,
-                                       given ? (const uint64_t *)c->rmotifword.p : nullptr, (inq_locus_motif_t *)c->rlocusmotif.p,
-                                       use ? (uint64_t *)c->rmotifuse.p : nullptr}, s);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(found, c->rlocusmotif.p, (size_t)n_loci * sizeof(inq_locus_motif_t), hipMemcpyDeviceToHost, s));
-    if (use) HIP_TRY(c, hipMemcpyAsync(use, c->rmotifuse.p, (size_t)n_loci * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));  // (the uploads' sources above live until here)
-    purge_retired(c);
-    return INQ_OK;
-}
-int inq_locus_motifs_find(inq_ctx_t *c, const inq_read_seq_t *recs, uint64_t n, const uint8_t *packed, uint64_t seq_bytes, const uint64_t *kept_off,
-                          uint64_t n_loci, const uint64_t *given, inq_locus_motif_t *found, uint64_t *use) {
-    return guarded([&] { return locus_motifs_find_impl(c, recs, n, packed, seq_bytes, kept_off, n_loci, given, found, use); });
-}
-
-// the window walk alone: the batch goes up as a call's does, two arrays come down
-static int seq_windows_impl(inq_ctx_t *c, const inq_batch_t *b, const uint32_t *l_seq, uint32_t *q_beg, uint32_t *n_bases) {
-    if (!c || !b) return INQ_ERR_ARG;
-    extras_reset(c);
-    if (b->n_loci && (!b->locus_pair_off || !b->locus_start || !b->locus_end)) return INQ_ERR_ARG;
-    if (b->n_pairs && (!b->pair_read || !b->reads || !b->n_reads || !q_beg || !n_bases)) return INQ_ERR_ARG;
-    if ((b->n_cigar_words && !b->cigar) || b->n_cigar_words % 4 != 0 || b->reserved != 0) return INQ_ERR_ARG;
-    if ((!b->n_loci && b->n_pairs) || b->n_loci >= 0xfffffff0ull || b->n_pairs >= (1ull << 40)) return INQ_ERR_ARG;
-    if (b->n_loci && (b->locus_pair_off[0] != 0 || b->locus_pair_off[b->n_loci] != b->n_pairs)) return INQ_ERR_ARG;
-    for (uint64_t j = 0; j < b->n_loci; ++j)
-        if (b->locus_pair_off[j] > b->locus_pair_off[j + 1]) return INQ_ERR_ARG;
-    if (!b->n_pairs) return INQ_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    int rc;
-    struct Up {
-        DevBuf *d;
-        const void *h;
-        size_t bytes;
-    } ups[] = {
-        {&c->cigar, b->cigar, (size_t)b->n_cigar_words * 4},
-        {&c->reads, b->reads, (size_t)b->n_reads * sizeof(inq_read_t)},
-        {&c->pair_read, b->pair_read, (size_t)b->n_pairs * 4},
-        {&c->off, b->locus_pair_off, (size_t)(b->n_loci + 1) * 8},
-        {&c->lstart, b->locus_start, (size_t)b->n_loci * 4},
-        {&c->lend, b->locus_end, (size_t)b->n_loci * 4},
-        {&c->rseqs.off, l_seq, l_seq ? (size_t)b->n_reads * 4 : 0},  // (scratch of the flushes' sequences, free between calls)
-    };
-    for (auto &u : ups) {
-        if ((rc = ensure(c, *u.d, u.bytes)) != INQ_OK) return rc;
-        if (u.bytes) HIP_TRY(c, hipMemcpyAsync(u.d->p, u.h, u.bytes, hipMemcpyHostToDevice, s));
-    }
-    if ((rc = ensure(c, c->rseqs.recs, (size_t)b->n_pairs * 8)) != INQ_OK) return rc;  // q_beg[n_pairs], n_bases[n_pairs]
-    uint32_t *const d_qbeg = (uint32_t *)c->rseqs.recs.p, *const d_len = d_qbeg + b->n_pairs;
-    SeqWindowArgs a{(const uint4 *)c->cigar.p, b->n_cigar_words / 4, (const uint4 *)c->reads.p, b->n_reads, (const uint32_t *)c->pair_read.p,
-                    (const uint64_t *)c->off.p, (const uint32_t *)c->lstart.p, (const uint32_t *)c->lend.p, b->n_loci, b->n_pairs, SeqLenSource{},
-                    d_qbeg, d_len};
-    if (l_seq) a.len.l_seq = (const uint32_t *)c->rseqs.off.p;
-    launch_seq_window(a, s);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(q_beg, d_qbeg, (size_t)b->n_pairs * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(n_bases, d_len, (size_t)b->n_pairs * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    purge_retired(c);
-    return INQ_OK;
-}
-int inq_seq_windows(inq_ctx_t *c, const inq_batch_t *b, const uint32_t *l_seq, uint32_t *q_beg, uint32_t *n_bases) {
-    return guarded([&] { return seq_windows_impl(c, b, l_seq, q_beg, n_bases); });
-}
-
 int inq_ctx_status(inq_ctx_t *c, uint64_t *n_tie_loci) {
     if (!c) return INQ_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -681,9 +484,10 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
     // host-side shape checks: everything the grid and the kernels' indexing assume
     uint64_t max_reads = 0;
     if (b->n_loci) {
-        if (b->locus_pair_off[0] != 0 || b->locus_pair_off[b->n_loci] != b->n_pairs) return INQ_ERR_ARG;
+        // (the offsets first, all of them: a locus's depth below is a difference of two that ascend)
+        const uint64_t *const off = b->locus_pair_off;
+        if (off[0] != 0 || off[b->n_loci] != b->n_pairs || !offsets_ok(off, b->n_loci, b->n_pairs)) return INQ_ERR_ARG;
         for (uint64_t j = 0; j < b->n_loci; ++j) {
-            if (b->locus_pair_off[j] > b->locus_pair_off[j + 1]) return INQ_ERR_ARG;
             if (!locus_ok(b->locus_start[j], b->locus_end[j])) return INQ_ERR_LOCUS;
             max_reads = std::max<uint64_t>(max_reads, b->locus_pair_off[j + 1] - b->locus_pair_off[j]);
         }
@@ -695,22 +499,13 @@ static int call_batch_impl(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, 
     }
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    struct Up {
-        DevBuf *d;
-        const void *h;
-        size_t bytes;
-    } ups[] = {
-        {&c->cigar, b->cigar, (size_t)b->n_cigar_words * 4},
-        {&c->reads, b->reads, (size_t)b->n_reads * sizeof(inq_read_t)},
-        {&c->pair_read, b->pair_read, (size_t)b->n_pairs * 4},
-        {&c->off, b->locus_pair_off, (size_t)(b->n_loci + 1) * 8},
-        {&c->lstart, b->locus_start, (size_t)b->n_loci * 4},
-        {&c->lend, b->locus_end, (size_t)b->n_loci * 4},
-    };
-    for (auto &u : ups) {
-        if ((rc = ensure(c, *u.d, u.bytes)) != INQ_OK) return rc;
-        if (u.bytes) HIP_TRY(c, hipMemcpyAsync(u.d->p, u.h, u.bytes, hipMemcpyHostToDevice, s));
-    }
+    rc = upload(c, s, {{&c->cigar, b->cigar, (size_t)b->n_cigar_words * 4},
+                       {&c->reads, b->reads, (size_t)b->n_reads * sizeof(inq_read_t)},
+                       {&c->pair_read, b->pair_read, (size_t)b->n_pairs * 4},
+                       {&c->off, b->locus_pair_off, (size_t)(b->n_loci + 1) * 8},
+                       {&c->lstart, b->locus_start, (size_t)b->n_loci * 4},
+                       {&c->lend, b->locus_end, (size_t)b->n_loci * 4}});
+    if (rc != INQ_OK) return rc;
     if ((rc = ensure(c, c->p1, (size_t)b->n_loci * 8)) != INQ_OK) return rc;
     if ((rc = ensure(c, c->p2, (size_t)b->n_loci * 8)) != INQ_OK) return rc;
     const bool want_call = r->pair_call || h.per_pair(), want_bits = r->pair_bits || h.per_pair();
@@ -999,101 +794,4 @@ void inq_free_pinned(void *p) {
 
 int inq::call_batch_device_impl(inq_ctx *c, const inq_batch_t *b, inq_result_t *r, void *hip_stream, const LocusExtras &x) {
     return enqueue_batch(c, b, r, hip_stream, x);
-}
-
-int inq::extras_prepare(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const HostExtras &h, LocusExtras *d) {
-    int rc;
-    if (h.flags && (rc = ensure(c, c->lflags, (size_t)n_loci)) != INQ_OK) return rc;
-    if (h.per_pair() && (rc = ensure(c, c->pcall, (size_t)n_pairs * 8)) != INQ_OK) return rc;
-    if (h.per_pair() && (rc = ensure(c, c->pbits, (size_t)n_pairs)) != INQ_OK) return rc;
-    if (h.evidence && (rc = ensure(c, c->levidence, (size_t)n_loci * sizeof(inq_locus_evidence_t))) != INQ_OK) return rc;
-    if (h.kept_off && (rc = ensure(c, c->rcoff, (size_t)(n_loci + 1) * 8)) != INQ_OK) return rc;
-    if (h.kept_off && (rc = ensure(c, c->rckept, (size_t)n_pairs * sizeof(inq_read_call_t))) != INQ_OK) return rc;
-    d->flags = h.flags ? (uint8_t *)c->lflags.p : nullptr;
-    d->evidence = h.evidence ? (inq_locus_evidence_t *)c->levidence.p : nullptr;
-    d->kept_off = h.kept_off ? (uint64_t *)c->rcoff.p : nullptr;
-    d->kept = h.kept_off ? (inq_read_call_t *)c->rckept.p : nullptr;
-    // a kind's records and the scan of their byte lengths (the batch's own names and slices, LocusExtras::name_off, seq_qbeg / seq_len,
-    // are the caller's to set: only a deferred batch has them)
-    auto runs = [&](KeptRuns &k, auto &out) -> int {
-        if ((rc = ensure(c, k.recs, (size_t)n_pairs * sizeof *out.recs)) != INQ_OK) return rc;
-        if ((rc = ensure(c, k.off, (size_t)(n_pairs + 1 + scan_tmp_words(std::max<uint64_t>(n_pairs, 1))) * 8)) != INQ_OK) return rc;
-        out.recs = (decltype(out.recs))k.recs.p;
-        out.off = (uint64_t *)k.off.p;
-        return INQ_OK;
-    };
-    if (h.name_bytes) {
-        if (!h.kept_off) return INQ_ERR_ARG;
-        if ((rc = runs(c->rnames, d->names)) != INQ_OK) return rc;
-    }
-    if (h.seq_bytes) {
-        if (!h.kept_off || !h.name_bytes) return INQ_ERR_ARG;
-        if ((rc = ensure(c, c->rkeptpair, (size_t)n_pairs * 8)) != INQ_OK) return rc;
-        if ((rc = runs(c->rseqs, d->seqs)) != INQ_OK) return rc;
-        d->kept_pair = (uint64_t *)c->rkeptpair.p;
-    }
-    if (h.motif_runs()) {
-        if (!h.seq_bytes) return INQ_ERR_ARG;
-        if ((rc = ensure(c, c->rmotifs, (size_t)n_pairs * sizeof(inq_read_motif_t))) != INQ_OK) return rc;
-        if ((rc = ensure(c, c->rmotifword, (size_t)n_loci * 8)) != INQ_OK) return rc;
-        d->motifs = (inq_read_motif_t *)c->rmotifs.p;
-        d->motif_word = (const uint64_t *)c->rmotifword.p;
-    }
-    if (h.found) {  // the motif kernel reads the words the search wrote, the given ones among them
-        if ((rc = ensure(c, c->rlocusmotif, (size_t)n_loci * sizeof(inq_locus_motif_t))) != INQ_OK) return rc;
-        if ((rc = ensure(c, c->rmotifuse, (size_t)n_loci * 8)) != INQ_OK) return rc;
-        d->locus_found = (inq_locus_motif_t *)c->rlocusmotif.p;
-        d->motif_given = h.motif ? (const uint64_t *)c->rmotifword.p : nullptr;
-        d->motif_use = (uint64_t *)c->rmotifuse.p;
-        d->motif_word = d->motif_use;
-    }
-    return INQ_OK;
-}
-
-int inq::extras_download(inq_ctx *c, uint64_t n_loci, const HostExtras &h, const LocusExtras &d, uint8_t *flags_dst, hipStream_t s) {
-    if (h.flags) HIP_TRY(c, hipMemcpyAsync(flags_dst, d.flags, (size_t)n_loci, hipMemcpyDeviceToHost, s));
-    if (h.evidence) HIP_TRY(c, hipMemcpyAsync(h.evidence, d.evidence, (size_t)n_loci * sizeof(inq_locus_evidence_t), hipMemcpyDeviceToHost, s));
-    if (h.kept_off) HIP_TRY(c, hipMemcpyAsync(h.kept_off, d.kept_off, (size_t)(n_loci + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (h.found) HIP_TRY(c, hipMemcpyAsync(h.found, d.locus_found, (size_t)n_loci * sizeof(inq_locus_motif_t), hipMemcpyDeviceToHost, s));
-    return INQ_OK;
-}
-
-int inq::extras_names(inq_ctx *c, uint64_t n_pairs, uint64_t n_kept, const HostExtras &h, const LocusExtras &d, const RunSource &names,
-                      const RunSource &seqs, hipStream_t s) {
-    // per kind: where its byte total goes (null: not asked for), the scan it sits behind, where the runs come from and where they go
-    const struct {
-        uint64_t *total;
-        const uint64_t *off;
-        const RunSource &src;
-        DevBuf &dst;
-    } kinds[] = {{h.name_bytes, d.names.off, names, c->rnames.bytes}, {h.seq_bytes, d.seqs.off, seqs, c->rseqs.bytes}};
-    for (auto &k : kinds)
-        if (k.total) *k.total = 0;
-    if (!h.name_bytes || !n_pairs || !n_kept) return INQ_OK;
-    // (each scan's total sits behind its last element; nothing else is in flight on s: plain 8-byte copies, one wait for all)
-    for (auto &k : kinds)
-        if (k.total) HIP_TRY(c, hipMemcpyAsync(k.total, k.off + n_pairs, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    bool any = false;
-    for (auto &k : kinds) {
-        if (!k.total || !*k.total) continue;
-        const int rc = ensure(c, k.dst, (size_t)*k.total);
-        if (rc != INQ_OK) return rc;
-        launch_name_copy(NameCopyArgs{k.src.bytes, k.src.n_bytes, k.src.off, k.src.n, 0, k.src.by_pair ? nullptr : d.kept, (uint8_t *)k.dst.p,
-                                      *k.total, k.off, std::min(n_kept, n_pairs), k.src.by_pair ? d.kept_pair : nullptr}, s);
-        any = true;
-    }
-    if (!any) return INQ_OK;
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return INQ_OK;
-}
-
-void inq::extras_finish(inq_ctx *c, uint64_t n_loci, uint64_t n_pairs, const HostExtras &h, uint32_t err) {
-    if (!h.kept_off) return;
-    if (!n_loci) h.kept_off[0] = 0;  // (nothing was launched: no list, no record)
-    if (err == 0) c->read_calls_total = std::min<uint64_t>(h.kept_off[n_loci], n_pairs);
-    if (h.name_bytes && err == 0) c->rnames.n_recs = c->read_calls_total, c->rnames.n_bytes = *h.name_bytes;
-    if (h.seq_bytes && err == 0) c->rseqs.n_recs = c->read_calls_total, c->rseqs.n_bytes = *h.seq_bytes;
-    if (h.motif_runs() && err == 0) c->read_motifs_total = c->read_calls_total;
 }

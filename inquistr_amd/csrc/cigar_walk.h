@@ -405,19 +405,7 @@ __device__ __forceinline__ void walk_pairs_whole(const BatchView &b, const PairM
 // u32 wrap of pos = -1); an unchecked one is walked to its end, with the device's own domain checks.
 constexpr uint32_t RP_CHECKED = 1u;  // INQ_READ_CHECKED
 
-constexpr int kRowLanes = 16;  // lanes of one row = one read stream = one DPP row
-
-// Inclusive prefix sum inside each row: the first four DPP steps of wave_inclusive_scan_u32.
-__device__ __forceinline__ uint32_t row_inclusive_scan_u32(uint32_t x) {
-    x += dpp_shr_zero<DPP_ROW_SHR1>(x);
-    x += dpp_shr_zero<DPP_ROW_SHR2>(x);
-    x += dpp_shr_zero<DPP_ROW_SHR4>(x);
-    x += dpp_shr_zero<DPP_ROW_SHR8>(x);
-    return x;
-}
-// Lane 15 of each row to every lane of the row: ds_swizzle in bit-mask mode reads lane
-// ((l & 0x10) | 0x0f) of its 32-lane half.
-__device__ __forceinline__ uint32_t row_last(uint32_t x) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, 0x10 | (0x0f << 5)); }
+// (a row behind the head = one read stream = one DPP row of kRowLanes lanes: its scan and its last lane are wave_primitives.h's)
 
 // The head phase's rows are half DPP rows: kHeadLanes = 8 lanes, one 128-byte line per load.
 constexpr int kHeadLanes = 8;

@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <string>
@@ -174,6 +175,20 @@ int ensure(inq_ctx *c, DevBuf &b, size_t bytes);
 int device_alloc(inq_ctx *c, void **out, size_t want, size_t exact, size_t *got);
 void retire(inq_ctx *c, void *p, size_t bytes);
 void purge_retired(inq_ctx *c);  // hipFree of everything retired (waits for the device: call where it is idle)
+// host arrays on their way into context buffers: each buffer is grown to its array (ensure), then the copy is enqueued on s (none for
+// 0 bytes).  The arrays live until the caller has waited for s
+struct Upload {
+    DevBuf *d;
+    const void *h;
+    size_t bytes;
+};
+int upload(inq_ctx *c, hipStream_t s, std::initializer_list<Upload> ups);
+// off[0 .. n] ascend and end at or in front of total (else INQ_ERR_ARG: the kernels' searches and grids assume it)
+inline bool offsets_ok(const uint64_t *off, uint64_t n, uint64_t total) {
+    for (uint64_t j = 0; j < n; ++j)
+        if (off[j] > off[j + 1]) return false;
+    return off[n] <= total;
+}
 // The per-locus side outputs of a call, as the launch sequence takes them: all DEVICE pointers.  Null = not asked for: nothing is added
 // to the launch sequence and nothing is allocated.  A further per-locus output is one more member here and in HostExtras.
 struct LocusExtras {
@@ -195,7 +210,9 @@ struct LocusExtras {
     uint64_t *kept_pair = nullptr;
     const uint32_t *seq_qbeg = nullptr, *seq_len = nullptr;  // [n_pairs]
     // the motif runs of those bases (needs seqs): a record per kept record out of motif_word[n_loci] and the batch's own per-pair
-    // slices, seq_len[p] bases packed from byte seq_off[p] of seq_bytes on
+    // slices, seq_len[p] bases packed from byte seq_off[p] of seq_bytes on.  The launch sequence hands kept_pair, kept_off and these
+    // slices to both motif kernels as one KeptSlices (kept_view.h); kept_pair and kept_off are written through here first, so the
+    // members stay what the compaction takes
     inq_read_motif_t *motifs = nullptr;
     const uint64_t *motif_word = nullptr;
     const uint8_t *seq_bytes = nullptr;

@@ -53,8 +53,6 @@ __device__ __forceinline__ void count_pair(const EvidenceArgs &a, uint64_t i, Pa
     p.mx = v > p.mx ? v : p.mx;
 }
 
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x) { return readlane_u32(wave_inclusive_scan_u32(x), kWave - 1); }
-
 // x moved along the DPP pattern CTRL; a lane the move does not reach (row start, rows outside ROW_MASK) keeps its own x, which min
 // and max absorb
 template <int CTRL, int ROW_MASK>

@@ -22,14 +22,12 @@
 #include <hip/hip_runtime.h>
 
 #include "locus_motifs.h"
-#include "segment_store.h"
 #include "slice_words.h"
-#include "wave_primitives.h"
 
 namespace inq {
 namespace {
 
-constexpr uint32_t kThreads = 256, kRowLanes = 16, kRows = kThreads / kRowLanes, kWaves = kThreads / (uint32_t)kWave;
+constexpr uint32_t kThreads = 256, kRows = kThreads / (uint32_t)kRowLanes, kWaves = kThreads / (uint32_t)kWave;
 constexpr uint32_t kBins = 1u << (2u * kLocusMotifMaxPeriod);
 static_assert(sizeof(inq_locus_motif_t) == 40, "five u64");
 
@@ -66,27 +64,6 @@ __device__ __forceinline__ uint32_t smallest_rotation(uint32_t v, uint32_t p) {
     return best;
 }
 
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t x) {  // every lane holds the sum
-    for (int d = 1; d < kWave; d *= 2) x += __shfl_xor((unsigned long long)x, d, kWave);
-    return x;
-}
-
-// a record's slice: n bases packed from seg on; n = 0: nothing to read
-struct Slice {
-    const uint8_t *seg;
-    uint64_t n;
-};
-__device__ __forceinline__ Slice slice_of(const LocusMotifArgs &a, uint64_t rec, bool has) {
-    Slice S{a.bytes, 0};
-    if (!has) return S;
-    const uint64_t p = a.kept_pair ? a.kept_pair[rec] : rec;
-    if (p >= a.n_segs) return S;
-    const uint64_t o = a.seg_off[p], n = a.seg_len[p], nb = (n + 1u) / 2u;
-    if (o > a.n_bytes || nb > a.n_bytes - o) return S;
-    S.seg += o, S.n = n;
-    return S;
-}
-
 // every 16-base word of the records [beg, end), the rows taking a record each and a row's lanes a word each: per_word(prev, cur, tail)
 // with the word, the word before it (0 in front of the first) and the mask of cur's positions that lie inside the slice; per_record(n)
 // once a record in lane 0 of its row.  No lane waits for another in here
@@ -116,8 +93,7 @@ __global__ __launch_bounds__(256) void locus_motif_kernel(LocusMotifArgs a) {
     __shared__ unsigned long long wave_best[kWaves];               // a wave's best class: its count
     __shared__ uint32_t wave_best_class[kWaves];
     const uint32_t tid = threadIdx.x, lane = (uint32_t)lane_id(), wave = tid / (uint32_t)kWave;
-    uint64_t total = a.n_kept ? *a.n_kept : a.n_recs;  // the records the compaction wrote
-    if (total > a.n_recs) total = a.n_recs;
+    const uint64_t total = kept_total(a.n_kept, a.n_recs);
     for (uint64_t j = blockIdx.x; j < a.n_loci; j += gridDim.x) {
         uint64_t end = a.kept_off[j + 1], beg = a.kept_off[j];
         end = end < total ? end : total;
@@ -231,13 +207,11 @@ __global__ __launch_bounds__(256) void locus_motif_kernel(LocusMotifArgs a) {
     }
 }
 
-constexpr uint32_t kGridCap = 1u << 16;  // workgroups of a launch (capped_grid)
-
 }  // namespace
 
 void launch_locus_motifs(const LocusMotifArgs &a, hipStream_t s) {
     if (!a.n_loci) return;
-    hipLaunchKernelGGL(locus_motif_kernel, dim3(capped_grid(a.n_loci, kGridCap)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(locus_motif_kernel, dim3(capped_grid(a.n_loci)), dim3(kThreads), 0, s, a);
 }
 
 }  // namespace inq

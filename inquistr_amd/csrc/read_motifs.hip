@@ -16,9 +16,7 @@
 // of the hits, so neither it nor the next segment's first base can extend a run.
 #include <hip/hip_runtime.h>
 
-#include "cigar_walk.h"
 #include "read_motifs.h"
-#include "segment_store.h"
 #include "slice_words.h"
 
 namespace inq {
@@ -46,73 +44,27 @@ __device__ __forceinline__ Motif decode_motif(uint64_t word) {
     return M;
 }
 
-__device__ __forceinline__ uint32_t row_or(uint32_t x) {  // lane 15 of the row holds the OR of its lanes
-    x |= dpp_shr_zero<DPP_ROW_SHR1>(x);
-    x |= dpp_shr_zero<DPP_ROW_SHR2>(x);
-    x |= dpp_shr_zero<DPP_ROW_SHR4>(x);
-    x |= dpp_shr_zero<DPP_ROW_SHR8>(x);
-    return x;
-}
-__device__ __forceinline__ uint64_t row_max_u64(uint64_t x) {  // ... the maximum
-#define INQ_STEP(CTRL)                                                                                                              \
-    {                                                                                                                               \
-        const uint64_t o = (uint64_t)dpp_shr_zero<CTRL>((uint32_t)x) | (uint64_t)dpp_shr_zero<CTRL>((uint32_t)(x >> 32)) << 32;    \
-        x = o > x ? o : x;                                                                                                          \
-    }
-    INQ_STEP(DPP_ROW_SHR1)
-    INQ_STEP(DPP_ROW_SHR2)
-    INQ_STEP(DPP_ROW_SHR4)
-    INQ_STEP(DPP_ROW_SHR8)
-#undef INQ_STEP
-    return x;
-}
-
 __global__ __launch_bounds__(256) void read_motif_kernel(ReadMotifArgs a) {
     const int lane = lane_id();
     const uint32_t rl = (uint32_t)lane & (kMotifRowLanes - 1u);
     const int row_shift = lane & ~(int)(kMotifRowLanes - 1u);  // where this row's bits lie in a ballot
-    uint64_t total = a.n_kept ? *a.n_kept : a.n_recs;  // the records the compaction wrote
-    if (total > a.n_recs) total = a.n_recs;
+    const uint64_t total = kept_total(a.n_kept, a.n_recs);
     // (the grid is capped, launch_read_motifs: a workgroup takes every gridDim.x-th tile)
     for (uint64_t base = (uint64_t)blockIdx.x * kReadMotifTile; base < total; base += (uint64_t)gridDim.x * kReadMotifTile) {
         const uint64_t rec = base + threadIdx.x / kMotifRowLanes;
         const bool has = rec < total;
 
-        // the record's locus: the j with kept_off[j] <= rec < kept_off[j + 1], sixteen probes a step (as seq_window_kernel finds a
-        // pair's).  Offsets that do not ascend end the search all the same, and what it found is checked below.
-        uint64_t lo = 0, hi = has ? a.n_loci : 0;
-        while (ballot64(hi - lo > 1u)) {
-            const uint64_t size = hi - lo, step = (size + kMotifRowLanes - 1u) / kMotifRowLanes, idx = lo + rl * step;
-            const bool below = size > 1u && idx < hi && a.kept_off[idx + 1] <= rec;
-            const uint32_t c = (uint32_t)__popc((uint32_t)(ballot64(below) >> row_shift) & 0xffffu);
-            if (size > 1u) {
-                if (c == 0u) {
-                    hi = lo + 1u;
-                } else {
-                    const uint64_t last = lo + (uint64_t)(c - 1u) * step;  // the last probe at or below rec; it lies in front of hi
-                    lo = last + 1u;
-                    hi = last + step + 1u < hi ? last + step + 1u : hi;
-                }
-            }
-        }
-        bool live = has && lo < a.n_loci && a.kept_off[lo] <= rec && rec < a.kept_off[lo + 1];
+        // the record's locus: the j with kept_off[j] <= rec < kept_off[j + 1]; what the search found is checked here
+        const uint64_t lo = row_find_interval(a.kept_off, a.n_loci, rec, has, rl, row_shift);
+        const bool found = has && lo < a.n_loci && a.kept_off[lo] <= rec && rec < a.kept_off[lo + 1];
         Motif M{0, 0u};
-        if (live) M = decode_motif(a.motif[lo]);
-        live = live && M.k != 0u;
-        const uint8_t *seg = a.bytes;
-        uint64_t n = 0;  // bases of the slice
-        if (live) {
-            const uint64_t p = a.kept_pair ? a.kept_pair[rec] : rec;
-            live = p < a.n_segs;
-            if (live) {
-                const uint64_t o = a.seg_off[p], nb = ((uint64_t)a.seg_len[p] + 1u) / 2u;
-                live = o <= a.n_bytes && nb <= a.n_bytes - o;
-                if (live) seg += o, n = a.seg_len[p];
-            }
-        }
-        const uint64_t n_words = (n + 15u) / 16u, nb = (n + 1u) / 2u;
+        if (found) M = decode_motif(a.motif[lo]);
+        // (a record without a motif or without a slice has n = 0: no word is read, no lane has a hit)
+        const Slice S = slice_of(a, rec, M.k != 0u);
+        const uint8_t *const seg = S.seg;
+        const uint64_t n = S.n, n_words = (n + 15u) / 16u, nb = (n + 1u) / 2u;
         const uint32_t k = M.k;
-        const bool mine = live && rl < k;         // this lane has a rotation
+        const bool mine = rl < k;                 // this lane has a rotation
         const uint32_t step16 = k ? 16u % k : 0u;  // what 16 bases add to the phase
         uint32_t ph = mine ? rl : 0u;             // (16 w + r) mod k
 
@@ -175,13 +127,11 @@ __global__ __launch_bounds__(256) void read_motif_kernel(ReadMotifArgs a) {
     }
 }
 
-constexpr uint32_t kGridCap = 1u << 16;  // workgroups of a launch (capped_grid)
-
 }  // namespace
 
 void launch_read_motifs(const ReadMotifArgs &a, hipStream_t s) {
     if (!a.n_recs || !a.motif) return;
-    hipLaunchKernelGGL(read_motif_kernel, dim3(capped_grid((a.n_recs + kReadMotifTile - 1) / kReadMotifTile, kGridCap)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(read_motif_kernel, dim3(capped_grid((a.n_recs + kReadMotifTile - 1) / kReadMotifTile)), dim3(kThreads), 0, s, a);
 }
 
 }  // namespace inq

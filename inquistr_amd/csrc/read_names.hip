@@ -17,6 +17,7 @@
 // it moves, and an index outside the source's offsets copies nothing.
 #include <hip/hip_runtime.h>
 
+#include "kept_view.h"
 #include "read_calls.h"
 #include "segment_store.h"
 
@@ -53,7 +54,7 @@ __global__ __launch_bounds__(256) void name_copy_kernel(NameCopyArgs a) {
 }
 
 __global__ __launch_bounds__(256) void read_origin_kernel(ReadOriginArgs a) {
-    const uint64_t total = *a.n_kept < a.n_pairs ? *a.n_kept : a.n_pairs;  // the records the compaction wrote
+    const uint64_t total = kept_total(a.n_kept, a.n_pairs);
     for (uint64_t k = (uint64_t)blockIdx.x * kThreads + threadIdx.x; k < total; k += (uint64_t)gridDim.x * kThreads) {
         const uint32_t r = a.kept[k].read;
         uint32_t pos = 0, tail = 0;  // (an index outside the descriptors is the locus kernels' INQ_ERR_INDEX: the record is all zero)
@@ -67,18 +68,18 @@ __global__ __launch_bounds__(256) void read_origin_kernel(ReadOriginArgs a) {
     }
 }
 
-constexpr uint32_t kGridCap = 1u << 20;  // workgroups of a launch (capped_grid)
+constexpr uint32_t kNameGridCap = 1u << 20;  // workgroups of a launch of this file (capped_grid), not the shared kGridCap
 
 }  // namespace
 
 void launch_name_copy(const NameCopyArgs &a, hipStream_t s) {
     if (!a.n) return;
-    hipLaunchKernelGGL(name_copy_kernel, dim3(capped_grid((a.n + kReadNameTile - 1) / kReadNameTile, kGridCap)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(name_copy_kernel, dim3(capped_grid((a.n + kReadNameTile - 1) / kReadNameTile, kNameGridCap)), dim3(kThreads), 0, s, a);
 }
 
 void launch_read_origins(const ReadOriginArgs &a, hipStream_t s) {
     if (!a.n_pairs) return;
-    hipLaunchKernelGGL(read_origin_kernel, dim3(capped_grid((a.n_pairs + kThreads - 1) / kThreads, kGridCap)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(read_origin_kernel, dim3(capped_grid((a.n_pairs + kThreads - 1) / kThreads, kNameGridCap)), dim3(kThreads), 0, s, a);
 }
 
 }  // namespace inq

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cigar_walk.h"
+#include "kept_view.h"
 #include "read_seqs.h"
 #include "segment_store.h"
 
@@ -34,17 +35,6 @@ static_assert(sizeof(inq_read_seq_t) == 8, "a record is one 8-byte store");
 
 // ops that consume query AND reference (M = X: bits 0, 7, 8) and query only (I S: bits 1, 4)
 constexpr uint32_t kMatchOps = 0x181u, kInsertOps = 0x012u;
-
-__device__ __forceinline__ uint64_t row_inclusive_scan_u64(uint64_t x) {
-#define INQ_STEP(CTRL) x += (uint64_t)dpp_shr_zero<CTRL>((uint32_t)x) | (uint64_t)dpp_shr_zero<CTRL>((uint32_t)(x >> 32)) << 32;
-    INQ_STEP(DPP_ROW_SHR1)
-    INQ_STEP(DPP_ROW_SHR2)
-    INQ_STEP(DPP_ROW_SHR4)
-    INQ_STEP(DPP_ROW_SHR8)
-#undef INQ_STEP
-    return x;
-}
-__device__ __forceinline__ uint64_t row_last_u64(uint64_t x) { return (uint64_t)row_last((uint32_t)x) | (uint64_t)row_last((uint32_t)(x >> 32)) << 32; }
 
 __device__ __forceinline__ uint32_t load_le32(const uint8_t *p) {
     uint32_t v;
@@ -76,23 +66,8 @@ __global__ __launch_bounds__(256) void seq_window_kernel(SeqWindowArgs a) {
         const uint64_t p = base + threadIdx.x / kSeqRowLanes;
         const bool has = p < a.n_pairs;
 
-        // the pair's locus: the j with off[j] <= p < off[j + 1], sixteen probes a step.  The answer lies in [lo, hi); offsets that do
-        // not ascend end the search all the same, and what it found is checked below.
-        uint64_t lo = 0, hi = has ? a.n_loci : 0;
-        while (ballot64(hi - lo > 1u)) {
-            const uint64_t size = hi - lo, step = (size + kSeqRowLanes - 1u) / kSeqRowLanes, idx = lo + rl * step;
-            const bool below = size > 1u && idx < hi && a.locus_pair_off[idx + 1] <= p;
-            const uint32_t c = (uint32_t)__popc((uint32_t)(ballot64(below) >> row_shift) & 0xffffu);
-            if (size > 1u) {
-                if (c == 0u) {
-                    hi = lo + 1u;
-                } else {
-                    const uint64_t last = lo + (uint64_t)(c - 1u) * step;  // the last probe at or below p; it lies in front of hi
-                    lo = last + 1u;
-                    hi = last + step + 1u < hi ? last + step + 1u : hi;
-                }
-            }
-        }
+        // the pair's locus: the j with off[j] <= p < off[j + 1]; what the search found is checked here
+        const uint64_t lo = row_find_interval(a.locus_pair_off, a.n_loci, p, has, rl, row_shift);
         bool live = has && lo < a.n_loci && a.locus_pair_off[lo] <= p && p < a.locus_pair_off[lo + 1];
         int64_t x1 = 0, x2 = 0;  // start_ext and end_ext - 1
         if (live) {
@@ -213,7 +188,7 @@ __global__ __launch_bounds__(256) void seq_slice_kernel(SeqSliceArgs a) {
 }
 
 __global__ __launch_bounds__(256) void read_seq_record_kernel(ReadSeqArgs a) {
-    const uint64_t total = *a.n_kept < a.n_pairs ? *a.n_kept : a.n_pairs;  // the records the compaction wrote
+    const uint64_t total = kept_total(a.n_kept, a.n_pairs);
     for (uint64_t k = (uint64_t)blockIdx.x * kThreads + threadIdx.x; k < total; k += (uint64_t)gridDim.x * kThreads) {
         const uint64_t p = a.kept_pair[k];
         uint2 rec = make_uint2(0u, 0u);
@@ -222,23 +197,21 @@ __global__ __launch_bounds__(256) void read_seq_record_kernel(ReadSeqArgs a) {
     }
 }
 
-constexpr uint32_t kGridCap = 1u << 16;  // workgroups of a launch (capped_grid)
-
 }  // namespace
 
 void launch_seq_window(const SeqWindowArgs &a, hipStream_t s) {
     if (!a.n_pairs) return;
-    hipLaunchKernelGGL(seq_window_kernel, dim3(capped_grid((a.n_pairs + kSeqWindowTile - 1) / kSeqWindowTile, kGridCap)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(seq_window_kernel, dim3(capped_grid((a.n_pairs + kSeqWindowTile - 1) / kSeqWindowTile)), dim3(kThreads), 0, s, a);
 }
 
 void launch_seq_slice(const SeqSliceArgs &a, hipStream_t s) {
     if (!a.n_pairs) return;
-    hipLaunchKernelGGL(seq_slice_kernel, dim3(capped_grid((a.n_pairs + kSeqSliceTile - 1) / kSeqSliceTile, kGridCap)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(seq_slice_kernel, dim3(capped_grid((a.n_pairs + kSeqSliceTile - 1) / kSeqSliceTile)), dim3(kThreads), 0, s, a);
 }
 
 void launch_read_seq_records(const ReadSeqArgs &a, hipStream_t s) {
     if (!a.n_pairs) return;
-    hipLaunchKernelGGL(read_seq_record_kernel, dim3(capped_grid((a.n_pairs + kThreads - 1) / kThreads, kGridCap)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(read_seq_record_kernel, dim3(capped_grid((a.n_pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
 }
 
 }  // namespace inq

@@ -5,9 +5,6 @@
 
 namespace inq {
 
-// one workgroup per tile up to `cap` of them, the rest by stride
-inline uint32_t capped_grid(uint64_t tiles, uint32_t cap) { return (uint32_t)(tiles < cap ? tiles : cap); }
-
 // The kLanes lanes of a segment (this one is `sub`) store its len bytes at dst as aligned words of the DESTINATION: [0, head) up to the
 // destination's first word boundary, then n_words whole words strided over the lanes, then what is left (< 4 bytes).  The up to three
 // bytes in front of the first whole word and behind the last go one by one, since the word they lie in is shared with the neighbouring

@@ -1,7 +1,7 @@
-// wave_primitives.h — wave64 cross-lane building blocks for gfx950 (CDNA4).
+// wave_primitives.h — wave64 cross-lane building blocks for gfx950 (CDNA4): the wave and its four 16-lane DPP rows.
 //
-// Everything here is wave-wide (64 lanes) and uses DPP row operations directly
-// (`__builtin_amdgcn_update_dpp`), not LDS and not 32-wide shuffle idioms.
+// Everything here is wave-wide (64 lanes) or row-wide (16) and uses DPP row operations directly
+// (`__builtin_amdgcn_update_dpp`), not LDS and not 32-wide shuffle idioms.  At the end: how a launch that strides sizes its grid.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,6 +9,7 @@
 namespace inq {
 
 constexpr int kWave = 64;
+constexpr int kRowLanes = 16;  // lanes of one DPP row: one read stream of the row walk, one record or pair of the side kernels
 
 // DPP control words (GFX9 encoding)
 constexpr int DPP_ROW_SHR1 = 0x111;
@@ -25,17 +26,55 @@ template <int CTRL>
 __device__ __forceinline__ uint32_t dpp_shr_zero(uint32_t x) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, true);
 }
+// ... of a 64-bit value: two 32-bit DPP moves
+template <int CTRL>
+__device__ __forceinline__ uint64_t dpp_shr_zero_u64(uint64_t x) {
+    return (uint64_t)dpp_shr_zero<CTRL>((uint32_t)x) | (uint64_t)dpp_shr_zero<CTRL>((uint32_t)(x >> 32)) << 32;
+}
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ uint32_t dpp_bcast(uint32_t x) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROW_MASK, 0xf, false);
 }
 
-// Inclusive prefix sum over the 64 lanes, wrapping u32 arithmetic.  6 DPP adds.
-__device__ __forceinline__ uint32_t wave_inclusive_scan_u32(uint32_t x) {
+// Inclusive prefix sum inside each row, wrapping arithmetic.  4 DPP adds (8 moves for u64).
+__device__ __forceinline__ uint32_t row_inclusive_scan_u32(uint32_t x) {
     x += dpp_shr_zero<DPP_ROW_SHR1>(x);
     x += dpp_shr_zero<DPP_ROW_SHR2>(x);
     x += dpp_shr_zero<DPP_ROW_SHR4>(x);
     x += dpp_shr_zero<DPP_ROW_SHR8>(x);
+    return x;
+}
+__device__ __forceinline__ uint64_t row_inclusive_scan_u64(uint64_t x) {
+    x += dpp_shr_zero_u64<DPP_ROW_SHR1>(x);
+    x += dpp_shr_zero_u64<DPP_ROW_SHR2>(x);
+    x += dpp_shr_zero_u64<DPP_ROW_SHR4>(x);
+    x += dpp_shr_zero_u64<DPP_ROW_SHR8>(x);
+    return x;
+}
+// Lane 15 of each row to every lane of the row: ds_swizzle in bit-mask mode reads lane
+// ((l & 0x10) | 0x0f) of its 32-lane half.
+__device__ __forceinline__ uint32_t row_last(uint32_t x) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, 0x10 | (0x0f << 5)); }
+__device__ __forceinline__ uint64_t row_last_u64(uint64_t x) { return (uint64_t)row_last((uint32_t)x) | (uint64_t)row_last((uint32_t)(x >> 32)) << 32; }
+// Lane 15 of the row holds the OR / the maximum of its lanes
+__device__ __forceinline__ uint32_t row_or(uint32_t x) {
+    x |= dpp_shr_zero<DPP_ROW_SHR1>(x);
+    x |= dpp_shr_zero<DPP_ROW_SHR2>(x);
+    x |= dpp_shr_zero<DPP_ROW_SHR4>(x);
+    x |= dpp_shr_zero<DPP_ROW_SHR8>(x);
+    return x;
+}
+__device__ __forceinline__ uint64_t row_max_u64(uint64_t x) {
+    const auto larger = [](uint64_t o, uint64_t v) { return o > v ? o : v; };
+    x = larger(dpp_shr_zero_u64<DPP_ROW_SHR1>(x), x);
+    x = larger(dpp_shr_zero_u64<DPP_ROW_SHR2>(x), x);
+    x = larger(dpp_shr_zero_u64<DPP_ROW_SHR4>(x), x);
+    x = larger(dpp_shr_zero_u64<DPP_ROW_SHR8>(x), x);
+    return x;
+}
+
+// Inclusive prefix sum over the 64 lanes, wrapping u32 arithmetic.  6 DPP adds.
+__device__ __forceinline__ uint32_t wave_inclusive_scan_u32(uint32_t x) {
+    x = row_inclusive_scan_u32(x);
     x += dpp_bcast<DPP_ROW_BCAST15, 0xa>(x);  // row0 total -> row1, row2 total -> row3
     x += dpp_bcast<DPP_ROW_BCAST31, 0xc>(x);  // rows0-1 total -> rows 2,3
     return x;
@@ -56,5 +95,16 @@ __device__ __forceinline__ uint32_t writelane_u32(uint32_t old, uint32_t value, 
     return (uint32_t)inq_llvm_writelane_i32((int)value, l, (int)old);
 }
 __device__ __forceinline__ uint64_t ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
+// The sum over the 64 lanes, in every lane
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x) { return readlane_u32(wave_inclusive_scan_u32(x), kWave - 1); }
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t x) {
+    for (int d = 1; d < kWave; d *= 2) x += __shfl_xor((unsigned long long)x, d, kWave);
+    return x;
+}
+
+// A launch whose workgroups stride over their tiles: one workgroup per tile up to `cap` of them, the rest by stride
+constexpr uint32_t kGridCap = 1u << 16;
+inline uint32_t capped_grid(uint64_t tiles, uint32_t cap = kGridCap) { return (uint32_t)(tiles < cap ? tiles : cap); }
 
 }  // namespace inq

@@ -20,6 +20,25 @@ OPS = "MIDNSHP=X"
 M_OPS, IS_OPS, REF_OPS = (0, 7, 8), (1, 4), (0, 2, 3, 7, 8)
 
 
+# locus counts at which the kernels' sixteen-probe search for "the j with off[j] <= x < off[j + 1]" takes 1, 2, 3 and 4 steps
+# (n <= 16, <= 256, <= 4 096, above), on and next to each threshold
+SEARCH_LOCUS_COUNTS = [1, 2, 15, 16, 17, 255, 256, 257, 4096, 4097]
+
+
+def search_probe_loci(n):
+    """The loci of n that a test of that search fills, every other one staying empty: the first, the last, and one on each side of every
+    boundary between two probes of the first step (step = ceil(n / 16): the loci k step - 1, k step, k step + 1) and of the first and
+    the last boundary of the second step inside the interval behind probe 7.  Ascending, at most 53"""
+    step = -(-n // 16)
+    want = {0, n - 1}
+    for k in range(1, 16):
+        want |= {k * step - 1, k * step, k * step + 1}
+    lo2, step2 = 7 * step + 1, -(-step // 16)  # the second step's interval is [lo2, lo2 + step)
+    for m in (1, 15):
+        want |= {lo2 + m * step2 - 1, lo2 + m * step2, lo2 + m * step2 + 1}
+    return sorted(j for j in want if 0 <= j < n)
+
+
 def words_of(cigar):
     """[(op letter or code, len)] -> packed ops"""
     return np.array([(n << 4) | (OPS.index(o) if isinstance(o, str) else o) for o, n in cigar], dtype=np.uint32)

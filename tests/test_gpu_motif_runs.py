@@ -8,6 +8,7 @@ import pytest
 from inquistr_amd import batch as B
 from inquistr_amd import hipcall
 from tests import read_motif_case as rm
+from tests import read_seq_case as rs
 
 pytestmark = pytest.mark.gpu
 
@@ -161,6 +162,27 @@ def test_records_per_launch_and_loci(ctx, n):
             slices.append(codes)
             words.append(int(locus_words[j]))
     run(ctx, slices, words, kept_off, locus_words)
+
+
+@pytest.mark.parametrize("n_loci", rs.SEARCH_LOCUS_COUNTS)
+def test_locus_search_steps(ctx, n_loci):
+    """a record's locus where the sixteen-probe search takes one to four steps: one record in the first locus, the last and on each side
+    of the probes' boundaries (read_seq_case.search_probe_loci), every other locus empty.  A slice is a pure repeat of its own locus's
+    motif, which differs from both non-empty neighbours': under a neighbour's word the run comes out shorter"""
+    motifs = ["CAG", "A", "GGCCCC", "AAG", "CA", "ACGTACGTACGTAAA", "T"]
+    filled = rs.search_probe_loci(n_loci)
+    assert len(filled) <= 60 and filled[0] == 0 and filled[-1] == n_loci - 1
+    counts = np.zeros(n_loci, dtype=np.uint64)
+    counts[filled] = 1
+    kept_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+    locus_words = np.array([rm.literal_word(motifs[j % len(motifs)]) for j in range(n_loci)], dtype=np.uint64)
+    slices, words = [], []
+    for i, j in enumerate(filled):  # (by rank: neighbours among the filled loci never share a word, whatever lies between them)
+        locus_words[j] = rm.literal_word(motifs[i % len(motifs)])
+        slices.append(rm.repeat_codes(motifs[i % len(motifs)], 20 + i % 21, i % 3))
+        words.append(int(locus_words[j]))
+    got = run(ctx, slices, words, kept_off, locus_words)
+    assert all(g[:3] == (0, len(s), len(s)) for g, s in zip(got, slices))
 
 
 def test_a_locus_of_300_records(ctx):

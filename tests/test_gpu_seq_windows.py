@@ -149,6 +149,25 @@ def test_row_walk_cases(ctx, seed):
     _check(ctx, batch, l_seq, f"row_walk_case {seed} with l_seq")
 
 
+@pytest.mark.parametrize("n_loci", rs.SEARCH_LOCUS_COUNTS)
+def test_locus_search_steps(ctx, n_loci):
+    """a pair's locus where the sixteen-probe search takes one to four steps: one or two pairs in the first locus, the last and on each
+    side of the probes' boundaries (read_seq_case.search_probe_loci), every other locus empty.  All pairs are one read of 200M; every
+    locus has a window of its own inside it, so a pair that took a neighbour's locus shows in q_beg and in n_bases"""
+    bb = BatchBuilder(minlen=5, support=3, unphased=True)
+    read = bb.add_read(950, rs.words_of([("M", 200)]))
+    filled = rs.search_probe_loci(n_loci)
+    rank = {j: i for i, j in enumerate(filled)}
+    for j in range(n_loci):
+        start = START + 3 * j % 97
+        bb.add_locus(start, start + 10 + rank.get(j, 0) % 7, [read] * (1 + rank[j] % 2) if j in rank else [])
+    batch = bb.build()
+    assert batch.n_loci == n_loci and len(filled) <= batch.n_pairs <= 2 * len(filled)
+    q, n = _check(ctx, batch, np.array([200], dtype=np.uint32), f"{n_loci} loci")
+    first = batch.locus_pair_off[filled].astype(np.int64)  # a filled locus's first pair
+    assert n.min() >= 29 and (np.diff(q[first].astype(np.int64)) != 0).all(), "neighbours among the filled loci differ in q_beg"
+
+
 def test_empty_batches(ctx):
     bb = BatchBuilder(unphased=True)
     q, n = ctx.seq_windows(bb.build())
