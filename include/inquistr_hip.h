@@ -620,6 +620,42 @@ int inq_outlier_rows(inq_ctx_t *ctx, const float *values, const uint32_t *row_le
                      int method, uint32_t minsize, float zscore_cutoff, uint32_t mincluster, uint8_t *flags,
                      uint8_t *keep);
 
+/* ==== `inquistr assoc` (the reference's scripts/STR_regression.R): one regression per locus ====
+ * values: HOST, row-major [n_rows][2 * n_samples] f32, the H1 / H2 of a sample side by side as a combined .inq holds them
+ * (NaN = no call).  y[n_samples], cov[k][n_samples]: HOST f64, finite, shared by every row; binary y is 0 (group 1) or 1
+ * (group 2), anything else INQ_ERR_ARG.  n_samples <= 65 535 and k <= 6, else INQ_ERR_ARG before any launch.
+ * Per sample x = max / min / mean of the two haplotypes, one missing: the other, both: missing (that sample is left out of
+ * this row).  Row filters, in this order: call rate n / n_samples >= missing_cutoff, more than one distinct x, both groups
+ * there (binary), n > p = 2 + k.  Model [1, x, cov...]: binary = logistic regression by R's glm.fit iteration (start
+ * mu = (y + 0.5) / 2, at most 25 steps, |dev - dev_old| / (|dev| + 0.1) < 1e-8, no step halving; Wald z, p = erfc(|z| / sqrt 2)),
+ * continuous = least squares (t with n - p degrees of freedom, two-sided Student t).  Only x's coefficient is reported.
+ * A pivot of the Cholesky factor of the centred normal equations at or below 1e-11 x their largest diagonal: SINGULAR.
+ *
+ * inq_assoc_row_t is 88 bytes: beta 0, se 8, stat 16, p 24, mean_all 32, mean_g1 40, mean_g2 48, min_x 56, max_x 64, n 72,
+ * n_g1 76, n_g2 80, status 84, n_iter 85, pad 86.  n, the means and min / max are over the samples with an x (NaN without
+ * one); the group fields are 0 / NaN for a continuous outcome; beta, se, stat, p are NaN unless status is OK or
+ * NOT_CONVERGED (which carries the last iterate); n_iter = glm.fit's iteration count (0: continuous, or no fit). */
+#define INQ_ASSOC_BINARY 0
+#define INQ_ASSOC_CONTINUOUS 1
+#define INQ_ASSOC_MAX 0
+#define INQ_ASSOC_MIN 1
+#define INQ_ASSOC_MEAN 2
+#define INQ_ASSOC_ROW_OK 0
+#define INQ_ASSOC_ROW_LOW_CALL_RATE 1
+#define INQ_ASSOC_ROW_CONSTANT 2
+#define INQ_ASSOC_ROW_ONE_GROUP 3
+#define INQ_ASSOC_ROW_TOO_FEW 4
+#define INQ_ASSOC_ROW_SINGULAR 5
+#define INQ_ASSOC_ROW_NOT_CONVERGED 6
+typedef struct inq_assoc_row {
+    double beta, se, stat, p, mean_all, mean_g1, mean_g2, min_x, max_x;
+    uint32_t n, n_g1, n_g2;
+    uint8_t status, n_iter;
+    uint8_t pad[2];
+} inq_assoc_row_t;
+int inq_assoc_rows(inq_ctx_t *ctx, const float *values, uint64_t n_rows, uint32_t n_samples, const double *y,
+                   const double *cov, uint32_t k, int outcome, int str_mode, double missing_cutoff, inq_assoc_row_t *rows);
+
 const char *inq_strerror(int code);
 const char *inq_backend_name(const inq_ctx_t *ctx); /* "hip:gfx950:<device name>" */
 const char *inq_last_error(const inq_ctx_t *ctx);   /* detail of the last INQ_ERR_HIP */

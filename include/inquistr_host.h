@@ -317,6 +317,35 @@ typedef struct inq_outlier_args {
 } inq_outlier_args_t;
 int inq_outlier(const inq_outlier_args_t *args, int out_fd, char *errbuf, size_t errcap);
 
+/* `inquistr assoc` (the reference's scripts/STR_regression.R): one regression per locus of a combined .inq (plain
+ * or gzip) of a sample's phenotype on its repeat length.  phenocovar: a tab-separated file with a header whose first column is the
+ * sample identifier.  Analysed are the samples of the combined file that the phenotype file lists with a usable phenotype (binary:
+ * one of the two values of binary_order "A,B", A = group 1 = 0; continuous: a finite number) and finite numbers in every named
+ * covariate.  The arithmetic runs on the GPU (inq_assoc_rows of include/inquistr_hip.h).  Prints the tested loci by ascending p in
+ * the R script's columns; all_rows appends the others with a `status` column.  Returns 0, 1 (no GPU) or 101 where the input is
+ * wrong (a file missing, binary without binary_order, a named column the file lacks, fewer than 2 samples left, a number of the
+ * combined file that does not parse, ...). */
+typedef struct inq_assoc_args {
+    const char *combined;     /* positional                                                     */
+    const char *phenocovar;   /* --phenocovar                                                   */
+    const char *phenotype;    /* --phenotype: a column of phenocovar                            */
+    const char *binary_order; /* --binary-order "A,B"; NULL if absent                           */
+    const char *covariates;   /* --covariates "c1,c2" (at most 6); NULL if absent               */
+    const char *chr;          /* --chr: only loci of this chromosome; NULL = all                */
+    int64_t chr_begin;        /* --chr-begin / --chr-end: only loci with begin >= chr_begin and */
+    int64_t chr_end;          /*   end <= chr_end; -1 = not given (both or neither, with chr)   */
+    double missing_cutoff;    /* --missing-cutoff, default 0.8                                  */
+    int32_t outcome;          /* --outcome: INQ_ASSOC_BINARY / INQ_ASSOC_CONTINUOUS             */
+    int32_t str_mode;         /* --str-mode: INQ_ASSOC_MAX (default) / _MIN / _MEAN             */
+    int32_t all_rows;         /* --all-rows                                                     */
+    int32_t device;           /* HIP device ordinal                                             */
+} inq_assoc_args_t;
+int inq_assoc(const inq_assoc_args_t *args, int out_fd, char *errbuf, size_t errcap);
+/* The samples that command would analyse, without a GPU: their names joined by commas into names (cut to names_cap), *n_samples and
+ * *k, and - where y / cov are given and cap >= *n_samples - y[i] and cov[j * *n_samples + i].  Same return values, never 1. */
+int inq_assoc_samples(const inq_assoc_args_t *args, char *names, size_t names_cap, double *y, double *cov, size_t cap, uint32_t *n_samples,
+                      uint32_t *k, char *errbuf, size_t errcap);
+
 /* ---- text side (src/call.rs:27-65, 91-101) ---- */
 size_t inq_host_format_f64(double v, char *buf, size_t cap);
 size_t inq_host_format_row(const char *chrom, uint32_t start, uint32_t end, double p1, double p2, char *buf, size_t cap);

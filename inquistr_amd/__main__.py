@@ -1,5 +1,6 @@
-"""`python -m inquistr_amd call|combine|outlier ...` — forwards to the native CLI (inquistr_amd/lib/inquistr), which is
-the program a user of the reference would run in place of `inquiSTR call` / `inquiSTR combine` / `inquiSTR outlier`."""
+"""`python -m inquistr_amd call|combine|outlier|assoc ...` — forwards to the native CLI (inquistr_amd/lib/inquistr), which is
+the program a user of the reference would run in place of `inquiSTR call` / `inquiSTR combine` / `inquiSTR outlier`, and of its
+scripts/STR_regression.R (`assoc`)."""
 import os
 import subprocess
 import sys

@@ -96,6 +96,8 @@ HOST_ABI_SYMBOLS = (
     "inq_spans_next",
     "inq_spans_close",
     "inq_outlier",
+    "inq_assoc",
+    "inq_assoc_samples",
 )
 
 
@@ -144,6 +146,25 @@ class OutlierArgsC(C.Structure):
         ("subset_file", C.c_char_p),
         ("device", C.c_int32),
         ("reserved", C.c_int32),
+    ]
+
+
+class AssocArgsC(C.Structure):
+    """inq_assoc_args_t"""
+    _fields_ = [
+        ("combined", C.c_char_p),
+        ("phenocovar", C.c_char_p),
+        ("phenotype", C.c_char_p),
+        ("binary_order", C.c_char_p),
+        ("covariates", C.c_char_p),
+        ("chr", C.c_char_p),
+        ("chr_begin", C.c_int64),
+        ("chr_end", C.c_int64),
+        ("missing_cutoff", C.c_double),
+        ("outcome", C.c_int32),
+        ("str_mode", C.c_int32),
+        ("all_rows", C.c_int32),
+        ("device", C.c_int32),
     ]
 
 
@@ -325,6 +346,11 @@ def load():
         L.inq_spans_close.argtypes = [vp]
         L.inq_outlier.restype = C.c_int
         L.inq_outlier.argtypes = [C.POINTER(OutlierArgsC), C.c_int, C.c_char_p, C.c_size_t]
+        L.inq_assoc.restype = C.c_int
+        L.inq_assoc.argtypes = [C.POINTER(AssocArgsC), C.c_int, C.c_char_p, C.c_size_t]
+        L.inq_assoc_samples.restype = C.c_int
+        L.inq_assoc_samples.argtypes = [C.POINTER(AssocArgsC), C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -664,6 +690,50 @@ def outlier(combined, minsize: int = 10, zscore: float = 3.0, method: str = "zsc
     out = sys.stdout if out is None else out
     out.flush()
     _checked(L.inq_outlier, C.byref(a), out.fileno())
+
+
+def _assoc_args(combined, phenocovar, phenotype, outcome, binary_order, covariates, str_mode, missing_cutoff, chr, chr_begin, chr_end,
+                all_rows, device) -> AssocArgsC:
+    def text(v):
+        return None if v is None else (",".join(v) if isinstance(v, (list, tuple)) else str(v)).encode()
+
+    a = AssocArgsC()
+    a.combined, a.phenocovar, a.phenotype = os.fspath(combined).encode(), os.fspath(phenocovar).encode(), phenotype.encode()
+    a.binary_order, a.covariates, a.chr = text(binary_order), text(covariates), text(chr)
+    a.chr_begin = -1 if chr_begin is None else int(chr_begin)
+    a.chr_end = -1 if chr_end is None else int(chr_end)
+    a.missing_cutoff = float(missing_cutoff)
+    a.outcome = {"binary": 0, "continuous": 1}[outcome]
+    a.str_mode = {"max": 0, "min": 1, "mean": 2}[str_mode]
+    a.all_rows, a.device = int(bool(all_rows)), device
+    return a
+
+
+def assoc(combined, phenocovar, phenotype: str, outcome: str, binary_order=None, covariates=None, str_mode: str = "max",
+          missing_cutoff: float = 0.8, chr: Optional[str] = None, chr_begin: Optional[int] = None, chr_end: Optional[int] = None,
+          all_rows: bool = False, out=None, device: int = 0) -> None:
+    """`inquistr assoc`: one regression per locus of a combined .inq of the phenotype on the repeat length (the reference's
+    scripts/STR_regression.R, on the GPU), the tested loci by ascending p-value.  binary_order / covariates: "A,B" or a list.
+    Raises CallError (101 where the input is wrong, 1 without a GPU)."""
+    L = load()
+    a = _assoc_args(combined, phenocovar, phenotype, outcome, binary_order, covariates, str_mode, missing_cutoff, chr, chr_begin, chr_end,
+                    all_rows, device)
+    out = sys.stdout if out is None else out
+    out.flush()
+    _checked(L.inq_assoc, C.byref(a), out.fileno())
+
+
+def assoc_samples(combined, phenocovar, phenotype: str, outcome: str, binary_order=None, covariates=None):
+    """The samples `assoc` would analyse, without a GPU: (names, y f64 [n], cov f64 [k, n])."""
+    L = load()
+    a = _assoc_args(combined, phenocovar, phenotype, outcome, binary_order, covariates, "max", 0.8, None, None, None, False, 0)
+    cap = 65535
+    names = C.create_string_buffer(1 << 22)
+    y, cov = np.zeros(cap), np.zeros(6 * cap)
+    n, k = C.c_uint32(0), C.c_uint32(0)
+    _checked(L.inq_assoc_samples, C.byref(a), names, len(names), y.ctypes.data, cov.ctypes.data, cap, C.byref(n), C.byref(k))
+    got = names.value.decode()
+    return (got.split(",") if got else []), y[: n.value].copy(), cov[: k.value * n.value].reshape(k.value, n.value).copy()
 
 
 class FrontEnd(_Handle):

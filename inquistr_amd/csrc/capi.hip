@@ -600,6 +600,69 @@ int inq_outlier_rows(inq_ctx_t *c, const float *values, const uint32_t *row_len,
     return guarded([&] { return outlier_rows_impl(c, values, row_len, n_rows, stride, method, minsize, zscore_cutoff, mincluster, flags, keep); });
 }
 
+static int assoc_rows_impl(inq_ctx_t *c, const float *values, uint64_t n_rows, uint32_t n_samples, const double *y, const double *cov,
+                           uint32_t k, int outcome, int str_mode, double missing_cutoff, inq_assoc_row_t *rows) {
+    if (!c || (outcome != INQ_ASSOC_BINARY && outcome != INQ_ASSOC_CONTINUOUS)) return INQ_ERR_ARG;
+    if (str_mode != INQ_ASSOC_MAX && str_mode != INQ_ASSOC_MIN && str_mode != INQ_ASSOC_MEAN) return INQ_ERR_ARG;
+    if (n_samples > kAssocMaxSamples || k > kAssocMaxCov || missing_cutoff != missing_cutoff) return INQ_ERR_ARG;
+    if (n_rows && (!rows || (n_samples && (!values || !y || (k && !cov))))) return INQ_ERR_ARG;
+    if (outcome == INQ_ASSOC_BINARY && n_rows)
+        for (uint32_t i = 0; i < n_samples; ++i)
+            if (y[i] != 0.0 && y[i] != 1.0) return INQ_ERR_ARG;
+    if (!n_rows) return INQ_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    // 1 / B(df / 2, 1 / 2) of the Student-t p-value for every df a row can have: c[df + 2] = c[df] (df + 1) / df from c[1] = 1 / pi,
+    // c[2] = 1 / 2 (no lgamma: a difference of two of its values near 600 loses three digits of the p-value)
+    std::vector<double> tcoef;
+    if (outcome == INQ_ASSOC_CONTINUOUS) {
+        tcoef.assign((size_t)n_samples + 3, 0.0);
+        tcoef[1] = 0.31830988618379067154, tcoef[2] = 0.5;
+        for (uint32_t df = 1; df + 2 <= n_samples; ++df) tcoef[df + 2] = tcoef[df] * (double)(df + 1) / (double)df;
+        tcoef.resize((size_t)n_samples + 1);
+    }
+    const size_t row_bytes = (size_t)n_samples * 8;
+    uint64_t tile = c->assoc_tile_rows ? c->assoc_tile_rows : std::max<uint64_t>(1, (256ull << 20) / std::max<size_t>(row_bytes, 1));
+    tile = std::min<uint64_t>({tile, n_rows, 1ull << 30});
+    int rc;
+    if ((rc = upload(c, s, {{&c->ay, y, (size_t)n_samples * 8}, {&c->acov, cov, (size_t)k * n_samples * 8},
+                            {&c->atcoef, tcoef.data(), tcoef.size() * 8}})) != INQ_OK)
+        return rc;
+    if ((rc = ensure(c, c->avalues, tile * row_bytes)) != INQ_OK) return rc;
+    if ((rc = ensure(c, c->arows, tile * sizeof(inq_assoc_row_t))) != INQ_OK) return rc;
+    AssocArgs a;
+    a.values = (const float *)c->avalues.p;
+    a.n_samples = n_samples;
+    a.k = k;
+    a.y = (const double *)c->ay.p;
+    a.cov = (const double *)c->acov.p;
+    a.tcoef = (const double *)c->atcoef.p;
+    a.outcome = outcome, a.str_mode = str_mode;
+    a.missing_cutoff = missing_cutoff;
+    a.rows = (inq_assoc_row_t *)c->arows.p;
+    // tile by tile on one stream: a tile's upload waits for the launch that read the buffer before it
+    for (uint64_t r0 = 0; r0 < n_rows; r0 += tile) {
+        a.n_rows = std::min<uint64_t>(tile, n_rows - r0);
+        if (row_bytes) HIP_TRY(c, hipMemcpyAsync(c->avalues.p, values + r0 * 2 * n_samples, a.n_rows * row_bytes, hipMemcpyHostToDevice, s));
+        EvTriple *ev;
+        if ((rc = timing_begin(c, s, &ev)) != INQ_OK) return rc;
+        launch_assoc(a, s);
+        HIP_TRY(c, hipGetLastError());
+        if (ev) {
+            HIP_TRY(c, hipEventRecord(ev->e1, s));
+            HIP_TRY(c, hipEventRecord(ev->e2, s));
+        }
+        HIP_TRY(c, hipMemcpyAsync(rows + r0, c->arows.p, a.n_rows * sizeof(inq_assoc_row_t), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return INQ_OK;
+}
+
+int inq_assoc_rows(inq_ctx_t *c, const float *values, uint64_t n_rows, uint32_t n_samples, const double *y, const double *cov, uint32_t k,
+                   int outcome, int str_mode, double missing_cutoff, inq_assoc_row_t *rows) {
+    return guarded([&] { return assoc_rows_impl(c, values, n_rows, n_samples, y, cov, k, outcome, str_mode, missing_cutoff, rows); });
+}
+
 int inq_ctx_timing_enable(inq_ctx_t *c, int on) {
     if (!c) return INQ_ERR_ARG;
     c->timing = on != 0;
@@ -720,6 +783,11 @@ int inq_ctx_set_option(inq_ctx_t *c, const char *key, int64_t value) {
     }
     if (std::strcmp(key, "outlier_tile") == 0) {
         c->outlier_tile = value != 0;
+        return INQ_OK;
+    }
+    if (std::strcmp(key, "assoc_tile_rows") == 0) {
+        if (value < 0) return INQ_ERR_ARG;
+        c->assoc_tile_rows = (uint64_t)value;
         return INQ_OK;
     }
     if (std::strcmp(key, "blocking_sync") == 0) {

@@ -134,4 +134,21 @@ constexpr uint32_t kOutlierTileMaxStride = 256;
 inline uint64_t outlier_rows_padded(uint64_t n_rows) { return (n_rows + 63) / 64 * 64; }
 void launch_outlier(const OutlierArgs &a, int method, float *transposed, hipStream_t s, bool use_tile = true);
 
+// assoc.hip
+struct AssocArgs {
+    const float *values;  // [n_rows][2 * n_samples], H1 / H2 of a sample side by side
+    uint64_t n_rows;
+    uint32_t n_samples;
+    uint32_t k;           // covariates, <= kAssocMaxCov
+    const double *y;      // [n_samples]; binary: 0 or 1
+    const double *cov;    // [k][n_samples]
+    const double *tcoef;  // continuous: [n_samples + 1], tcoef[df] = Gamma((df + 1) / 2) / (Gamma(df / 2) sqrt(pi)); binary: not read
+    int outcome, str_mode;
+    double missing_cutoff;
+    inq_assoc_row_t *rows;  // [n_rows]
+};
+constexpr uint32_t kAssocMaxCov = 6, kAssocMaxSamples = 65535;
+// one wave per row, four rows per workgroup, one instantiation per number of columns p = 2 + k and outcome
+void launch_assoc(const AssocArgs &a, hipStream_t s);
+
 }  // namespace inq

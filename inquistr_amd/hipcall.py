@@ -99,6 +99,7 @@ ABI_SYMBOLS = (
     "inq_read_motif_tile",
     "inq_call_flush_locus_motifs",
     "inq_locus_motifs_find",
+    "inq_assoc_rows",
 )
 
 
@@ -112,6 +113,22 @@ BGZF_BLOCK_DTYPE = np.dtype([("comp_off", "<u8"), ("comp_len", "<u4"), ("isize",
 
 
 ANCHOR_SEGMENT_END = 1 << 63
+
+
+class AssocRowC(C.Structure):
+    """inq_assoc_row_t"""
+
+    _fields_ = [("beta", C.c_double), ("se", C.c_double), ("stat", C.c_double), ("p", C.c_double), ("mean_all", C.c_double),
+                ("mean_g1", C.c_double), ("mean_g2", C.c_double), ("min_x", C.c_double), ("max_x", C.c_double), ("n", C.c_uint32),
+                ("n_g1", C.c_uint32), ("n_g2", C.c_uint32), ("status", C.c_uint8), ("n_iter", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+ASSOC_ROW_DTYPE = np.dtype([("beta", "<f8"), ("se", "<f8"), ("stat", "<f8"), ("p", "<f8"), ("mean_all", "<f8"), ("mean_g1", "<f8"),
+                            ("mean_g2", "<f8"), ("min_x", "<f8"), ("max_x", "<f8"), ("n", "<u4"), ("n_g1", "<u4"), ("n_g2", "<u4"),
+                            ("status", "u1"), ("n_iter", "u1"), ("pad", "u1", (2,))])
+ASSOC_OUTCOMES = {"binary": 0, "continuous": 1}
+ASSOC_MODES = {"max": 0, "min": 1, "mean": 2}
+ASSOC_STATUS = ("OK", "LOW_CALL_RATE", "CONSTANT", "ONE_GROUP", "TOO_FEW", "SINGULAR", "NOT_CONVERGED")
 
 
 class SpanC(C.Structure):
@@ -419,6 +436,8 @@ def load(path: Optional[str] = None):
     L.inq_outlier_rows.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_float, C.c_uint32, vp, vp]
     L.inq_span_fetch_batch.restype = C.c_int
     L.inq_span_fetch_batch.argtypes = [vp, vp, vp, vp, vp]
+    L.inq_assoc_rows.restype = C.c_int
+    L.inq_assoc_rows.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_double, vp]
     if path is None:
         _lib = L
     return L
@@ -879,6 +898,23 @@ class Context:
         if rc != INQ_OK and check:
             self._raise(rc)
         return rc, flags, keep
+
+    def assoc_rows(self, values: np.ndarray, y: np.ndarray, cov: Optional[np.ndarray] = None, outcome: str = "binary",
+                   str_mode: str = "max", missing_cutoff: float = 0.8) -> np.ndarray:
+        """inq_assoc_rows: values f32 [n_rows, 2 * n_samples] (H1 / H2 of a sample side by side), y f64 [n_samples], cov f64
+        [k, n_samples] or None; returns the rows as a structured array (ASSOC_ROW_DTYPE)."""
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        n_samples = len(y)
+        cov = np.zeros((0, n_samples)) if cov is None else np.ascontiguousarray(cov, dtype=np.float64).reshape(-1, n_samples)
+        if values.ndim != 2 or values.shape[1] != 2 * n_samples:
+            raise ValueError("values must be [n_rows, 2 * len(y)]")
+        rows = np.zeros(values.shape[0], dtype=ASSOC_ROW_DTYPE)
+        rc = self._L.inq_assoc_rows(self._h, values.ctypes.data, values.shape[0], n_samples, y.ctypes.data, cov.ctypes.data, cov.shape[0],
+                                    ASSOC_OUTCOMES[outcome], ASSOC_MODES[str_mode], missing_cutoff, rows.ctypes.data)
+        if rc != INQ_OK:
+            self._raise(rc)
+        return rows
 
     def status(self) -> Tuple[int, int]:
         ties = C.c_uint64(0)

@@ -19,6 +19,7 @@ struct HostApi {
     decltype(&::inq_host_ctx_option) ctx_option;
     decltype(&::inq_combine) combine;
     decltype(&::inq_outlier) outlier;
+    decltype(&::inq_assoc) assoc;
     decltype(&::inq_host_sample_name) host_sample_name;
     decltype(&::inq_session_open) session_open;
     decltype(&::inq_session_call_many) session_call_many;
@@ -57,6 +58,7 @@ inline const HostApi &host_api() {
         a.ctx_option = reinterpret_cast<decltype(a.ctx_option)>(sym("inq_host_ctx_option"));
         a.combine = reinterpret_cast<decltype(a.combine)>(sym("inq_combine"));
         a.outlier = reinterpret_cast<decltype(a.outlier)>(sym("inq_outlier"));
+        a.assoc = reinterpret_cast<decltype(a.assoc)>(sym("inq_assoc"));
         a.host_sample_name = reinterpret_cast<decltype(a.host_sample_name)>(sym("inq_host_sample_name"));
         a.session_open = reinterpret_cast<decltype(a.session_open)>(sym("inq_session_open"));
         a.session_call_many = reinterpret_cast<decltype(a.session_call_many)>(sym("inq_session_call_many"));

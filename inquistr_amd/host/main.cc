@@ -125,6 +125,81 @@ int main(int argc, char **argv) {
         ::setenv("INQ_FAST_EXIT", "1", 0);  // this process ends with the command: the device context is left to the operating system
         return leave(inq::host_api().outlier(&o, 1, err, sizeof err), err);
     }
+    if (argc >= 2 && std::strcmp(argv[1], "assoc") == 0) {
+        // Not a subcommand of the reference's binary: its scripts/STR_regression.R (one glm() per locus), the regressions on the device
+        static const char *const kUsage =
+            "Usage: inquistr assoc <COMBINED> --phenocovar <FILE> --phenotype <COL> --outcome <binary|continuous>\n"
+            "                      [--binary-order <A,B>] [--covariates <c1,c2,...>] [--str-mode <max|min|mean>]\n"
+            "                      [--missing-cutoff <0.8>] [--chr <CHR> [--chr-begin <N> --chr-end <N>]] [--all-rows] [--device <N>]\n";
+        inq_assoc_args_t o;
+        std::memset(&o, 0, sizeof o);
+        o.missing_cutoff = 0.8;
+        o.outcome = -1;
+        o.str_mode = INQ_ASSOC_MAX;
+        o.chr_begin = o.chr_end = -1;
+        auto number = [&](const char *s, const char *flag) {
+            char *e = nullptr;
+            const double v = std::strtod(s, &e);
+            if (!*s || *e) {
+                std::fprintf(stderr, "error: invalid value '%s' for '%s'\n", s, flag);
+                std::exit(2);
+            }
+            return v;
+        };
+        for (int i = 2; i < argc; ++i) {
+            std::string s = argv[i];
+            auto eq = s.find('=');
+            std::string key = (s.size() > 2 && s[0] == '-' && s[1] == '-' && eq != std::string::npos) ? s.substr(0, eq) : s;
+            const char *inl = (key.size() != s.size()) ? argv[i] + eq + 1 : nullptr;
+            auto val = [&] { return need(argc, argv, i, inl); };
+            if (key == "--phenocovar") o.phenocovar = val();
+            else if (key == "--phenotype") o.phenotype = val();
+            else if (key == "--binary-order") o.binary_order = val();
+            else if (key == "--covariates") o.covariates = val();
+            else if (key == "--chr") o.chr = val();
+            else if (key == "--chr-begin") o.chr_begin = (int64_t)number(val(), "--chr-begin <N>");
+            else if (key == "--chr-end") o.chr_end = (int64_t)number(val(), "--chr-end <N>");
+            else if (key == "--missing-cutoff") o.missing_cutoff = number(val(), "--missing-cutoff <CUTOFF>");
+            else if (key == "--all-rows") o.all_rows = 1;
+            else if (key == "--device") o.device = (int32_t)number(val(), "--device <N>");
+            else if (key == "--outcome") {
+                const std::string m = val();
+                if (m == "binary") o.outcome = INQ_ASSOC_BINARY;
+                else if (m == "continuous") o.outcome = INQ_ASSOC_CONTINUOUS;
+                else {
+                    std::fprintf(stderr, "error: invalid value '%s' for '--outcome <OUTCOME>'\n  [possible values: binary, continuous]\n", m.c_str());
+                    return 2;
+                }
+            } else if (key == "--str-mode") {
+                const std::string m = val();
+                if (m == "max") o.str_mode = INQ_ASSOC_MAX;
+                else if (m == "min") o.str_mode = INQ_ASSOC_MIN;
+                else if (m == "mean") o.str_mode = INQ_ASSOC_MEAN;
+                else {
+                    std::fprintf(stderr, "error: invalid value '%s' for '--str-mode <MODE>'\n  [possible values: max, min, mean]\n", m.c_str());
+                    return 2;
+                }
+            } else if (key == "-h" || key == "--help") {
+                std::fputs(kUsage, stdout);
+                return 0;
+            } else if (!s.empty() && s[0] == '-' && s.size() > 1) {
+                std::fprintf(stderr, "error: unexpected argument '%s' found\n", s.c_str());
+                return 2;
+            } else if (!o.combined) o.combined = argv[i];
+            else {
+                std::fprintf(stderr, "error: unexpected argument '%s' found\n", s.c_str());
+                return 2;
+            }
+        }
+        if (!o.combined || !o.phenocovar || !o.phenotype || o.outcome < 0) {
+            std::fputs("error: the following required arguments were not provided:\n  <COMBINED> --phenocovar <FILE> --phenotype <COL> --outcome <OUTCOME>\n\n", stderr);
+            std::fputs(kUsage, stderr);
+            return 2;
+        }
+        char err[1024] = {0};
+        ::setenv("INQ_FAST_EXIT", "1", 0);  // this process ends with the command: the device context is left to the operating system
+        return leave(inq::host_api().assoc(&o, 1, err, sizeof err), err);
+    }
     if (argc >= 2 && std::strcmp(argv[1], "cohort") == 0) {
         // Not a subcommand of the reference: the loop a user writes around `inquiSTR call` for a cohort (one call per BAM with the
         // same targets, then `combine`), run in ONE process so that the HIP runtime starts once.  Every <out-dir>/<sample>.inq is
@@ -235,7 +310,7 @@ int main(int argc, char **argv) {
             std::puts("Tool to genotype STRs from long reads (MI355X build: `call` only)\n\nUsage: inquistr call [OPTIONS] <BAM>");
             return 0;
         }
-        std::fputs("error: this build provides the `call`, `combine`, `outlier` (and `cohort`: many `call`s in one process; `serve`: a process that keeps the device context for `call`s with INQ_SERVER set) subcommands only\n\nUsage: inquistr call [OPTIONS] <BAM>\n", stderr);
+        std::fputs("error: this build provides the `call`, `combine`, `outlier`, `assoc` (and `cohort`: many `call`s in one process; `serve`: a process that keeps the device context for `call`s with INQ_SERVER set) subcommands only\n\nUsage: inquistr call [OPTIONS] <BAM>\n", stderr);
         return 2;
     }
     if (argc == 2) {  // arg_required_else_help
