@@ -656,6 +656,39 @@ typedef struct inq_assoc_row {
 int inq_assoc_rows(inq_ctx_t *ctx, const float *values, uint64_t n_rows, uint32_t n_samples, const double *y,
                    const double *cov, uint32_t k, int outcome, int str_mode, double missing_cutoff, inq_assoc_row_t *rows);
 
+/* ---- Firth's penalised logistic regression for the rows whose maximum-likelihood fit breaks down ----
+ * inq_assoc_rows for a binary outcome (rows[] gets the same bytes), and behind it, on the device, Firth's fit of the rows that
+ * `when` selects: ALWAYS = every row whose status is OK or NOT_CONVERGED; FALLBACK = of those the NOT_CONVERGED ones and the ones
+ * whose ordinary fit left min over the kept samples of min(mu, 1 - mu) below 1e-6 at its last pass (separation that stopped on the
+ * deviance; the bound is the context option "assoc_firth_mu_ppb", in units of 1e-9, default 1000).  Any other `when`: INQ_ERR_ARG
+ * before any launch.  Limits, tiling ("assoc_tile_rows") and the other argument errors are those of inq_assoc_rows.
+ * The model: columns, centring, x, rank tolerance and the mu clamp of the ordinary fit.  With pi = 1 / (1 + exp(-eta)),
+ * w = pi (1 - pi), I = X'WX: penalised log-likelihood l* = sum [y log pi + (1 - y) log(1 - pi)] + 1/2 log det I, hat values
+ * h_i = w_i x_i' I^-1 x_i, modified score U* = sum (y - pi + h (1/2 - pi)) x_i.  From beta = 0: evaluate I, U*, l* at beta and
+ * delta = I^-1 U* over the free coefficients; stop, OK, when max_j |delta_j| sqrt(I_jj) < 1e-9 (beta as it stands is the
+ * estimate); else scale delta to max_j |delta_j| <= 5, beta += delta.  No step halving.  A non-finite l*, or no stop at the
+ * evaluation after 100 steps: NOT_CONVERGED with the last iterate.  A failed pivot at any evaluation: SINGULAR, numbers NaN.
+ * Full fit: all p coefficients free.  Null fit: beta_x held at 0, the others free, h and log det I from the full p x p matrix.
+ * beta = beta_x of the full fit, se = sqrt((I^-1)_xx) there, chi2 = max(0, 2 (pll_full - pll_null)), p = erfc(sqrt(chi2 / 2))
+ * (one degree of freedom); n_iter_* = steps taken.  The row's status is the worse of its two fits'.
+ *
+ * inq_assoc_firth_row_t is 56 bytes: beta 0, se 8, chi2 16, p 24, pll_full 32, pll_null 40, n_iter_full 48, n_iter_null 49,
+ * status 50, pad 51.  A row that is not fitted: NOT_FITTED, numbers NaN, counts 0. */
+#define INQ_ASSOC_FIRTH_FALLBACK 1
+#define INQ_ASSOC_FIRTH_ALWAYS 2
+#define INQ_ASSOC_FIRTH_ROW_OK 0
+#define INQ_ASSOC_FIRTH_ROW_NOT_FITTED 1
+#define INQ_ASSOC_FIRTH_ROW_SINGULAR 2
+#define INQ_ASSOC_FIRTH_ROW_NOT_CONVERGED 3
+typedef struct inq_assoc_firth_row {
+    double beta, se, chi2, p, pll_full, pll_null;
+    uint8_t n_iter_full, n_iter_null, status;
+    uint8_t pad[5];
+} inq_assoc_firth_row_t;
+int inq_assoc_rows_firth(inq_ctx_t *ctx, const float *values, uint64_t n_rows, uint32_t n_samples, const double *y,
+                         const double *cov, uint32_t k, int str_mode, double missing_cutoff, int when, inq_assoc_row_t *rows,
+                         inq_assoc_firth_row_t *firth);
+
 const char *inq_strerror(int code);
 const char *inq_backend_name(const inq_ctx_t *ctx); /* "hip:gfx950:<device name>" */
 const char *inq_last_error(const inq_ctx_t *ctx);   /* detail of the last INQ_ERR_HIP */

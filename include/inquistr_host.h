@@ -324,7 +324,15 @@ int inq_outlier(const inq_outlier_args_t *args, int out_fd, char *errbuf, size_t
  * covariate.  The arithmetic runs on the GPU (inq_assoc_rows of include/inquistr_hip.h).  Prints the tested loci by ascending p in
  * the R script's columns; all_rows appends the others with a `status` column.  Returns 0, 1 (no GPU) or 101 where the input is
  * wrong (a file missing, binary without binary_order, a named column the file lacks, fewer than 2 samples left, a number of the
- * combined file that does not parse, ...). */
+ * combined file that does not parse, ...).
+ * firth (binary only; with continuous, or another value: 101): Firth's penalised logistic regression (inq_assoc_rows_firth) for the
+ * rows whose ordinary fit broke down under separation (FALLBACK) or for every fitted row (ALWAYS).  A row whose Firth fit is OK
+ * prints OR, its interval, OR_stdErr and Pvalue (the penalised likelihood-ratio test's) from that fit; every other row prints what
+ * it prints without the flag.  A last column `method` (glm / firth) is appended to every line, and the order is by the printed p.
+ * With INQ_HOST_FIRTH_NO the output is byte for byte that of a struct without the field. */
+#define INQ_HOST_FIRTH_NO 0
+#define INQ_HOST_FIRTH_FALLBACK 1
+#define INQ_HOST_FIRTH_ALWAYS 2
 typedef struct inq_assoc_args {
     const char *combined;     /* positional                                                     */
     const char *phenocovar;   /* --phenocovar                                                   */
@@ -339,6 +347,8 @@ typedef struct inq_assoc_args {
     int32_t str_mode;         /* --str-mode: INQ_ASSOC_MAX (default) / _MIN / _MEAN             */
     int32_t all_rows;         /* --all-rows                                                     */
     int32_t device;           /* HIP device ordinal                                             */
+    int32_t firth;            /* --firth: INQ_HOST_FIRTH_NO (default) / _FALLBACK / _ALWAYS      */
+    int32_t reserved;
 } inq_assoc_args_t;
 int inq_assoc(const inq_assoc_args_t *args, int out_fd, char *errbuf, size_t errcap);
 /* The samples that command would analyse, without a GPU: their names joined by commas into names (cut to names_cap), *n_samples and

@@ -168,6 +168,14 @@ class AssocArgsC(C.Structure):
     ]
 
 
+class AssocArgsFirthC(AssocArgsC):
+    """inq_assoc_args_t whole: AssocArgsC is the struct as it stood before `firth` was appended, this is what the entries are given"""
+    _fields_ = [("firth", C.c_int32), ("reserved", C.c_int32)]
+
+
+ASSOC_FIRTH = {"no": 0, "fallback": 1, "always": 2}
+
+
 class CallError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"inquistr call failed (exit status {status}): {message}")
@@ -693,11 +701,11 @@ def outlier(combined, minsize: int = 10, zscore: float = 3.0, method: str = "zsc
 
 
 def _assoc_args(combined, phenocovar, phenotype, outcome, binary_order, covariates, str_mode, missing_cutoff, chr, chr_begin, chr_end,
-                all_rows, device) -> AssocArgsC:
+                all_rows, device, firth="no") -> AssocArgsFirthC:
     def text(v):
         return None if v is None else (",".join(v) if isinstance(v, (list, tuple)) else str(v)).encode()
 
-    a = AssocArgsC()
+    a = AssocArgsFirthC()
     a.combined, a.phenocovar, a.phenotype = os.fspath(combined).encode(), os.fspath(phenocovar).encode(), phenotype.encode()
     a.binary_order, a.covariates, a.chr = text(binary_order), text(covariates), text(chr)
     a.chr_begin = -1 if chr_begin is None else int(chr_begin)
@@ -706,18 +714,21 @@ def _assoc_args(combined, phenocovar, phenotype, outcome, binary_order, covariat
     a.outcome = {"binary": 0, "continuous": 1}[outcome]
     a.str_mode = {"max": 0, "min": 1, "mean": 2}[str_mode]
     a.all_rows, a.device = int(bool(all_rows)), device
+    a.firth = ASSOC_FIRTH.get(firth, -1)  # a value that is none of the three: the entry refuses it (101), as the CLI's does
     return a
 
 
 def assoc(combined, phenocovar, phenotype: str, outcome: str, binary_order=None, covariates=None, str_mode: str = "max",
           missing_cutoff: float = 0.8, chr: Optional[str] = None, chr_begin: Optional[int] = None, chr_end: Optional[int] = None,
-          all_rows: bool = False, out=None, device: int = 0) -> None:
+          all_rows: bool = False, out=None, device: int = 0, firth: str = "no") -> None:
     """`inquistr assoc`: one regression per locus of a combined .inq of the phenotype on the repeat length (the reference's
     scripts/STR_regression.R, on the GPU), the tested loci by ascending p-value.  binary_order / covariates: "A,B" or a list.
+    firth ("no" / "fallback" / "always", binary only): Firth's penalised fit for the rows separation broke, or for all, printed in the
+    ordinary fit's place with a last column `method`.
     Raises CallError (101 where the input is wrong, 1 without a GPU)."""
     L = load()
     a = _assoc_args(combined, phenocovar, phenotype, outcome, binary_order, covariates, str_mode, missing_cutoff, chr, chr_begin, chr_end,
-                    all_rows, device)
+                    all_rows, device, firth)
     out = sys.stdout if out is None else out
     out.flush()
     _checked(L.inq_assoc, C.byref(a), out.fileno())

@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "../../include/inquistr_hip.h"
+#include "assoc_fit.h"
 #include "front_kernels.h"
 #include "wave_primitives.h"
 
@@ -23,82 +24,7 @@ namespace {
 
 constexpr int kAssocMaxIter = 25;                    // glm.control(maxit = 25)
 constexpr double kAssocConverged = 1e-8;             // glm.control(epsilon = 1e-8)
-constexpr double kAssocMuEps = 2.220446049250313e-16;  // 2^-52: mu stays in [eps, 1 - eps]
-constexpr double kAssocRankTol = 1e-11;
 constexpr int kBetaCfMaxIter = 1000;  // Lentz: about sqrt(max(a, b)) steps are needed, a = df / 2 <= 32 768
-
-// the sum over the 64 lanes, the same bits in every lane (all 64 lanes must be here)
-__device__ __forceinline__ double wave_sum_f64(double x) {
-    for (int d = 1; d < kWave; d *= 2) x += __shfl_xor(x, d, kWave);
-    return x;
-}
-__device__ __forceinline__ double wave_min_f64(double x) {
-    for (int d = 1; d < kWave; d *= 2) {
-        const double o = __shfl_xor(x, d, kWave);
-        x = o < x ? o : x;
-    }
-    return x;
-}
-__device__ __forceinline__ double wave_max_f64(double x) {
-    for (int d = 1; d < kWave; d *= 2) {
-        const double o = __shfl_xor(x, d, kWave);
-        x = o > x ? o : x;
-    }
-    return x;
-}
-
-// pmax / pmin(H1, H2, na.rm = TRUE) and their mean: NaN only when both are
-__device__ __forceinline__ double assoc_x(const float2 *row, uint32_t i, int mode) {
-    const float2 h = row[i];
-    const bool m1 = h.x != h.x, m2 = h.y != h.y;
-    const float hi = m1 ? h.y : m2 ? h.x : (h.x > h.y ? h.x : h.y);
-    const float lo = m1 ? h.y : m2 ? h.x : (h.x < h.y ? h.x : h.y);
-    return mode == INQ_ASSOC_MAX ? (double)hi : mode == INQ_ASSOC_MIN ? (double)lo : ((double)hi + (double)lo) * 0.5;
-}
-
-__host__ __device__ constexpr int tix(int i, int j) { return i * (i + 1) / 2 + j; }  // j <= i, lower triangle by rows
-
-// In place: M (lower triangle of a symmetric matrix) -> its Cholesky factor L.  False when a pivot is not above tol (NaN included);
-// the factor is then unusable.
-template <int P>
-__device__ __forceinline__ bool cholesky(double (&M)[P * (P + 1) / 2], double tol) {
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-        double d = M[tix(j, j)];
-#pragma unroll
-        for (int k = 0; k < j; ++k) d -= M[tix(j, k)] * M[tix(j, k)];
-        ok = ok && d > tol;
-        const double ljj = sqrt(d);
-        M[tix(j, j)] = ljj;
-#pragma unroll
-        for (int i = j + 1; i < P; ++i) {
-            double s = M[tix(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s -= M[tix(i, k)] * M[tix(j, k)];
-            M[tix(i, j)] = s / ljj;
-        }
-    }
-    return ok;
-}
-// L L' v = r
-template <int P>
-__device__ __forceinline__ void cholesky_solve(const double (&L)[P * (P + 1) / 2], const double (&r)[P], double (&v)[P]) {
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-        double s = r[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s -= L[tix(i, k)] * v[k];
-        v[i] = s / L[tix(i, i)];
-    }
-#pragma unroll
-    for (int i = P - 1; i >= 0; --i) {
-        double s = v[i];
-#pragma unroll
-        for (int k = i + 1; k < P; ++k) s -= L[tix(k, i)] * v[k];
-        v[i] = s / L[tix(i, i)];
-    }
-}
 
 // Continued fraction of the incomplete beta function by the modified Lentz method
 __device__ double beta_cf(double a, double b, double x) {
@@ -154,36 +80,10 @@ __global__ __launch_bounds__(256) void assoc_kernel(AssocArgs a) {
     const double nan = __builtin_nan("");
 
     // pass 0: what the filters and the centring need
-    uint32_t n = 0, n1 = 0, n2 = 0;
-    double sx = 0.0, s1 = 0.0, s2 = 0.0, mn = INFINITY, mx = -INFINITY;
-    double mean[P];  // [0] unused, [1] x, [2 + j] covariate j: sums first, then means
-#pragma unroll
-    for (int j = 0; j < P; ++j) mean[j] = 0.0;
-    for (uint32_t i = lane; i < ns; i += 64u) {
-        const double x = assoc_x(v, i, mode);
-        if (x != x) continue;
-        ++n;
-        sx += x;
-        mn = x < mn ? x : mn;
-        mx = x > mx ? x : mx;
-        if (BINARY) {
-            if (a.y[i] != 0.0) ++n2, s2 += x;
-            else ++n1, s1 += x;
-        }
-#pragma unroll
-        for (int j = 0; j < K; ++j) mean[2 + j] += a.cov[(uint64_t)j * ns + i];
-    }
-    n = wave_sum_u32(n);
-    sx = wave_sum_f64(sx);
-    mn = wave_min_f64(mn);
-    mx = wave_max_f64(mx);
-    if (BINARY) {
-        n1 = wave_sum_u32(n1), n2 = wave_sum_u32(n2);
-        s1 = wave_sum_f64(s1), s2 = wave_sum_f64(s2);
-    }
-#pragma unroll
-    for (int j = 0; j < K; ++j) mean[2 + j] = wave_sum_f64(mean[2 + j]) / (double)n;
-    mean[1] = sx / (double)n;
+    const AssocMoments<P> mo = assoc_moments<P, BINARY>(a, v, lane);
+    const uint32_t n = mo.n, n1 = mo.n1, n2 = mo.n2;
+    const double sx = mo.sx, s1 = mo.s1, s2 = mo.s2, mn = mo.mn, mx = mo.mx;
+    const double (&mean)[P] = mo.mean;
 
     inq_assoc_row_t out;
     out.beta = out.se = out.stat = out.p = nan;
@@ -262,11 +162,12 @@ __global__ __launch_bounds__(256) void assoc_kernel(AssocArgs a) {
     };
 
     if (BINARY) {
-        double dev_old = 0.0;
+        double dev_old = 0.0, mu_min = 1.0;  // mu_min: the smallest min(mu, 1 - mu) of the last pass, this lane's samples
 #pragma unroll 1
         for (int t = 0; t <= kAssocMaxIter; ++t) {
             // the deviance of iterate t (t = 0: of the start values) comes out of the same pass as the sums of step t + 1
             double dev = 0.0;
+            mu_min = 1.0;
             pass([&](double y, const double (&xc)[P], double &w, double &z) {
                 double eta, mu;
                 if (t == 0) {
@@ -278,6 +179,8 @@ __global__ __launch_bounds__(256) void assoc_kernel(AssocArgs a) {
                     mu = mu < kAssocMuEps ? kAssocMuEps : mu > 1.0 - kAssocMuEps ? 1.0 - kAssocMuEps : mu;
                 }
                 dev += -2.0 * log(y != 0.0 ? mu : 1.0 - mu);
+                const double tail = mu < 1.0 - mu ? mu : 1.0 - mu;
+                mu_min = tail < mu_min ? tail : mu_min;
                 w = mu * (1.0 - mu);
                 z = eta + (y - mu) / w;
             });
@@ -307,6 +210,11 @@ __global__ __launch_bounds__(256) void assoc_kernel(AssocArgs a) {
             out.p = erfc(fabs(out.stat) * 0.70710678118654752440);
         } else {
             out.n_iter = 0;
+        }
+        // the side output inq_assoc_rows_firth's fallback rule reads; rows stopped before the fit or SINGULAR ones leave it unread
+        if (a.min_mu) {
+            mu_min = wave_min_f64(mu_min);
+            if (lane == 0) a.min_mu[row] = mu_min;
         }
     } else {
         pass([&](double y, const double (&)[P], double &w, double &z) { w = 1.0, z = y; });
@@ -341,22 +249,11 @@ __global__ __launch_bounds__(256) void assoc_kernel(AssocArgs a) {
 void launch_assoc(const AssocArgs &a, hipStream_t s) {
     if (!a.n_rows) return;
     const dim3 grid((uint32_t)((a.n_rows + 3) / 4));
-    auto go = [&](auto p_c) {
+    assoc_for_p(a.k, [&](auto p_c) {
         constexpr int P = decltype(p_c)::value;
         if (a.outcome == INQ_ASSOC_BINARY) hipLaunchKernelGGL((assoc_kernel<P, true>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((assoc_kernel<P, false>), grid, dim3(256), 0, s, a);
-    };
-    // one instantiation per p: p = 2 (no covariate, the common case) keeps 5 accumulators, p = 8 keeps 44.  Rounding a smaller p up
-    // with zero columns would put zero pivots into the rank test
-    switch (a.k) {
-    case 0: go(std::integral_constant<int, 2>{}); break;
-    case 1: go(std::integral_constant<int, 3>{}); break;
-    case 2: go(std::integral_constant<int, 4>{}); break;
-    case 3: go(std::integral_constant<int, 5>{}); break;
-    case 4: go(std::integral_constant<int, 6>{}); break;
-    case 5: go(std::integral_constant<int, 7>{}); break;
-    default: go(std::integral_constant<int, 8>{}); break;
-    }
+    });
 }
 
 }  // namespace inq

@@ -600,9 +600,13 @@ int inq_outlier_rows(inq_ctx_t *c, const float *values, const uint32_t *row_len,
     return guarded([&] { return outlier_rows_impl(c, values, row_len, n_rows, stride, method, minsize, zscore_cutoff, mincluster, flags, keep); });
 }
 
+// firth_when 0: inq_assoc_rows.  Else inq_assoc_rows_firth: the same launches, the ordinary kernel also leaving each row's smallest
+// min(mu, 1 - mu), and behind each the Firth kernel, which picks its rows on the device
 static int assoc_rows_impl(inq_ctx_t *c, const float *values, uint64_t n_rows, uint32_t n_samples, const double *y, const double *cov,
-                           uint32_t k, int outcome, int str_mode, double missing_cutoff, inq_assoc_row_t *rows) {
+                           uint32_t k, int outcome, int str_mode, double missing_cutoff, inq_assoc_row_t *rows, int firth_when = 0,
+                           inq_assoc_firth_row_t *firth = nullptr) {
     if (!c || (outcome != INQ_ASSOC_BINARY && outcome != INQ_ASSOC_CONTINUOUS)) return INQ_ERR_ARG;
+    if (n_rows && firth_when && !firth) return INQ_ERR_ARG;
     if (str_mode != INQ_ASSOC_MAX && str_mode != INQ_ASSOC_MIN && str_mode != INQ_ASSOC_MEAN) return INQ_ERR_ARG;
     if (n_samples > kAssocMaxSamples || k > kAssocMaxCov || missing_cutoff != missing_cutoff) return INQ_ERR_ARG;
     if (n_rows && (!rows || (n_samples && (!values || !y || (k && !cov))))) return INQ_ERR_ARG;
@@ -630,6 +634,10 @@ static int assoc_rows_impl(inq_ctx_t *c, const float *values, uint64_t n_rows, u
         return rc;
     if ((rc = ensure(c, c->avalues, tile * row_bytes)) != INQ_OK) return rc;
     if ((rc = ensure(c, c->arows, tile * sizeof(inq_assoc_row_t))) != INQ_OK) return rc;
+    if (firth_when) {
+        if ((rc = ensure(c, c->aminmu, tile * sizeof(double))) != INQ_OK) return rc;
+        if ((rc = ensure(c, c->afirth, tile * sizeof(inq_assoc_firth_row_t))) != INQ_OK) return rc;
+    }
     AssocArgs a;
     a.values = (const float *)c->avalues.p;
     a.n_samples = n_samples;
@@ -640,6 +648,12 @@ static int assoc_rows_impl(inq_ctx_t *c, const float *values, uint64_t n_rows, u
     a.outcome = outcome, a.str_mode = str_mode;
     a.missing_cutoff = missing_cutoff;
     a.rows = (inq_assoc_row_t *)c->arows.p;
+    if (firth_when) {
+        a.min_mu = (double *)c->aminmu.p;
+        a.firth = (inq_assoc_firth_row_t *)c->afirth.p;
+        a.firth_when = firth_when;
+        a.firth_mu_bound = (double)c->assoc_firth_mu_ppb / 1e9;
+    }
     // tile by tile on one stream: a tile's upload waits for the launch that read the buffer before it
     for (uint64_t r0 = 0; r0 < n_rows; r0 += tile) {
         a.n_rows = std::min<uint64_t>(tile, n_rows - r0);
@@ -648,11 +662,16 @@ static int assoc_rows_impl(inq_ctx_t *c, const float *values, uint64_t n_rows, u
         if ((rc = timing_begin(c, s, &ev)) != INQ_OK) return rc;
         launch_assoc(a, s);
         HIP_TRY(c, hipGetLastError());
+        if (firth_when) {
+            launch_assoc_firth(a, s);
+            HIP_TRY(c, hipGetLastError());
+        }
         if (ev) {
             HIP_TRY(c, hipEventRecord(ev->e1, s));
             HIP_TRY(c, hipEventRecord(ev->e2, s));
         }
         HIP_TRY(c, hipMemcpyAsync(rows + r0, c->arows.p, a.n_rows * sizeof(inq_assoc_row_t), hipMemcpyDeviceToHost, s));
+        if (firth_when) HIP_TRY(c, hipMemcpyAsync(firth + r0, c->afirth.p, a.n_rows * sizeof(inq_assoc_firth_row_t), hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     return INQ_OK;
@@ -661,6 +680,12 @@ static int assoc_rows_impl(inq_ctx_t *c, const float *values, uint64_t n_rows, u
 int inq_assoc_rows(inq_ctx_t *c, const float *values, uint64_t n_rows, uint32_t n_samples, const double *y, const double *cov, uint32_t k,
                    int outcome, int str_mode, double missing_cutoff, inq_assoc_row_t *rows) {
     return guarded([&] { return assoc_rows_impl(c, values, n_rows, n_samples, y, cov, k, outcome, str_mode, missing_cutoff, rows); });
+}
+
+int inq_assoc_rows_firth(inq_ctx_t *c, const float *values, uint64_t n_rows, uint32_t n_samples, const double *y, const double *cov,
+                         uint32_t k, int str_mode, double missing_cutoff, int when, inq_assoc_row_t *rows, inq_assoc_firth_row_t *firth) {
+    if (when != INQ_ASSOC_FIRTH_FALLBACK && when != INQ_ASSOC_FIRTH_ALWAYS) return INQ_ERR_ARG;
+    return guarded([&] { return assoc_rows_impl(c, values, n_rows, n_samples, y, cov, k, INQ_ASSOC_BINARY, str_mode, missing_cutoff, rows, when, firth); });
 }
 
 int inq_ctx_timing_enable(inq_ctx_t *c, int on) {
@@ -788,6 +813,11 @@ int inq_ctx_set_option(inq_ctx_t *c, const char *key, int64_t value) {
     if (std::strcmp(key, "assoc_tile_rows") == 0) {
         if (value < 0) return INQ_ERR_ARG;
         c->assoc_tile_rows = (uint64_t)value;
+        return INQ_OK;
+    }
+    if (std::strcmp(key, "assoc_firth_mu_ppb") == 0) {
+        if (value < 0) return INQ_ERR_ARG;
+        c->assoc_firth_mu_ppb = (uint64_t)value;
         return INQ_OK;
     }
     if (std::strcmp(key, "blocking_sync") == 0) {

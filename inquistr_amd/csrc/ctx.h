@@ -70,11 +70,12 @@ struct inq_ctx {
     inq::DevBuf rlocusmotif, rmotifuse;
     inq::DevBuf ovalues, olen, oflags, okeep, otrans;  // inq_outlier_rows
     inq::DevBuf avalues, ay, acov, atcoef, arows;      // inq_assoc_rows: one tile of the matrix and of its rows, the shared columns
+    inq::DevBuf aminmu, afirth;                        // inq_assoc_rows_firth: a tile's smallest min(mu, 1 - mu) per row, its Firth rows
     // every DevBuf above, for inq_ctx_destroy (DevBuf frees nothing itself): a member missing here leaks
     auto bufs() {
         std::vector<inq::DevBuf *> all{&worklist, &sval, &smeta, &deep, &cigar, &reads, &pair_read, &off, &lstart, &lend, &p1, &p2, &pcall, &pbits,
                                        &lflags, &levidence, &evwork, &rctiles, &rcoff, &rckept, &rkeptpair, &rmotifs, &rmotifword, &rlocusmotif, &rmotifuse, &ovalues, &olen, &oflags, &okeep, &otrans,
-                                       &avalues, &ay, &acov, &atcoef, &arows};
+                                       &avalues, &ay, &acov, &atcoef, &arows, &aminmu, &afirth};
         for (inq::KeptRuns *k : {&rnames, &rseqs})
             for (inq::DevBuf *b : k->bufs()) all.push_back(b);
         return all;
@@ -101,6 +102,7 @@ struct inq_ctx {
     int inflate_ahead = 1;
     int outlier_tile = 1;   // z-score of rows of <= 256 values through an LDS tile (0: the transposed-copy kernel for every width)
     uint64_t assoc_tile_rows = 0;  // rows inq_assoc_rows uploads and fits per launch (0: as many as fill 256 MB)
+    uint64_t assoc_firth_mu_ppb = 1000;  // inq_assoc_rows_firth, FALLBACK: min(mu, 1 - mu) below this many 1e-9 selects a row
     int blocking_sync = 0;  // waits give the core back (hipDeviceScheduleBlockingSync, blocking events): for a caller short of cores
     // the gather's stores bypass the caches (bam_scan.hip): the batch it builds is read by a later launch, not by this one; the locus
     // kernels behind it run at 5.4 - 6.2 instead of 4.9 - 5.3 TB/s of algorithmic bytes (profiles/r04_results/locus_kernels_in_the_cli.txt)

@@ -146,9 +146,19 @@ struct AssocArgs {
     int outcome, str_mode;
     double missing_cutoff;
     inq_assoc_row_t *rows;  // [n_rows]
+    // binary, or null: [n_rows], the smallest min(mu, 1 - mu) over a fitted row's kept samples at the fit's last pass (rows that are
+    // not OK or NOT_CONVERGED leave theirs unwritten)
+    double *min_mu = nullptr;
+    // launch_assoc_firth only
+    int firth_when = 0;             // INQ_ASSOC_FIRTH_FALLBACK / _ALWAYS
+    double firth_mu_bound = 1e-6;   // FALLBACK: fit the rows whose min_mu is below this (and the NOT_CONVERGED ones)
+    inq_assoc_firth_row_t *firth = nullptr;  // [n_rows]
 };
 constexpr uint32_t kAssocMaxCov = 6, kAssocMaxSamples = 65535;
 // one wave per row, four rows per workgroup, one instantiation per number of columns p = 2 + k and outcome
 void launch_assoc(const AssocArgs &a, hipStream_t s);
+// assoc_firth.hip: behind launch_assoc on the same stream (binary, min_mu set), one wave per row again: reads rows[] and min_mu[],
+// fits the rows `firth_when` selects by Firth's penalised likelihood (full and null model) and writes firth[] for every row
+void launch_assoc_firth(const AssocArgs &a, hipStream_t s);
 
 }  // namespace inq

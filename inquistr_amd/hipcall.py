@@ -100,6 +100,7 @@ ABI_SYMBOLS = (
     "inq_call_flush_locus_motifs",
     "inq_locus_motifs_find",
     "inq_assoc_rows",
+    "inq_assoc_rows_firth",
 )
 
 
@@ -129,6 +130,20 @@ ASSOC_ROW_DTYPE = np.dtype([("beta", "<f8"), ("se", "<f8"), ("stat", "<f8"), ("p
 ASSOC_OUTCOMES = {"binary": 0, "continuous": 1}
 ASSOC_MODES = {"max": 0, "min": 1, "mean": 2}
 ASSOC_STATUS = ("OK", "LOW_CALL_RATE", "CONSTANT", "ONE_GROUP", "TOO_FEW", "SINGULAR", "NOT_CONVERGED")
+
+
+class AssocFirthRowC(C.Structure):
+    """inq_assoc_firth_row_t"""
+
+    _fields_ = [("beta", C.c_double), ("se", C.c_double), ("chi2", C.c_double), ("p", C.c_double), ("pll_full", C.c_double),
+                ("pll_null", C.c_double), ("n_iter_full", C.c_uint8), ("n_iter_null", C.c_uint8), ("status", C.c_uint8),
+                ("pad", C.c_uint8 * 5)]
+
+
+ASSOC_FIRTH_ROW_DTYPE = np.dtype([("beta", "<f8"), ("se", "<f8"), ("chi2", "<f8"), ("p", "<f8"), ("pll_full", "<f8"), ("pll_null", "<f8"),
+                                  ("n_iter_full", "u1"), ("n_iter_null", "u1"), ("status", "u1"), ("pad", "u1", (5,))])
+ASSOC_FIRTH_WHEN = {"fallback": 1, "always": 2}
+ASSOC_FIRTH_STATUS = ("OK", "NOT_FITTED", "SINGULAR", "NOT_CONVERGED")
 
 
 class SpanC(C.Structure):
@@ -438,6 +453,8 @@ def load(path: Optional[str] = None):
     L.inq_span_fetch_batch.argtypes = [vp, vp, vp, vp, vp]
     L.inq_assoc_rows.restype = C.c_int
     L.inq_assoc_rows.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_double, vp]
+    L.inq_assoc_rows_firth.restype = C.c_int
+    L.inq_assoc_rows_firth.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint32, C.c_int, C.c_double, C.c_int, vp, vp]
     if path is None:
         _lib = L
     return L
@@ -915,6 +932,25 @@ class Context:
         if rc != INQ_OK:
             self._raise(rc)
         return rows
+
+    def assoc_rows_firth(self, values: np.ndarray, y: np.ndarray, cov: Optional[np.ndarray] = None, str_mode: str = "max",
+                         missing_cutoff: float = 0.8, when: str = "fallback") -> Tuple[np.ndarray, np.ndarray]:
+        """inq_assoc_rows_firth: the inputs of assoc_rows for a binary outcome, when = "fallback" / "always"; returns (rows
+        ASSOC_ROW_DTYPE, as assoc_rows gives them, firth rows ASSOC_FIRTH_ROW_DTYPE)."""
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        n_samples = len(y)
+        cov = np.zeros((0, n_samples)) if cov is None else np.ascontiguousarray(cov, dtype=np.float64).reshape(-1, n_samples)
+        if values.ndim != 2 or values.shape[1] != 2 * n_samples:
+            raise ValueError("values must be [n_rows, 2 * len(y)]")
+        rows = np.zeros(values.shape[0], dtype=ASSOC_ROW_DTYPE)
+        firth = np.zeros(values.shape[0], dtype=ASSOC_FIRTH_ROW_DTYPE)
+        rc = self._L.inq_assoc_rows_firth(self._h, values.ctypes.data, values.shape[0], n_samples, y.ctypes.data, cov.ctypes.data,
+                                          cov.shape[0], ASSOC_MODES[str_mode], missing_cutoff, ASSOC_FIRTH_WHEN[when], rows.ctypes.data,
+                                          firth.ctypes.data)
+        if rc != INQ_OK:
+            self._raise(rc)
+        return rows, firth
 
     def status(self) -> Tuple[int, int]:
         ties = C.c_uint64(0)

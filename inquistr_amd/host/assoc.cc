@@ -1,6 +1,7 @@
 // assoc.cc — `inquistr assoc` (the reference's scripts/STR_regression.R): reads a combined .inq and a phenotype
 // file, hands the H1 / H2 pairs of the analysed samples of all loci to the GPU in one matrix (inq_assoc_rows) and prints the tested
-// loci by ascending p-value.  Text in, text out; the regressions are not here.
+// loci by ascending p-value.  With --firth the rows whose fit separation broke print Firth's fit (inq_assoc_rows_firth) in its place.
+// Text in, text out; the regressions are not here.
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -72,6 +73,10 @@ void check_args(const inq_assoc_args_t *a) {
     if (!(a->missing_cutoff == a->missing_cutoff)) throw Failure{INQ_EXIT_PANIC, "the missing cutoff is not a number"};
     if ((a->chr_begin >= 0) != (a->chr_end >= 0) || (a->chr_begin >= 0 && !a->chr))
         throw Failure{INQ_EXIT_PANIC, "--chr-begin and --chr-end go together, and with --chr"};
+    if (a->firth != INQ_HOST_FIRTH_NO && a->firth != INQ_HOST_FIRTH_FALLBACK && a->firth != INQ_HOST_FIRTH_ALWAYS)
+        throw Failure{INQ_EXIT_PANIC, "--firth takes no, fallback or always"};
+    if (a->firth != INQ_HOST_FIRTH_NO && a->outcome != INQ_ASSOC_BINARY)
+        throw Failure{INQ_EXIT_PANIC, "--firth is for --outcome binary: a continuous outcome has no separation"};
 }
 
 // header: the first line of the combined file
@@ -259,23 +264,40 @@ int assoc_impl(const inq_assoc_args_t *a, int out_fd) {
     lap("device context there");
     if (hrc != INQ_OK) throw Failure{INQ_EXIT_ERROR, std::string("cannot open HIP device: ") + inq_strerror(hrc)};
     std::vector<inq_assoc_row_t> rows(n_rows);
-    hrc = inq_assoc_rows(ctx, mat, n_rows, (uint32_t)ns, d.y.data(), d.cov.data(), (uint32_t)k, a->outcome, a->str_mode, a->missing_cutoff,
-                         rows.data());
+    // --firth: the same rows, and beside them Firth's fit of the ones the device picks
+    const bool firth_on = a->firth != INQ_HOST_FIRTH_NO;
+    std::vector<inq_assoc_firth_row_t> firth(firth_on ? n_rows : 0);
+    if (firth_on)
+        hrc = inq_assoc_rows_firth(ctx, mat, n_rows, (uint32_t)ns, d.y.data(), d.cov.data(), (uint32_t)k, a->str_mode, a->missing_cutoff,
+                                   a->firth == INQ_HOST_FIRTH_ALWAYS ? INQ_ASSOC_FIRTH_ALWAYS : INQ_ASSOC_FIRTH_FALLBACK, rows.data(), firth.data());
+    else
+        hrc = inq_assoc_rows(ctx, mat, n_rows, (uint32_t)ns, d.y.data(), d.cov.data(), (uint32_t)k, a->outcome, a->str_mode, a->missing_cutoff,
+                             rows.data());
     if (hrc != INQ_OK) {
         const std::string detail = hrc == INQ_ERR_HIP ? inq_last_error(ctx) : "";
         throw Failure{INQ_EXIT_ERROR, std::string("device call failed: ") + inq_strerror(hrc) + (detail.empty() ? "" : " [" + detail + "]")};
     }
     lap("kernels done");
 
-    // tested rows by ascending p (a NaN behind every number), ties in file order; then, with all_rows, the others in file order
+    // what a row prints as beta, se and p: its Firth fit's where that is there and OK, else the ordinary fit's
+    struct Printed {
+        double beta, se, p;
+        bool firth;
+    };
+    auto printed = [&](size_t r) {
+        if (firth_on && firth[r].status == INQ_ASSOC_FIRTH_ROW_OK) return Printed{firth[r].beta, firth[r].se, firth[r].p, true};
+        return Printed{rows[r].beta, rows[r].se, rows[r].p, false};
+    };
+    // tested rows by ascending printed p (a NaN behind every number), ties in file order; then, with all_rows, the others in file order
     std::vector<size_t> order;
-    size_t per_status[7] = {0, 0, 0, 0, 0, 0, 0};
+    size_t per_status[7] = {0, 0, 0, 0, 0, 0, 0}, n_firth = 0;
     for (size_t r = 0; r < n_rows; ++r) {
         ++per_status[rows[r].status < 7 ? rows[r].status : INQ_ASSOC_ROW_SINGULAR];
         if (rows[r].status == INQ_ASSOC_ROW_OK || rows[r].status == INQ_ASSOC_ROW_NOT_CONVERGED) order.push_back(r);
+        n_firth += printed(r).firth;
     }
     std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) {
-        const double px = rows[x].p, py = rows[y].p;
+        const double px = printed(x).p, py = printed(y).p;
         if (std::isnan(px) || std::isnan(py)) return !std::isnan(px) && std::isnan(py);
         return px < py;
     });
@@ -293,7 +315,8 @@ int assoc_impl(const inq_assoc_args_t *a, int out_fd) {
     } else {
         out = "VariantID\tBeta\tBeta_L95\tBeta_U95\tBeta_stdErr\tPvalue\tN\tAvgSize\tMinSize\tMaxSize\tMax_Min_absSizeDiff\tMax_Min_Beta_for_absSizeDiff\tmodel";
     }
-    out += a->all_rows ? "\tstatus\n" : "\n";
+    if (a->all_rows) out += "\tstatus";
+    out += firth_on ? "\tmethod\n" : "\n";
     auto num = [&](double v) {
         inqhost::append_f64(out, v);
         out += '\t';
@@ -317,12 +340,13 @@ int assoc_impl(const inq_assoc_args_t *a, int out_fd) {
             out.append(t2 + 1, t3 ? t3 : end);
             out += '\t';
         }
-        const double lo = w.beta - z95 * w.se, hi = w.beta + z95 * w.se;
+        const Printed f = printed(r);
+        const double lo = f.beta - z95 * f.se, hi = f.beta + z95 * f.se;
         if (binary) {
             const double diff = std::fabs(w.mean_g2 - w.mean_g1);
-            num(std::exp(w.beta)), num(std::exp(lo)), num(std::exp(hi)), num(w.se), num(w.p);
+            num(std::exp(f.beta)), num(std::exp(lo)), num(std::exp(hi)), num(f.se), num(f.p);
             count(w.n), count(w.n_g1), count(w.n_g2);
-            num(w.mean_all), num(w.mean_g1), num(w.mean_g2), num(diff), num(std::exp(diff * w.beta));
+            num(w.mean_all), num(w.mean_g1), num(w.mean_g2), num(diff), num(std::exp(diff * f.beta));
             out += model + "\t" + d.group1 + "," + d.group2;
         } else {
             const double diff = std::fabs(w.max_x - w.min_x);
@@ -332,6 +356,7 @@ int assoc_impl(const inq_assoc_args_t *a, int out_fd) {
             out += model;
         }
         if (a->all_rows) out += std::string("\t") + kStatusNames[w.status < 7 ? w.status : INQ_ASSOC_ROW_SINGULAR];
+        if (firth_on) out += f.firth ? "\tfirth" : "\tglm";
         out += '\n';
         if (out.size() > (1u << 20)) {
             if (!write_all(out_fd, out)) return INQ_EXIT_PANIC;
@@ -341,6 +366,7 @@ int assoc_impl(const inq_assoc_args_t *a, int out_fd) {
     if (!write_all(out_fd, out)) return INQ_EXIT_PANIC;
     std::string tally = "[inq assoc] " + std::to_string(n_rows) + " loci, " + std::to_string(ns) + " samples:";
     for (int s = 0; s < 7; ++s) tally += std::string(" ") + kStatusNames[s] + " " + std::to_string(per_status[s]);
+    if (firth_on) tally += "; fitted by Firth " + std::to_string(n_firth);
     std::fprintf(stderr, "%s\n", tally.c_str());
     return INQ_EXIT_OK;
 }

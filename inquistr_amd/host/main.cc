@@ -130,7 +130,8 @@ int main(int argc, char **argv) {
         static const char *const kUsage =
             "Usage: inquistr assoc <COMBINED> --phenocovar <FILE> --phenotype <COL> --outcome <binary|continuous>\n"
             "                      [--binary-order <A,B>] [--covariates <c1,c2,...>] [--str-mode <max|min|mean>]\n"
-            "                      [--missing-cutoff <0.8>] [--chr <CHR> [--chr-begin <N> --chr-end <N>]] [--all-rows] [--device <N>]\n";
+            "                      [--missing-cutoff <0.8>] [--chr <CHR> [--chr-begin <N> --chr-end <N>]] [--all-rows] [--device <N>]\n"
+            "                      [--firth <no|fallback|always>]\n";
         inq_assoc_args_t o;
         std::memset(&o, 0, sizeof o);
         o.missing_cutoff = 0.8;
@@ -161,6 +162,11 @@ int main(int argc, char **argv) {
             else if (key == "--chr-end") o.chr_end = (int64_t)number(val(), "--chr-end <N>");
             else if (key == "--missing-cutoff") o.missing_cutoff = number(val(), "--missing-cutoff <CUTOFF>");
             else if (key == "--all-rows") o.all_rows = 1;
+            else if (key == "--firth") {
+                // a value that is none of the three goes on as it is: the host entry refuses it (101), as it does --firth with continuous
+                const std::string m = val();
+                o.firth = m == "no" ? INQ_HOST_FIRTH_NO : m == "fallback" ? INQ_HOST_FIRTH_FALLBACK : m == "always" ? INQ_HOST_FIRTH_ALWAYS : -1;
+            }
             else if (key == "--device") o.device = (int32_t)number(val(), "--device <N>");
             else if (key == "--outcome") {
                 const std::string m = val();
