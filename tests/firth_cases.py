@@ -12,12 +12,15 @@ chi2 and its relative error.  chi2 = 2 (l*_full - l*_null) is a difference: one 
 beside l* = -40 would set it (or miss it, where the routes happen to round alike there) by what a single rounding of l* does, a
 million times what the kernel is held to in every other field.  An ordinary row is drawn again until chi2 >= |l*_full| / 8: a unit
 in the last place of l* is then at most 16 eps of chi2, a quarter of the tolerance's floor.  That leaves out the rows without an
-effect; what Firth's fit makes of those is held by the constructed cases, whose 100 ordinary rows are assoc_cases' own."""
+effect here; compare()'s per-row check holds chi2 at the scale of l* instead (tests/assoc_reference.py: firth_row_errors), and
+no_effect_case below is made of such rows."""
 import functools
+import math
 
 import numpy as np
 
 from tests import assoc_cases as ac
+from tests import assoc_reference as rf
 from tests import assoc_restatement as ar
 from tests import firth_restatement as fr
 
@@ -42,6 +45,17 @@ class Case:
         """10 x the routes' largest relative disagreement on the rows `when` fits, never below 64 * 2^-52"""
         d = fr.disagreement(self.R.want(when, "chol"), self.R.want(when, "qr"))
         return max(10.0 * d, FLOOR), d
+
+    @functools.cached_property
+    def ref(self):
+        """the long-double reference's Firth rows of every row the ordinary fit lets through (tests/assoc_reference.py)"""
+        return rf.firth_rows(rf.REFERENCE, self.values, self.y, self.cov, self.mode, self.cutoff)
+
+    @functools.lru_cache(maxsize=None)
+    def tol_row(self, when):
+        """(tol_row, e_row, e_typ) of assoc_reference.tolerances over the rows `when` fits"""
+        fitted = self.R.fitted(when)
+        return rf.tolerances(rf.firth_row_errors(self.R.chol, self.ref, fitted), rf.firth_row_errors(self.R.qr, self.ref, fitted), fitted)
 
 
 def random_values(rng, n_rows, y, cov, mode):
@@ -115,4 +129,124 @@ def compare(case_, when, rows, firth, ordinary):
     print(f"firth device-vs-restatement ({when}): worst relative difference {worst:.3e}, tolerance {tol:.3e} "
           f"(routes disagree by {d:.3e}), ratio {ratio:.3f} [{each}]")
     assert worst <= tol, (worst, tol)
+    compare_rows(case_, when, firth)
+    compare_p(case_, when, firth)
     return ratio
+
+
+def compare_rows(case_, when, firth, what="device"):
+    """Every fitted row's scaled error against the long-double reference, held to that row's own tolerance
+    (tests/assoc_reference.py: firth_row_errors, tolerances).  -> the worst share of a tolerance"""
+    fitted = case_.R.fitted(when)
+    tol, e_row, e_typ = case_.tol_row(when)
+    err = rf.firth_row_errors(firth, case_.ref, fitted)
+    share, i = rf.worst_share(err, tol, fitted)
+    typical = fitted & (e_row <= e_typ)
+    print(f"firth {what}-vs-long-double per row ({when}): worst share {share:.3f} of its tolerance at row {i} (error {err[max(i, 0)]:.2e}, "
+          f"tolerance {tol[max(i, 0)]:.2e}); tolerances {tol[fitted].min() if fitted.any() else 0:.2e} .. "
+          f"{tol[fitted].max() if fitted.any() else 0:.2e}; largest error on the ordinary rows "
+          f"{err[typical].max() if typical.any() else 0:.2e}, the f64 routes' there {e_row[typical].max() if typical.any() else 0:.2e}")
+    bad = np.nonzero(err > tol)[0]
+    assert not len(bad), (what, when, bad[:8].tolist(), err[bad[:8]].tolist(), tol[bad[:8]].tolist())
+    return share
+
+
+def compare_p(case_, when, firth, what="device"):
+    """p as erfc(sqrt(chi2 / 2)) of the chi2 beside it (assoc_reference.check_p)"""
+    host = np.array([math.erfc(math.sqrt(c / 2.0)) if c == c else math.nan for c in firth["chi2"].tolist()])
+    allowed = rf.p_allowed(rf.P_UNITS_ERFC)
+    share, units = rf.check_p(firth["p"], host, f"{what} {when}", allowed)
+    print(f"firth {what} p against the host's erfc of its own chi2 ({when}): {units:.1f} units of 2^-52 max(1, |log p|), "
+          f"{allowed:.0f} allowed")
+    return share
+
+
+# ---- the inputs of tests/test_gpu_firth_edges.py ----------------------------------------------------------------------------------
+
+def _in_band(v, y, cov, mode):
+    return fr.in_band(fr.fit_row(v[0::2], v[1::2], y, cov, mode, "chol")[1])
+
+
+@functools.lru_cache(maxsize=None)
+def chi2_case():
+    """assoc_cases.wald_case for the likelihood ratio: 8192 samples, no covariate, 16 rows whose sqrt(chi2) runs from 0 to 45.  The
+    search reads chi2 and the criteria off the wave-order route, which costs a hundredth of the restatement here; that no row
+    ends in the band is the restatement's to say, in Case"""
+    rng = np.random.default_rng(4301)
+    y = (rng.random(ac.Z_NS) < 0.35).astype(np.float64)
+    cov = np.zeros((0, ac.Z_NS))
+    root = lambda v: math.sqrt(float(rf.firth_fit_row(rf.WAVE, v[0::2], v[1::2], y, cov, "max")["chi2"]))
+
+    def band(v):
+        fits = []
+        rf.firth_fit_row(rf.WAVE, v[0::2], v[1::2], y, cov, "max", fits)
+        return fr.in_band(fits)
+
+    rows = [ac.shifted_halves(rng, y, z, root, band, 3.0) for z in ac.Z_TARGETS]
+    out = Case(np.array(rows, dtype=np.float32), y, cov, "max")
+    z, p = np.sqrt(np.array(out.ref["chi2"], dtype=np.float64)), out.ref["p"]
+    assert (out.R.chol["status"] == fr.OK).all() and z.min() < 1.5 and z.max() > 44.0 and np.all(np.diff(np.sort(z)) < 4.5), z.tolist()
+    assert ((z > 30.0) & (p >= rf.P_MIN_NORMAL)).sum() >= 2 and ((p > 0.0) & (p < rf.P_MIN_NORMAL)).any() and (p == 0.0).any(), p.tolist()
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def no_effect_case():
+    """What most loci of a real file are: 24 rows of ordinary_row without an effect (129 samples, one covariate; drawn again only
+    for the convergence band, not for the size of chi2), and a 25th that is symmetric between the groups - samples 2 j and 2 j + 1
+    share y and the covariate and carry x = 20 + d and 20 - d, the last one x = 20 - so that beta_x = 0 solves the full fit's
+    equations exactly, the two fits are one and chi2 is whatever the roundings of two l* leave: the device may give 0 there."""
+    rng = np.random.default_rng(4400)
+    ns = 129
+    y, cov = ac.design(rng, 64, 1, "binary")
+    y, cov = np.concatenate([np.repeat(y, 2), [1.0]]), np.concatenate([np.repeat(cov, 2, axis=1), [[0.25]]], axis=1)
+    rows = []
+    for _ in range(24):
+        for _ in range(40):
+            v = ac.ordinary_row(rng, y, "binary", eff=0.0)
+            o, _ = ar.fit_row(v[0::2], v[1::2], y, cov, "binary", "max", 0.8, "chol")
+            if o["status"] not in (ar.OK, ar.NOT_CONVERGED):
+                continue  # a row a filter stops is no row of this case
+            if not _in_band(v, y, cov, "max"):
+                break
+        else:
+            raise AssertionError("no fitted row outside the band in 40 draws")
+        rows.append(v)
+    d = rng.integers(1, 6, 64).astype(np.float64)
+    x = np.concatenate([np.stack([20.0 + d, 20.0 - d], axis=1).reshape(-1), [20.0]])
+    rows.append(np.repeat(x, 2).astype(np.float32))
+    out = Case(np.array(rows, dtype=np.float32), y, cov, "max")
+    ref = out.ref
+    assert (out.R.chol["status"] == fr.OK).all()
+    assert ref["chi2"][24] < 1e-12 * abs(ref["pll_full"][24]), (ref["chi2"][24], ref["pll_full"][24])
+    small = np.array(ref["chi2"][:24] < np.abs(ref["pll_full"][:24]) / 8.0)
+    assert small.sum() >= 20, small.tolist()  # the rows random_values would have drawn again
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def empty_case(ns):
+    c = ac.empty_case(ns, "binary")
+    return Case(c.values, c.y, c.cov, "max")
+
+
+@functools.lru_cache(maxsize=None)
+def invariance_case():
+    c = ac.invariance_case("binary")
+    return Case(c.values, c.y, c.cov, "max")
+
+
+def derived_case(c, d):
+    """d (assoc_cases.permuted / shifted of the ordinary case) as a Firth case with c's reference and tolerances"""
+    out = Case(d.values, d.y, d.cov, d.mode, d.cutoff)
+    out.ref, out.tol_row = c.ref, c.tol_row
+    return out
+
+
+def edge_cases():
+    """(name, case, whens) of everything tests/test_gpu_firth_edges.py compares with a reference"""
+    yield "chi2", chi2_case(), ("always",)
+    yield "no effect", no_effect_case(), WHENS
+    for ns in (0, 1):
+        yield f"empty ns {ns}", empty_case(ns), WHENS
+    yield "invariance", invariance_case(), ("always",)

@@ -6,7 +6,8 @@ rows where the last or the last-but-one criterion of either fit lies within 1 % 
 case is built, tests/firth_cases.py).  beta, se, chi2, log(p) and both l* are held, per case, to 10 x the largest relative
 disagreement of the restatement's QR route and its Cholesky route on that same input, never below 64 * 2^-52: the rule of
 tests/test_gpu_assoc.py, the factor covering the wave's order of summation, which is neither route's.  Every test prints the share
-of the tolerance it used."""
+of the tolerance it used.  compare() also holds every fitted row to a tolerance of its own against a long-double fit of the same
+iteration, chi2 at the scale of l* (tests/assoc_reference.py), and p to the host's erfc of the device's own chi2."""
 import json
 import math
 import os
