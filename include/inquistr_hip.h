@@ -339,7 +339,10 @@ int inq_ctx_timing_reset(inq_ctx_t *ctx);
 
 /* Tuning knobs.  key: "grid_medium" = workgroups of the kernel that takes the 65..256-read loci and walks the deeper ones
  * (default 4096); "grid_tail" ("grid_big" up to ABI v4) = workgroups of the persistent kernel that reduces the deeper ones (default
- * 256, never more than the device's compute units: they meet at grid barriers); "max_reads_hint" = N > 0 promises that no locus of
+ * 256, never more than the device's compute units: they meet at grid barriers); "grid_side" = 1 .. 65535: no launch of a side
+ * kernel (the locus and read motif kernels, the window walk, the packed gather, the byte gather of names and slices, the origins, the
+ * slices' records) has more workgroups than that - each takes every gridDim.x-th tile, so the outputs do not change; 0 (default) =
+ * each launch's own cap (65 536 workgroups, 2^20 for the names and origins); anything else: INQ_ERR_ARG; "max_reads_hint" = N > 0 promises that no locus of
  * the following batches is offered more than N reads (N <= 64 skips the two launches behind the first kernel - which cost a few
  * microseconds when nothing deep is there; a violated promise is reported as INQ_ERR_ARG), 0 (default) = unknown;
  * "verify_crc" = 0 skips the CRC32 check of the device front end (default 1);

@@ -425,8 +425,8 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
         return hipGetLastError();
     };
     // an origin per record (its read's descriptor and name length); the slice of the pair each record came from
-    const auto origins = [&] { launch_read_origins(ReadOriginArgs{x.kept, n_kept, view.read_words, b->n_reads, x.name_off, x.names.recs, b->n_pairs}, s); };
-    const auto slices = [&] { launch_read_seq_records(ReadSeqArgs{x.kept_pair, n_kept, x.seq_qbeg, x.seq_len, x.seqs.recs, b->n_pairs}, s); };
+    const auto origins = [&] { launch_read_origins(ReadOriginArgs{x.kept, n_kept, view.read_words, b->n_reads, x.name_off, x.names.recs, b->n_pairs}, c->grid_side, s); };
+    const auto slices = [&] { launch_read_seq_records(ReadSeqArgs{x.kept_pair, n_kept, x.seq_qbeg, x.seq_len, x.seqs.recs, b->n_pairs}, c->grid_side, s); };
     HIP_TRY(c, place_runs(x.names, origins));
     HIP_TRY(c, place_runs(x.seqs, slices));
     // what both motif kernels read: the records the scatter wrote, locus by locus, and the batch's own slices, a segment per pair
@@ -435,12 +435,12 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     // the words this writes.  No pair: no record, every locus's answer is zeros
     if (x.locus_found && !b->n_pairs) HIP_TRY(c, hipMemsetAsync(x.locus_found, 0, (size_t)b->n_loci * sizeof(inq_locus_motif_t), s));
     if (x.locus_found && b->n_pairs) {
-        launch_locus_motifs(LocusMotifArgs{kept, x.motif_given, x.locus_found, x.motif_use}, s);
+        launch_locus_motifs(LocusMotifArgs{kept, x.motif_given, x.locus_found, x.motif_use}, c->grid_side, s);
         HIP_TRY(c, hipGetLastError());
     }
     // the motif runs of each record's bases: in front of nothing
     if (x.motifs && b->n_pairs) {
-        launch_read_motifs(ReadMotifArgs{kept, x.motif_word, x.motifs}, s);
+        launch_read_motifs(ReadMotifArgs{kept, x.motif_word, x.motifs}, c->grid_side, s);
         HIP_TRY(c, hipGetLastError());
     }
     if (ev) HIP_TRY(c, hipEventRecord(ev->e2, s));
@@ -787,6 +787,11 @@ int inq_ctx_set_option(inq_ctx_t *c, const char *key, int64_t value) {
     if (std::strcmp(key, "grid_medium") == 0) {
         if (value < 1 || value > 65535) return INQ_ERR_ARG;
         c->grid_medium = (uint32_t)value;
+        return INQ_OK;
+    }
+    if (std::strcmp(key, "grid_side") == 0) {  // 0: every side kernel's launcher keeps its own cap
+        if (value < 0 || value > 65535) return INQ_ERR_ARG;
+        c->grid_side = (uint32_t)value;
         return INQ_OK;
     }
     if (std::strcmp(key, "max_reads_hint") == 0) {

@@ -83,6 +83,7 @@ struct inq_ctx {
     uint32_t n_cus = 0;        // compute units of the device
     uint32_t grid_tail = 256;  // workgroups of the persistent locus_call_tail: they meet at grid barriers, so never more than n_cus
     uint32_t grid_medium = 4096;  // (8 192: + 3 us for the launch that finds the lists empty, 0 - 4 % quicker where they are full)
+    uint32_t grid_side = 0;       // workgroups at most of a side kernel's launch (side_grid); 0: each launcher's own cap
     uint32_t max_reads_hint = 0;  // 0 = unknown; else the caller's bound on reads per locus
     uint32_t call_hint = 0;       // set by the host-buffer entry, which sees the offsets, for its own launch
     int nt_loads = -1;  // -1 auto: non-temporal when no read is shared between loci

@@ -19,6 +19,6 @@ struct LocusMotifArgs : KeptSlices {
     inq_locus_motif_t *found;  // [n_loci]
     uint64_t *use;             // [n_loci] or null
 };
-void launch_locus_motifs(const LocusMotifArgs &a, hipStream_t s);  // n_loci == 0 launches nothing
+void launch_locus_motifs(const LocusMotifArgs &a, uint32_t grid_side, hipStream_t s);  // n_loci == 0 launches nothing
 
 }  // namespace inq

@@ -209,9 +209,9 @@ __global__ __launch_bounds__(256) void locus_motif_kernel(LocusMotifArgs a) {
 
 }  // namespace
 
-void launch_locus_motifs(const LocusMotifArgs &a, hipStream_t s) {
+void launch_locus_motifs(const LocusMotifArgs &a, uint32_t grid_side, hipStream_t s) {
     if (!a.n_loci) return;
-    hipLaunchKernelGGL(locus_motif_kernel, dim3(capped_grid(a.n_loci)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(locus_motif_kernel, dim3(side_grid(a.n_loci, grid_side)), dim3(kThreads), 0, s, a);
 }
 
 }  // namespace inq

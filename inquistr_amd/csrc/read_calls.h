@@ -45,7 +45,7 @@ struct NameCopyArgs {
     uint64_t n;
     const uint64_t *index64 = nullptr;  // [n] or null; read where index is null
 };
-void launch_name_copy(const NameCopyArgs &a, hipStream_t s);  // n == 0 launches nothing
+void launch_name_copy(const NameCopyArgs &a, uint32_t grid_side, hipStream_t s);  // n == 0 launches nothing
 
 // one inq_read_origin_t per record the compaction wrote, k < min(*n_kept, n_pairs): reads[kept[k].read] and that read's name length
 struct ReadOriginArgs {
@@ -57,6 +57,6 @@ struct ReadOriginArgs {
     inq_read_origin_t *origins;  // [n_pairs], 8-byte aligned
     uint64_t n_pairs;
 };
-void launch_read_origins(const ReadOriginArgs &a, hipStream_t s);
+void launch_read_origins(const ReadOriginArgs &a, uint32_t grid_side, hipStream_t s);
 
 }  // namespace inq

@@ -17,6 +17,6 @@ struct ReadMotifArgs : KeptSlices {
     const uint64_t *motif;   // [n_loci]
     inq_read_motif_t *recs;  // [n_recs], 16-byte aligned
 };
-void launch_read_motifs(const ReadMotifArgs &a, hipStream_t s);  // n_recs == 0 or no motif array launches nothing
+void launch_read_motifs(const ReadMotifArgs &a, uint32_t grid_side, hipStream_t s);  // n_recs == 0 or no motif array launches nothing
 
 }  // namespace inq

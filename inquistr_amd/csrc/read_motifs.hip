@@ -129,9 +129,9 @@ __global__ __launch_bounds__(256) void read_motif_kernel(ReadMotifArgs a) {
 
 }  // namespace
 
-void launch_read_motifs(const ReadMotifArgs &a, hipStream_t s) {
+void launch_read_motifs(const ReadMotifArgs &a, uint32_t grid_side, hipStream_t s) {
     if (!a.n_recs || !a.motif) return;
-    hipLaunchKernelGGL(read_motif_kernel, dim3(capped_grid((a.n_recs + kReadMotifTile - 1) / kReadMotifTile)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(read_motif_kernel, dim3(side_grid((a.n_recs + kReadMotifTile - 1) / kReadMotifTile, grid_side)), dim3(kThreads), 0, s, a);
 }
 
 }  // namespace inq

@@ -68,18 +68,18 @@ __global__ __launch_bounds__(256) void read_origin_kernel(ReadOriginArgs a) {
     }
 }
 
-constexpr uint32_t kNameGridCap = 1u << 20;  // workgroups of a launch of this file (capped_grid), not the shared kGridCap
+constexpr uint32_t kNameGridCap = 1u << 20;  // workgroups of a launch of this file (side_grid), not the shared kGridCap
 
 }  // namespace
 
-void launch_name_copy(const NameCopyArgs &a, hipStream_t s) {
+void launch_name_copy(const NameCopyArgs &a, uint32_t grid_side, hipStream_t s) {
     if (!a.n) return;
-    hipLaunchKernelGGL(name_copy_kernel, dim3(capped_grid((a.n + kReadNameTile - 1) / kReadNameTile, kNameGridCap)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(name_copy_kernel, dim3(side_grid((a.n + kReadNameTile - 1) / kReadNameTile, grid_side, kNameGridCap)), dim3(kThreads), 0, s, a);
 }
 
-void launch_read_origins(const ReadOriginArgs &a, hipStream_t s) {
+void launch_read_origins(const ReadOriginArgs &a, uint32_t grid_side, hipStream_t s) {
     if (!a.n_pairs) return;
-    hipLaunchKernelGGL(read_origin_kernel, dim3(capped_grid((a.n_pairs + kThreads - 1) / kThreads, kNameGridCap)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(read_origin_kernel, dim3(side_grid((a.n_pairs + kThreads - 1) / kThreads, grid_side, kNameGridCap)), dim3(kThreads), 0, s, a);
 }
 
 }  // namespace inq

@@ -35,7 +35,7 @@ struct SeqWindowArgs {
     SeqLenSource len;
     uint32_t *q_beg, *n_bases;  // [n_pairs]
 };
-void launch_seq_window(const SeqWindowArgs &a, hipStream_t s);  // n_pairs == 0 launches nothing
+void launch_seq_window(const SeqWindowArgs &a, uint32_t grid_side, hipStream_t s);  // n_pairs == 0 launches nothing
 
 // seq_slice_kernel: segment p writes (n_bases[p] + 1) / 2 bytes at dst + dst_off[p], the bases [q_beg[p], q_beg[p] + n_bases[p]) of
 // record pair_read[p] - read_base, first base in the high nibble of the first byte
@@ -50,7 +50,7 @@ struct SeqSliceArgs {
     const uint64_t *dst_off;  // [n_pairs + 1]
     uint64_t n_pairs;
 };
-void launch_seq_slice(const SeqSliceArgs &a, hipStream_t s);
+void launch_seq_slice(const SeqSliceArgs &a, uint32_t grid_side, hipStream_t s);
 
 // one inq_read_seq_t per record the compaction wrote, k < min(*n_kept, n_pairs): that of pair kept_pair[k]
 struct ReadSeqArgs {
@@ -60,6 +60,6 @@ struct ReadSeqArgs {
     inq_read_seq_t *recs;  // [n_pairs], 8-byte aligned
     uint64_t n_pairs;
 };
-void launch_read_seq_records(const ReadSeqArgs &a, hipStream_t s);
+void launch_read_seq_records(const ReadSeqArgs &a, uint32_t grid_side, hipStream_t s);
 
 }  // namespace inq

@@ -199,19 +199,19 @@ __global__ __launch_bounds__(256) void read_seq_record_kernel(ReadSeqArgs a) {
 
 }  // namespace
 
-void launch_seq_window(const SeqWindowArgs &a, hipStream_t s) {
+void launch_seq_window(const SeqWindowArgs &a, uint32_t grid_side, hipStream_t s) {
     if (!a.n_pairs) return;
-    hipLaunchKernelGGL(seq_window_kernel, dim3(capped_grid((a.n_pairs + kSeqWindowTile - 1) / kSeqWindowTile)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(seq_window_kernel, dim3(side_grid((a.n_pairs + kSeqWindowTile - 1) / kSeqWindowTile, grid_side)), dim3(kThreads), 0, s, a);
 }
 
-void launch_seq_slice(const SeqSliceArgs &a, hipStream_t s) {
+void launch_seq_slice(const SeqSliceArgs &a, uint32_t grid_side, hipStream_t s) {
     if (!a.n_pairs) return;
-    hipLaunchKernelGGL(seq_slice_kernel, dim3(capped_grid((a.n_pairs + kSeqSliceTile - 1) / kSeqSliceTile)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(seq_slice_kernel, dim3(side_grid((a.n_pairs + kSeqSliceTile - 1) / kSeqSliceTile, grid_side)), dim3(kThreads), 0, s, a);
 }
 
-void launch_read_seq_records(const ReadSeqArgs &a, hipStream_t s) {
+void launch_read_seq_records(const ReadSeqArgs &a, uint32_t grid_side, hipStream_t s) {
     if (!a.n_pairs) return;
-    hipLaunchKernelGGL(read_seq_record_kernel, dim3(capped_grid((a.n_pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(read_seq_record_kernel, dim3(side_grid((a.n_pairs + kThreads - 1) / kThreads, grid_side)), dim3(kThreads), 0, s, a);
 }
 
 }  // namespace inq

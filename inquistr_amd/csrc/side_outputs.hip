@@ -98,7 +98,7 @@ int motif_runs_impl(inq_ctx_t *c, const HostSlices &h, const uint64_t *motif, in
     if (rc != INQ_OK) return rc;
     hipStream_t s = c->stream;
     if ((rc = ensure(c, c->rmotifs, (size_t)h.n * sizeof(inq_read_motif_t))) != INQ_OK) return rc;
-    launch_read_motifs(ReadMotifArgs{up.view, (const uint64_t *)c->rmotifword.p, (inq_read_motif_t *)c->rmotifs.p}, s);
+    launch_read_motifs(ReadMotifArgs{up.view, (const uint64_t *)c->rmotifword.p, (inq_read_motif_t *)c->rmotifs.p}, c->grid_side, s);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(out, c->rmotifs.p, (size_t)h.n * sizeof(inq_read_motif_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));  // (the uploads' sources live until here)
@@ -117,7 +117,7 @@ int locus_motifs_find_impl(inq_ctx_t *c, const HostSlices &h, const uint64_t *gi
     if ((rc = ensure(c, c->rlocusmotif, (size_t)h.n_loci * sizeof(inq_locus_motif_t))) != INQ_OK) return rc;
     if (use && (rc = ensure(c, c->rmotifuse, (size_t)h.n_loci * 8)) != INQ_OK) return rc;
     launch_locus_motifs(LocusMotifArgs{up.view, given ? (const uint64_t *)c->rmotifword.p : nullptr, (inq_locus_motif_t *)c->rlocusmotif.p,
-                                       use ? (uint64_t *)c->rmotifuse.p : nullptr}, s);
+                                       use ? (uint64_t *)c->rmotifuse.p : nullptr}, c->grid_side, s);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(found, c->rlocusmotif.p, (size_t)h.n_loci * sizeof(inq_locus_motif_t), hipMemcpyDeviceToHost, s));
     if (use) HIP_TRY(c, hipMemcpyAsync(use, c->rmotifuse.p, (size_t)h.n_loci * 8, hipMemcpyDeviceToHost, s));
@@ -153,7 +153,7 @@ int seq_windows_impl(inq_ctx_t *c, const inq_batch_t *b, const uint32_t *l_seq, 
                     (const uint64_t *)c->off.p, (const uint32_t *)c->lstart.p, (const uint32_t *)c->lend.p, b->n_loci, b->n_pairs, SeqLenSource{},
                     d_qbeg, d_len};
     if (l_seq) a.len.l_seq = (const uint32_t *)c->rseqs.off.p;
-    launch_seq_window(a, s);
+    launch_seq_window(a, c->grid_side, s);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(q_beg, d_qbeg, (size_t)b->n_pairs * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(n_bases, d_len, (size_t)b->n_pairs * 4, hipMemcpyDeviceToHost, s));
@@ -277,7 +277,7 @@ int inq::extras_names(inq_ctx *c, uint64_t n_pairs, uint64_t n_kept, const HostE
         const int rc = ensure(c, k.dst, (size_t)*k.total);
         if (rc != INQ_OK) return rc;
         launch_name_copy(NameCopyArgs{k.src.bytes, k.src.n_bytes, k.src.off, k.src.n, 0, k.src.by_pair ? nullptr : d.kept, (uint8_t *)k.dst.p,
-                                      *k.total, k.off, std::min(n_kept, n_pairs), k.src.by_pair ? d.kept_pair : nullptr}, s);
+                                      *k.total, k.off, std::min(n_kept, n_pairs), k.src.by_pair ? d.kept_pair : nullptr}, c->grid_side, s);
         any = true;
     }
     if (!any) return INQ_OK;

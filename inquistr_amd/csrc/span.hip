@@ -529,7 +529,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
         // the names of the placed records, one run per read, out of the inflated bytes (rec_off[i] + 36)
         if ((rc = append_runs(c, A.names, A.n_spans == 0, A.n_reads, n_valid, name_bytes, span_name_off, s)) != INQ_OK) return rc;
         launch_name_copy(NameCopyArgs{a.u, a.u_bytes, a.rec_off, n_valid, 36, nullptr, (uint8_t *)A.names.bytes.p + A.names.n_bytes, name_bytes,
-                                      span_name_off, n_valid}, s);
+                                      span_name_off, n_valid}, c->grid_side, s);
     }
     if (defer && n_valid)  // the descriptors, CIGAR offsets already counted from the start of the accumulated buffer
         HIP_TRY(c, hipMemcpyAsync((inq_read_t *)A.reads.p + A.n_reads, a.reads, n_valid * sizeof(inq_read_t), hipMemcpyDeviceToDevice, s));
@@ -593,7 +593,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
             SeqLenSource lens;
             lens.u = a.u, lens.u_bytes = a.u_bytes, lens.rec_off = a.rec_off, lens.n_records = n_valid, lens.read_base = A.n_reads;
             launch_seq_window(SeqWindowArgs{(const uint4 *)A.cigar.p, A.n_units + n_units, (const uint4 *)A.reads.p, A.n_reads + n_valid, a.pair_read,
-                                            a.locus_pair_off, a.locus_start, a.locus_end, nl, n_pairs, lens, span_qbeg, span_len}, s);
+                                            a.locus_pair_off, a.locus_start, a.locus_end, nl, n_pairs, lens, span_qbeg, span_len}, c->grid_side, s);
             launch_scan_seq_bytes(span_len, span_seq_off, n_pairs, span_seq_off + n_pairs + 1, s);
             HIP_TRY(c, hipMemcpyAsync(&S->h->seq_bytes, span_seq_off + n_pairs, 8, hipMemcpyDeviceToHost, s));
         }
@@ -611,7 +611,7 @@ int call_span_impl(inq_ctx *c, const inq_span_t *sp, inq_result_t *r, inq_span_s
             // given back
             if ((rc = append_runs(c, A.seqs, A.n_spans == 0, A.n_pairs, n_pairs, seq_bytes, span_seq_off, s)) != INQ_OK) return rc;
             launch_seq_slice(SeqSliceArgs{a.u, a.u_bytes, a.rec_off, n_valid, A.n_reads, a.pair_read, span_qbeg, span_len,
-                                          (uint8_t *)A.seqs.bytes.p + A.seqs.n_bytes, seq_bytes, span_seq_off, n_pairs}, s);
+                                          (uint8_t *)A.seqs.bytes.p + A.seqs.n_bytes, seq_bytes, span_seq_off, n_pairs}, c->grid_side, s);
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, hipStreamSynchronize(s));
         }

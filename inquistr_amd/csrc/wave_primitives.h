@@ -106,5 +106,9 @@ __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t x) {
 // A launch whose workgroups stride over their tiles: one workgroup per tile up to `cap` of them, the rest by stride
 constexpr uint32_t kGridCap = 1u << 16;
 inline uint32_t capped_grid(uint64_t tiles, uint32_t cap = kGridCap) { return (uint32_t)(tiles < cap ? tiles : cap); }
+// ... of a side kernel: the context option "grid_side" lowers the launcher's own cap (0, the default, leaves it)
+inline uint32_t side_grid(uint64_t tiles, uint32_t grid_side, uint32_t cap = kGridCap) {
+    return capped_grid(tiles, grid_side && grid_side < cap ? grid_side : cap);
+}
 
 }  // namespace inq
