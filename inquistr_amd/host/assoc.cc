@@ -1,8 +1,8 @@
 // assoc.cc — `inquistr assoc` (the reference's scripts/STR_regression.R): reads a combined .inq and a phenotype
 // file, hands the H1 / H2 pairs of the analysed samples of all loci to the GPU in one matrix (inq_assoc_rows) and prints the tested
 // loci by ascending p-value.  With --firth the rows whose fit separation broke print Firth's fit (inq_assoc_rows_firth) in its place.
-// Text in, text out; the regressions are not here.
-#include <chrono>
+// Text in, text out; the regressions are not here.  The steps in the order they run: check_args, the text and its lines, make_design,
+// pick_loci, fill_matrix, fit_rows, print_order, print_table, tally; what `outlier` does the same way is in text_input.h.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -11,7 +11,6 @@
 #include <algorithm>
 #include <memory>
 #include <string>
-#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -53,11 +52,6 @@ struct Design {
     std::vector<std::string> cov_names;
     std::string group1, group2;
     size_t file_columns = 0;  // value columns in the combined file's header
-};
-
-struct Failure {
-    int status;
-    std::string message;
 };
 
 void check_args(const inq_assoc_args_t *a) {
@@ -156,260 +150,222 @@ Design make_design(const inq_assoc_args_t *a, const std::string &header) {
 }
 
 const char *const kStatusNames[] = {"OK", "LOW_CALL_RATE", "CONSTANT", "ONE_GROUP", "TOO_FEW", "SINGULAR", "NOT_CONVERGED"};
+const char *status_name(uint32_t status) { return kStatusNames[status < 7 ? status : INQ_ASSOC_ROW_SINGULAR]; }
+bool tested(const inq_assoc_row_t &w) { return w.status == INQ_ASSOC_ROW_OK || w.status == INQ_ASSOC_ROW_NOT_CONVERGED; }
 
-int assoc_impl(const inq_assoc_args_t *a, int out_fd) {
-    check_args(a);
-    // the HIP runtime starts while the text is read and parsed (as in outlier.cc)
-    inq_ctx_t *ctx = nullptr;
-    int hrc = INQ_OK;
-    std::thread ctx_thread([&] { hrc = inq_ctx_create(a->device, &ctx); });
-    struct CtxGuard {
-        inq_ctx_t *&c;
-        std::thread &t;
-        ~CtxGuard() {
-            if (t.joinable()) t.join();
-            const char *fast = std::getenv("INQ_FAST_EXIT");  // set by the CLI, which is about to leave the process
-            if (!(fast && fast[0] == '1')) inq_ctx_destroy(c);
-        }
-    } ctx_guard{ctx, ctx_thread};
-    using clk = std::chrono::steady_clock;
-    const bool timing = std::getenv("INQ_TIMING") != nullptr;
-    const auto t_begin = clk::now();
-    auto lap = [&](const char *what) {
-        if (timing) std::fprintf(stderr, "[inq assoc] %-22s at %7.1f ms\n", what, std::chrono::duration<double, std::milli>(clk::now() - t_begin).count());
-    };
-    TextFile tf;
-    {
-        std::string lerr;
-        if (!tf.load(a->combined, lerr)) throw Failure{INQ_EXIT_PANIC, lerr};
-    }
-    const char *const tdata = tf.data;
-    lap("text in memory");
-    std::vector<std::pair<size_t, size_t>> lines;
-    find_lines(tdata, tf.size, lines);
-    if (lines.empty()) throw Failure{INQ_EXIT_PANIC, "called `Option::unwrap()` on a `None` value (empty combined file)"};  // src/assoc.rs:49
-    const Design d = make_design(a, std::string(tdata + lines[0].first, lines[0].second));
-    const size_t ns = d.names.size(), k = d.cov_names.size();
-    // value column -> where it goes in a row of the matrix (-1: a sample that is not analysed)
-    std::vector<int32_t> dest(d.file_columns, -1);
-    for (size_t i = 0; i < ns; ++i) dest[2 * d.column[i]] = (int32_t)(2 * i), dest[2 * d.column[i] + 1] = (int32_t)(2 * i + 1);
-
-    // the loci asked for (--chr, --chr-begin / --chr-end), in file order
-    const size_t n_lines = lines.size() - 1;
+// the loci asked for (--chr, --chr-begin / --chr-end), in file order
+std::vector<size_t> pick_loci(const inq_assoc_args_t *a, const CombinedText &txt) {
     const std::string want_chr = a->chr ? a->chr : "";
-    std::vector<size_t> picked;  // line numbers
-    picked.reserve(n_lines);
-    for (size_t i = 0; i < n_lines; ++i) {
-        const char *p = tdata + lines[i + 1].first, *end = p + lines[i + 1].second;
-        if (p == end) continue;  // an empty line
-        const char *t1 = (const char *)std::memchr(p, '\t', (size_t)(end - p));
-        const char *t2 = t1 ? (const char *)std::memchr(t1 + 1, '\t', (size_t)(end - t1 - 1)) : nullptr;
-        const char *t3 = t2 ? (const char *)std::memchr(t2 + 1, '\t', (size_t)(end - t2 - 1)) : nullptr;
-        if (!t2) throw Failure{INQ_EXIT_PANIC, "index out of bounds: a line with fewer than three fields"};
+    std::vector<size_t> picked;
+    picked.reserve(txt.loci());
+    for (size_t i = 0; i < txt.loci(); ++i) {
+        if (txt.begin(i) == txt.end(i)) continue;  // an empty line
+        Span c[3];
+        if (!first_three(txt.begin(i), txt.end(i), c)) throw Failure{INQ_EXIT_PANIC, "index out of bounds: a line with fewer than three fields"};
         if (a->chr) {
-            if ((size_t)(t1 - p) != want_chr.size() || std::memcmp(p, want_chr.data(), want_chr.size()) != 0) continue;
+            if (c[0].n != want_chr.size() || std::memcmp(c[0].p, want_chr.data(), want_chr.size()) != 0) continue;
             if (a->chr_begin >= 0) {
                 double b = 0, e = 0;
-                if (!parse_finite(std::string(t1 + 1, t2), &b) || !parse_finite(std::string(t2 + 1, t3 ? t3 : end), &e))
+                if (!parse_finite(std::string(c[1].p, c[1].n), &b) || !parse_finite(std::string(c[2].p, c[2].n), &e))
                     throw Failure{INQ_EXIT_PANIC, "Failed to parse number"};
                 if (!(b >= (double)a->chr_begin && e <= (double)a->chr_end)) continue;
             }
         }
-        picked.push_back(i + 1);
+        picked.push_back(i);
     }
-    const size_t n_rows = picked.size();
-    std::unique_ptr<float[]> mat_mem(new float[std::max<size_t>(n_rows * 2 * ns, 1)]);
-    float *const mat = mat_mem.get();
-    const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    const size_t n_thr = std::max<size_t>(1, std::min<size_t>(hw, n_rows / 2048 + 1));
+    return picked;
+}
+
+// [picked.size()][2 * samples]: the H1 / H2 pairs of the analysed samples, parsed by several threads.  Every value of a line is
+// parsed, as the reference does (src/assoc.rs:82), also those of samples that are not analysed.
+std::unique_ptr<float[]> fill_matrix(const CombinedText &txt, const std::vector<size_t> &picked, const Design &d) {
+    const size_t ns = d.names.size(), n_rows = picked.size();
+    // value column -> where it goes in a row of the matrix (-1: a sample that is not analysed)
+    std::vector<int32_t> dest(d.file_columns, -1);
+    for (size_t i = 0; i < ns; ++i) dest[2 * d.column[i]] = (int32_t)(2 * i), dest[2 * d.column[i] + 1] = (int32_t)(2 * i + 1);
+    std::unique_ptr<float[]> mat(new float[std::max<size_t>(n_rows * 2 * ns, 1)]);
+    const size_t n_thr = thread_count(n_rows, kLinesPerThread);
     std::vector<std::string> bad(n_thr);
-    auto work = [&](size_t t) {
+    on_threads(n_thr, [&](size_t t) {
         const size_t lo = n_rows * t / n_thr, hi = n_rows * (t + 1) / n_thr;
         for (size_t r = lo; r < hi; ++r) {
-            const char *p = tdata + lines[picked[r]].first, *end = p + lines[picked[r]].second;
-            float *row = mat + r * 2 * ns;
-            size_t field = 0;
-            const char *f0 = p;
-            for (const char *q = p;; ++q) {
-                if (q == end || *q == '\t') {
-                    if (field >= 3 && field - 3 < dest.size()) {
-                        float v;
-                        if (!parse_f32(f0, (size_t)(q - f0), &v)) {  // src/assoc.rs:82
-                            bad[t] = "Failed to parse number";
-                            return;
-                        }
-                        if (dest[field - 3] >= 0) row[dest[field - 3]] = v;
-                    }
-                    ++field;
-                    f0 = q + 1;
-                    if (q == end) break;
-                }
-            }
-            if (field < 3 + dest.size()) {
-                bad[t] = "a line with fewer values than the header has sample columns";
-                return;
-            }
+            float *row = mat.get() + r * 2 * ns;
+            const size_t fields = walk_values(txt.begin(picked[r]), txt.end(picked[r]), [row, to = dest.data(), n_dest = dest.size()](size_t k, const char *s, size_t n) {  // (captured by value: they stay in registers)
+                if (k >= n_dest) return true;
+                float v;
+                if (!parse_f32(s, n, &v)) return false;
+                if (to[k] >= 0) row[to[k]] = v;
+                return true;
+            });
+            if (fields == kWalkStopped) bad[t] = "Failed to parse number";
+            else if (fields < 3 + dest.size()) bad[t] = "a line with fewer values than the header has sample columns";
+            if (!bad[t].empty()) return;
         }
-    };
-    {
-        std::vector<std::thread> th;
-        for (size_t t = 1; t < n_thr; ++t) th.emplace_back(work, t);
-        work(0);
-        for (auto &x : th) x.join();
-    }
+    });
     for (const auto &b : bad)
         if (!b.empty()) throw Failure{INQ_EXIT_PANIC, b};
-    lap("numbers parsed");
-    ctx_thread.join();
-    lap("device context there");
-    if (hrc != INQ_OK) throw Failure{INQ_EXIT_ERROR, std::string("cannot open HIP device: ") + inq_strerror(hrc)};
-    std::vector<inq_assoc_row_t> rows(n_rows);
-    // --firth: the same rows, and beside them Firth's fit of the ones the device picks
-    const bool firth_on = a->firth != INQ_HOST_FIRTH_NO;
-    std::vector<inq_assoc_firth_row_t> firth(firth_on ? n_rows : 0);
-    if (firth_on)
-        hrc = inq_assoc_rows_firth(ctx, mat, n_rows, (uint32_t)ns, d.y.data(), d.cov.data(), (uint32_t)k, a->str_mode, a->missing_cutoff,
-                                   a->firth == INQ_HOST_FIRTH_ALWAYS ? INQ_ASSOC_FIRTH_ALWAYS : INQ_ASSOC_FIRTH_FALLBACK, rows.data(), firth.data());
-    else
-        hrc = inq_assoc_rows(ctx, mat, n_rows, (uint32_t)ns, d.y.data(), d.cov.data(), (uint32_t)k, a->outcome, a->str_mode, a->missing_cutoff,
-                             rows.data());
-    if (hrc != INQ_OK) {
-        const std::string detail = hrc == INQ_ERR_HIP ? inq_last_error(ctx) : "";
-        throw Failure{INQ_EXIT_ERROR, std::string("device call failed: ") + inq_strerror(hrc) + (detail.empty() ? "" : " [" + detail + "]")};
-    }
-    lap("kernels done");
+    return mat;
+}
 
-    // what a row prints as beta, se and p: its Firth fit's where that is there and OK, else the ordinary fit's
-    struct Printed {
-        double beta, se, p;
-        bool firth;
-    };
-    auto printed = [&](size_t r) {
-        if (firth_on && firth[r].status == INQ_ASSOC_FIRTH_ROW_OK) return Printed{firth[r].beta, firth[r].se, firth[r].p, true};
-        return Printed{rows[r].beta, rows[r].se, rows[r].p, false};
-    };
-    // tested rows by ascending printed p (a NaN behind every number), ties in file order; then, with all_rows, the others in file order
-    std::vector<size_t> order;
-    size_t per_status[7] = {0, 0, 0, 0, 0, 0, 0}, n_firth = 0;
-    for (size_t r = 0; r < n_rows; ++r) {
-        ++per_status[rows[r].status < 7 ? rows[r].status : INQ_ASSOC_ROW_SINGULAR];
-        if (rows[r].status == INQ_ASSOC_ROW_OK || rows[r].status == INQ_ASSOC_ROW_NOT_CONVERGED) order.push_back(r);
-        n_firth += printed(r).firth;
+// The regressions.  --firth: the same rows, and beside them Firth's fit of the ones the device picks (firth stays empty without)
+void fit_rows(inq_ctx_t *ctx, const inq_assoc_args_t *a, const Design &d, const float *mat, std::vector<inq_assoc_row_t> &rows,
+              std::vector<inq_assoc_firth_row_t> &firth) {
+    const uint32_t ns = (uint32_t)d.names.size(), k = (uint32_t)d.cov_names.size();
+    int rc;
+    if (a->firth != INQ_HOST_FIRTH_NO) {
+        firth.resize(rows.size());
+        rc = inq_assoc_rows_firth(ctx, mat, rows.size(), ns, d.y.data(), d.cov.data(), k, a->str_mode, a->missing_cutoff,
+                                  a->firth == INQ_HOST_FIRTH_ALWAYS ? INQ_ASSOC_FIRTH_ALWAYS : INQ_ASSOC_FIRTH_FALLBACK, rows.data(), firth.data());
+    } else {
+        rc = inq_assoc_rows(ctx, mat, rows.size(), ns, d.y.data(), d.cov.data(), k, a->outcome, a->str_mode, a->missing_cutoff, rows.data());
     }
+    if (rc != INQ_OK) device_call_failed(rc, ctx);
+}
+
+// what a row prints as beta, se and p: its Firth fit's where that is there and OK, else the ordinary fit's
+struct Printed {
+    double beta, se, p;
+    bool firth;
+};
+Printed printed(const std::vector<inq_assoc_row_t> &rows, const std::vector<inq_assoc_firth_row_t> &firth, size_t r) {
+    if (!firth.empty() && firth[r].status == INQ_ASSOC_FIRTH_ROW_OK) return Printed{firth[r].beta, firth[r].se, firth[r].p, true};
+    return Printed{rows[r].beta, rows[r].se, rows[r].p, false};
+}
+
+// tested rows by ascending printed p (a NaN behind every number), ties in file order; then, with all_rows, the others in file order
+std::vector<size_t> print_order(bool all_rows, const std::vector<inq_assoc_row_t> &rows, const std::vector<inq_assoc_firth_row_t> &firth) {
+    std::vector<size_t> order;
+    for (size_t r = 0; r < rows.size(); ++r)
+        if (tested(rows[r])) order.push_back(r);
     std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) {
-        const double px = printed(x).p, py = printed(y).p;
+        const double px = printed(rows, firth, x).p, py = printed(rows, firth, y).p;
         if (std::isnan(px) || std::isnan(py)) return !std::isnan(px) && std::isnan(py);
         return px < py;
     });
-    if (a->all_rows)
-        for (size_t r = 0; r < n_rows; ++r)
-            if (rows[r].status != INQ_ASSOC_ROW_OK && rows[r].status != INQ_ASSOC_ROW_NOT_CONVERGED) order.push_back(r);
-    const bool binary = a->outcome == INQ_ASSOC_BINARY;
+    if (all_rows)
+        for (size_t r = 0; r < rows.size(); ++r)
+            if (!tested(rows[r])) order.push_back(r);
+    return order;
+}
+
+// the header and one line per row of `order`
+void print_table(const inq_assoc_args_t *a, const Design &d, const CombinedText &txt, const std::vector<size_t> &picked,
+                 const std::vector<size_t> &order, const std::vector<inq_assoc_row_t> &rows, const std::vector<inq_assoc_firth_row_t> &firth,
+                 OutBuffer &out) {
+    const bool binary = a->outcome == INQ_ASSOC_BINARY, firth_on = a->firth != INQ_HOST_FIRTH_NO;
     std::string model = std::string(a->phenotype) + "~x";
     for (const auto &c : d.cov_names) model += "+" + c;
-    std::string out;
     if (binary) {
         const std::string &A = d.group1, &B = d.group2;
-        out = "VariantID\tOR\tOR_L95\tOR_U95\tOR_stdErr\tPvalue\tN\t" + A + "_N\t" + B + "_N\tAvgSize\t" + A + "_AvgSize\t" + B + "_AvgSize\t" + B +
-              "_" + A + "_absAvgSizeDiff\t" + B + "_" + A + "_OR_for_absAvgSizeDiff\tmodel\tbinaryOrder";
+        out.text = "VariantID\tOR\tOR_L95\tOR_U95\tOR_stdErr\tPvalue\tN\t" + A + "_N\t" + B + "_N\tAvgSize\t" + A + "_AvgSize\t" + B + "_AvgSize\t" + B +
+                   "_" + A + "_absAvgSizeDiff\t" + B + "_" + A + "_OR_for_absAvgSizeDiff\tmodel\tbinaryOrder";
     } else {
-        out = "VariantID\tBeta\tBeta_L95\tBeta_U95\tBeta_stdErr\tPvalue\tN\tAvgSize\tMinSize\tMaxSize\tMax_Min_absSizeDiff\tMax_Min_Beta_for_absSizeDiff\tmodel";
+        out.text = "VariantID\tBeta\tBeta_L95\tBeta_U95\tBeta_stdErr\tPvalue\tN\tAvgSize\tMinSize\tMaxSize\tMax_Min_absSizeDiff\tMax_Min_Beta_for_absSizeDiff\tmodel";
     }
-    if (a->all_rows) out += "\tstatus";
-    out += firth_on ? "\tmethod\n" : "\n";
+    if (a->all_rows) out.text += "\tstatus";
+    out.text += firth_on ? "\tmethod\n" : "\n";
     auto num = [&](double v) {
-        inqhost::append_f64(out, v);
-        out += '\t';
+        inqhost::append_f64(out.text, v);
+        out.text += '\t';
     };
     auto count = [&](uint32_t v) {
-        out += std::to_string(v);
-        out += '\t';
+        out.text += std::to_string(v);
+        out.text += '\t';
     };
     constexpr double z95 = 1.959963984540054;
     for (size_t r : order) {
         const inq_assoc_row_t &w = rows[r];
-        {  // VariantID = chrom:begin_end, as the file spells them
-            const char *p = tdata + lines[picked[r]].first, *end = p + lines[picked[r]].second;
-            const char *t1 = (const char *)std::memchr(p, '\t', (size_t)(end - p));
-            const char *t2 = (const char *)std::memchr(t1 + 1, '\t', (size_t)(end - t1 - 1));
-            const char *t3 = (const char *)std::memchr(t2 + 1, '\t', (size_t)(end - t2 - 1));
-            out.append(p, t1);
-            out += ':';
-            out.append(t1 + 1, t2);
-            out += '_';
-            out.append(t2 + 1, t3 ? t3 : end);
-            out += '\t';
-        }
-        const Printed f = printed(r);
+        Span c[3];  // VariantID = chrom:begin_end, as the file spells them
+        first_three(txt.begin(picked[r]), txt.end(picked[r]), c);
+        out.text.append(c[0].p, c[0].n), out.text += ':';
+        out.text.append(c[1].p, c[1].n), out.text += '_';
+        out.text.append(c[2].p, c[2].n), out.text += '\t';
+        const Printed f = printed(rows, firth, r);
         const double lo = f.beta - z95 * f.se, hi = f.beta + z95 * f.se;
         if (binary) {
             const double diff = std::fabs(w.mean_g2 - w.mean_g1);
             num(std::exp(f.beta)), num(std::exp(lo)), num(std::exp(hi)), num(f.se), num(f.p);
             count(w.n), count(w.n_g1), count(w.n_g2);
             num(w.mean_all), num(w.mean_g1), num(w.mean_g2), num(diff), num(std::exp(diff * f.beta));
-            out += model + "\t" + d.group1 + "," + d.group2;
+            out.text += model + "\t" + d.group1 + "," + d.group2;
         } else {
             const double diff = std::fabs(w.max_x - w.min_x);
             num(w.beta), num(lo), num(hi), num(w.se), num(w.p);
             count(w.n);
             num(w.mean_all), num(w.min_x), num(w.max_x), num(diff), num(diff * w.beta);
-            out += model;
+            out.text += model;
         }
-        if (a->all_rows) out += std::string("\t") + kStatusNames[w.status < 7 ? w.status : INQ_ASSOC_ROW_SINGULAR];
-        if (firth_on) out += f.firth ? "\tfirth" : "\tglm";
-        out += '\n';
-        if (out.size() > (1u << 20)) {
-            if (!write_all(out_fd, out)) return INQ_EXIT_PANIC;
-            out.clear();
-        }
+        if (a->all_rows) out.text += std::string("\t") + status_name(w.status);
+        if (firth_on) out.text += f.firth ? "\tfirth" : "\tglm";
+        out.text += '\n';
+        out.line_done();
     }
-    if (!write_all(out_fd, out)) return INQ_EXIT_PANIC;
-    std::string tally = "[inq assoc] " + std::to_string(n_rows) + " loci, " + std::to_string(ns) + " samples:";
-    for (int s = 0; s < 7; ++s) tally += std::string(" ") + kStatusNames[s] + " " + std::to_string(per_status[s]);
-    if (firth_on) tally += "; fitted by Firth " + std::to_string(n_firth);
-    std::fprintf(stderr, "%s\n", tally.c_str());
+}
+
+// the line on stderr: how many loci ended in each status, and how many print Firth's fit
+std::string tally(const Design &d, const std::vector<inq_assoc_row_t> &rows, const std::vector<inq_assoc_firth_row_t> &firth, bool firth_on) {
+    size_t per_status[7] = {0, 0, 0, 0, 0, 0, 0}, n_firth = 0;
+    for (size_t r = 0; r < rows.size(); ++r) {
+        ++per_status[rows[r].status < 7 ? rows[r].status : INQ_ASSOC_ROW_SINGULAR];
+        n_firth += printed(rows, firth, r).firth;
+    }
+    std::string line = "[inq assoc] " + std::to_string(rows.size()) + " loci, " + std::to_string(d.names.size()) + " samples:";
+    for (int s = 0; s < 7; ++s) line += std::string(" ") + kStatusNames[s] + " " + std::to_string(per_status[s]);
+    if (firth_on) line += "; fitted by Firth " + std::to_string(n_firth);
+    return line;
+}
+
+int assoc_impl(const inq_assoc_args_t *a, int out_fd) {
+    check_args(a);
+    BackgroundCtx device(a->device);
+    const Laps lap{"assoc"};
+    CombinedText txt;
+    txt.read(a->combined);
+    lap("text in memory");
+    txt.split();
+    const Design d = make_design(a, txt.header());
+    const std::vector<size_t> picked = pick_loci(a, txt);
+    const std::unique_ptr<float[]> mat = fill_matrix(txt, picked, d);
+    lap("numbers parsed");
+    inq_ctx_t *ctx = device.wait(lap);
+    std::vector<inq_assoc_row_t> rows(picked.size());
+    std::vector<inq_assoc_firth_row_t> firth;
+    fit_rows(ctx, a, d, mat.get(), rows, firth);
+    lap("kernels done");
+    OutBuffer out{out_fd, ""};
+    print_table(a, d, txt, picked, print_order(a->all_rows != 0, rows, firth), rows, firth, out);
+    out.flush();
+    std::fprintf(stderr, "%s\n", tally(d, rows, firth, a->firth != INQ_HOST_FIRTH_NO).c_str());
     return INQ_EXIT_OK;
 }
 
-template <class F> int reported(char *errbuf, size_t errcap, F &&body) {
-    try {
-        return body();
-    } catch (const Failure &f) {
-        set_err(errbuf, errcap, f.message);
-        return f.status;
-    } catch (const std::exception &e) {
-        set_err(errbuf, errcap, std::string("internal error: ") + e.what());
-        return INQ_EXIT_ERROR;
-    } catch (...) {
-        set_err(errbuf, errcap, "internal error");
-        return INQ_EXIT_ERROR;
+int assoc_samples_impl(const inq_assoc_args_t *args, char *names, size_t names_cap, double *y, double *cov, size_t cap, uint32_t *n_samples,
+                       uint32_t *k) {
+    check_args(args);
+    Lines in;
+    std::string header;
+    if (!in.open(args->combined)) throw Failure{INQ_EXIT_PANIC, "Problem opening file"};
+    if (!in.next(header)) throw Failure{INQ_EXIT_PANIC, "called `Option::unwrap()` on a `None` value (empty combined file)"};
+    const Design d = make_design(args, header);
+    std::string joined;
+    for (size_t i = 0; i < d.names.size(); ++i) joined += (i ? "," : "") + d.names[i];
+    if (names && names_cap) std::snprintf(names, names_cap, "%s", joined.c_str());
+    if (n_samples) *n_samples = (uint32_t)d.names.size();
+    if (k) *k = (uint32_t)d.cov_names.size();
+    if (cap >= d.names.size()) {
+        if (y) std::copy(d.y.begin(), d.y.end(), y);
+        if (cov) std::copy(d.cov.begin(), d.cov.end(), cov);
     }
+    return INQ_EXIT_OK;
 }
 
 }  // namespace
 
 extern "C" int inq_assoc(const inq_assoc_args_t *args, int out_fd, char *errbuf, size_t errcap) {
-    return reported(errbuf, errcap, [&] { return assoc_impl(args, out_fd); });
+    INQ_GUARD(assoc_impl(args, out_fd), errbuf, errcap)
 }
 
 extern "C" int inq_assoc_samples(const inq_assoc_args_t *args, char *names, size_t names_cap, double *y, double *cov, size_t cap,
                                  uint32_t *n_samples, uint32_t *k, char *errbuf, size_t errcap) {
-    return reported(errbuf, errcap, [&] {
-        check_args(args);
-        Lines in;
-        std::string header;
-        if (!in.open(args->combined)) throw Failure{INQ_EXIT_PANIC, "Problem opening file"};
-        if (!in.next(header)) throw Failure{INQ_EXIT_PANIC, "called `Option::unwrap()` on a `None` value (empty combined file)"};
-        const Design d = make_design(args, header);
-        std::string joined;
-        for (size_t i = 0; i < d.names.size(); ++i) joined += (i ? "," : "") + d.names[i];
-        if (names && names_cap) std::snprintf(names, names_cap, "%s", joined.c_str());
-        if (n_samples) *n_samples = (uint32_t)d.names.size();
-        if (k) *k = (uint32_t)d.cov_names.size();
-        if (cap >= d.names.size()) {
-            if (y) std::copy(d.y.begin(), d.y.end(), y);
-            if (cov) std::copy(d.cov.begin(), d.cov.end(), cov);
-        }
-        return INQ_EXIT_OK;
-    });
+    INQ_GUARD(assoc_samples_impl(args, names, names_cap, y, cov, cap, n_samples, k), errbuf, errcap)
 }

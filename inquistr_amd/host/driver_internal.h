@@ -32,6 +32,7 @@
 #include "../csrc/run_bytes.h"
 #include "front_end.h"
 #include "front_pool.h"
+#include "host_common.h"
 #include "inq_text.h"
 #include "sa2d.h"
 #include "span_pipeline.h"
@@ -50,24 +51,8 @@ inline const char *debug_env(const char *name) { return std::getenv(name); }
 inline const char *debug_env(const char *) { return nullptr; }
 #endif
 
-// The two switches every piece of the driver asks about, each read from the environment here and nowhere else in the library.
-// INQ_FAST_EXIT=1 (the CLI sets it): the process is about to end, what it holds may be left to the operating system.
-inline bool fast_exit() {
-    const char *e = std::getenv("INQ_FAST_EXIT");
-    return e && e[0] == '1';
-}
-// INQ_TIMING: 0 = silent, 1 = the [inq timing] lines of a call, 2 = every stage as well
-inline int timing_level() {
-    const char *e = std::getenv("INQ_TIMING");
-    return !e ? 0 : e[0] == '2' ? 2 : 1;
-}
-using Clock = std::chrono::steady_clock;
-inline double secs(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
-inline double ms(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
-
-inline void set_err(char *buf, size_t cap, const std::string &m) {
-    if (buf && cap) std::snprintf(buf, cap, "%s", m.c_str());
-}
+// fast_exit(), timing_level(), Clock / secs / ms, set_err, write_all, Failure and INQ_GUARD: host_common.h, which the text commands
+// (outlier.cc, assoc.cc) include without the rest of this header
 inline bool starts_with(const std::string &s, const char *p) { return s.compare(0, std::strlen(p), p) == 0; }
 inline bool ends_with(const std::string &s, const char *p) {
     size_t n = std::strlen(p);
@@ -77,8 +62,6 @@ inline bool is_file(const std::string &p) {
     struct stat st;
     return ::stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode);
 }
-bool write_all(int fd, const char *data, size_t len);
-inline bool write_all(int fd, const std::string &s) { return write_all(fd, s.data(), s.size()); }
 
 struct Prepared {
     std::unique_ptr<BamFile> bam;
@@ -656,16 +639,3 @@ struct OwnedArgs {
 };
 
 }  // namespace inqhost
-
-// public entries: no C++ exception may unwind across the C ABI; `fail` is what the entry returns for one
-#define INQ_GUARD_AS(fail, expr, errbuf, errcap)                           \
-    try {                                                                  \
-        return expr;                                                       \
-    } catch (const std::exception &e) {                                    \
-        set_err(errbuf, errcap, std::string("internal error: ") + e.what()); \
-        return fail;                                                       \
-    } catch (...) {                                                        \
-        set_err(errbuf, errcap, "internal error");                         \
-        return fail;                                                       \
-    }
-#define INQ_GUARD(expr, errbuf, errcap) INQ_GUARD_AS(INQ_EXIT_ERROR, expr, errbuf, errcap)

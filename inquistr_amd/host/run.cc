@@ -120,16 +120,6 @@ int ReportFile::open(const char *path, const char *what, std::string &msg) {
     return INQ_EXIT_ERROR;
 }
 
-bool write_all(int fd, const char *data, size_t len) {
-    size_t off = 0;
-    while (off < len) {
-        ssize_t w = ::write(fd, data + off, len - off);
-        if (w <= 0) return false;
-        off += (size_t)w;
-    }
-    return true;
-}
-
 int device_call_failed(int rc, inq_ctx_t *ctx, char *errbuf, size_t errcap, const std::string &suffix) {
     std::string m = std::string("device call failed: ") + inq_strerror(rc);
     if (rc == INQ_ERR_HIP) m += std::string(" [") + inq_last_error(ctx) + "]";

@@ -4,6 +4,7 @@
 #include "serve.h"
 
 #include "hostapi.h"
+#include "host_common.h"
 
 #include <poll.h>
 #include <signal.h>
@@ -358,8 +359,7 @@ int serve_main(const char *socket_path, int device, double idle_exit_s) {
     ::unlink(socket_path);
     std::fprintf(stderr, "serve: leaving after %llu calls\n", (unsigned long long)served);
     std::fflush(nullptr);
-    const char *fast = std::getenv("INQ_FAST_EXIT");  // as the other commands: the context is left to the operating system
-    if (fast && fast[0] == '1') std::_Exit(0);
+    if (inqhost::fast_exit()) std::_Exit(0);  // as the other commands: the context is left to the operating system
     host_api().session_close(S);
     return 0;
 }
