@@ -332,7 +332,9 @@ int inq_ctx_status(inq_ctx_t *ctx, uint64_t *n_tie_loci);
 /* Kernel timing with HIP events on the launch stream (for bench.py's roofline block).
  * which: 0 = whole inq_call_batch_device launch sequence, 1 = the CIGAR-walk kernel,
  * 2 = the BGZF inflate kernel of the last inq_bgzf_inflate / inq_call_span (launches = 1).
- * Returns accumulated milliseconds and launch count since the last reset. */
+ * Returns accumulated milliseconds and launch count since the last reset.  A sequence that is the CIGAR-walk kernel alone (a depth
+ * hint of at most 64 reads; no evidence, per-read Calls or other side output that a kernel behind it writes) is timed by the two
+ * events around that kernel: which = 0 and which = 1 then return the same time. */
 int inq_ctx_timing_enable(inq_ctx_t *ctx, int on);
 int inq_ctx_timing_read(inq_ctx_t *ctx, int which, double *total_ms, uint64_t *launches);
 int inq_ctx_timing_reset(inq_ctx_t *ctx);

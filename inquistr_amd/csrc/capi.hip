@@ -154,6 +154,7 @@ static int timing_begin(inq_ctx *c, hipStream_t s, EvTriple **ev) {
         c->ev_pool.push_back(t);
     }
     *ev = &c->ev_pool[c->ev_used++];
+    (*ev)->one_kernel = false;
     HIP_TRY(c, hipEventRecord((*ev)->e0, s));
     return INQ_OK;
 }
@@ -398,7 +399,7 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
     if ((rc = timing_begin(c, s, &ev)) != INQ_OK) return rc;
     if (x.flags) HIP_TRY(c, hipMemsetAsync(x.flags, 0, (size_t)b->n_loci, s));  // the kernels store tie loci only
     if (x.evidence) HIP_TRY(c, hipMemsetAsync(c->evwork.p, 0, sizeof(EvidenceWork), s));  // the slice list starts empty
-    launch_locus_call(a, b->unphased != 0, nt, grid_small, c->grid_medium, c->grid_tail, s, ev ? ev->e1 : nullptr, deep_possible ? c->deep.p : nullptr);
+    const bool more_kernels = launch_locus_call(a, b->unphased != 0, nt, grid_small, c->grid_medium, c->grid_tail, s, ev ? ev->e1 : nullptr, deep_possible ? c->deep.p : nullptr);
     HIP_TRY(c, hipGetLastError());
     // what both kernels behind the locus kernels read: the batch's pairs, and what was just written for each
     const PairView view{b->locus_pair_off, r->pair_bits, r->pair_call, b->pair_read, (const uint32_t *)b->reads, b->n_reads, b->n_pairs, b->n_loci};
@@ -443,7 +444,13 @@ static int enqueue_batch(inq_ctx_t *c, const inq_batch_t *b, inq_result_t *r, vo
         launch_read_motifs(ReadMotifArgs{kept, x.motif_word, x.motifs}, c->grid_side, s);
         HIP_TRY(c, hipGetLastError());
     }
-    if (ev) HIP_TRY(c, hipEventRecord(ev->e2, s));
+    // e2 ends the sequence - unless the sequence was locus_call_small alone (a depth hint of at most 64 reads and no side output, which
+    // are all launched behind it): e1 stands behind that already, and a second record right behind it would only hold the stream
+    const bool side_outputs = x.evidence || x.kept || x.names.recs || x.seqs.recs || x.locus_found || x.motifs;
+    if (ev) {
+        ev->one_kernel = !more_kernels && !side_outputs;
+        if (!ev->one_kernel) HIP_TRY(c, hipEventRecord(ev->e2, s));
+    }
     return INQ_OK;
 }
 
@@ -715,9 +722,10 @@ int inq_ctx_timing_read(inq_ctx_t *c, int which, double *total_ms, uint64_t *lau
     double tot = 0.0;
     for (size_t i = 0; i < c->ev_used; ++i) {
         EvTriple &e = c->ev_pool[i];
-        HIP_TRY(c, hipEventSynchronize(e.e2));
+        const hipEvent_t last = e.one_kernel ? e.e1 : e.e2;
+        HIP_TRY(c, hipEventSynchronize(last));
         float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, e.e0, which == 0 ? e.e2 : e.e1));
+        HIP_TRY(c, hipEventElapsedTime(&ms, e.e0, which == 0 ? last : e.e1));
         tot += (double)ms;
     }
     if (total_ms) *total_ms = tot;

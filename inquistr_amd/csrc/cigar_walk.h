@@ -172,9 +172,12 @@ __device__ __forceinline__ uint32_t ref_advance(uint32_t op, uint32_t len) {
 }
 // Same from the raw packed word, without extracting the op: v_bfe_i32 takes its bit offset from
 // the low FIVE bits of the word (op | len&1 << 4), so the 9-entry table is laid down twice.
+// The table's answer (-1 or 0) is then the WIDTH of a v_bfe_u32 at offset 4 in place of a shift and an and: the
+// instruction takes its width from the low five bits of that operand, so -1 asks for 31 bits from bit 4 - the word
+// has only the 28 length bits there and none is lost - and 0 asks for none, which yields 0.  Two instructions per op.
 constexpr uint32_t kConsume32 = kConsume | (kConsume << 16);
 __device__ __forceinline__ uint32_t ref_advance_raw(uint32_t w) {
-    return (w >> 4) & (uint32_t)__builtin_amdgcn_sbfe((int)kConsume32, w, 1u);
+    return __builtin_amdgcn_ubfe(w, 4u, (uint32_t)__builtin_amdgcn_sbfe((int)kConsume32, w, 1u));
 }
 // bit 0 of (kBadOp32 >> (w & 31)) is set iff the op code is 9..15 (rust-htslib cigar() panics)
 constexpr uint32_t kBadOp32 = 0xFE00FE00u;

@@ -23,8 +23,11 @@ struct DevBuf {
     size_t cap = 0;
 };
 
+// e0 in front of a launch sequence, e1 behind its first kernel, e2 behind its last.  one_kernel: nothing was launched behind e1, so
+// e2 was not recorded and e1 ends the sequence too (an event record with nothing in front of it still costs the stream ~5 us)
 struct EvTriple {
     hipEvent_t e0, e1, e2;
+    bool one_kernel = false;
 };
 
 // The byte runs behind the kept records of a flush, one kind each (the names: read_names.hip; the packed bases: read_seqs.hip): one

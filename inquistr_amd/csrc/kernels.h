@@ -61,8 +61,9 @@ struct KArgs {
 
 // deep_scratch: deep_select_scratch_bytes(n_pairs) of ctx scratch for the loci the grid-wide select takes (may be null when the
 // depth hint rules them out, or no locus can be that deep); grid_tail: workgroups of the persistent locus_call_tail - they wait
-// for one another at grid barriers, so all of them must be resident at once: at most one per compute unit of the device
-void launch_locus_call(const KArgs &a, bool unphased, bool nt_loads, uint32_t grid_small, uint32_t grid_medium,
+// for one another at grid barriers, so all of them must be resident at once: at most one per compute unit of the device.
+// ev_mid (may be null) is recorded behind locus_call_small; returns whether anything was launched behind that
+bool launch_locus_call(const KArgs &a, bool unphased, bool nt_loads, uint32_t grid_small, uint32_t grid_medium,
                        uint32_t grid_tail, hipStream_t s, hipEvent_t ev_mid, void *deep_scratch);
 
 // deep_select.hip: loci with more offered reads than this are reduced by the whole grid instead of one workgroup

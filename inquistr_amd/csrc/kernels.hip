@@ -122,6 +122,82 @@ struct LaneOrder {
     }
 };
 
+// ---- One key per lane, sorted across the wave: the bitonic network, blocks kk = 2, 4 .. 64, in each the partners at
+// xor j = kk / 2 .. 1.  Lane l of a block sorts ascending iff (l & kk) == 0 and is the lower partner iff (l & j) == 0, so it
+// keeps the larger key of the pair iff exactly one of the two holds: a 64-bit constant per stage.  A stage is the partner's key
+// (lane_xor: one DS instruction), one v_cmp, the constant xor-ed onto its mask on the scalar side, one v_cndmask.
+constexpr uint64_t keep_max_mask(int kk, int j) {
+    uint64_t m = 0;
+    for (int l = 0; l < kWave; ++l)
+        if (((l & kk) == 0) != ((l & j) == 0)) m |= 1ull << l;
+    return m;
+}
+template <int KK, int J>
+__device__ __forceinline__ int32_t bitonic_stage(int32_t k, int lane) {
+    const int32_t p = (int32_t)lane_xor<J>((uint32_t)k, lane);
+    return __builtin_amdgcn_inverse_ballot_w64(ballot64(p < k) ^ keep_max_mask(KK, J)) ? p : k;  // equal keys: either is the same
+}
+// the stages from (KK, J) to the end of block KK_LAST
+template <int KK, int J, int KK_LAST>
+__device__ __forceinline__ int32_t bitonic_stages(int32_t k, int lane) {
+    k = bitonic_stage<KK, J>(k, lane);
+    if constexpr (J > 1)
+        return bitonic_stages<KK, J / 2, KK_LAST>(k, lane);
+    else if constexpr (KK < KK_LAST)
+        return bitonic_stages<KK * 2, KK, KK_LAST>(k, lane);
+    else
+        return k;
+}
+// Ascending over the 64 lanes.  `upper_all_max`: lanes 32 .. 63 all hold INT32_MAX, and then the 15 stages of blocks 2 .. 32 are
+// enough - block 32 sorts lanes 0 .. 31 ascending, and nothing below INT32_MAX is above them - of the 21.  Wave-uniform flag.
+__device__ __forceinline__ int32_t wave_sort_asc(int32_t k, int lane, bool upper_all_max) {
+    k = bitonic_stages<2, 1, 32>(k, lane);
+    if (!upper_all_max) k = bitonic_stages<64, 32, 64>(k, lane);
+    return k;
+}
+
+// The same network on the host side of the compiler, held to a few fixed inputs: what the stage constants must get right.
+struct SortSim {
+    int32_t k[kWave];
+};
+constexpr SortSim sort_sim_run(SortSim a, int kk_last) {
+    for (int kk = 2; kk <= kk_last; kk *= 2)
+        for (int j = kk / 2; j >= 1; j /= 2) {
+            const uint64_t keep_max = keep_max_mask(kk, j);
+            SortSim r = a;
+            for (int l = 0; l < kWave; ++l) {
+                const int32_t p = a.k[l ^ j];
+                if ((p < a.k[l]) != (((keep_max >> l) & 1ull) != 0ull)) r.k[l] = p;
+            }
+            a = r;
+        }
+    return a;
+}
+// pattern 0: values ascending with the lane, 1: descending, 2: alternating 7 / -5, 3: all equal; key = value << 6 | lane as
+// LaneOrder packs it, INT32_MAX in the lanes of `pads`.  Sorted by the 15 stages when pads cover the upper half, else by the 21;
+// the result must ascend and hold every input key as often as the input does.
+constexpr bool sort_sim_ok(int pattern, uint64_t pads) {
+    SortSim a{};
+    for (int l = 0; l < kWave; ++l) {
+        const int32_t v = pattern == 0 ? l - 20 : pattern == 1 ? 43 - l : pattern == 2 ? ((l & 1) ? -5 : 7) : 3;
+        a.k[l] = ((pads >> l) & 1ull) ? INT32_MAX : (int32_t)(((uint32_t)v << 6) | (uint32_t)l);
+    }
+    const SortSim s = sort_sim_run(a, (pads >> 32) == 0xffffffffull ? 32 : 64);
+    for (int l = 0; l + 1 < kWave; ++l)
+        if (s.k[l] > s.k[l + 1]) return false;
+    for (int l = 0; l < kWave; ++l) {
+        int in = 0, out = 0;
+        for (int t = 0; t < kWave; ++t) in += a.k[t] == a.k[l], out += s.k[t] == a.k[l];
+        if (in != out) return false;
+    }
+    return true;
+}
+constexpr bool sort_sim_all(uint64_t pads) { return sort_sim_ok(0, pads) && sort_sim_ok(1, pads) && sort_sim_ok(2, pads) && sort_sim_ok(3, pads); }
+static_assert(sort_sim_all(0ull), "21 stages, every lane kept");
+static_assert(sort_sim_all(0xaaaaaaaaaaaaaaaaull) && sort_sim_all(0x00000000ffffffffull) && sort_sim_all(0x8000000000000001ull), "21 stages, pads");
+static_assert(sort_sim_all(0xffffffff00000000ull) && sort_sim_all(0xffffffffc0000003ull) && sort_sim_all(0xffffffff55555555ull), "15 stages");
+static_assert(sort_sim_all(~0ull) && sort_sim_all(~1ull) && sort_sim_all(~(1ull << 63)), "nothing or one read kept");
+
 // median_str_length (src/call.rs:497-522) for the elements flagged in `g`.  Wave-uniform result.
 template <bool FIT, int E>
 __device__ __forceinline__ double median_in_lanes(const Masks<E> &g, const Masks<E> &clip, const LaneOrder<FIT, E> &o,
@@ -165,6 +241,26 @@ __device__ __forceinline__ void reduce_locus_in_lanes(const int64_t (&val)[E], c
         // src/call.rs:311-313: sort by value (ties: file order), h1 = lower n/2, h2 = the rest
         const uint32_t mcount = kept.count();
         const uint32_t ks = mcount / 2u;
+        if constexpr (FIT && E == 1) {
+            if (!clip.any()) {
+                // The common locus: at most 64 reads, no soft-clipped Call, every value in a key.  The packed keys are sorted across
+                // the wave, the lanes that hold no kept read behind them as INT32_MAX, and lane r then holds the Call of rank r:
+                // no rank is computed.  Keys are unique (the index is in them), so the order is (value, file order) as below.  One key
+                // can EQUAL the pad - the value kFit - 1 in lane 63 -: it is the largest Call then, and whichever of the equal words
+                // comes to its rank reads as that value.
+                const int32_t sorted = wave_sort_asc(((kept.m[0] >> lane) & 1ull) ? o.key_asc[0] : INT32_MAX, lane, (kept.m[0] >> 32) == 0ull);
+                auto med = [&](uint32_t base, uint32_t cnt) -> double {
+                    if (!group_live(cnt, support)) return qnan();  // (support >= 1: a live group has a Call at each rank asked for)
+                    const auto at = [&](uint32_t r) { return (int64_t)((int32_t)readlane_u32((uint32_t)sorted, (int)r) >> LaneOrder<FIT, E>::IDX_BITS); };
+                    const int64_t vhi = at(base + cnt / 2u);
+                    const int64_t vlo = (cnt & 1u) ? vhi : at(base + cnt / 2u - 1u);
+                    return median_finish(vlo, vhi, cnt);
+                };
+                out1 = med(0u, ks);
+                out2 = med(ks, mcount - ks);
+                return;
+            }
+        }
         uint32_t rank[E];
         o.rank_asc(kept, rank);
         if (!clip.any()) {
@@ -426,37 +522,32 @@ __global__ void clear_lists(KArgs a) {
 // one-wave clear_lists in its place).  Three launches whatever the batch holds; with nothing deep the last two find empty lists
 // and leave at once.
 template <bool UNPHASED, int AUX>
-static void launch_t(const KArgs &a, uint32_t grid_small, uint32_t grid_medium, uint32_t grid_tail, hipStream_t s,
+static bool launch_t(const KArgs &a, uint32_t grid_small, uint32_t grid_medium, uint32_t grid_tail, hipStream_t s,
                      hipEvent_t ev_mid, void *deep_scratch) {
     if (grid_small) hipLaunchKernelGGL((locus_call_small<UNPHASED, AUX>), dim3(grid_small), dim3(256), 0, s, a);
     if (ev_mid) (void)hipEventRecord(ev_mid, s);
     // launches a promised depth makes pointless are skipped (a broken promise is flagged by locus_call_small)
     const uint32_t h = a.max_reads_hint;
-    if (h && h <= 64u) return;  // no locus can be on a work list
+    if (h && h <= 64u) return false;  // no locus can be on a work list: nothing follows ev_mid
     hipLaunchKernelGGL((locus_call_mid_walk<UNPHASED, AUX>), dim3(grid_medium), dim3(256), 0, s, a);
     if (h && h <= 64u * kMediumSlots) {
         // nothing can be on the deep list: the medium list is emptied by a one-wave kernel instead of the persistent tail, whose
         // workgroups need a whole CU's LDS each and would wait for a CU to drain while a span's inflate (eight 20 KB workgroups
         // per CU, on the ahead stream) is in flight - the CLI's case for data of 65 - 256-fold depth
         hipLaunchKernelGGL(clear_lists, dim3(1), dim3(128), 0, s, a);
-        return;
+        return true;
     }
     launch_locus_tail(a, UNPHASED, deep_scratch, a.n_pairs, grid_tail, s);
+    return true;
 }
 
-void launch_locus_call(const KArgs &a, bool unphased, bool nt_loads, uint32_t grid_small, uint32_t grid_medium,
+bool launch_locus_call(const KArgs &a, bool unphased, bool nt_loads, uint32_t grid_small, uint32_t grid_medium,
                        uint32_t grid_tail, hipStream_t s, hipEvent_t ev_mid, void *deep_scratch) {
-    if (unphased) {
-        if (nt_loads)
-            launch_t<true, 2>(a, grid_small, grid_medium, grid_tail, s, ev_mid, deep_scratch);
-        else
-            launch_t<true, 0>(a, grid_small, grid_medium, grid_tail, s, ev_mid, deep_scratch);
-    } else {
-        if (nt_loads)
-            launch_t<false, 2>(a, grid_small, grid_medium, grid_tail, s, ev_mid, deep_scratch);
-        else
-            launch_t<false, 0>(a, grid_small, grid_medium, grid_tail, s, ev_mid, deep_scratch);
-    }
+    if (unphased)
+        return nt_loads ? launch_t<true, 2>(a, grid_small, grid_medium, grid_tail, s, ev_mid, deep_scratch)
+                        : launch_t<true, 0>(a, grid_small, grid_medium, grid_tail, s, ev_mid, deep_scratch);
+    return nt_loads ? launch_t<false, 2>(a, grid_small, grid_medium, grid_tail, s, ev_mid, deep_scratch)
+                    : launch_t<false, 0>(a, grid_small, grid_medium, grid_tail, s, ev_mid, deep_scratch);
 }
 
 // An empty launch makes the runtime load this translation unit's code object now (inq_ctx_create, on the

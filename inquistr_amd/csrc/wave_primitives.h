@@ -55,6 +55,16 @@ __device__ __forceinline__ uint64_t row_inclusive_scan_u64(uint64_t x) {
 // ((l & 0x10) | 0x0f) of its 32-lane half.
 __device__ __forceinline__ uint32_t row_last(uint32_t x) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, 0x10 | (0x0f << 5)); }
 __device__ __forceinline__ uint64_t row_last_u64(uint64_t x) { return (uint64_t)row_last((uint32_t)x) | (uint64_t)row_last((uint32_t)(x >> 32)) << 32; }
+// The value of lane (l ^ J), J a power of two: ds_swizzle in bit-mask mode (and 0x1f, or 0, xor J) inside a 32-lane half,
+// ds_bpermute between the halves.  Every lane of the wave must be active.
+template <int J>
+__device__ __forceinline__ uint32_t lane_xor(uint32_t x, int lane) {
+    static_assert(J == 1 || J == 2 || J == 4 || J == 8 || J == 16 || J == 32, "one lane bit");
+    if constexpr (J < 32)
+        return (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, 0x1f | (J << 10));
+    else
+        return (uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, (int)x);
+}
 // Lane 15 of the row holds the OR / the maximum of its lanes
 __device__ __forceinline__ uint32_t row_or(uint32_t x) {
     x |= dpp_shr_zero<DPP_ROW_SHR1>(x);
